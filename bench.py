@@ -20,6 +20,11 @@ binds to the uninitialised copy.
 `python bench.py --gpus N` without a launcher starts its own N ranks (launch_ranks): the parent never touches
 the GPU, it spawns N fresh interpreters with RANK / LOCAL_RANK / WORLD_SIZE set and relays rank 0's line.
 
+A plain run sets up, warms up, times the steps and prints the line (headline + `roofline` from the timed steps' own
+stamps).  `--full` adds everything that takes runs of its own behind the timed region: `kernels`, `cpu_baseline`,
+`configs`, `sharded` and `vendor` (the --no-* options leave parts of it out).  `--dump-outputs DIR` writes what the
+last timed step computed as DIR/<name>.npy (dump_outputs); the inputs are generated from fixed seeds.
+
 Extra objects on the JSON line:
   roofline      the potrf trailing SYRK/GEMM update (fp64 MFMA bound), the dominant kernel: algorithmic FLOP of
                 every launch divided by its duration, measured live inside the timed region by in-kernel
@@ -606,6 +611,27 @@ def kernel_rows(eng, step, _lib, N, M):
     return rows
 
 
+def l_sample_index(n, count=65536):
+    """Fixed, seeded positions (i, j), j <= i, of the Cholesky factor's lower triangle that --dump-outputs writes."""
+    rng = np.random.default_rng(7)
+    i = rng.integers(0, n, size=count)
+    return i, rng.integers(0, i + 1)
+
+
+def dump_outputs(dirname, gp, mu, sigma):
+    """What the last timed step computed, as float64 DIR/<name>.npy: the predictive mean and standard deviation at the
+    query points, alpha and the log-determinant of the fit, and of the factor L (N x N, too large to keep whole) its
+    diagonal and the entries at l_sample_index.  Under 1 MB at the default sizes."""
+    os.makedirs(dirname, exist_ok=True)
+    L = gp.engine.get_L()  # (not gp.L: that would keep the N x N copy alive for the rest of the run)
+    i, j = l_sample_index(L.shape[0])
+    out = {"mu": mu, "sigma": sigma, "alpha": gp.alpha, "logdet": [gp._logdet], "L_diagonal": np.diagonal(L).copy(),
+           "L_sample": L[i, j]}
+    del L
+    for name, arr in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.asarray(arr, dtype=np.float64))
+
+
 def sharded_configs(args, wl, sharding, rank, world, local_rank, rdv, gather, eng_comm, _lib):
     """BASELINE configs 3 and 5 through the sharded drivers, AFTER the timed headline region (not part of `value`):
     config 3 = the 64-point RationalQuadratic hyper-parameter grid at N = 16384, d = 16 through
@@ -717,6 +743,12 @@ def main():
     ap.add_argument("--n", type=int, default=16384)
     ap.add_argument("--d", type=int, default=8)
     ap.add_argument("--m", type=int, default=1024)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-kernel pass, the CPU baselines, the device timings of the other "
+                         "BASELINE configurations, the sharded configs 3 / 5 and the vendor comparator (minutes); the --no-* "
+                         "options below leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, under 1 MB at the default sizes)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cpu-metric-size", action="store_true",
                     help="skip the one CPU run at the metric's own size (about a minute of host time)")
@@ -726,6 +758,8 @@ def main():
     ap.add_argument("--no-cpu-configs", action="store_true",
                     help="skip the CPU oracle at the sizes of BASELINE configs 2-5 (about two minutes of host time)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "RANK" not in os.environ and args.gpus > 1:
         launch_ranks(args.gpus)  # parent: spawns the ranks before anything touches the GPU, relays, exits
@@ -847,9 +881,12 @@ def run(args, wl, sharding, GpRegressor, SquaredExponential, _lib, rank, world, 
             return eng.comm_allgather(vec)  # RCCL over xGMI: the only collective of the path
         return np.array(rdv.allgather_obj(np.asarray(vec, dtype=float), tag=f"values {np.size(vec)}"))
 
+    last = {}  # the arrays a caller receives from the latest step (--dump-outputs)
+
     def step():
         gp.set_hyperparameters(theta)  # K-build + potrf + alpha
         mu, sig = gp(pts)  # cross-covariance + TRSM + reductions
+        last["mu"], last["sigma"] = mu, sig
         # plain NumPy reductions only: a BLAS call here (np.linalg.norm -> OpenBLAS nrm2) starts OpenBLAS's
         # spinning worker pool, which starves the HIP runtime's completion handling and doubled the
         # step time from the next step on (round-2 probe, profiles/HISTORY.md)
@@ -894,8 +931,11 @@ def run(args, wl, sharding, GpRegressor, SquaredExponential, _lib, rank, world, 
     flops_step = N**3 / 3.0 + M * float(N) ** 2
     value = flops_step * args.steps * world / dt / 1e9
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gp, last["mu"], last["sigma"])
+
     sharded = None
-    if not args.no_sharded:
+    if args.full and not args.no_sharded:
         try:
             sharded = sharded_configs(args, wl, sharding, rank, world, local_rank, rdv, gather,
                                       eng if gather == "rccl" else None, _lib)
@@ -1018,14 +1058,14 @@ def run(args, wl, sharding, GpRegressor, SquaredExponential, _lib, rank, world, 
         }
         if sharded is not None:
             line["sharded"] = sharded
-        if world == 1:
+        if world == 1 and args.full:
             line["roofline"]["kernels"] = kernel_rows(eng, step, _lib, N, M)
-        if world == 1 and not args.no_configs:
+        if world == 1 and args.full and not args.no_configs:
             try:
                 line["configs"] = device_configs(wl, dev_index, gp, theta, N)
             except Exception as err:  # the headline line must not be lost to a failure behind the timed region
                 line["configs"] = {"error": f"{type(err).__name__}: {err}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # the bounded N = 4096 sample first: it also warms the BLAS pool for the run at the metric's own size, whose
             # figure is the one `value` carries (round 5; until round 4 `value` was the sample's)
             sample = cpu_baseline(4096, d, 256)  # ~10-15 s of host work in all
@@ -1051,7 +1091,7 @@ def run(args, wl, sharding, GpRegressor, SquaredExponential, _lib, rank, world, 
                     line["cpu_baseline"]["configs"] = cpu_configs(wl, d)
                 except Exception as err:
                     line["cpu_baseline"]["configs"] = {"error": f"{type(err).__name__}: {err}"}
-        if world == 1 and not args.no_configs:
+        if world == 1 and args.full and not args.no_configs:
             line["vendor"] = vendor_yardstick()
         print(json.dumps(flatten_for_the_record(line)), flush=True)
 

@@ -741,7 +741,7 @@ def test_bench_eight_ranks_on_one_device(tmp_path):
     env.update(BENCH_CFG3_POINTS="8", BENCH_CFG5_LADDERS="8", BENCH_CFG5_STEPS="4", BENCH_CFG3_N="4096",
                GPMI_RDV_DIR=str(tmp_path), MASTER_PORT="29533", GPMI_DEBUG_INFO="1")
     run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-                          "--n", "4096", "--m", "256"], env=env, capture_output=True, text=True, timeout=900)
+                          "--n", "4096", "--m", "256", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert run.returncode == 0, run.stderr[-3000:]
     line = json.loads(run.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 8 and line["steps"] == 2
@@ -754,6 +754,45 @@ def test_bench_eight_ranks_on_one_device(tmp_path):
     assert "error" not in sh and sh["config3"]["lml_evals_per_s"] > 0 and sh["config5"]["lml_evals_per_s"] > 0, (sh, [l for l in run.stderr.splitlines() if "[gpmi]" in l or "Error" in l or "line " in l][-40:])
     assert np.isfinite(line["value"]) and line["value"] > 0
     assert glob.glob(str(tmp_path / "*")) == [], "the rendezvous directory is removed at the end"
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """`bench.py` without --full times its steps and prints the headline line only; --dump-outputs writes what the last
+    timed step computed, which must be the fit + predict of the seeded workload (reduced sizes, against the oracle)."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import bench
+    from oracle import gp_oracle as orc
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, d, m = 4096, 8, 256
+    out = tmp_path / "dump"
+    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--n", str(n), "--d", str(d), "--m", str(m), "--dump-outputs", str(out)],
+                         capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, run.stderr[-3000:]
+    line = json.loads(run.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "GFLOP/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert not {"cpu_baseline", "configs", "sharded", "vendor"} & set(line) and "kernels" not in line["roofline"]
+    got = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert set(got) == {"mu", "sigma", "alpha", "logdet", "L_diagonal", "L_sample"}
+    assert all(a.dtype == np.float64 for a in got.values()) and sum(a.nbytes for a in got.values()) < 64 << 20
+
+    x, y, e = wl.synthetic_dataset(2, n, d)
+    theta = wl.timing_theta(wl.SE, y, d)
+    ref = orc.OracleGp(x, y, e, kernel=orc.SE, hyperpars=theta)
+    mu, sig = ref(wl.query_points(2, m, d))
+    i, j = bench.l_sample_index(n)
+    check(got["mu"], mu, what="bench dump: mu")
+    check(got["sigma"], sig, what="bench dump: sigma")
+    check(got["alpha"], ref.alpha, what="bench dump: alpha")
+    check(got["logdet"], [np.log(np.diagonal(ref.L)).sum()], what="bench dump: log-determinant")
+    check(got["L_diagonal"], np.diagonal(ref.L), what="bench dump: diagonal of L")
+    check(got["L_sample"], ref.L[i, j], what="bench dump: sampled entries of L")
 
 
 # ---------------------------------------------------------------------------------------

@@ -69,7 +69,7 @@ NAMES = {"update128": "gemm_dma_kernel<1, 0> (trailing update, 128x128 tiles)",
          "panel_trsm": "gemm_nt_kernel<0, 1, 0, {64,32}, 128> (panel TRSM as a product with the inverse block)",
          "syrk_kskip": "gemm_dma_kernel<., 1> (k-skipped SYRK K^-1 = L^-T L^-1; regression.py:556-557)"}
 out = {
-    "command": "tools/pmc_run.sh: rocprofv3 --pmc <one group per pass> --output-format csv -- <command>, GPMI_FLOW=0; passes: FETCH_SIZE | WRITE_SIZE | SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F64 | TCC_HIT_sum TCC_MISS_sum | GRBM_GUI_ACTIVE; commands: bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-sharded | tools/grad_times.py 16384 | tools/config5_bench.py 4",
+    "command": "tools/pmc_run.sh: rocprofv3 --pmc <one group per pass> --output-format csv -- <command>, GPMI_FLOW=0; passes: FETCH_SIZE | WRITE_SIZE | SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F64 | TCC_HIT_sum TCC_MISS_sum | GRBM_GUI_ACTIVE; commands: bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-sharded | tools/grad_times.py 16384 | tools/config5_bench.py 4",
     "correction": "FETCH_SIZE x 2 (gfx950 reports half the bytes of wide coalesced reads, MI355X_MICROARCH.md), WRITE_SIZE exact; both in KiB",
     "same_schedule": "traffic and algorithmic bytes of the dominant kernel come from the SAME run: the FETCH_SIZE pass prints its own bench line (GPMI_FLOW=0: stream-ordered tail), whose same_kernel_name_all_launches.algorithmic_bytes_per_launch_avg is quoted below",
     "kernels": {},

@@ -19,7 +19,7 @@ done
 for c in "${groups[@]}"; do
   d=$out/bench/$(echo $c | tr ' ' '+')
   mkdir -p $out/bench
-  GPMI_FLOW=0 timeout 600 rocprofv3 --pmc $c --output-format csv -d $d -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-sharded --no-configs > $d.log 2>&1
+  GPMI_FLOW=0 timeout 600 rocprofv3 --pmc $c --output-format csv -d $d -- python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-sharded --no-configs > $d.log 2>&1
 done
 python3 - "$out" <<'PY'
 # per run and queue (bench: the update stream's full-round launches, the slices on the panel stream's 32 CUs and the first
