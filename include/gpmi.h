@@ -38,6 +38,12 @@ extern "C" {
 /* covariance kernels (covariance.py:181-279 SquaredExponential, 282-368 RationalQuadratic) */
 #define GPMI_KERNEL_SE 0 /* theta = [ln a, ln l_1..ln l_d]            n_theta = d+1 */
 #define GPMI_KERNEL_RQ 1 /* theta = [ln a, ln kappa, ln l_1..ln l_d]  n_theta = d+2 */
+/* sum of 2..4 SE / RQ kernels (CompositeCovariance, covariance.py:33-36,47-105) declared per handle by gpmi_set_sum:
+ * theta = the components' own parameter vectors back to back, in component order; n_theta = the sum of theirs.
+ * Accepted by gpmi_fit, gpmi_lml, gpmi_lml_batch(_submit), gpmi_lml_grad(_batch), gpmi_loo_terms, gpmi_loo_grad(_batch),
+ * gpmi_covariance, gpmi_cross_covariance; a sum fit serves gpmi_predict, gpmi_posterior, gpmi_get_K, gpmi_get_L and
+ * gpmi_append_point.  Every other entry point returns GPMI_ERR_ARG for it. */
+#define GPMI_KERNEL_SUM 2
 
 #define GPMI_OK 0
 #define GPMI_ERR_ARG (-1)     /* bad argument / call order */
@@ -246,6 +252,12 @@ int gpmi_loo_terms(gpmi_ctx* ctx, int kernel, const double* theta_host, int n_th
  * replaces the diagonal term with this call before gpmi_fit / gpmi_lml / gpmi_lml_grad (n values; ignored
  * when a dense y_cov was given to gpmi_set_data). */
 int gpmi_set_noise(gpmi_ctx* ctx, const double* noise_var_host);
+
+/* ---- sums of stationary kernels (GPMI_KERNEL_SUM) ------------------------------------
+ * Declares the components of the handle's sum: nk in 2..4, kernels[m] GPMI_KERNEL_SE or GPMI_KERNEL_RQ in the order of
+ * the sum.  K = sum_m a_m^2 (C_m + 1e-12 I) + extra_diag I + data errors (every component carries its own jitter,
+ * covariance.py:254-255,348); a query point's prior variance is sum_m a_m^2. */
+int gpmi_set_sum(gpmi_ctx* ctx, int nk, const int* kernels);
 /* q_i = alpha_i^2 - (K^-1)_ii of the most recent gpmi_lml_grad call (n values): the gradient with respect to
  * ln sigma_i is 1/2 Q_ii 2 sigma_i^2 = sigma_i^2 q_i (covariance.py:682-686, regression.py:561-565). */
 int gpmi_lml_grad_qdiag(gpmi_ctx* ctx, double* qdiag_host);

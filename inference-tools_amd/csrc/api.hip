@@ -236,6 +236,8 @@ void free_data(gpmi_ctx* c) {
   c->bInfo = nullptr;
   if (c->bParams) (void)hipFree(c->bParams);
   c->bParams = nullptr;
+  if (c->bSum) (void)hipFree(c->bSum);
+  c->bSum = nullptr;
   if (c->h_bRed) (void)hipHostFree(c->h_bRed);
   c->h_bRed = nullptr;
   if (c->h_bInfo) (void)hipHostFree(c->h_bInfo);
@@ -255,6 +257,7 @@ void free_data(gpmi_ctx* c) {
 int make_params(gpmi_ctx* c, int kernel, const double* theta, int n_theta, double extra,
                 KParams& p) {
   ARGCHK(c, c->n > 0, "gpmi_set_data has not been called");
+  ARGCHK(c, kernel != GPMI_KERNEL_SUM, "this entry point does not take sums of kernels (GPMI_KERNEL_SUM)");
   ARGCHK(c, kernel == GPMI_KERNEL_SE || kernel == GPMI_KERNEL_RQ, "unknown kernel id");
   const int off = (kernel == GPMI_KERNEL_SE) ? 1 : 2;
   ARGCHK(c, n_theta == c->d + off, "n_theta does not match the kernel and the data dimension");
@@ -269,6 +272,48 @@ int make_params(gpmi_ctx* c, int kernel, const double* theta, int n_theta, doubl
   for (int k = 0; k < p.d; ++k) {
     const double l = std::exp(theta[off + k]);
     p.inv_l2[k] = 1.0 / (l * l);
+  }
+  return GPMI_OK;
+}
+
+int make_cov(gpmi_ctx* c, int kernel, const double* theta, int n_theta, double extra, CovParams& p) {
+  p = CovParams();
+  if (kernel != GPMI_KERNEL_SUM) return make_params(c, kernel, theta, n_theta, extra, p);
+  ARGCHK(c, c->n > 0, "gpmi_set_data has not been called");
+  ARGCHK(c, c->sum_nk >= 2, "GPMI_KERNEL_SUM: declare the components of the sum with gpmi_set_sum first");
+  ARGCHK(c, theta != nullptr, "theta is NULL");
+  int need = 0;
+  for (int m = 0; m < c->sum_nk; ++m) need += (c->sum_kinds[m] == GPMI_KERNEL_SE ? 1 : 2) + (int)c->d;
+  ARGCHK(c, n_theta == need, "n_theta does not match the sum declared by gpmi_set_sum and the data dimension");
+  p.kernel = GPMI_KERNEL_SUM;
+  p.d = (int)c->d;
+  p.kappa = 1.0;
+  p.extra_diag = extra;
+  p.nk = c->sum_nk;
+  int off = 0;
+  double a2 = 0.0;
+  for (int m = 0; m < p.nk; ++m) {
+    const int nt = (c->sum_kinds[m] == GPMI_KERNEL_SE ? 1 : 2) + (int)c->d;
+    if (int rc = make_params(c, c->sum_kinds[m], theta + off, nt, 0.0, p.comp[m])) return rc;
+    a2 += p.comp[m].a2;  // K_qq = sum_m a_m^2 in component order (regression.py:210 through covariance.py:87-90)
+    off += nt;
+  }
+  p.a2 = a2;
+  return GPMI_OK;
+}
+
+int make_batch_params(gpmi_ctx* c, int kernel, int64_t T, const double* thetas, int n_theta, const double* extra,
+                      std::vector<KParams>& ps, std::vector<CovParams>& sps) {
+  ps.clear();
+  sps.clear();
+  if (kernel == GPMI_KERNEL_SUM) {
+    sps.resize((size_t)T);
+    for (int64_t t = 0; t < T; ++t)
+      if (int rc = make_cov(c, kernel, thetas + t * n_theta, n_theta, extra ? extra[t] : 0.0, sps[(size_t)t])) return rc;
+  } else {
+    ps.resize((size_t)T);
+    for (int64_t t = 0; t < T; ++t)
+      if (int rc = make_params(c, kernel, thetas + t * n_theta, n_theta, extra ? extra[t] : 0.0, ps[(size_t)t])) return rc;
   }
   return GPMI_OK;
 }
@@ -296,7 +341,7 @@ void build_mix_square(gpmi_ctx* c, hipStream_t s, const MixEval& mx, double* dst
 // K(theta) + sig into lane.A (lower tiles), factorise, forward-solve the residual, reduce.
 // Leaves: lane.A = L, lane.invD, vec[0:np] = v = L^-1 (y - mu), red[2*slot..] = {v.v, sum ln L_ii},
 // info[slot].  `mu_dev` may be null (then mu_const is used).  `mix` != nullptr: mixture covariance.
-int enqueue_factor_and_forward(gpmi_ctx* c, Lane& L, const KParams& p, const double* mu_dev,
+int enqueue_factor_and_forward(gpmi_ctx* c, Lane& L, const CovParams& p, const double* mu_dev,
                                double mu_const, int slot, bool allow_lookahead,
                                const MixEval* mix, bool prebuild_inv2, double* backward_out, double* early_identity) {
   hipStream_t s = L.stream;
@@ -456,10 +501,12 @@ int ensure_batch_ws(gpmi_ctx* c, int want) {
   c->bgrad_cap = c->bgrad_ntheta = 0;
   if (c->bInfo) (void)hipFree(c->bInfo);
   if (c->bParams) (void)hipFree(c->bParams);
+  if (c->bSum) (void)hipFree(c->bSum);
   if (c->h_bRed) (void)hipHostFree(c->h_bRed);
   if (c->h_bInfo) (void)hipHostFree(c->h_bInfo);
   c->bInfo = nullptr;
   c->bParams = nullptr;
+  c->bSum = nullptr;
   c->h_bRed = nullptr;
   c->h_bInfo = nullptr;
   c->bcap = 0;
@@ -472,6 +519,7 @@ int ensure_batch_ws(gpmi_ctx* c, int want) {
   HIPCHK(c, hipMalloc(&c->bMu, sizeof(double) * want * c->np));
   HIPCHK(c, hipMalloc(&c->bInfo, sizeof(int) * want));
   HIPCHK(c, hipMalloc(&c->bParams, sizeof(KParams) * want));
+  HIPCHK(c, hipMalloc(&c->bSum, sizeof(CovParams) * want));
   HIPCHK(c, hipHostMalloc(&c->h_bRed, sizeof(double) * 2 * want));
   HIPCHK(c, hipHostMalloc(&c->h_bInfo, sizeof(int) * want));
   c->bcap = want;
@@ -741,6 +789,18 @@ int gpmi_set_streams(gpmi_ctx* c, int n_streams) {
     c->lanes.pop_back();
   }
   return ensure_lanes(c, 1 + (size_t)n_streams);
+}
+
+int gpmi_set_sum(gpmi_ctx* c, int nk, const int* kernels) {
+  if (!c) return GPMI_ERR_ARG;
+  ARGCHK(c, nk >= 2 && nk <= GPMI_MAX_SUM, "gpmi_set_sum: a sum has 2 to 4 components");
+  ARGCHK(c, kernels != nullptr, "kernels is NULL");
+  for (int m = 0; m < nk; ++m)
+    ARGCHK(c, kernels[m] == GPMI_KERNEL_SE || kernels[m] == GPMI_KERNEL_RQ,
+           "gpmi_set_sum: every component is GPMI_KERNEL_SE or GPMI_KERNEL_RQ");
+  c->sum_nk = nk;
+  for (int m = 0; m < GPMI_MAX_SUM; ++m) c->sum_kinds[m] = (m < nk) ? kernels[m] : 0;
+  return GPMI_OK;
 }
 
 int gpmi_set_option(gpmi_ctx* c, int option, int value) {

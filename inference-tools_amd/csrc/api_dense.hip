@@ -57,7 +57,7 @@ int gpmi_capacity(gpmi_ctx* c, int64_t* capacity) {
 int gpmi_append_point(gpmi_ctx* c, const double* x_new, double y_new, double noise_var_new, const double* mu,
                       double* alpha_out, double* logdet_out, int* info) {
   if (!c) return GPMI_ERR_ARG;
-  ARGCHK(c, c->fitted && c->fit_params.kernel >= 0 && c->mix_nk == 0, "gpmi_append_point needs a fit by gpmi_fit (SE / RQ)");
+  ARGCHK(c, c->fitted && c->fit_params.kernel >= 0 && c->mix_nk == 0, "gpmi_append_point needs a fit by gpmi_fit (SE / RQ / a sum of them)");
   ARGCHK(c, !c->ycov, "gpmi_append_point: diagonal data errors only");
   ARGCHK(c, x_new && mu, "x_new / mu is NULL");
   ARGCHK(c, c->n < c->np, "no capacity left: set GPMI_OPT_RESERVE_POINTS before gpmi_set_data");
@@ -65,7 +65,7 @@ int gpmi_append_point(gpmi_ctx* c, const double* x_new, double y_new, double noi
   Lane& L = c->lanes[0];
   hipStream_t s = L.stream;
   const int64_t n = c->n;
-  const KParams p = c->fit_params;
+  const CovParams& p = c->fit_params;  // (a sum: the cross-covariance builder sees through to its components)
   if (int rc = ensure_query_ws(c, GPMI_NB)) return rc;
   HIPCHK(c, hipMemcpyAsync(c->x + n * c->d, x_new, sizeof(double) * c->d, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpyAsync(c->pts, x_new, sizeof(double) * c->d, hipMemcpyHostToDevice, s));
@@ -75,7 +75,13 @@ int gpmi_append_point(gpmi_ctx* c, const double* x_new, double y_new, double noi
   HIPCHK(c, hipMemsetAsync(L.info, 0, sizeof(int), s));
   trsv_forward(c, s, L.A, c->np, c->ld, L.invD, c->Q, lvec, L.info);
   // K_nn = a^2 (1 + 1e-12) + WhiteNoise + data variance (covariance.py:254-255, regression.py:239)
-  const double knn = p.a2 * (1.0 + 1e-12) + p.extra_diag + noise_var_new;
+  // (a sum: sum_m a_m^2 (1 + 1e-12), each component with its own jitter, as in the fused build)
+  double kdiag = p.a2 * (1.0 + 1e-12);
+  if (p.kernel == GPMI_KERNEL_SUM) {
+    kdiag = 0.0;
+    for (int m = 0; m < p.nk; ++m) kdiag += p.comp[m].a2 * (1.0 + 1e-12);
+  }
+  const double knn = kdiag + p.extra_diag + noise_var_new;
   hipLaunchKernelGGL(append_row_kernel, dim3(1), dim3(1024), 0, s, L.A, c->ld, n, lvec, knn, L.red + 4);
   hipLaunchKernelGGL(append_invd_kernel, dim3(1), dim3(GPMI_NB), 0, s, L.A, c->ld, n, L.invD, L.red + 4);
   HIPCHK(c, hipGetLastError());
@@ -189,7 +195,7 @@ int gpmi_fit_dense(gpmi_ctx* c, const double* K_host, const double* mu, double* 
   if (logdet_out) *logdet_out = L.h_red[1];
   INFOCHK(c, L.h_info[0]);
   if (info) *info = L.h_info[0];
-  c->fit_params = KParams{};
+  c->fit_params = CovParams();
   c->fit_params.kernel = -1;  // dense: the kernel-specific entry points (gpmi_predict, ...) do not apply
   c->fitted = (L.h_info[0] == 0);
   c->mix_nk = 0;

@@ -160,9 +160,14 @@ void lane_free(Lane& L);
 int ensure_lanes(gpmi_ctx* c, size_t count);
 void free_data(gpmi_ctx* c);
 int make_params(gpmi_ctx* c, int kernel, const double* theta, int n_theta, double extra, KParams& p);
+// make_params for the entry points that also take sums (GPMI_KERNEL_SUM: the layout of gpmi_set_sum)
+int make_cov(gpmi_ctx* c, int kernel, const double* theta, int n_theta, double extra, CovParams& p);
+// T evaluations: single kernels into ps, sums into sps (the other vector is left empty)
+int make_batch_params(gpmi_ctx* c, int kernel, int64_t T, const double* thetas, int n_theta, const double* extra,
+                      std::vector<KParams>& ps, std::vector<CovParams>& sps);
 int set_device(gpmi_ctx* c);
 void build_mix_square(gpmi_ctx* c, hipStream_t s, const MixEval& mx, double* dst, bool lower_only);
-int enqueue_factor_and_forward(gpmi_ctx* c, Lane& L, const KParams& p, const double* mu_dev, double mu_const, int slot, bool allow_lookahead = true,
+int enqueue_factor_and_forward(gpmi_ctx* c, Lane& L, const CovParams& p, const double* mu_dev, double mu_const, int slot, bool allow_lookahead = true,
                                const MixEval* mix = nullptr, bool prebuild_inv2 = false, double* backward_out = nullptr,
                                double* early_identity = nullptr);
 int ensure_second_matrix(gpmi_ctx* c, Lane& L);

@@ -67,7 +67,7 @@ int gpmi_fit_mix(gpmi_ctx* c, int nk, const int* kernels, const double* thetas, 
   double* mu_dev = L.vec + 3 * c->np;
   const MixEval mx{nk, ps, c->mix_g, extra_diag, c->mix_scratch, c->mix_zero};
   HIPCHK(c, hipMemcpyAsync(mu_dev, mu, sizeof(double) * c->n, hipMemcpyHostToDevice, s));
-  if (int rc = enqueue_factor_and_forward(c, L, ps[0], mu_dev, 0.0, 0, true, &mx)) return rc;
+  if (int rc = enqueue_factor_and_forward(c, L, CovParams(ps[0]), mu_dev, 0.0, 0, true, &mx)) return rc;
   trsv_backward(c, s, L.A, c->np, c->ld, L.invD, L.vec, c->alpha, L.info);
   HIPCHK(c, hipMemcpyAsync(L.h_red, L.red, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipMemcpyAsync(L.h_info, L.info, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -79,7 +79,7 @@ int gpmi_fit_mix(gpmi_ctx* c, int nk, const int* kernels, const double* thetas, 
   if (info) *info = L.h_info[0];
   c->mix_nk = nk;
   for (int m = 0; m < nk; ++m) c->mix_p[m] = ps[m];
-  c->fit_params = ps[0];
+  c->fit_params = CovParams(ps[0]);
   c->fitted = (L.h_info[0] == 0);
   return GPMI_OK;
 }
@@ -99,7 +99,7 @@ int gpmi_lml_mix(gpmi_ctx* c, int nk, const int* kernels, const double* thetas, 
   double* mu_dev = L.vec + 3 * c->np;
   const MixEval mx{nk, ps, c->mix_g, extra_diag, c->mix_scratch, c->mix_zero};
   HIPCHK(c, hipMemcpyAsync(mu_dev, mu, sizeof(double) * c->n, hipMemcpyHostToDevice, s));
-  if (int rc = enqueue_factor_and_forward(c, L, ps[0], mu_dev, 0.0, 0, true, &mx)) return rc;
+  if (int rc = enqueue_factor_and_forward(c, L, CovParams(ps[0]), mu_dev, 0.0, 0, true, &mx)) return rc;
   HIPCHK(c, hipMemcpyAsync(L.h_red, L.red, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipMemcpyAsync(L.h_info, L.info, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
@@ -145,7 +145,7 @@ int gpmi_lml_grad_mix(gpmi_ctx* c, int nk, const int* kernels, const double* the
   double* wdev = c->mix_scratch + (int64_t)2 * GPMI_MAX_MIX * c->np;
   const MixEval mx{nk, ps, c->mix_g, extra_diag, c->mix_scratch, c->mix_zero};
   HIPCHK(c, hipMemcpyAsync(mu_dev, mu, sizeof(double) * c->n, hipMemcpyHostToDevice, s));
-  if (int rc = enqueue_factor_and_forward(c, L, ps[0], mu_dev, 0.0, 0, true, &mx)) return rc;
+  if (int rc = enqueue_factor_and_forward(c, L, CovParams(ps[0]), mu_dev, 0.0, 0, true, &mx)) return rc;
   if (hw_host) {
     HIPCHK(c, hipMemsetAsync(wdev, 0, sizeof(double) * 2 * nk * c->np, s));
     HIPCHK(c, hipMemcpy2DAsync(wdev, sizeof(double) * c->np, hw_host, sizeof(double) * c->n, sizeof(double) * c->n,
@@ -644,7 +644,7 @@ int gpmi_loo_terms_mix(gpmi_ctx* c, int nk, const int* kernels, const double* th
   double* diag_dev = L.vec + 2 * c->np;
   const MixEval mx{nk, ps, c->mix_g, extra_diag, c->mix_scratch, c->mix_zero};
   HIPCHK(c, hipMemcpyAsync(mu_dev, mu, sizeof(double) * c->n, hipMemcpyHostToDevice, s));
-  if (int rc = enqueue_factor_and_forward(c, L, ps[0], mu_dev, 0.0, 0, true, &mx)) return rc;
+  if (int rc = enqueue_factor_and_forward(c, L, CovParams(ps[0]), mu_dev, 0.0, 0, true, &mx)) return rc;
   trsv_backward(c, s, L.A, c->np, c->ld, L.invD, L.vec, alpha_dev, L.info);
   if (int rc = enqueue_inverse_factor(c, L, L)) return rc;
   launch_rows_sumsq(s, L.B2, c->ld, c->np, c->np, 0.0, diag_dev);  // -diag(K^-1): squared row norms of L^-T

@@ -9,8 +9,8 @@ extern "C" {
 int gpmi_fit(gpmi_ctx* c, int kernel, const double* theta, int n_theta, double extra_diag,
              const double* mu, double* alpha_out, double* logdet_out, int* info) {
   if (!c) return GPMI_ERR_ARG;
-  KParams p;
-  if (int rc = make_params(c, kernel, theta, n_theta, extra_diag, p)) return rc;
+  CovParams p;
+  if (int rc = make_cov(c, kernel, theta, n_theta, extra_diag, p)) return rc;
   ARGCHK(c, mu != nullptr, "mu is NULL");
   if (int rc = set_device(c)) return rc;
   Lane& L = c->lanes[0];
@@ -65,11 +65,9 @@ int gpmi_lml_batch(gpmi_ctx* c, int kernel, int64_t T, const double* thetas, int
   if (c->lanes.size() < 2)
     if (int rc = ensure_lanes(c, 2)) return rc;
   const int S = (int)c->lanes.size() - 1;
-  std::vector<KParams> ps((size_t)T);
-  for (int64_t t = 0; t < T; ++t)
-    if (int rc = make_params(c, kernel, thetas + t * n_theta, n_theta, extra ? extra[t] : 0.0,
-                             ps[(size_t)t]))
-      return rc;
+  std::vector<KParams> ps;
+  std::vector<CovParams> sps;  // (a sum: its parameters, ps stays empty)
+  if (int rc = make_batch_params(c, kernel, T, thetas, n_theta, extra, ps, sps)) return rc;
   if ((T >= 2 || c->lockstep_always) && c->np <= 4096 && !c->ycov) {
     // small problems: all evaluations of a chunk advance in lockstep, one launch per step for the
     // whole chunk (blockIdx.z), instead of one latency-bound launch sequence per evaluation
@@ -93,14 +91,20 @@ int gpmi_lml_batch(gpmi_ctx* c, int kernel, int64_t T, const double* thetas, int
       double* Inv = c->bInv + (int64_t)off * bs.sInv;
       double* Vec = c->bVec + (int64_t)off * bs.sVec;
       double* Mu = c->bMu + (int64_t)off * (mus ? c->n : 1);
-      HIPCHK(c, hipMemcpyAsync(c->bParams + off, ps.data() + t_first, sizeof(KParams) * B, hipMemcpyHostToDevice, s));
+      if (sps.empty())
+        HIPCHK(c, hipMemcpyAsync(c->bParams + off, ps.data() + t_first, sizeof(KParams) * B, hipMemcpyHostToDevice, s));
+      else
+        HIPCHK(c, hipMemcpyAsync(c->bSum + off, sps.data() + t_first, sizeof(CovParams) * B, hipMemcpyHostToDevice, s));
       if (mus)
         HIPCHK(c, hipMemcpyAsync(Mu, mus + t_first * c->n, sizeof(double) * B * c->n, hipMemcpyHostToDevice, s));
       else
         HIPCHK(c, hipMemcpyAsync(Mu, mu_const + t_first, sizeof(double) * B, hipMemcpyHostToDevice, s));
       HIPCHK(c, hipMemsetAsync(c->bInfo + off, 0, sizeof(int) * B, s));
-      launch_kbuild_square_batched(s, ps[0].kernel, c->bParams + off, B, c->x, c->n, c->np, c->noise, A, c->ld, bs.sMat,
-                                   (int)c->d);
+      if (sps.empty())
+        launch_kbuild_square_batched(s, kernel, c->bParams + off, B, c->x, c->n, c->np, c->noise, A, c->ld, bs.sMat,
+                                     (int)c->d);
+      else
+        launch_kbuild_square_batched(s, c->bSum + off, B, c->x, c->n, c->np, c->noise, A, c->ld, bs.sMat, (int)c->d);
       potrf_lower_batched(c, s, A, c->np, c->ld, Inv, c->bInfo + off, bs);
       launch_residual_batched(s, c->y, mus ? Mu : nullptr, mus ? nullptr : Mu, Vec + 2 * c->np, c->n, c->np, bs);
       trsv_forward(c, s, A, c->np, c->ld, Inv, Vec + 2 * c->np, Vec, c->bInfo + off, bs);
@@ -140,7 +144,8 @@ int gpmi_lml_batch(gpmi_ctx* c, int kernel, int64_t T, const double* thetas, int
       HIPCHK(c, hipMemcpyAsync(mu_dev, mus + t * c->n, sizeof(double) * c->n,
                                hipMemcpyHostToDevice, L.stream));
     }
-    if (int rc = enqueue_factor_and_forward(c, L, ps[(size_t)t], mu_dev,
+    const CovParams pt = sps.empty() ? CovParams(ps[(size_t)t]) : sps[(size_t)t];
+    if (int rc = enqueue_factor_and_forward(c, L, pt, mu_dev,
                                             mu_const ? mu_const[t] : 0.0, slot, S == 1 || T == 1))
       return rc;
   }
@@ -202,7 +207,8 @@ int gpmi_lml_batch_submit(gpmi_ctx* c, int kernel, int64_t T, const double* thet
   const int off = slot * (c->bcap / 2);
   // inputs through pinned staging that lives until the wait (the copies are asynchronous)
   const int64_t mu_doubles = mus ? T * c->n : T;
-  const int64_t need = (int64_t)sizeof(KParams) * T + (int64_t)sizeof(double) * mu_doubles;
+  const size_t psize = (kernel == GPMI_KERNEL_SUM) ? sizeof(CovParams) : sizeof(KParams);
+  const int64_t need = (int64_t)psize * T + (int64_t)sizeof(double) * mu_doubles;
   if (c->h_bStage_bytes[slot] < need) {
     if (c->h_bStage[slot]) (void)hipHostFree(c->h_bStage[slot]);
     c->h_bStage[slot] = nullptr;
@@ -210,10 +216,16 @@ int gpmi_lml_batch_submit(gpmi_ctx* c, int kernel, int64_t T, const double* thet
     HIPCHK(c, hipHostMalloc(&c->h_bStage[slot], (size_t)need));
     c->h_bStage_bytes[slot] = need;
   }
-  KParams* ps = reinterpret_cast<KParams*>(c->h_bStage[slot]);
-  double* mu_stage = reinterpret_cast<double*>(c->h_bStage[slot] + sizeof(KParams) * T);
-  for (int64_t t = 0; t < T; ++t)
-    if (int rc = make_params(c, kernel, thetas + t * n_theta, n_theta, extra ? extra[t] : 0.0, ps[t])) return rc;
+  double* mu_stage = reinterpret_cast<double*>(c->h_bStage[slot] + psize * T);
+  if (kernel == GPMI_KERNEL_SUM) {
+    CovParams* sps = reinterpret_cast<CovParams*>(c->h_bStage[slot]);
+    for (int64_t t = 0; t < T; ++t)
+      if (int rc = make_cov(c, kernel, thetas + t * n_theta, n_theta, extra ? extra[t] : 0.0, sps[t])) return rc;
+  } else {
+    KParams* ps = reinterpret_cast<KParams*>(c->h_bStage[slot]);
+    for (int64_t t = 0; t < T; ++t)
+      if (int rc = make_params(c, kernel, thetas + t * n_theta, n_theta, extra ? extra[t] : 0.0, ps[t])) return rc;
+  }
   std::memcpy(mu_stage, mus ? mus : mu_const, sizeof(double) * mu_doubles);
   hipStream_t s = c->lanes[1 + slot].stream;
   BatchShape bs{(int)T, c->np * c->ld, (c->np / GPMI_NB) * GPMI_NB * GPMI_NB, 4 * c->np};
@@ -221,11 +233,18 @@ int gpmi_lml_batch_submit(gpmi_ctx* c, int kernel, int64_t T, const double* thet
   double* Inv = c->bInv + (int64_t)off * bs.sInv;
   double* Vec = c->bVec + (int64_t)off * bs.sVec;
   double* Mu = c->bMu + (int64_t)off * (mus ? c->n : 1);
-  HIPCHK(c, hipMemcpyAsync(c->bParams + off, ps, sizeof(KParams) * T, hipMemcpyHostToDevice, s));
+  const bool sum = (kernel == GPMI_KERNEL_SUM);
+  if (sum)
+    HIPCHK(c, hipMemcpyAsync(c->bSum + off, c->h_bStage[slot], sizeof(CovParams) * T, hipMemcpyHostToDevice, s));
+  else
+    HIPCHK(c, hipMemcpyAsync(c->bParams + off, c->h_bStage[slot], sizeof(KParams) * T, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpyAsync(Mu, mu_stage, sizeof(double) * mu_doubles, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemsetAsync(c->bInfo + off, 0, sizeof(int) * T, s));
-  launch_kbuild_square_batched(s, ps[0].kernel, c->bParams + off, (int)T, c->x, c->n, c->np, c->noise, A, c->ld, bs.sMat,
-                               (int)c->d);
+  if (sum)
+    launch_kbuild_square_batched(s, c->bSum + off, (int)T, c->x, c->n, c->np, c->noise, A, c->ld, bs.sMat, (int)c->d);
+  else
+    launch_kbuild_square_batched(s, kernel, c->bParams + off, (int)T, c->x, c->n, c->np, c->noise, A, c->ld, bs.sMat,
+                                 (int)c->d);
   potrf_lower_batched(c, s, A, c->np, c->ld, Inv, c->bInfo + off, bs);
   launch_residual_batched(s, c->y, mus ? Mu : nullptr, mus ? nullptr : Mu, Vec + 2 * c->np, c->n, c->np, bs);
   trsv_forward(c, s, A, c->np, c->ld, Inv, Vec + 2 * c->np, Vec, c->bInfo + off, bs);
@@ -277,7 +296,7 @@ static int ensure_gradient_lane(gpmi_ctx* c, int n_theta) {
 int gpmi_prepare_gradient(gpmi_ctx* c, int n_theta) {
   if (!c) return GPMI_ERR_ARG;
   ARGCHK(c, c->n > 0, "gpmi_set_data has not been called");
-  ARGCHK(c, n_theta >= 1 && n_theta <= GPMI_MAX_D + 2, "n_theta out of range");
+  ARGCHK(c, n_theta >= 1 && n_theta <= GPMI_MAX_SUM * (GPMI_MAX_D + 2), "n_theta out of range");
   if (int rc = set_device(c)) return rc;
   if (int rc = ensure_gradient_lane(c, n_theta)) return rc;
   HIPCHK(c, hipDeviceSynchronize());  // the allocations have happened when this returns
@@ -288,8 +307,8 @@ int gpmi_lml_grad(gpmi_ctx* c, int kernel, const double* theta, int n_theta, dou
                   const double* mu, double* lml, double* grad_theta, double* trace_q,
                   double* alpha_out, int* info) {
   if (!c) return GPMI_ERR_ARG;
-  KParams p;
-  if (int rc = make_params(c, kernel, theta, n_theta, extra_diag, p)) return rc;
+  CovParams p;
+  if (int rc = make_cov(c, kernel, theta, n_theta, extra_diag, p)) return rc;
   ARGCHK(c, mu && lml && grad_theta, "mu / lml / grad_theta is NULL");
   if (int rc = set_device(c)) return rc;
   if (int rc = ensure_gradient_lane(c, n_theta)) return rc;
@@ -297,7 +316,7 @@ int gpmi_lml_grad(gpmi_ctx* c, int kernel, const double* theta, int n_theta, dou
   hipStream_t s = L.stream;
   double* mu_dev = L.vec + 3 * c->np;
   double* alpha_dev = L.vec + c->np;
-  double* gout = L.red + 16;  // n_theta + 1 values (n_theta <= GPMI_MAX_D + 2)
+  double* gout = L.red + 16;  // n_theta + 1 values (n_theta <= GPMI_MAX_SUM (GPMI_MAX_D + 2))
   HIPCHK(c, hipMemcpyAsync(mu_dev, mu, sizeof(double) * c->n, hipMemcpyHostToDevice, s));
   if (int rc = enqueue_factor_and_forward(c, L, p, mu_dev, 0.0, 0, true, nullptr, false, nullptr, L.B2)) return rc;
   trsv_backward(c, s, L.A, c->np, c->ld, L.invD, L.vec, alpha_dev, L.info);
@@ -355,9 +374,9 @@ static int lml_grad_batch_impl(gpmi_ctx* c, int kernel, int64_t T, const double*
   }
   if (c->lanes.size() < 2)
     if (int rc = ensure_lanes(c, 2)) return rc;
-  std::vector<KParams> ps((size_t)T);
-  for (int64_t t = 0; t < T; ++t)
-    if (int rc = make_params(c, kernel, thetas + t * n_theta, n_theta, extra ? extra[t] : 0.0, ps[(size_t)t])) return rc;
+  std::vector<KParams> ps;
+  std::vector<CovParams> sps;  // (a sum: its parameters, ps stays empty)
+  if (int rc = make_batch_params(c, kernel, T, thetas, n_theta, extra, ps, sps)) return rc;
   // lockstep: every launch carries the chunk in blockIdx.z - K-build, factorisation, both sweeps, L^-T by forward
   // substitution on the identity, the k-skipped SYRK K^-1 = L^-T L^-1 (regression.py:556-557) and the fused contraction
   ARGCHK(c, c->bpend[0] == 0 && c->bpend[1] == 0,
@@ -377,12 +396,16 @@ static int lml_grad_batch_impl(gpmi_ctx* c, int kernel, int64_t T, const double*
   const int W = n_theta + 1;
   const size_t rowb = sizeof(double) * c->n;
   RowStage stage(c, s);  // strided rows travel between the caller's arrays and the device through pinned memory (api_internal.h)
-  if (int rc = stage.reserve((size_t)c->bgrad_cap * (7 * (rowb + 256) + sizeof(KParams) + 512))) return rc;
+  if (int rc = stage.reserve((size_t)c->bgrad_cap * (7 * (rowb + 256) + sizeof(CovParams) + 512))) return rc;
   for (int64_t t0 = 0; t0 < T; t0 += c->bgrad_cap) {
     const int B = (int)((T - t0 < c->bgrad_cap) ? T - t0 : c->bgrad_cap);
     BatchShape bs = shape0;
     bs.count = B;
-    if (int rc = stage.put_copy(c->bParams, ps.data() + t0, sizeof(KParams) * B)) return rc;  // (inputs leave from pinned memory)
+    if (sps.empty()) {
+      if (int rc = stage.put_copy(c->bParams, ps.data() + t0, sizeof(KParams) * B)) return rc;  // (inputs leave from pinned memory)
+    } else {
+      if (int rc = stage.put_copy(c->bSum, sps.data() + t0, sizeof(CovParams) * B)) return rc;
+    }
     if (mus) {
       if (int rc = stage.put_copy(c->bMu, mus + t0 * c->n, sizeof(double) * B * c->n)) return rc;
     } else {
@@ -391,8 +414,11 @@ static int lml_grad_batch_impl(gpmi_ctx* c, int kernel, int64_t T, const double*
     HIPCHK(c, hipMemsetAsync(c->bInfo, 0, sizeof(int) * B, s));
     if (noise_batch)
       if (int rc = stage.up(c->bNoise, sizeof(double) * c->np, noise_batch + t0 * c->n, rowb, rowb, B)) return rc;
-    launch_kbuild_square_batched(s, ps[0].kernel, c->bParams, B, c->x, c->n, c->np, noise_batch ? c->bNoise : c->noise,
-                                 c->bA, c->ld, bs.sMat, (int)c->d, noise_batch ? c->np : 0);
+    if (sps.empty())
+      launch_kbuild_square_batched(s, kernel, c->bParams, B, c->x, c->n, c->np, noise_batch ? c->bNoise : c->noise,
+                                   c->bA, c->ld, bs.sMat, (int)c->d, noise_batch ? c->np : 0);
+    else  // (sums take no per-problem noise: the *_noise entry points refuse them)
+      launch_kbuild_square_batched(s, c->bSum, B, c->x, c->n, c->np, c->noise, c->bA, c->ld, bs.sMat, (int)c->d);
     potrf_lower_batched(c, s, c->bA, c->np, c->ld, c->bInv, c->bInfo, bs);
     launch_residual_batched(s, c->y, mus ? c->bMu : nullptr, mus ? nullptr : c->bMu, c->bVec + 2 * c->np, c->n, c->np,
                             bs);
@@ -404,8 +430,12 @@ static int lml_grad_batch_impl(gpmi_ctx* c, int kernel, int64_t T, const double*
     const GemmBatch syrk{B, bs.sMat, bs.sMat, bs.sMat};
     launch_gemm(s, TILES_LOWER, OP_ASSIGN, false, 1, c->bA, c->ld, c->bB2, c->ld, c->bB2, c->ld, nt, nt, (int)c->np,
                 nullptr, syrk);
-    launch_lml_grad_batched(s, c->bParams, B, n_theta, c->x, c->n, c->np, c->bA, c->ld, bs.sMat, alpha_dev, alpha_dev,
-                            bs.sVec, c->bGws, c->bGout);
+    if (sps.empty())
+      launch_lml_grad_batched(s, c->bParams, B, n_theta, c->x, c->n, c->np, c->bA, c->ld, bs.sMat, alpha_dev, alpha_dev,
+                              bs.sVec, c->bGws, c->bGout);
+    else
+      launch_lml_grad_batched(s, c->bSum, B, n_theta, c->x, c->n, c->np, c->bA, c->ld, bs.sMat, alpha_dev, alpha_dev,
+                              bs.sVec, c->bGws, c->bGout, (int)c->d);
     if (qdiag_out) {  // diag(alpha alpha^T - K^-1) per problem, into the noise buffer (consumed by the build above)
       launch_qdiag_batched(s, B, c->bA, c->ld, alpha_dev, c->bNoise, c->n, bs.sMat, bs.sVec, c->np);
       if (int rc = stage.down(qdiag_out + t0 * c->n, rowb, c->bNoise, sizeof(double) * c->np, rowb, B)) return rc;
@@ -443,6 +473,7 @@ int gpmi_lml_grad_batch_noise(gpmi_ctx* c, int kernel, int64_t T, const double* 
                               double* grad_theta, double* trace_q, double* alpha_out, double* qdiag_out, int* info) {
   if (!c) return GPMI_ERR_ARG;
   ARGCHK(c, noise_var && qdiag_out, "noise_var / qdiag is NULL");
+  ARGCHK(c, kernel != GPMI_KERNEL_SUM, "gpmi_lml_grad_batch_noise does not take sums of kernels (GPMI_KERNEL_SUM)");
   ARGCHK(c, !c->ycov, "per-point noise hyper-parameters need diagonal data errors");
   return lml_grad_batch_impl(c, kernel, T, thetas, n_theta, extra, mus, mu_const, noise_var, lml, grad_theta, trace_q,
                              alpha_out, qdiag_out, info);
@@ -481,9 +512,9 @@ static int loo_grad_batch_impl(gpmi_ctx* c, int kernel, int64_t T, const double*
   }
   if (c->lanes.size() < 2)
     if (int rc = ensure_lanes(c, 2)) return rc;
-  std::vector<KParams> ps((size_t)T);
-  for (int64_t t = 0; t < T; ++t)
-    if (int rc = make_params(c, kernel, thetas + t * n_theta, n_theta, extra ? extra[t] : 0.0, ps[(size_t)t])) return rc;
+  std::vector<KParams> ps;
+  std::vector<CovParams> sps;  // (a sum: its parameters, ps stays empty)
+  if (int rc = make_batch_params(c, kernel, T, thetas, n_theta, extra, ps, sps)) return rc;
   ARGCHK(c, c->bpend[0] == 0 && c->bpend[1] == 0,
          "gpmi_loo_grad_batch: an asynchronous batch is pending on this handle (gpmi_lml_batch_wait first)");
   if (int rc = ensure_batch_ws(c, (int)(T < 64 ? (T < 2 ? 2 : T) : 64))) return rc;
@@ -511,12 +542,16 @@ static int loo_grad_batch_impl(gpmi_ctx* c, int kernel, int64_t T, const double*
   const int W = n_theta + 1;
   const size_t rowb = sizeof(double) * c->n;
   RowStage stage(c, s);  // strided rows travel between the caller's arrays and the device through pinned memory (api_internal.h)
-  if (int rc = stage.reserve((size_t)c->bgrad_cap * (7 * (rowb + 256) + sizeof(KParams) + 512))) return rc;
+  if (int rc = stage.reserve((size_t)c->bgrad_cap * (7 * (rowb + 256) + sizeof(CovParams) + 512))) return rc;
   for (int64_t t0 = 0; t0 < T; t0 += c->bgrad_cap) {
     const int B = (int)((T - t0 < c->bgrad_cap) ? T - t0 : c->bgrad_cap);
     BatchShape bs = shape0;
     bs.count = B;
-    if (int rc = stage.put_copy(c->bParams, ps.data() + t0, sizeof(KParams) * B)) return rc;  // (inputs leave from pinned memory)
+    if (sps.empty()) {
+      if (int rc = stage.put_copy(c->bParams, ps.data() + t0, sizeof(KParams) * B)) return rc;  // (inputs leave from pinned memory)
+    } else {
+      if (int rc = stage.put_copy(c->bSum, sps.data() + t0, sizeof(CovParams) * B)) return rc;
+    }
     if (mus) {
       if (int rc = stage.put_copy(c->bMu, mus + t0 * c->n, sizeof(double) * B * c->n)) return rc;
     } else {
@@ -525,8 +560,11 @@ static int loo_grad_batch_impl(gpmi_ctx* c, int kernel, int64_t T, const double*
     HIPCHK(c, hipMemsetAsync(c->bInfo, 0, sizeof(int) * B, s));
     if (noise_batch)
       if (int rc = stage.up(c->bNoise, sizeof(double) * c->np, noise_batch + t0 * c->n, rowb, rowb, B)) return rc;
-    launch_kbuild_square_batched(s, ps[0].kernel, c->bParams, B, c->x, c->n, c->np, noise_batch ? c->bNoise : c->noise,
-                                 c->bA, c->ld, bs.sMat, (int)c->d, noise_batch ? c->np : 0);
+    if (sps.empty())
+      launch_kbuild_square_batched(s, kernel, c->bParams, B, c->x, c->n, c->np, noise_batch ? c->bNoise : c->noise,
+                                   c->bA, c->ld, bs.sMat, (int)c->d, noise_batch ? c->np : 0);
+    else  // (sums take no per-problem noise: the *_noise entry points refuse them)
+      launch_kbuild_square_batched(s, c->bSum, B, c->x, c->n, c->np, c->noise, c->bA, c->ld, bs.sMat, (int)c->d);
     potrf_lower_batched(c, s, c->bA, c->np, c->ld, c->bInv, c->bInfo, bs);
     launch_residual_batched(s, c->y, mus ? c->bMu : nullptr, mus ? nullptr : c->bMu, c->bVec + 2 * c->np, c->n, c->np,
                             bs);
@@ -552,8 +590,12 @@ static int loo_grad_batch_impl(gpmi_ctx* c, int kernel, int64_t T, const double*
     if (mdiag_out) launch_rows_sumsq(s, c->bB2, c->ld, c->np, c->np, 0.0, mdiag_dev, B, bs.sMat, sLoo, -1.0);  // M_ii = |row i of G|^2
     launch_gemm(s, TILES_LOWER, OP_ASSIGN, false, 0, c->bA, c->ld, c->bB2, c->ld, c->bB2, c->ld, nt, nt, (int)c->np,
                 nullptr, syrk);
-    launch_lml_grad_batched(s, c->bParams, B, n_theta, c->x, c->n, c->np, c->bA, c->ld, bs.sMat, p_dev, alpha_dev, sLoo,
-                            c->bGws, c->bGout);
+    if (sps.empty())
+      launch_lml_grad_batched(s, c->bParams, B, n_theta, c->x, c->n, c->np, c->bA, c->ld, bs.sMat, p_dev, alpha_dev, sLoo,
+                              c->bGws, c->bGout);
+    else
+      launch_lml_grad_batched(s, c->bSum, B, n_theta, c->x, c->n, c->np, c->bA, c->ld, bs.sMat, p_dev, alpha_dev, sLoo,
+                              c->bGws, c->bGout, (int)c->d);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(c->h_bGout, c->bGout, sizeof(double) * W * B, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(c->h_bInfo, c->bInfo, sizeof(int) * B, hipMemcpyDeviceToHost, s));
@@ -590,6 +632,7 @@ int gpmi_loo_grad_batch_noise(gpmi_ctx* c, int kernel, int64_t T, const double* 
                               int* info) {
   if (!c) return GPMI_ERR_ARG;
   ARGCHK(c, noise_var && mdiag_out, "noise_var / mdiag is NULL");
+  ARGCHK(c, kernel != GPMI_KERNEL_SUM, "gpmi_loo_grad_batch_noise does not take sums of kernels (GPMI_KERNEL_SUM)");
   ARGCHK(c, !c->ycov, "per-point noise hyper-parameters need diagonal data errors");
   return loo_grad_batch_impl(c, kernel, T, thetas, n_theta, extra, mus, mu_const, noise_var, alpha_out, ikdiag_out, p_out,
                              mdiag_out, grad_theta, trace_q, info);
@@ -605,7 +648,7 @@ int gpmi_predict(gpmi_ctx* c, const double* pts, int64_t m, double* mu_out, doub
   Lane& L = c->lanes[0];
   hipStream_t s = L.stream;
   const int64_t chunk = 2048;
-  KParams p = c->fit_params;
+  const CovParams& p = c->fit_params;
   for (int64_t m0 = 0; m0 < m; m0 += chunk) {
     const int64_t mc = (m - m0 < chunk) ? m - m0 : chunk;
     const int64_t mp = round_up(mc, GPMI_NB);
@@ -643,7 +686,7 @@ int gpmi_posterior(gpmi_ctx* c, const double* pts, int64_t m, double* mu_out, do
   if (int rc = set_device(c)) return rc;
   Lane& L = c->lanes[0];
   hipStream_t s = L.stream;
-  KParams p = c->fit_params;
+  const CovParams& p = c->fit_params;
   const int64_t mp = round_up(m, GPMI_NB);
   if (int rc = ensure_query_ws(c, mp)) return rc;
   HIPCHK(c, hipMemcpyAsync(c->pts, pts, sizeof(double) * m * c->d, hipMemcpyHostToDevice, s));
@@ -680,12 +723,12 @@ int gpmi_spatial_derivatives(gpmi_ctx* c, const double* pts, int64_t m, double* 
   ARGCHK(c, c->fitted, "gpmi_spatial_derivatives needs a successful gpmi_fit");
   ARGCHK(c, c->fit_params.kernel >= 0 || c->mix_nk > 0,
          "gpmi_spatial_derivatives: the model was fitted with a caller-built covariance (gpmi_fit_dense) - use gpmi_predict_dense / gpmi_solve_rows");
-  ARGCHK(c, c->fit_params.kernel == GPMI_KERNEL_SE, "spatial derivatives: SquaredExponential only");
+  ARGCHK(c, c->fit_params.kernel == GPMI_KERNEL_SE, "spatial derivatives: SquaredExponential only (not sums of kernels)");
   ARGCHK(c, pts && m > 0 && dmu_out && dvar_out, "NULL argument or m <= 0");
   if (int rc = set_device(c)) return rc;
   Lane& L = c->lanes[0];
   hipStream_t s = L.stream;
-  KParams p = c->fit_params;
+  const CovParams& p = c->fit_params;
   const int64_t chunk = 1024, d = c->d;
   for (int64_t m0 = 0; m0 < m; m0 += chunk) {
     const int64_t mc = (m - m0 < chunk) ? m - m0 : chunk;
@@ -716,12 +759,12 @@ int gpmi_gradient(gpmi_ctx* c, const double* pts, int64_t m, double* gmu_out, do
   ARGCHK(c, c->fitted, "gpmi_gradient needs a successful gpmi_fit");
   ARGCHK(c, c->fit_params.kernel >= 0 || c->mix_nk > 0,
          "gpmi_gradient: the model was fitted with a caller-built covariance (gpmi_fit_dense) - use gpmi_predict_dense / gpmi_solve_rows");
-  ARGCHK(c, c->fit_params.kernel == GPMI_KERNEL_SE, "gradient: SquaredExponential only");
+  ARGCHK(c, c->fit_params.kernel == GPMI_KERNEL_SE, "gradient: SquaredExponential only (not sums of kernels)");
   ARGCHK(c, pts && m > 0 && gmu_out && gcov_out, "NULL argument or m <= 0");
   if (int rc = set_device(c)) return rc;
   Lane& L = c->lanes[0];
   hipStream_t s = L.stream;
-  KParams p = c->fit_params;
+  const CovParams& p = c->fit_params;
   const int64_t d = c->d;
   int64_t chunk = 1024 / d;  // d right-hand sides per point
   if (chunk < 1) chunk = 1;
@@ -769,8 +812,8 @@ int gpmi_loo_diag(gpmi_ctx* c, double* ikdiag) {
 int gpmi_loo_terms(gpmi_ctx* c, int kernel, const double* theta, int n_theta, double extra_diag,
                    const double* mu, double* alpha_out, double* ikdiag, int* info) {
   if (!c) return GPMI_ERR_ARG;
-  KParams p;
-  if (int rc = make_params(c, kernel, theta, n_theta, extra_diag, p)) return rc;
+  CovParams p;
+  if (int rc = make_cov(c, kernel, theta, n_theta, extra_diag, p)) return rc;
   ARGCHK(c, mu && alpha_out && ikdiag, "mu / alpha / ikdiag is NULL");
   if (int rc = set_device(c)) return rc;
   if (int rc = ensure_lanes(c, 2)) return rc;
@@ -800,8 +843,8 @@ int gpmi_loo_grad(gpmi_ctx* c, int kernel, const double* theta, int n_theta, dou
                   const double* mu, double* alpha_out, double* ikdiag, double* p_out,
                   double* grad_theta, double* trace_q, int* info) {
   if (!c) return GPMI_ERR_ARG;
-  KParams p;
-  if (int rc = make_params(c, kernel, theta, n_theta, extra_diag, p)) return rc;
+  CovParams p;
+  if (int rc = make_cov(c, kernel, theta, n_theta, extra_diag, p)) return rc;
   ARGCHK(c, mu && alpha_out && ikdiag && p_out && grad_theta, "NULL argument");
   if (int rc = set_device(c)) return rc;
   if (int rc = ensure_lanes(c, 2)) return rc;
@@ -862,8 +905,8 @@ int gpmi_loo_grad(gpmi_ctx* c, int kernel, const double* theta, int n_theta, dou
 int gpmi_covariance(gpmi_ctx* c, int kernel, const double* theta, int n_theta, double extra_diag,
                     int with_noise, double* K_host) {
   if (!c) return GPMI_ERR_ARG;
-  KParams p;
-  if (int rc = make_params(c, kernel, theta, n_theta, extra_diag, p)) return rc;
+  CovParams p;
+  if (int rc = make_cov(c, kernel, theta, n_theta, extra_diag, p)) return rc;
   ARGCHK(c, K_host != nullptr, "K_host is NULL");
   if (int rc = set_device(c)) return rc;
   if (int rc = ensure_lanes(c, 2)) return rc;
@@ -888,8 +931,8 @@ int gpmi_covariance(gpmi_ctx* c, int kernel, const double* theta, int n_theta, d
 int gpmi_cross_covariance(gpmi_ctx* c, int kernel, const double* theta, int n_theta,
                           const double* pts, int64_t m, double* out) {
   if (!c) return GPMI_ERR_ARG;
-  KParams p;
-  if (int rc = make_params(c, kernel, theta, n_theta, 0.0, p)) return rc;
+  CovParams p;
+  if (int rc = make_cov(c, kernel, theta, n_theta, 0.0, p)) return rc;
   ARGCHK(c, pts && out && m > 0, "pts / out is NULL or m <= 0");
   if (int rc = set_device(c)) return rc;
   hipStream_t s = c->lanes[0].stream;

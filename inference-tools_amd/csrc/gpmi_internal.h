@@ -28,6 +28,20 @@ struct KParams {
   double inv_l2[GPMI_MAX_D];  // 1 / l_k^2
 };
 
+// A covariance evaluation the entry points hold: one SE / RQ kernel (the KParams base, nk = 0), or a sum of nk = 2..4 of
+// them (GPMI_KERNEL_SUM, gpmi_set_sum).  For a sum the base carries kernel = GPMI_KERNEL_SUM, d, a2 = sum_m a_m^2 (the
+// prior variance of a query point, regression.py:210) and the WhiteNoise variance; comp[m] are the components' own
+// parameters (extra_diag 0).  The launchers of kbuild.hip / grad.hip have CovParams overloads, which launch the fused
+// sum kernels for GPMI_KERNEL_SUM, and KParams forms, which take one SE / RQ kernel and assert so (a sum copied into a
+// KParams would lose its components).  KParams itself keeps its layout: it is the kernarg of every single-kernel launch.
+constexpr int GPMI_MAX_SUM = 4;
+struct CovParams : KParams {
+  int nk = 0;
+  KParams comp[GPMI_MAX_SUM] = {};
+  CovParams() : KParams{} {}
+  explicit CovParams(const KParams& k) : KParams(k) {}
+};
+
 struct ProfSlot {
   hipEvent_t e0, e1;
   int klass;
@@ -125,7 +139,9 @@ struct gpmi_ctx {
   bool lockstep_always = false;  // GPMI_OPT_LOCKSTEP_ALWAYS
   bool no_flow = false;          // GPMI_OPT_NO_FLOW
   int64_t reserve = 0;           // GPMI_OPT_RESERVE_POINTS: extra rows of padding at the next gpmi_set_data
-  KParams fit_params{};
+  CovParams fit_params;
+  int sum_nk = 0;                   // gpmi_set_sum: components of this handle's GPMI_KERNEL_SUM (0: none declared)
+  int sum_kinds[GPMI_MAX_SUM] = {};
   double* alpha = nullptr;  // np (device) — fitted alpha
   // prediction workspace
   double* Q = nullptr;      // mq_cap x ld
@@ -164,6 +180,7 @@ struct gpmi_ctx {
   int bgrad_cap = 0, bgrad_ntheta = 0;
   int* bInfo = nullptr;
   KParams* bParams = nullptr;
+  CovParams* bSum = nullptr;  // the per-problem parameters of a lockstep batch of sums (bcap of them)
   // asynchronous lockstep batches (gpmi_lml_batch_submit / _wait): two slots = the two halves of the workspace, on the
   // streams of lanes 1 and 2; evaluations pending per slot (0: free), pinned staging of their inputs
   int bpend[2] = {0, 0};
@@ -227,6 +244,18 @@ void launch_kbuild_square_part(hipStream_t s, const KParams& p, const double* x,
 void launch_kbuild_cross(hipStream_t s, const KParams& p, const double* U, int64_t mu, int64_t mp,
                          const double* V, int64_t n, int64_t np, double* out, int64_t ld);
 void launch_add_full(hipStream_t s, double* A, int64_t ld, const double* Y, int64_t n);
+// The same builders for a CovParams: the fused sum build when p.kernel == GPMI_KERNEL_SUM, else its base's build.  (The
+// KParams forms take SE / RQ only: a sum is never passed as its base.)
+void launch_kbuild_square(hipStream_t s, const CovParams& p, const double* x, int64_t n, int64_t np,
+                          const double* noise, double* A, int64_t ld, bool lower_only);
+void launch_kbuild_square_part(hipStream_t s, const CovParams& p, const double* x, int64_t n, int64_t np,
+                               const double* noise, double* A, int64_t ld, int part, int split_cols);
+void launch_kbuild_cross(hipStream_t s, const CovParams& p, const double* U, int64_t mu, int64_t mp,
+                         const double* V, int64_t n, int64_t np, double* out, int64_t ld);
+// lockstep batch of sums (pdev: batch CovParams of kind GPMI_KERNEL_SUM), the square lower tiles as
+// launch_kbuild_square_batched
+void launch_kbuild_square_batched(hipStream_t s, const CovParams* pdev, int batch, const double* x, int64_t n,
+                                  int64_t np, const double* noise, double* A, int64_t ld, int64_t stride, int d);
 
 // grad.hip: fused contraction 1/2 sum (alpha alpha^T - K^-1) o dK/dtheta_j with dK recomputed from x.
 // out[0..n_theta) = gradient, out[n_theta] = sum_i (alpha_i^2 - K^-1_ii).  iK holds K^-1 (lower tiles).
@@ -238,6 +267,14 @@ void launch_lml_grad(hipStream_t s, const KParams& p, int n_theta, const double*
 void launch_lml_grad_batched(hipStream_t s, const KParams* pdev, int batch, int n_theta, const double* x, int64_t n,
                              int64_t np, const double* iK, int64_t ld, int64_t sK, const double* u, const double* v,
                              int64_t sV, double* ws, double* out);
+// the same for a CovParams (the fused contraction of a sum: partials [component 1, ..., component nk, trace]) and for a
+// lockstep batch of sums
+void launch_lml_grad(hipStream_t s, const CovParams& p, int n_theta, const double* x, int64_t n,
+                     int64_t np, const double* iK, int64_t ld, const double* u, const double* v,
+                     double* ws, double* out);
+void launch_lml_grad_batched(hipStream_t s, const CovParams* pdev, int batch, int n_theta, const double* x, int64_t n,
+                             int64_t np, const double* iK, int64_t ld, int64_t sK, const double* u, const double* v,
+                             int64_t sV, double* ws, double* out, int d);
 void launch_mirror_lower(hipStream_t s, double* A, int64_t ld, int64_t np, int batch = 1, int64_t sMat = 0);
 // (batch > 1: problem z works on A / G + z sMat and on vectors sVec (sAlpha, sLoo) apart)
 void launch_scale_columns(hipStream_t s, const double* A, const double* sc, double* G, int64_t ld,

@@ -9,6 +9,8 @@
 // staged point panels, weights them with Q_ab = alpha_a alpha_b - K^-1_ab (off-diagonal elements
 // counted twice) and reduces to one partial per tile and parameter; a second kernel sums the
 // partials in a fixed order (bit-reproducible).  HBM-read bound: 8 bytes per element of K^-1.
+#include <cassert>
+
 #include "gpmi_internal.h"
 
 namespace {
@@ -213,7 +215,145 @@ __global__ void loo_vectors_kernel(const double* __restrict__ alpha, const doubl
   sc2[i] = b;
 }
 
+// ---- sums of stationary kernels (GPMI_KERNEL_SUM) ------------------------------------------------------------------
+// The same one-pass contraction for K = sum_m K_m: the weights Q_ab of a tile's elements are formed once, then every
+// component recomputes its s_m and K_m from the shared panels and reduces its amplitude / shape / length-scale partials
+// (the partials of lml_grad_body, with the component's own parameters).  One partial per tile and parameter, laid out
+// [component 1's parameters, ..., component nk's parameters, trace]; the components' weight arrays are held one at a
+// time (wk reuses the registers of s), so a sum costs the kernel no occupancy beyond the 16 weights of Q.
+__device__ __forceinline__ void sum_grad_body(const CovParams& p, int n_theta, const double* __restrict__ x, int64_t n,
+                                              const double* __restrict__ iK, int64_t ld,
+                                              const double* __restrict__ uvec, const double* __restrict__ vvec,
+                                              double* __restrict__ ws) {
+  const int ti = blockIdx.y, tj = blockIdx.x;
+  if (tj > ti) return;
+  extern __shared__ double sg_lds[];  // two panels of d x 64 doubles
+  __shared__ double red[4];
+  const int tid = threadIdx.x, d = __builtin_amdgcn_readfirstlane(p.d);  // (uniform: see ksum_body)
+  double* su = sg_lds;
+  double* sv = sg_lds + d * KT;
+  const int64_t i0 = (int64_t)ti * KT, j0 = (int64_t)tj * KT;
+  for (int idx = tid; idx < KT * d; idx += 256) {
+    int pt = idx / d, k = idx - pt * d;
+    int64_t gi = i0 + pt, gj = j0 + pt;
+    su[k * KT + pt] = (gi < n) ? x[gi * d + k] : 0.0;
+    sv[k * KT + pt] = (gj < n) ? x[gj * d + k] : 0.0;
+  }
+  __syncthreads();
+  const int ty = tid >> 4, tx = tid & 15;
+  // w = 1/2 * multiplicity * Q_ab (as in lml_grad_body)
+  double w[4][4];
+  double tq = 0.0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int64_t ga = i0 + ty * 4 + r;
+    const double ua = (ga < n) ? uvec[ga] : 0.0;
+    const double va = (ga < n) ? vvec[ga] : 0.0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int64_t gb = j0 + tx * 4 + c;
+      double wv = 0.0;
+      if (ga < n && gb <= ga) {
+        const double q = 0.5 * (ua * vvec[gb] + va * uvec[gb]) - iK[ga * ld + gb];
+        wv = (ga == gb) ? 0.5 * q : q;
+        if (ga == gb) tq += q;
+      }
+      w[r][c] = wv;
+    }
+  }
+  const int64_t tile = (int64_t)ti * (ti + 1) / 2 + tj;
+  double* out = ws + tile * (n_theta + 1);
+  double v = block_sum(tq, red);
+  if (tid == 0) out[n_theta] = v;
+  int off = 0;
+  const int nk = __builtin_amdgcn_readfirstlane(p.nk);
+  for (int m = 0; m < nk; ++m) {
+    const KParams& q = p.comp[m];
+    const bool rq = (__builtin_amdgcn_readfirstlane(q.kernel) == GPMI_KERNEL_RQ);
+    double s[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) s[r][c] = 0.0;
+    for (int k = 0; k < d; ++k) {
+      const double il2 = q.inv_l2[k];
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const double dx = su[k * KT + ty * 4 + r] - sv[k * KT + tx * 4 + c];
+          s[r][c] = fma(0.5 * dx * dx, il2, s[r][c]);
+        }
+    }
+    double g_amp = 0.0, g_shape = 0.0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int64_t ga = i0 + ty * 4 + r;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int64_t gb = j0 + tx * 4 + c;
+        const double z = s[r][c];
+        const double wv = w[r][c];
+        if (!rq) {
+          double K = q.a2 * exp(-z);
+          if (ga == gb) K = q.a2 * (exp(-z) + 1e-12);
+          g_amp = fma(wv, 2.0 * K, g_amp);  // dK_m/d ln a_m = 2 K_m             (covariance.py:273)
+          s[r][c] = wv * K;                 // dK_m/d ln l_k = (dx_k^2 / l_k^2) K_m (covariance.py:275)
+        } else {
+          const double F = 1.0 + z / q.kappa;
+          const double lnF = log(F);
+          double K = q.a2 * exp(-q.kappa * lnF);  // covariance.py:356-360
+          if (ga == gb) K = q.a2 * (exp(-q.kappa * lnF) + 1e-12);
+          g_amp = fma(wv, 2.0 * K, g_amp);
+          g_shape = fma(wv, -K * (lnF * q.kappa - z / F), g_shape);  // covariance.py:361
+          s[r][c] = wv * K / F;                                      // covariance.py:362-364
+        }
+      }
+    }
+    v = block_sum(g_amp, red);
+    if (tid == 0) out[off] = v;
+    if (rq) {
+      v = block_sum(g_shape, red);
+      if (tid == 0) out[off + 1] = v;
+    }
+    const int lo = off + (rq ? 2 : 1);
+    for (int k = 0; k < d; ++k) {
+      const double il2 = q.inv_l2[k];
+      double acc = 0.0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const double dx = su[k * KT + ty * 4 + r] - sv[k * KT + tx * 4 + c];
+          acc = fma(s[r][c], dx * dx * il2, acc);
+        }
+      v = block_sum(acc, red);
+      if (tid == 0) out[lo + k] = v;
+    }
+    off = lo + d;
+  }
+}
+
+__global__ __launch_bounds__(256) void sum_grad_kernel(CovParams p, int n_theta, const double* __restrict__ x,
+                                                       int64_t n, const double* __restrict__ iK, int64_t ld,
+                                                       const double* __restrict__ uvec,
+                                                       const double* __restrict__ vvec, double* __restrict__ ws) {
+  sum_grad_body(p, n_theta, x, n, iK, ld, uvec, vvec, ws);
+}
+
+__global__ __launch_bounds__(256) void sum_grad_batched_kernel(const CovParams* __restrict__ pdev, int n_theta,
+                                                               const double* __restrict__ x, int64_t n,
+                                                               const double* __restrict__ iK, int64_t ld,
+                                                               const double* __restrict__ uvec,
+                                                               const double* __restrict__ vvec, double* __restrict__ ws,
+                                                               int64_t sK, int64_t sV, int64_t sW) {
+  const int64_t z = blockIdx.z;
+  sum_grad_body(pdev[z], n_theta, x, n, iK + z * sK, ld, uvec + z * sV, vvec + z * sV, ws + z * sW);
+}
+
 }  // namespace
+
+static size_t sum_grad_lds_bytes(int d) { return sizeof(double) * 2 * (size_t)d * KT; }
 
 void launch_mirror_lower(hipStream_t s, double* A, int64_t ld, int64_t np, int batch, int64_t sMat) {
   dim3 grid((unsigned)(np / 64), (unsigned)(np / 64), (unsigned)batch);
@@ -240,9 +380,25 @@ int64_t grad_ws_doubles(int64_t np, int n_theta) {
 void launch_lml_grad(hipStream_t s, const KParams& p, int n_theta, const double* x, int64_t n,
                      int64_t np, const double* iK, int64_t ld, const double* u, const double* v,
                      double* ws, double* out) {
+  assert((p.kernel == GPMI_KERNEL_SE || p.kernel == GPMI_KERNEL_RQ) && "a sum of kernels must be passed as a CovParams");
   const int64_t t = np / KT;
   dim3 grid((unsigned)t, (unsigned)t);
   hipLaunchKernelGGL(lml_grad_kernel, grid, dim3(256), 0, s, p, n_theta, x, n, iK, ld, u, v, ws);
+  hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)(n_theta + 1)), dim3(256), 0, s, ws,
+                     t * (t + 1) / 2, n_theta + 1, out, (int64_t)0);
+}
+
+// a CovParams: the fused contraction of its sum, or the single-kernel one of its base
+void launch_lml_grad(hipStream_t s, const CovParams& p, int n_theta, const double* x, int64_t n,
+                     int64_t np, const double* iK, int64_t ld, const double* u, const double* v,
+                     double* ws, double* out) {
+  if (p.kernel != GPMI_KERNEL_SUM) {
+    launch_lml_grad(s, static_cast<const KParams&>(p), n_theta, x, n, np, iK, ld, u, v, ws, out);
+    return;
+  }
+  const int64_t t = np / KT;
+  dim3 grid((unsigned)t, (unsigned)t);
+  hipLaunchKernelGGL(sum_grad_kernel, grid, dim3(256), sum_grad_lds_bytes(p.d), s, p, n_theta, x, n, iK, ld, u, v, ws);
   hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)(n_theta + 1)), dim3(256), 0, s, ws,
                      t * (t + 1) / 2, n_theta + 1, out, (int64_t)0);
 }
@@ -256,6 +412,19 @@ void launch_lml_grad_batched(hipStream_t s, const KParams* pdev, int batch, int 
   const int64_t sW = grad_ws_doubles(np, n_theta);
   dim3 grid((unsigned)t, (unsigned)t, (unsigned)batch);
   hipLaunchKernelGGL(lml_grad_batched_kernel, grid, dim3(256), 0, s, pdev, n_theta, x, n, iK, ld, u, v, ws, sK, sV, sW);
+  hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)(n_theta + 1), 1, (unsigned)batch), dim3(256), 0, s, ws,
+                     t * (t + 1) / 2, n_theta + 1, out, sW);
+}
+
+// a batch of sums (every pdev[z] of kind GPMI_KERNEL_SUM, d spatial dimensions)
+void launch_lml_grad_batched(hipStream_t s, const CovParams* pdev, int batch, int n_theta, const double* x, int64_t n,
+                             int64_t np, const double* iK, int64_t ld, int64_t sK, const double* u, const double* v,
+                             int64_t sV, double* ws, double* out, int d) {
+  const int64_t t = np / KT;
+  const int64_t sW = grad_ws_doubles(np, n_theta);
+  dim3 grid((unsigned)t, (unsigned)t, (unsigned)batch);
+  hipLaunchKernelGGL(sum_grad_batched_kernel, grid, dim3(256), sum_grad_lds_bytes(d), s, pdev, n_theta, x, n, iK, ld, u, v,
+                     ws, sK, sV, sW);
   hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)(n_theta + 1), 1, (unsigned)batch), dim3(256), 0, s, ws,
                      t * (t + 1) / 2, n_theta + 1, out, sW);
 }

@@ -4,6 +4,8 @@
 // by a tiled kernel: a workgroup stages the two 64-point panels in LDS (transposed, [dim][point]) and
 // every thread produces a 4 x 4 block of K, written as 32-byte row segments (16 threads -> 512
 // contiguous bytes per row).  HBM-write bound: 8 bytes per element, x is read once per tile from L2.
+#include <cassert>
+
 #include "gpmi_internal.h"
 #include "kmath.h"
 
@@ -170,12 +172,151 @@ __global__ void add_full_kernel(double* __restrict__ A, int64_t ld, const double
 
 }  // namespace
 
+// ---- sums of stationary kernels (GPMI_KERNEL_SUM) ---------------------------------------------------------------------
+// K = sum_m a_m^2 C_m (+ a_m^2 1e-12 each on the diagonal, covariance.py:254-255,348) + WhiteNoise + data errors in ONE
+// pass per 64 x 64 tile: the two point panels are staged once and shared by the components; per component the thread
+// accumulates s_m = sum_k 1/2 dx_k^2 / l_{m,k}^2 with that component's length scales and applies its covariance function
+// (kfun, the same lockstep exp / log1p as the single-kernel build), summing in component order - the order of the
+// reference's sum(...) (covariance.py:94-98).  The component's kind is a uniform run-time branch (one per component and
+// half-block), not a template parameter: one kernel serves all 28 combinations of two to four SE / RQ components instead
+// of 28 instantiations competing for the instruction cache.  The choice rests on that code size: a per-combination
+// instantiation was not built or timed.  Timings of this form: DESIGN.md (kernel table) and tools/sum_time.py.
+// ksum_body is force-inlined: used by two kernels, the compiler otherwise made it a called function, and the batched
+// kernel then took 248 VGPRs and a scratch spill behind the call (inlined: 130 VGPRs, no scratch, as ksum_kernel).
+namespace {
+
+template <bool SQUARE>
+__device__ __forceinline__ void ksum_body(const CovParams& p, const double* __restrict__ U, int64_t nu,
+                                 const double* __restrict__ V, int64_t nv, const double* __restrict__ noise,
+                                 double* __restrict__ out, int64_t ld, int lower_only) {
+  int ti = blockIdx.y, tj = blockIdx.x;
+  const int tile_off = lower_only >> 8;  // (tile selection as in kbuild_body)
+  lower_only &= 0xff;
+  if (SQUARE && lower_only == 2) {
+    const int id = blockIdx.x;
+    ti = (int)((sqrt(8.0 * id + 1.0) - 1.0) * 0.5);
+    while ((ti + 1) * (ti + 2) / 2 <= id) ++ti;
+    while (ti * (ti + 1) / 2 > id) --ti;
+    tj = id - ti * (ti + 1) / 2 + tile_off;
+    ti += tile_off;
+  } else if (SQUARE && lower_only && tj > ti) {
+    return;
+  }
+  extern __shared__ double ks_lds[];
+  const int tid = threadIdx.x;
+  // (uniform values, read first-lane: a batched launch takes its parameters from memory, and the component branch and
+  // the loop bounds stay scalar)
+  const int d = __builtin_amdgcn_readfirstlane(p.d);
+  double* su = ks_lds;
+  double* sv = ks_lds + d * KT;
+  const int64_t i0 = (int64_t)ti * KT, j0 = (int64_t)tj * KT;
+  for (int idx = tid; idx < KT * d; idx += 256) {
+    int pt = idx / d, k = idx - pt * d;
+    int64_t gi = i0 + pt, gj = j0 + pt;
+    su[k * KT + pt] = (gi < nu) ? U[gi * d + k] : 0.0;
+    sv[k * KT + pt] = (gj < nv) ? V[gj * d + k] : 0.0;
+  }
+  __syncthreads();
+  const int ty = tid >> 4, tx = tid & 15;
+  const int nk = __builtin_amdgcn_readfirstlane(p.nk);
+  // two halves of eight elements (rows 2h, 2h + 1 of the thread's 4 x 4 block), each summed over all components and
+  // written before the next: eight accumulators, one half's distances and covariance temporaries live at a time.  Still
+  // about twice the single-kernel build's footprint: 130 VGPRs at occupancy 3 (124 / 4 for the cross build) against
+  // 70 - 78 VGPRs at 6 - 7 for kbuild_kernel - both covariance functions are inlined behind the run-time branch, and
+  // this VALU-bound kernel has half the waves to hide latency with.
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    double acc[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] = 0.0;
+    for (int m = 0; m < nk; ++m) {
+      const KParams& q = p.comp[m];
+      double sv8[8], cf8[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) sv8[i] = 0.0;
+      for (int k = 0; k < d; ++k) {
+        const double il2 = q.inv_l2[k];
+        double ur[2], vc[4];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) ur[r] = su[k * KT + ty * 4 + 2 * h + r];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) vc[c] = sv[k * KT + tx * 4 + c];
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            double dx = ur[r] - vc[c];
+            sv8[4 * r + c] = fma(0.5 * dx * dx, il2, sv8[4 * r + c]);
+          }
+      }
+      if (__builtin_amdgcn_readfirstlane(q.kernel) == GPMI_KERNEL_RQ)
+        kfun<GPMI_KERNEL_RQ>(q, sv8, cf8);
+      else
+        kfun<GPMI_KERNEL_SE>(q, sv8, cf8);
+      const double a2 = q.a2;
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int64_t gi = i0 + ty * 4 + 2 * h + r, gj = j0 + tx * 4 + c;
+          const double cfun = cf8[4 * r + c];
+          // a_m^2 (C_m + 1e-12) on the diagonal, a_m^2 C_m off it (covariance.py:254-255, 348), in component order
+          acc[4 * r + c] += (SQUARE && gi == gj) ? a2 * (cfun + 1e-12) : a2 * cfun;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int64_t gi = i0 + ty * 4 + 2 * h + r;
+      double v[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int64_t gj = j0 + tx * 4 + c;
+        double val;
+        if (gi < nu && gj < nv) {
+          val = acc[4 * r + c];
+          if (SQUARE && gi == gj) {
+            val += p.extra_diag;  // + WhiteNoise + sig, in kbuild_body's order
+            val += noise[gi];
+          }
+        } else {
+          val = (SQUARE && gi == gj) ? 1.0 : 0.0;  // identity padding
+        }
+        v[c] = val;
+      }
+      double* dst = out + gi * ld + j0 + tx * 4;
+      *reinterpret_cast<d2_t*>(dst) = d2_t{v[0], v[1]};
+      *reinterpret_cast<d2_t*>(dst + 2) = d2_t{v[2], v[3]};
+    }
+  }
+}
+
+template <bool SQUARE>
+__global__ __launch_bounds__(256) void ksum_kernel(CovParams p, const double* __restrict__ U, int64_t nu,
+                                                   const double* __restrict__ V, int64_t nv,
+                                                   const double* __restrict__ noise, double* __restrict__ out,
+                                                   int64_t ld, int lower_only) {
+  ksum_body<SQUARE>(p, U, nu, V, nv, noise, out, ld, lower_only);
+}
+
+// batched square build of sums: problem z uses pdev[z], writes out + z * stride
+__global__ __launch_bounds__(256) void ksum_batched_kernel(const CovParams* __restrict__ pdev,
+                                                           const double* __restrict__ x, int64_t n,
+                                                           const double* __restrict__ noise, double* __restrict__ out,
+                                                           int64_t ld, int64_t stride) {
+  ksum_body<true>(pdev[blockIdx.z], x, n, x, n, noise, out + (int64_t)blockIdx.z * stride, ld, 2);
+}
+
+}  // namespace
+
 static size_t kb_lds_bytes(int d) { return sizeof(double) * 2 * (size_t)d * KT; }
 
-// dispatch on the covariance function (a template parameter of the kernels)
+// dispatch on the covariance function (a template parameter of the kernels).  A KParams is one SE / RQ kernel: a sum
+// reaches the builders only as a CovParams (the overloads below), so a KParams whose kind is GPMI_KERNEL_SUM is a sliced
+// copy - a bug of the caller.
 template <bool SQUARE>
 static void launch_kb(dim3 grid, hipStream_t s, const KParams& p, const double* U, int64_t nu, const double* V,
                       int64_t nv, const double* noise, double* out, int64_t ld, int lower_only) {
+  assert((p.kernel == GPMI_KERNEL_SE || p.kernel == GPMI_KERNEL_RQ) && "a sum of kernels must be passed as a CovParams");
   if (p.kernel == GPMI_KERNEL_SE)
     hipLaunchKernelGGL((kbuild_kernel<SQUARE, GPMI_KERNEL_SE>), grid, dim3(256), kb_lds_bytes(p.d), s, p, U, nu, V, nv,
                        noise, out, ld, lower_only);
@@ -184,8 +325,20 @@ static void launch_kb(dim3 grid, hipStream_t s, const KParams& p, const double* 
                        noise, out, ld, lower_only);
 }
 
-void launch_kbuild_square(hipStream_t s, const KParams& p, const double* x, int64_t n, int64_t np,
-                          const double* noise, double* A, int64_t ld, bool lower_only) {
+// a CovParams: the fused build of its sum, or the single-kernel build of its base
+template <bool SQUARE>
+static void launch_kb(dim3 grid, hipStream_t s, const CovParams& p, const double* U, int64_t nu, const double* V,
+                      int64_t nv, const double* noise, double* out, int64_t ld, int lower_only) {
+  if (p.kernel == GPMI_KERNEL_SUM)
+    hipLaunchKernelGGL(ksum_kernel<SQUARE>, grid, dim3(256), kb_lds_bytes(p.d), s, p, U, nu, V, nv, noise, out, ld,
+                       lower_only);
+  else
+    launch_kb<SQUARE>(grid, s, static_cast<const KParams&>(p), U, nu, V, nv, noise, out, ld, lower_only);
+}
+
+template <class P>
+static void kbuild_square(hipStream_t s, const P& p, const double* x, int64_t n, int64_t np, const double* noise,
+                          double* A, int64_t ld, bool lower_only) {
   const unsigned nt = (unsigned)(np / KT);
   dim3 grid = lower_only ? dim3(nt * (nt + 1) / 2) : dim3(nt, nt);
   launch_kb<true>(grid, s, p, x, n, x, n, noise, A, ld, lower_only ? 2 : 0);
@@ -194,8 +347,9 @@ void launch_kbuild_square(hipStream_t s, const KParams& p, const double* x, int6
 // The lower tiles in two launches: part 1 = the first `split_cols` columns (all rows), part 2 = everything to the right
 // of them.  The fit starts factoring the first outer panel behind part 1 while part 2 is still being built on the
 // update stream (api.hip: enqueue_factor_and_forward).
-void launch_kbuild_square_part(hipStream_t s, const KParams& p, const double* x, int64_t n, int64_t np,
-                               const double* noise, double* A, int64_t ld, int part, int split_cols) {
+template <class P>
+static void kbuild_square_part(hipStream_t s, const P& p, const double* x, int64_t n, int64_t np, const double* noise,
+                               double* A, int64_t ld, int part, int split_cols) {
   const unsigned nt = (unsigned)(np / KT), sp = (unsigned)(split_cols / KT);
   if (part == 1) {
     launch_kb<true>(dim3(sp, nt), s, p, x, n, x, n, noise, A, ld, 1);
@@ -205,9 +359,35 @@ void launch_kbuild_square_part(hipStream_t s, const KParams& p, const double* x,
   }
 }
 
+template <class P>
+static void kbuild_cross(hipStream_t s, const P& p, const double* U, int64_t mu, int64_t mp, const double* V, int64_t n,
+                         int64_t np, double* out, int64_t ld) {
+  dim3 grid((unsigned)(np / KT), (unsigned)(mp / KT));
+  launch_kb<false>(grid, s, p, U, mu, V, n, nullptr, out, ld, 0);
+}
+
+void launch_kbuild_square(hipStream_t s, const KParams& p, const double* x, int64_t n, int64_t np,
+                          const double* noise, double* A, int64_t ld, bool lower_only) {
+  kbuild_square(s, p, x, n, np, noise, A, ld, lower_only);
+}
+void launch_kbuild_square(hipStream_t s, const CovParams& p, const double* x, int64_t n, int64_t np,
+                          const double* noise, double* A, int64_t ld, bool lower_only) {
+  kbuild_square(s, p, x, n, np, noise, A, ld, lower_only);
+}
+
+void launch_kbuild_square_part(hipStream_t s, const KParams& p, const double* x, int64_t n, int64_t np,
+                               const double* noise, double* A, int64_t ld, int part, int split_cols) {
+  kbuild_square_part(s, p, x, n, np, noise, A, ld, part, split_cols);
+}
+void launch_kbuild_square_part(hipStream_t s, const CovParams& p, const double* x, int64_t n, int64_t np,
+                               const double* noise, double* A, int64_t ld, int part, int split_cols) {
+  kbuild_square_part(s, p, x, n, np, noise, A, ld, part, split_cols);
+}
+
 void launch_kbuild_square_batched(hipStream_t s, int kernel, const KParams* pdev, int batch, const double* x,
                                   int64_t n, int64_t np, const double* noise, double* A, int64_t ld,
                                   int64_t stride, int d, int64_t noise_stride) {
+  assert((kernel == GPMI_KERNEL_SE || kernel == GPMI_KERNEL_RQ) && "a batch of sums is an array of CovParams");
   const unsigned nt = (unsigned)(np / KT);
   dim3 grid(nt * (nt + 1) / 2, 1, (unsigned)batch);  // lower tiles only, one-dimensional (kbuild_body, mode 2)
   if (kernel == GPMI_KERNEL_SE)
@@ -218,10 +398,21 @@ void launch_kbuild_square_batched(hipStream_t s, int kernel, const KParams* pdev
                        ld, stride, noise_stride);
 }
 
+// a batch of sums (every pdev[z] of kind GPMI_KERNEL_SUM; the data variances are shared)
+void launch_kbuild_square_batched(hipStream_t s, const CovParams* pdev, int batch, const double* x, int64_t n,
+                                  int64_t np, const double* noise, double* A, int64_t ld, int64_t stride, int d) {
+  const unsigned nt = (unsigned)(np / KT);
+  dim3 grid(nt * (nt + 1) / 2, 1, (unsigned)batch);
+  hipLaunchKernelGGL(ksum_batched_kernel, grid, dim3(256), kb_lds_bytes(d), s, pdev, x, n, noise, A, ld, stride);
+}
+
 void launch_kbuild_cross(hipStream_t s, const KParams& p, const double* U, int64_t mu, int64_t mp,
                          const double* V, int64_t n, int64_t np, double* out, int64_t ld) {
-  dim3 grid((unsigned)(np / KT), (unsigned)(mp / KT));
-  launch_kb<false>(grid, s, p, U, mu, V, n, nullptr, out, ld, 0);
+  kbuild_cross(s, p, U, mu, mp, V, n, np, out, ld);
+}
+void launch_kbuild_cross(hipStream_t s, const CovParams& p, const double* U, int64_t mu, int64_t mp,
+                         const double* V, int64_t n, int64_t np, double* out, int64_t ld) {
+  kbuild_cross(s, p, U, mu, mp, V, n, np, out, ld);
 }
 
 void launch_add_full(hipStream_t s, double* A, int64_t ld, const double* Y, int64_t n) {

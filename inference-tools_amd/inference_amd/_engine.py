@@ -278,6 +278,11 @@ class GpEngine(_DeviceCommMixin):
         self.h.call("gpmi_posterior_mix", dptr(p), m, dptr(gq), dptr(mu), dptr(cov))
         return mu, cov
 
+    def set_sum(self, kernels):
+        """gpmi_set_sum: the components (GPMI_KERNEL_SE / _RQ ids, in order) of this handle's GPMI_KERNEL_SUM."""
+        ks = np.ascontiguousarray(kernels, dtype=np.int32)
+        self.h.call("gpmi_set_sum", int(ks.size), ks.ctypes.data_as(C.POINTER(C.c_int)))
+
     def set_noise(self, noise_var):
         self.h.call("gpmi_set_noise", dptr(as_f64(noise_var)))
 

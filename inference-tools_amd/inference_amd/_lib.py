@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("GPMI_LIB") or os.path.join(_HERE, "lib", "libgpmi.so"
 
 KERNEL_SE = 0
 KERNEL_RQ = 1
+KERNEL_SUM = 2  # GPMI_KERNEL_SUM: a sum of SE / RQ kernels declared by gpmi_set_sum
 PROF_KBUILD, PROF_SYRK, PROF_PANEL, PROF_SOLVE, PROF_SYRK_REST, PROF_TRSM, PROF_SYRK_SLICE, PROF_FLOW = 0, 1, 2, 3, 4, 5, 6, 7
 OPT_LOCKSTEP_ALWAYS, OPT_RESERVE_POINTS, OPT_NO_FLOW = 1, 2, 3
 _TRACE_MS = float(os.environ["GPMI_TRACE_CALLS"]) if os.environ.get("GPMI_TRACE_CALLS") else None
@@ -82,6 +83,7 @@ SIGNATURES = {
     "gpmi_predict_mix": (C.c_int, [_vp, _dp, _i64, _dp, _dp, _dp]),
     "gpmi_posterior_mix": (C.c_int, [_vp, _dp, _i64, _dp, _dp, _dp]),
     "gpmi_set_noise": (C.c_int, [_vp, _dp]),
+    "gpmi_set_sum": (C.c_int, [_vp, C.c_int, _ip]),
     "gpmi_lml_grad_qdiag": (C.c_int, [_vp, _dp]),
     "gpmi_linv_set": (C.c_int, [_vp, _dp, _i64, _dp, _dp]),
     "gpmi_linv_lml": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double, _dp, _dp, _ip]),

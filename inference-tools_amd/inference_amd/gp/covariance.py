@@ -472,12 +472,18 @@ def _is_device_mixture(comp):
             and all(isinstance(K, _StationaryDeviceKernel) for K in comp.cov))
 
 
+MAX_SUM = 4  # components of a device sum (gpmi_set_sum)
+
+
 def device_plan(cov):
     """How `GpRegressor` maps a covariance object onto the device kernels:
     returns (kernel_id, main_component, slice_of_its_theta, white_noise_index or None)
     or None when the object is not a supported combination: one stationary kernel (SquaredExponential /
     RationalQuadratic) or one ChangePoint over such kernels (kernel_id -1), optionally plus one WhiteNoise
-    and / or one HeteroscedasticNoise (see `heteroscedastic_slice`)."""
+    and / or one HeteroscedasticNoise (see `heteroscedastic_slice`); or a sum of 2 to 4 stationary kernels with at
+    most one WhiteNoise, in any order (kernel_id `_lib.KERNEL_SUM`: the main component is the CompositeCovariance
+    itself, the "slice" an index array that gathers the stationary components' parameters in component order, and
+    `sum_kernels` gives their kernel ids)."""
     if isinstance(cov, _StationaryDeviceKernel):
         return cov._gpmi_kernel, cov, slice(0, cov.n_params), None
     if _is_device_mixture(cov):
@@ -487,11 +493,21 @@ def device_plan(cov):
                 if isinstance(c, _StationaryDeviceKernel) or _is_device_mixture(c)]
         wn = [(i, c) for i, c in enumerate(cov.components) if isinstance(c, WhiteNoise)]
         het = [c for c in cov.components if isinstance(c, HeteroscedasticNoise)]
+        if (2 <= len(main) <= MAX_SUM and len(wn) <= 1 and len(main) + len(wn) == len(cov.components)
+                and all(isinstance(c, _StationaryDeviceKernel) for _, c in main)):
+            idx = np.concatenate([np.arange(cov.slices[i].start, cov.slices[i].stop) for i, _ in main])
+            wn_index = cov.slices[wn[0][0]].start if wn else None
+            return _lib.KERNEL_SUM, cov, idx, wn_index
         if len(main) == 1 and len(wn) <= 1 and len(het) <= 1 and len(main) + len(wn) + len(het) == len(cov.components):
             i, c = main[0]
             wn_index = cov.slices[wn[0][0]].start if wn else None
             return (c._gpmi_kernel if isinstance(c, _StationaryDeviceKernel) else -1), c, cov.slices[i], wn_index
     return None
+
+
+def sum_kernels(cov):
+    """Kernel ids of the stationary components of a device sum (`device_plan` kernel id `_lib.KERNEL_SUM`), in order."""
+    return [c._gpmi_kernel for c in cov.components if isinstance(c, _StationaryDeviceKernel)]
 
 
 def heteroscedastic_slice(cov):

@@ -20,6 +20,7 @@ from numpy import ndarray
 from numpy.linalg import LinAlgError
 from scipy.optimize import minimize
 
+from inference_amd import _lib
 from inference_amd._engine import LinvEngine
 from inference_amd.gp import _messages as msg
 from inference_amd.gp.covariance import CovarianceFunction, SquaredExponential, device_plan, heteroscedastic_slice
@@ -75,7 +76,9 @@ class GpLinearInverter:
         # CovarianceFunction object (the reference takes any, inversion.py:117-127) the host evaluates the object's
         # own build_covariance / covariance_and_gradients and the device does every O(n^3) step (gpmi_linv_*_dense)
         plan = device_plan(self.cov)
-        self._dense = plan is None or plan[0] < 0 or heteroscedastic_slice(self.cov) is not None  # -1: ChangePoint mixture
+        # (-1: ChangePoint mixture, _lib.KERNEL_SUM: a sum of stationary kernels - both through the dense path)
+        self._dense = (plan is None or plan[0] not in (_lib.KERNEL_SE, _lib.KERNEL_RQ)
+                       or heteroscedastic_slice(self.cov) is not None)
         if not self._dense:
             self._kernel_id, self._stat, self._stat_slice, self._wn_index = plan
         self._device = device
