@@ -415,6 +415,30 @@ int gpmi_predict_dense(gpmi_ctx* ctx, const double* Kq_host, int64_t m, double* 
  * block of build_posterior (regression.py:447-448) and of gradient / spatial_derivatives (:374-383, :410-417) */
 int gpmi_solve_rows(gpmi_ctx* ctx, const double* Q_host, int64_t m, double* X_host, double* gram_host);
 
+/* ---- kernel-density estimation (GaussianKDE, inference/pdf/kde.py) -------------------
+ * A density object holds a sorted sample and its region table on the device; the handle owns it, and gpmi_destroy
+ * releases the objects still alive.  Its calls run on a stream of the handle that every density object shares; like every
+ * call on a handle they must be serialised by the caller (inference_amd.pdf holds a lock per handle around each one).
+ * Replaces GaussianKDE.__init__'s slice table (kde.py:48-90): region r covers the sorted samples [lo_host[r], hi_host[r]),
+ * 0 <= lo <= hi <= n. */
+typedef struct gpmi_kde gpmi_kde;
+int gpmi_kde_create(gpmi_ctx* ctx, int64_t n, const double* sorted_sample_host, int64_t n_regions,
+                    const int64_t* lo_host, const int64_t* hi_host, gpmi_kde** out);
+/* release a density object (NULL: GPMI_ERR_ARG); not after gpmi_destroy of its handle, which has released it already */
+int gpmi_kde_destroy(gpmi_kde* kde);
+/* Replaces the slice sums of GaussianKDE.__call__ and .cdf (kde.py:96-133): for the m points x_host[i] of regions
+ * region_host[i] (0 <= region < n_regions), over the samples s_j of the region's slice,
+ *   pdf_sum_host[i] = sum_j exp(-((x_i - s_j) q)^2),   cdf_sum_host[i] = sum_j (1 + erf((x_i - s_j) q))
+ * Either output may be NULL (not both); q is finite and positive.  The caller applies norm, 0.5 / n and the offsets.
+ * A point's values do not depend on the other points of the call; repeated calls are bit-identical. */
+int gpmi_kde_eval(gpmi_kde* kde, int64_t m, const double* x_host, const int64_t* region_host, double q,
+                  double* pdf_sum_host, double* cdf_sum_host);
+/* Replaces GaussianKDE.cross_validation_logprob (kde.py:195-218) for n_widths finite, positive bandwidths at once: the
+ * leave-one-out log-probability of the n finite samples (any order), with S_i(h) = sum_j exp(-(x_i - x_j)^2 / (2 h^2)),
+ *   logprob_host[k] = sum_i [log S_i - log(h_k n sqrt(2 pi)) + log(1 - c / S_i)],   0 < c < 1 */
+int gpmi_kde_cv_logprob(gpmi_ctx* ctx, int64_t n, const double* samples_host, int n_widths,
+                        const double* widths_host, double c, double* logprob_host);
+
 /* ---- instrumentation ---------------------------------------------------------------
  * HIP-event timing on the handle's own stream (torch.cuda.Event would not see it). */
 int gpmi_timer_start(gpmi_ctx* ctx);

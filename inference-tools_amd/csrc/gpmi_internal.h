@@ -122,6 +122,8 @@ struct LinvState {
   int64_t gws_doubles = 0;
 };
 
+struct KdeState;  // kde.hip
+
 struct gpmi_ctx {
   int device = 0;
   int ncu = 256;      // compute units of the device
@@ -204,6 +206,7 @@ struct gpmi_ctx {
   double* comm_buf = nullptr;
   int64_t comm_buf_doubles = 0;
   hipStream_t dev_masked = nullptr;  // tools: CU-masked stream of the device-pointer entry points (GPMI_DEV_CUS)
+  KdeState* kde = nullptr;  // kde.hip: stream, workspaces and live objects of the gpmi_kde_* entry points
   // instrumentation
   hipEvent_t t0 = nullptr, t1 = nullptr;
   unsigned prof_mask = 0;
@@ -219,6 +222,9 @@ struct gpmi_ctx {
   double prof_bytes[GPMI_PROF_NCLASS] = {};
   int64_t prof_launches[GPMI_PROF_NCLASS] = {};
 };
+
+// kde.hip: destroy the handle's density objects and their stream / workspaces (gpmi_destroy)
+void kde_release_all(gpmi_ctx* c);
 
 // instrumentation helpers (api.hip)
 constexpr int GPMI_STAMP_SLOTS = 16384;

@@ -106,6 +106,10 @@ SIGNATURES = {
     "gpmi_comm_broadcast": (C.c_int, [_vp, _dp, _i64, C.c_int]),
     "gpmi_comm_count": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "gpmi_comm_destroy": (C.c_int, [_vp]),
+    "gpmi_kde_create": (C.c_int, [_vp, _i64, _dp, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_vp)]),
+    "gpmi_kde_destroy": (C.c_int, [_vp]),
+    "gpmi_kde_eval": (C.c_int, [_vp, _i64, _dp, C.POINTER(_i64), C.c_double, _dp, _dp]),
+    "gpmi_kde_cv_logprob": (C.c_int, [_vp, _i64, _dp, C.c_int, _dp, C.c_double, _dp]),
     "gpmi_timer_start": (C.c_int, [_vp]),
     "gpmi_timer_stop": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "gpmi_profile_enable": (C.c_int, [_vp, C.c_int]),
@@ -157,6 +161,14 @@ def device_identity(device: int) -> str:
     return buf.value.decode() if rc == 0 else ""
 
 
+def default_device() -> int:
+    """The device `Handle(None)` binds: GPMI_DEVICE, else LOCAL_RANK, else 0, modulo the number of visible devices."""
+    device = int(os.environ.get("GPMI_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+    cnt = C.c_int(0)
+    load().gpmi_device_count(C.byref(cnt))
+    return device % cnt.value if cnt.value > 0 else device
+
+
 def dptr(a):
     """double* view of a C-contiguous float64 array (None -> NULL)."""
     if a is None:
@@ -190,11 +202,7 @@ class Handle:
     def __init__(self, device=None):
         lib = load()
         if device is None:
-            device = int(os.environ.get("GPMI_DEVICE", os.environ.get("LOCAL_RANK", "0")))
-            cnt = C.c_int(0)
-            lib.gpmi_device_count(C.byref(cnt))
-            if cnt.value > 0:
-                device %= cnt.value
+            device = default_device()
         self.lib = lib
         self.device = device
         self.ctx = _vp()

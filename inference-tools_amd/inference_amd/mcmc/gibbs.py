@@ -6,9 +6,11 @@ adaptation (`Parameter`, gibbs.py:16-160): every step is a sequence of 1-D
 Metropolis-Hastings updates, one per parameter, each retried until accepted,
 with proposal widths tuned towards a 50 % acceptance rate.
 
-Only what `ParallelTempering` needs is provided (`inv_temp`, `take_step`,
-`get_last`, `replace_last`, `probs`, sample access, boundaries); plotting, KDE
-marginals and save / load of the reference are out of scope.
+Provided: what `ParallelTempering` needs (`inv_temp`, `take_step`, `get_last`,
+`replace_last`, `probs`, sample access, boundaries) and the reference's read-out
+of results (base.py:75-160, gibbs.py:370-377): `get_marginal` (a device
+`GaussianKDE` of one parameter), `get_interval` and `mode`.  Plotting,
+`UnimodalPdf` marginals and save / load of the reference are out of scope.
 
 MI355X-specific addition: `advance_lockstep` advances MANY chains together so
 that each round of proposals is ONE batched posterior evaluation on the device
@@ -19,8 +21,8 @@ and one-by-one execution produce identical trajectories.
 from copy import copy
 
 import numpy as np
-from numpy import array, exp, float64, isfinite, log, sqrt
-from numpy.random import default_rng
+from numpy import argmax, array, exp, float64, isfinite, log, sqrt
+from numpy.random import default_rng, permutation
 
 
 class Parameter:
@@ -200,6 +202,51 @@ class GibbsChain:
 
     def get_sample(self, burn: int = 1, thin: int = 1):
         return array([self.get_parameter(i, burn=burn, thin=thin) for i in range(self.n_parameters)]).T
+
+    # -- results (reference: base.py:75-160, gibbs.py:370-377) ------------------------------
+    def get_marginal(self, index: int, burn: int = 1, thin: int = 1, unimodal=False):
+        """Estimate of the 1D marginal distribution of parameter `index`: a `GaussianKDE` of
+        `get_parameter(index, burn, thin)`.  `unimodal=True` (a `UnimodalPdf` in the reference) is not provided."""
+        from inference_amd.pdf import GaussianKDE
+        from inference_amd.pdf._messages import marginal_unimodal
+
+        if unimodal:
+            raise NotImplementedError(marginal_unimodal())
+        return GaussianKDE(self.get_parameter(index, burn=burn, thin=thin))
+
+    def get_interval(self, interval: float = 0.95, burn: int = 1, thin: int = 1, samples: int = None):
+        """The samples in the highest-probability fraction `interval` of the chain, ordered by increasing
+        log-probability, and their log-probabilities.  `samples` overrides `thin`.  As in the reference, the trim to
+        `samples` draws `numpy.random.permutation` and then indexes with the None that `ndarray.sort()` returns: no
+        sample is removed and both arrays gain a leading axis of length 1."""
+        probs = self.get_probabilities(burn=burn)
+        if samples is not None:
+            thin = max(probs.size // samples, 1)
+
+        sample = self.get_sample(burn=burn, thin=thin)
+        probs = probs[::thin]
+
+        sorter = probs.argsort()
+        sample = sample[sorter, :]
+        probs = probs[sorter]
+        # trim the lowest-probability samples
+        cutoff = int(probs.size * (1 - interval))
+        sample = sample[cutoff:, :]
+        probs = probs[cutoff:]
+
+        if samples is not None:
+            n_trim = probs.size - samples
+            if n_trim > 0:
+                subsample = permutation(probs.size)[n_trim:].sort()
+                sample = sample[subsample, :]
+                probs = probs[subsample]
+
+        return sample, probs
+
+    def mode(self):
+        """The sample with the highest log-probability so far."""
+        ind = argmax(self.probs)
+        return array([p.samples[ind] for p in self.params])
 
     def set_non_negative(self, parameter: int, flag=True):
         self.params[parameter].non_negative = flag

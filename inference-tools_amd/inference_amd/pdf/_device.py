@@ -1,0 +1,102 @@
+"""Device side of the density estimators: one lazily created `_lib.Handle` per device for the whole module (thousands
+of KDEs from a tempering run share its stream and workspaces), the density objects of csrc/kde.hip and the
+leave-one-out log-probability.  No CPU fallback: without the library or a GPU, `GpmiUnavailable` is raised.
+
+The library expects the calls on one handle to be serialised (include/gpmi.h), and ctypes releases the GIL during a
+call, so every gpmi_kde_* call - with the read of its error text - holds the handle's lock: KDEs built and evaluated
+on several threads at once share the handle safely.  The lock is re-entrant, because a density object's finaliser
+(which releases it on the device) can run inside a locked region of the same thread."""
+import ctypes as C
+import sys
+import threading
+
+import numpy as np
+
+from inference_amd import _lib
+
+_handles = {}
+_handles_lock = threading.Lock()
+
+
+def resolve_device(device=None) -> int:
+    """The device index a call binds to: None means the default device of `_lib.Handle`."""
+    return _lib.default_device() if device is None else int(device)
+
+
+def handle(device=None) -> "_lib.Handle":
+    """The module's handle for `device`, created on first use and again after it has been closed.  It carries the
+    lock (`kde_lock`) that serialises the density calls made on it."""
+    dev = resolve_device(device)
+    with _handles_lock:
+        h = _handles.get(dev)
+        if h is None or not h.ctx:
+            h = _lib.Handle(dev)
+            h.kde_lock = threading.RLock()
+            _handles[dev] = h
+        return h
+
+
+def _call(h, name, *args):
+    """One gpmi_kde_* call on handle h, serialised with every other call on it; a non-zero status raises GpmiError
+    with the handle's error text of that very call."""
+    with h.kde_lock:
+        if not h.ctx:
+            raise _lib.GpmiUnavailable("the device handle of this density has been closed")
+        rc = getattr(h.lib, name)(*args)
+        if rc != 0:
+            text = h.lib.gpmi_last_error(h.ctx).decode()
+            raise _lib.GpmiError(f"{name} failed with status {rc}: {text}")
+
+
+def _i64(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+class DeviceDensity:
+    """A sorted sample and its region table [lo[r], hi[r]) on the device (gpmi_kde_create)."""
+
+    def __init__(self, sorted_sample, lo, hi, device=None):
+        self.h = handle(device)
+        s = np.ascontiguousarray(sorted_sample, dtype=np.float64)
+        lo = np.ascontiguousarray(lo, dtype=np.int64)
+        hi = np.ascontiguousarray(hi, dtype=np.int64)
+        self.n_regions = lo.size
+        self.ptr = C.c_void_p()
+        _call(self.h, "gpmi_kde_create", self.h.ctx, s.size, _lib.dptr(s), lo.size, _i64(lo), _i64(hi), C.byref(self.ptr))
+
+    def sums(self, x, regions, q, pdf=True, cdf=True):
+        """Raw slice sums at the points x of the given regions: (pdf_sum or None, cdf_sum or None)."""
+        x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        r = np.ascontiguousarray(regions, dtype=np.int64).ravel()
+        ps = np.empty(x.size) if pdf else None
+        cs = np.empty(x.size) if cdf else None
+        _call(self.h, "gpmi_kde_eval", self.ptr, x.size, _lib.dptr(x), _i64(r), float(q), _lib.dptr(ps), _lib.dptr(cs))
+        return ps, cs
+
+    def __del__(self):
+        # a handle that has been closed (interpreter exit, _close_all_handles) has released its density objects already
+        if sys.is_finalizing():
+            return
+        h = getattr(self, "h", None)
+        if h is None or not getattr(self, "ptr", None):
+            return
+        with h.kde_lock:
+            if h.ctx and self.ptr:
+                h.lib.gpmi_kde_destroy(self.ptr)
+            self.ptr = C.c_void_p()
+
+
+def cv_logprob(samples, widths, c=0.99, device=None):
+    """Leave-one-out log-probabilities of `samples` for every width (gpmi_kde_cv_logprob, one call).  A width that is
+    not finite and positive gives NaN without a device call, as the reference's arithmetic does for width = inf."""
+    widths = np.asarray(widths, dtype=np.float64).ravel()
+    out = np.full(widths.size, np.nan)
+    ok = np.isfinite(widths) & (widths > 0)
+    if ok.any():
+        h = handle(device)
+        s = np.ascontiguousarray(samples, dtype=np.float64).ravel()
+        w = np.ascontiguousarray(widths[ok])
+        lp = np.empty(w.size)
+        _call(h, "gpmi_kde_cv_logprob", h.ctx, s.size, _lib.dptr(s), w.size, _lib.dptr(w), float(c), _lib.dptr(lp))
+        out[ok] = lp
+    return out
