@@ -439,6 +439,29 @@ int gpmi_kde_eval(gpmi_kde* kde, int64_t m, const double* x_host, const int64_t*
 int gpmi_kde_cv_logprob(gpmi_ctx* ctx, int64_t n, const double* samples_host, int n_widths,
                         const double* widths_host, double c, double* logprob_host);
 
+/* ---- two-dimensional kernel-density estimation (KDE2D, inference/pdf/kde.py:256-280) ----
+ * A 2-D density object holds the n finite samples (x_j, y_j) on the device, binned into tiles of nearby samples; the
+ * handle owns it (gpmi_destroy releases the objects still alive), and its calls share the stream and the workspaces of
+ * the 1-D density objects, serialised by the caller in the same way.  Every evaluation returns the raw, untruncated sum
+ *   S(a, b) = sum_j exp(-((x_j - a) q_x)^2 - ((y_j - b) q_y)^2)
+ * (KDE2D.density, kde.py:272-275, without `norm`, which the caller applies); q_x and q_y are finite and positive.
+ * Repeated calls are bit-identical, and a point's value does not depend on the other points of a call.  Every call
+ * names the handle: a pointer that is not a live object of it (one already destroyed, say) is GPMI_ERR_ARG. */
+typedef struct gpmi_kde2d gpmi_kde2d;
+int gpmi_kde2d_create(gpmi_ctx* ctx, int64_t n, const double* x_host, const double* y_host, gpmi_kde2d** out);
+int gpmi_kde2d_destroy(gpmi_ctx* ctx, gpmi_kde2d* kde);
+/* S at the m >= 0 finite points (a_host[i], b_host[i]) (m = 0 returns at once) */
+int gpmi_kde2d_eval(gpmi_ctx* ctx, gpmi_kde2d* kde, int64_t m, const double* a_host, const double* b_host, double q_x,
+                    double q_y, double* sum_host);
+/* S at every sample, in the order the samples were given (sum_host[n]).  Tiles of samples whose every term is below
+ * e^-80 are skipped (S_i >= 1 here: what is left out is below 4e-26).  tiles_host, if not NULL, receives the number of
+ * tile pairs computed and the nominal number ({done, total}; a tile is 256 samples). */
+int gpmi_kde2d_self(gpmi_ctx* ctx, gpmi_kde2d* kde, double q_x, double q_y, double* sum_host, int64_t* tiles_host);
+/* S on the grid of an x axis (g_x finite values) and a y axis (g_y values), sum_host[b * g_x + a] = S(x_axis[a],
+ * y_axis[b]), as the product of the two factor matrices exp(-((x_j - a) q_x)^2), exp(-((y_j - b) q_y)^2) (fp64 MFMA) */
+int gpmi_kde2d_grid(gpmi_ctx* ctx, gpmi_kde2d* kde, int64_t g_x, const double* x_axis_host, int64_t g_y,
+                    const double* y_axis_host, double q_x, double q_y, double* sum_host);
+
 /* ---- instrumentation ---------------------------------------------------------------
  * HIP-event timing on the handle's own stream (torch.cuda.Event would not see it). */
 int gpmi_timer_start(gpmi_ctx* ctx);

@@ -18,6 +18,7 @@
 // order and reduces log S_i - log(h n sqrt(2 pi)) + log(1 - c / S_i) over a workgroup in a fixed tree; the host adds the
 // workgroup sums in order.
 #include "api_internal.h"
+#include "kde_state.h"
 #include "kmath.h"
 
 namespace {
@@ -221,21 +222,7 @@ struct gpmi_kde {
   std::vector<int> lo, hi;
 };
 
-// Per-handle state of the density entry points: one stream and workspaces shared by every density object of the handle
-// (calls on one handle are serialised), and the live objects, which gpmi_destroy releases.
-struct KdeState {
-  hipStream_t stream = nullptr;
-  std::vector<gpmi_kde*> live;
-  char* h_stage = nullptr;  // pinned staging of inputs and outputs
-  size_t h_bytes = 0;
-  char* d_in = nullptr;     // device copy of the staged inputs
-  size_t d_in_bytes = 0;
-  double* d_work = nullptr; // partials / outputs
-  size_t d_work_bytes = 0;
-};
-
-namespace {
-
+// Per-handle state of the density entry points (KdeState, kde_state.h), shared with kde2d.hip
 int kde_state(gpmi_ctx* c, KdeState*& st) {
   if (!c->kde) c->kde = new KdeState();
   st = c->kde;
@@ -243,7 +230,7 @@ int kde_state(gpmi_ctx* c, KdeState*& st) {
   return GPMI_OK;
 }
 
-int grow_pinned(gpmi_ctx* c, KdeState* st, size_t bytes) {
+int kde_grow_pinned(gpmi_ctx* c, KdeState* st, size_t bytes) {
   if (bytes <= st->h_bytes) return GPMI_OK;
   if (st->h_stage) (void)hipHostFree(st->h_stage);
   st->h_stage = nullptr;
@@ -254,7 +241,7 @@ int grow_pinned(gpmi_ctx* c, KdeState* st, size_t bytes) {
   return GPMI_OK;
 }
 
-int grow_device(gpmi_ctx* c, void** ptr, size_t* have, size_t bytes) {
+int kde_grow_device(gpmi_ctx* c, void** ptr, size_t* have, size_t bytes) {
   if (bytes <= *have) return GPMI_OK;
   if (*ptr) (void)hipFree(*ptr);
   *ptr = nullptr;
@@ -265,7 +252,11 @@ int grow_device(gpmi_ctx* c, void** ptr, size_t* have, size_t bytes) {
   return GPMI_OK;
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+namespace {
+
+int grow_pinned(gpmi_ctx* c, KdeState* st, size_t bytes) { return kde_grow_pinned(c, st, bytes); }
+int grow_device(gpmi_ctx* c, void** ptr, size_t* have, size_t bytes) { return kde_grow_device(c, ptr, have, bytes); }
+size_t align256(size_t b) { return kde_align256(b); }
 
 void kde_free(gpmi_kde* k) {
   if (k->s) (void)hipFree(k->s);
@@ -280,6 +271,8 @@ void kde_release_all(gpmi_ctx* c) {
   if (st->stream) (void)hipStreamSynchronize(st->stream);
   for (gpmi_kde* k : st->live) kde_free(k);
   st->live.clear();
+  for (gpmi_kde2d* k : st->live2d) kde2d_free(k);
+  st->live2d.clear();
   if (st->h_stage) (void)hipHostFree(st->h_stage);
   if (st->d_in) (void)hipFree(st->d_in);
   if (st->d_work) (void)hipFree(st->d_work);

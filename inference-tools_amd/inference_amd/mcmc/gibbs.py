@@ -9,7 +9,8 @@ with proposal widths tuned towards a 50 % acceptance rate.
 Provided: what `ParallelTempering` needs (`inv_temp`, `take_step`, `get_last`,
 `replace_last`, `probs`, sample access, boundaries) and the reference's read-out
 of results (base.py:75-160, gibbs.py:370-377): `get_marginal` (a device
-`GaussianKDE` of one parameter), `get_interval` and `mode`.  Plotting,
+`GaussianKDE` of one parameter), `get_interval`, `mode` and `matrix_plot`
+(base.py:162-189, over `inference_amd.plotting`).  The other plots,
 `UnimodalPdf` marginals and save / load of the reference are out of scope.
 
 MI355X-specific addition: `advance_lockstep` advances MANY chains together so
@@ -247,6 +248,28 @@ class GibbsChain:
         """The sample with the highest log-probability so far."""
         ind = argmax(self.probs)
         return array([p.samples[ind] for p in self.params])
+
+    def matrix_plot(self, params=None, burn: int = 0, thin: int = 1, **kwargs):
+        """The matrix plot of the parameters (or of those whose indices `params` lists): all 1D and 2D marginal
+        distributions of the samples left after `burn` and `thin`.  The other keyword arguments are those of
+        `inference_amd.plotting.matrix_plot`, whose figure is returned (the reference returns None)."""
+        from inference_amd.plotting import matrix_plot
+
+        self._plot_checks(burn, thin, "matrix")
+        params = params if params is not None else range(self.n_parameters)
+        samples = [self.get_parameter(i, burn=burn, thin=thin) for i in params]
+        return matrix_plot(samples, **kwargs)
+
+    def _plot_checks(self, burn: int, thin: int, plot_type: str):
+        """base.py:218-237."""
+        from inference_amd.pdf._messages import plot_burn_thin, plot_no_samples
+
+        name = self.__class__.__name__
+        if self.chain_length < 2:
+            raise ValueError(plot_no_samples(name, plot_type, self.chain_length))
+        reduced_length = max(self.chain_length - burn - 1, 0) // thin + 1
+        if reduced_length < 2:
+            raise ValueError(plot_burn_thin(name, plot_type, reduced_length))
 
     def set_non_negative(self, parameter: int, flag=True):
         self.params[parameter].non_negative = flag

@@ -1,10 +1,10 @@
 """Device side of the density estimators: one lazily created `_lib.Handle` per device for the whole module (thousands
-of KDEs from a tempering run share its stream and workspaces), the density objects of csrc/kde.hip and the
-leave-one-out log-probability.  No CPU fallback: without the library or a GPU, `GpmiUnavailable` is raised.
+of KDEs from a tempering run share its stream and workspaces), the density objects of csrc/kde.hip and csrc/kde2d.hip
+and the leave-one-out log-probability.  No CPU fallback: without the library or a GPU, `GpmiUnavailable` is raised.
 
 The library expects the calls on one handle to be serialised (include/gpmi.h), and ctypes releases the GIL during a
-call, so every gpmi_kde_* call - with the read of its error text - holds the handle's lock: KDEs built and evaluated
-on several threads at once share the handle safely.  The lock is re-entrant, because a density object's finaliser
+call, so every gpmi_kde_* / gpmi_kde2d_* call - with the read of its error text - holds the handle's lock: KDEs built
+and evaluated on several threads at once share the handle safely.  The lock is re-entrant, because a density object's finaliser
 (which releases it on the device) can run inside a locked region of the same thread."""
 import ctypes as C
 import sys
@@ -83,6 +83,57 @@ class DeviceDensity:
         with h.kde_lock:
             if h.ctx and self.ptr:
                 h.lib.gpmi_kde_destroy(self.ptr)
+            self.ptr = C.c_void_p()
+
+
+class DeviceDensity2D:
+    """The samples (x_j, y_j) of a 2-D estimate on the device (gpmi_kde2d_create, csrc/kde2d.hip).  Every method returns
+    raw sums S(a, b) = sum_j exp(-((x_j - a) q_x)^2 - ((y_j - b) q_y)^2); the caller applies the normalisation."""
+
+    def __init__(self, x, y, device=None):
+        self.h = handle(device)
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        self.n = x.size
+        self.ptr = C.c_void_p()
+        _call(self.h, "gpmi_kde2d_create", self.h.ctx, x.size, _lib.dptr(x), _lib.dptr(y), C.byref(self.ptr))
+
+    def sums(self, a, b, q_x, q_y):
+        """S at the scattered points (a_i, b_i): the direct sum (gpmi_kde2d_eval)."""
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        b = np.ascontiguousarray(b, dtype=np.float64).ravel()
+        out = np.empty(a.size)
+        _call(self.h, "gpmi_kde2d_eval", self.h.ctx, self.ptr, a.size, _lib.dptr(a), _lib.dptr(b), float(q_x), float(q_y),
+              _lib.dptr(out))
+        return out
+
+    def self_sums(self, q_x, q_y, count_tiles=False):
+        """S at every sample, in the order given (gpmi_kde2d_self); with count_tiles also (tile pairs computed, tile
+        pairs in all) of its skip rule."""
+        out = np.empty(self.n)
+        tiles = np.zeros(2, dtype=np.int64)
+        _call(self.h, "gpmi_kde2d_self", self.h.ctx, self.ptr, float(q_x), float(q_y), _lib.dptr(out),
+              _i64(tiles) if count_tiles else None)
+        return (out, (int(tiles[0]), int(tiles[1]))) if count_tiles else out
+
+    def grid_sums(self, x_axis, y_axis, q_x, q_y):
+        """S on the grid of the two axes, shape (len(y_axis), len(x_axis)): the factorised product (gpmi_kde2d_grid)."""
+        xa = np.ascontiguousarray(x_axis, dtype=np.float64).ravel()
+        ya = np.ascontiguousarray(y_axis, dtype=np.float64).ravel()
+        out = np.empty((ya.size, xa.size))
+        _call(self.h, "gpmi_kde2d_grid", self.h.ctx, self.ptr, xa.size, _lib.dptr(xa), ya.size, _lib.dptr(ya), float(q_x),
+              float(q_y), _lib.dptr(out))
+        return out
+
+    def __del__(self):
+        if sys.is_finalizing():
+            return
+        h = getattr(self, "h", None)
+        if h is None or not getattr(self, "ptr", None):
+            return
+        with h.kde_lock:
+            if h.ctx and self.ptr:
+                h.lib.gpmi_kde2d_destroy(h.ctx, self.ptr)
             self.ptr = C.c_void_p()
 
 

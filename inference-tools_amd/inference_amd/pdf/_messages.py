@@ -1,5 +1,7 @@
-"""Error / warning texts of the density estimators.  The wording, line breaks and indentation follow the reference
-(pdf/kde.py:53-60, pdf/base.py:41-48, pdf/hdi.py:27-91) so that callers that match on messages keep working."""
+"""Error / warning texts of the density estimators, of the matrix plot and of the chains' plot checks.  The wording, line
+breaks and indentation follow the reference (pdf/kde.py:53-60, pdf/base.py:41-48, pdf/hdi.py:27-91, plotting.py:91-135,
+mcmc/base.py:218-237) so that callers that match on messages keep working; the KDE2D texts are this package's own (the
+reference has none)."""
 
 
 def _framed(indent: int, owner: str, kind: str, *lines: str) -> str:
@@ -51,3 +53,51 @@ def hdi_inaccurate() -> str:
 def marginal_unimodal() -> str:
     return ("\n\n[ GibbsChain error ]\n>> unimodal=True asks for a UnimodalPdf, which inference_amd does not provide:"
             "\n>> use the default GaussianKDE marginal (unimodal=False).\n")
+
+
+def kde2d_bad_samples(x_shape, y_shape) -> str:
+    return _framed(16, "KDE2D", "error", "The 'x' and 'y' arguments must be one-dimensional arrays of equal",
+                   f"length, at least 2, but their shapes are {x_shape} and {y_shape}.")
+
+
+def kde2d_bad_point(x_shape, y_shape) -> str:
+    return _framed(16, "KDE2D", "error", "A single point is given as two scalars (pass two iterables for several points),",
+                   f"but the arguments have shapes {x_shape} and {y_shape}.")
+
+
+def kde2d_bad_axes(x_shape, y_shape) -> str:
+    return _framed(16, "KDE2D", "error", "The axes of a grid must be one-dimensional arrays,",
+                   f"but their shapes are {x_shape} and {y_shape}.")
+
+
+def matrix_plot_labels() -> str:
+    return _framed(16, "matrix_plot", "error", "The number of labels given does not match",
+                   "the number of plotted parameters.")
+
+
+def matrix_plot_reference() -> str:
+    return _framed(16, "matrix_plot", "error", "The number of reference values given does not match",
+                   "the number of plotted parameters.")
+
+
+def matrix_plot_hdi_fractions() -> str:
+    return _framed(12, "matrix_plot", "error", "The 'hdi_fractions' argument must be given as an",
+                   "iterable of floats, each in the range [0, 1].")
+
+
+def matrix_plot_style() -> str:
+    return "'plot_style' must be set as either 'contour', 'hdi', 'histogram' or 'scatter'"
+
+
+def matrix_plot_colormap(colormap) -> str:
+    return f"'{colormap}' is not a valid colormap from matplotlib.colormaps"
+
+
+def plot_no_samples(owner: str, plot_type: str, chain_length) -> str:
+    return _framed(16, owner, "error", f"Cannot generate the {plot_type} plot as no samples have",
+                   f"been produced - current chain length is {chain_length}.")
+
+
+def plot_burn_thin(owner: str, plot_type: str, reduced_length) -> str:
+    return _framed(16, owner, "error", "The given values of 'burn' and 'thin' leave insufficient",
+                   f"samples to generate the {plot_type} plot.", f"Number of samples after burn / thin is {reduced_length}.")

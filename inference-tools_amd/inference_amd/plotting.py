@@ -1,0 +1,190 @@
+"""
+The matrix plot of a set of variables: every 1D and 2D marginal distribution (reference: plotting.py:19-303).
+
+`matrix_plot_data` computes everything the plot shows - axis limits and arrays, the 1D estimates, the 2D densities and
+the highest-density levels - as plain arrays; that is where the device works (`GaussianKDE`, `KDE2D.grid` and
+`KDE2D.at_samples`).  `matrix_plot` is the renderer over those arrays.  matplotlib is imported inside `matrix_plot`
+only: importing this module, or the package, never needs it.
+"""
+from warnings import warn
+
+import numpy as np
+from numpy import array, linspace, percentile
+
+from inference_amd.pdf import _messages as msg
+from inference_amd.pdf.hdi import sample_hdi
+from inference_amd.pdf.kde import GaussianKDE
+from inference_amd.pdf.kde2d import KDE2D
+
+STYLES = ("contour", "hdi", "histogram", "scatter")
+AXIS_POINTS = 200  # points of a parameter's axis array; the 2D densities take every fourth
+GRID_STEP = 4
+
+
+def _check_hdi_fractions(hdi_fractions):
+    iterable = hasattr(hdi_fractions, "__iter__")
+    if not iterable or not all(0 < f < 1 for f in hdi_fractions):
+        raise ValueError(msg.matrix_plot_hdi_fractions())
+
+
+def matrix_plot_data(samples, plot_style="contour", hdi_fractions=(0.35, 0.65, 0.95), *, device=None):
+    """
+    Everything `matrix_plot` draws for `samples` (a list of 1D arrays, one per parameter), as a dict of plain arrays:
+
+    - "axis_limits" (N, 2): the 98 % highest-density interval of each parameter, widened by 0.3 of its width;
+    - "axis_arrays" (N, 200): the axis of each parameter (the interval widened by 0.35);
+    - "marginals" (N, 200): the `GaussianKDE` estimate of each parameter on its axis;
+    - "pairs": for the styles "contour" and "hdi", a dict keyed (i, j), i > j, of dicts with "x" and "y" (every fourth
+      axis value of parameters j and i) and "prob" (50, 50), the `KDE2D(x=samples[j], y=samples[i])` density on their
+      grid; for "hdi" also "levels": the percentiles 100 (1 - f) of the density at the samples for f in
+      `hdi_fractions`, with the grid's maximum appended, sorted.  Empty for "histogram" and "scatter".
+    """
+    if plot_style not in STYLES:
+        raise ValueError(msg.matrix_plot_style())
+    _check_hdi_fractions(hdi_fractions)
+    samples = [np.asarray(s) for s in samples]
+    axis_limits, axis_arrays, marginals = [], [], []
+    for sample in samples:
+        # the 98% HDI sets the plot limits
+        lwr, upr = sample_hdi(sample, fraction=0.98)
+        axis_limits.append([lwr - (upr - lwr) * 0.3, upr + (upr - lwr) * 0.3])
+        axis_arrays.append(linspace(lwr - (upr - lwr) * 0.35, upr + (upr - lwr) * 0.35, AXIS_POINTS))
+        marginals.append(array(GaussianKDE(sample, device=device)(axis_arrays[-1])))
+
+    pairs = {}
+    if plot_style in ("contour", "hdi"):
+        for i in range(len(samples)):
+            for j in range(i):
+                pdf = KDE2D(x=samples[j], y=samples[i], device=device)
+                x_ax = axis_arrays[j][::GRID_STEP]
+                y_ax = axis_arrays[i][::GRID_STEP]
+                entry = {"x": x_ax, "y": y_ax}
+                if plot_style == "hdi":
+                    sample_probs = pdf.at_samples()
+                    pcts = [100 * (1 - f) for f in hdi_fractions]
+                    levels = [lv for lv in percentile(sample_probs, pcts)]
+                entry["prob"] = prob = pdf.grid(x_ax, y_ax)
+                if plot_style == "hdi":
+                    levels.append(prob.max())
+                    entry["levels"] = array(sorted(levels))
+                pairs[(i, j)] = entry
+    return {"axis_limits": array(axis_limits), "axis_arrays": array(axis_arrays), "marginals": array(marginals),
+            "pairs": pairs}
+
+
+def matrix_plot(samples, labels=None, show=True, reference=None, filename=None, plot_style="contour", colormap="Blues",
+                show_ticks=None, point_colors=None, hdi_fractions=(0.35, 0.65, 0.95), point_size=1, label_size=10, *,
+                device=None):
+    """
+    Construct a 'matrix plot' for a set of variables which shows all possible 1D and 2D marginal distributions, and
+    return the figure.
+
+    :param samples: A list of array-like objects containing the samples for each variable.
+    :param labels: A list of strings to be used as axis labels for each parameter being plotted.
+    :param bool show: Sets whether the plot is displayed.
+    :param reference: A list of reference values for each parameter which will be over-plotted.
+    :param str filename: File path to which the matrix plot will be saved (if specified).
+    :param str plot_style: The type of plot of the 2D marginals: 'contour' for filled contours, 'hdi' for
+        highest-density interval contours, 'histogram' for a hexagonal-bin histogram, 'scatter' for a scatterplot.
+    :param str colormap: The name of a colormap in ``matplotlib.colormaps``.
+    :param bool show_ticks: Axis ticks are shown for fewer than 6 variables unless this is set to True or False.
+    :param point_colors: Data which sets the colors of the points of the 'scatter' style.
+    :param point_size: The size of the points of the 'scatter' style.
+    :param hdi_fractions: The highest-density intervals of the 'hdi' style, as the fraction of the total probability
+        contained in each: an iterable of floats, each in the range [0, 1].
+    :param int label_size: The font-size used for axis labels.
+    :param device: (not in the reference) device index of the density estimates.
+    """
+    N_par = len(samples)
+    if labels is None:  # default axis labels
+        labels = [f"p{i}" for i in range(N_par)] if N_par >= 10 else [f"param {i}" for i in range(N_par)]
+    elif len(labels) != N_par:
+        raise ValueError(msg.matrix_plot_labels())
+    if reference is not None and len(reference) != N_par:
+        raise ValueError(msg.matrix_plot_reference())
+    # an unknown style falls back to the contours
+    if plot_style not in STYLES:
+        plot_style = "contour"
+        warn(msg.matrix_plot_style())
+    _check_hdi_fractions(hdi_fractions)
+    if show_ticks is None:  # ticks are suppressed from 6 parameters on, to keep things tidy
+        show_ticks = N_par < 6
+
+    import matplotlib.pyplot as plt
+    from matplotlib import colormaps
+
+    if colormap in colormaps:
+        cmap = colormaps[colormap]
+    else:
+        cmap = colormaps["Blues"]
+        warn(msg.matrix_plot_colormap(colormap))
+    # the darker end of the colormap draws the 1D marginals
+    marginal_color = min(cmap(10), cmap(245), key=lambda c: sum(c[:-1]))
+
+    samples = [np.asarray(s) for s in samples]
+    data = matrix_plot_data(samples, plot_style=plot_style, hdi_fractions=hdi_fractions, device=device)
+
+    fig = plt.figure(figsize=(8, 8))
+    grid = fig.add_gridspec(N_par, N_par)
+    axes = {}
+    # bottom row and left column first: the other panels share their axes
+    cells = sorted(((i, j) for i in range(N_par) for j in range(i + 1)), key=lambda c: (c[0] != N_par - 1, c[1] != 0))
+    for i, j in cells:
+        share_x = axes[(N_par - 1, j)] if i < N_par - 1 else None
+        share_y = axes[(i, 0)] if (j > 0 and i != j) else None  # the diagonal keeps its own y axis
+        axes[(i, j)] = fig.add_subplot(grid[i, j], sharex=share_x, sharey=share_y)
+
+    for (i, j), ax in axes.items():
+        if i == j:
+            curve = 0.9 * (data["marginals"][i] / data["marginals"][i].max())
+            ax.plot(data["axis_arrays"][i], curve, lw=1, color=marginal_color)
+            ax.fill_between(data["axis_arrays"][i], curve, color=marginal_color, alpha=0.1)
+            if reference is not None:
+                ax.plot([reference[i], reference[i]], [0, 1], lw=1.5, ls="dashed", color="red")
+            ax.set_ylim([0, 1])
+        else:
+            x, y = samples[j], samples[i]
+            if plot_style == "contour":
+                pair = data["pairs"][(i, j)]
+                ax.set_facecolor(cmap(256 // 20))
+                ax.contourf(pair["x"], pair["y"], pair["prob"], 10, cmap=cmap)
+            elif plot_style == "hdi":
+                pair = data["pairs"][(i, j)]
+                ax.contourf(pair["x"], pair["y"], pair["prob"], levels=pair["levels"], cmap=cmap)
+                ax.contour(pair["x"], pair["y"], pair["prob"], levels=pair["levels"], alpha=0.2)
+            elif plot_style == "histogram":
+                ax.set_facecolor(cmap(0))
+                ax.hexbin(x, y, gridsize=35, cmap=cmap)
+            elif point_colors is None:
+                ax.scatter(x, y, color=marginal_color, s=point_size)
+            else:
+                ax.scatter(x, y, c=point_colors, s=point_size, cmap=cmap)
+            if reference is not None:  # a red ring on a white one
+                for edge, width in (("white", 3.5), ("red", 2)):
+                    ax.plot(reference[j], reference[i], marker="o", markersize=7, markerfacecolor="none",
+                            markeredgecolor=edge, markeredgewidth=width)
+
+        if i == N_par - 1:  # bottom row: labels and limits in x
+            ax.set_xlabel(labels[j], fontsize=label_size)
+            ax.set_xlim(data["axis_limits"][j])
+        if j == 0 and i != 0:  # left column, except the top-left corner: labels and limits in y
+            ax.set_ylabel(labels[i], fontsize=label_size)
+            ax.set_ylim(data["axis_limits"][i])
+        if show_ticks:
+            if i < N_par - 1:
+                plt.setp(ax.get_xticklabels(), visible=False)
+            if j > 0:
+                plt.setp(ax.get_yticklabels(), visible=False)
+            if i == j:
+                ax.set_yticks([])
+        else:
+            ax.set_xticks([])
+            ax.set_yticks([])
+
+    fig.tight_layout()
+    fig.subplots_adjust(wspace=0.0, hspace=0.0)
+    if filename is not None:
+        fig.savefig(filename)
+    if show:
+        plt.show()
+    return fig
