@@ -462,6 +462,24 @@ int gpmi_kde2d_self(gpmi_ctx* ctx, gpmi_kde2d* kde, double q_x, double q_y, doub
 int gpmi_kde2d_grid(gpmi_ctx* ctx, gpmi_kde2d* kde, int64_t g_x, const double* x_axis_host, int64_t g_y,
                     const double* y_axis_host, double q_x, double q_y, double* sum_host);
 
+/* ---- UnimodalPdf, inference/pdf/unimodal.py ------------------------------------------
+ * A unimodal object holds a sample on the device, in the order given (the reduced first stage of the fit reads
+ * sample[::skip]); the handle owns it (gpmi_destroy releases the objects still alive), and its calls share the stream
+ * and the workspaces of the density objects above, serialised by the caller in the same way.  Every call names the
+ * handle: a pointer that is not a live object of it is GPMI_ERR_ARG. */
+typedef struct gpmi_unimodal gpmi_unimodal;
+int gpmi_unimodal_create(gpmi_ctx* ctx, int64_t n, const double* sample_host, gpmi_unimodal** out);
+int gpmi_unimodal_destroy(gpmi_ctx* ctx, gpmi_unimodal* pdf);
+/* Replaces the sum of UnimodalPdf.posterior (unimodal.py:132-134, the model of :144-151) for n_theta >= 1 parameter
+ * vectors theta = (x0, s0, ln v, f, k, q) at once, over every stride-th sample (stride >= 1):
+ *   out_host[t] = sum over i = 0, stride, 2 stride, ... < n of -(1 + v) / 2 * log(1 + |z_i|^q / v),   v = exp(ln v),
+ *   z_i = z0_i exp(-f tanh(z0_i / k)),   z0_i = (sample[i] - x0) / s0
+ * The caller subtracts n_fit log(norm(theta)).  theta is not checked: non-finite or out-of-range values give what IEEE
+ * arithmetic gives (NaN in, NaN out), as the reference's NumPy does.  The sum is reduced in a fixed order that depends
+ * on n and stride alone: one theta alone and the same theta inside a batch give the same bits, as do repeated calls. */
+int gpmi_unimodal_logpdf_sums(gpmi_ctx* ctx, gpmi_unimodal* pdf, int64_t stride, int n_theta,
+                              const double* theta_host, double* out_host);
+
 /* ---- instrumentation ---------------------------------------------------------------
  * HIP-event timing on the handle's own stream (torch.cuda.Event would not see it). */
 int gpmi_timer_start(gpmi_ctx* ctx);

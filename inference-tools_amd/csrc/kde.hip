@@ -273,6 +273,8 @@ void kde_release_all(gpmi_ctx* c) {
   st->live.clear();
   for (gpmi_kde2d* k : st->live2d) kde2d_free(k);
   st->live2d.clear();
+  for (gpmi_unimodal* k : st->live_uni) unimodal_free(k);
+  st->live_uni.clear();
   if (st->h_stage) (void)hipHostFree(st->h_stage);
   if (st->d_in) (void)hipFree(st->d_in);
   if (st->d_work) (void)hipFree(st->d_work);

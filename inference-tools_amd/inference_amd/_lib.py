@@ -115,6 +115,9 @@ SIGNATURES = {
     "gpmi_kde2d_eval": (C.c_int, [_vp, _vp, _i64, _dp, _dp, C.c_double, C.c_double, _dp]),
     "gpmi_kde2d_self": (C.c_int, [_vp, _vp, C.c_double, C.c_double, _dp, C.POINTER(_i64)]),
     "gpmi_kde2d_grid": (C.c_int, [_vp, _vp, _i64, _dp, _i64, _dp, C.c_double, C.c_double, _dp]),
+    "gpmi_unimodal_create": (C.c_int, [_vp, _i64, _dp, C.POINTER(_vp)]),
+    "gpmi_unimodal_destroy": (C.c_int, [_vp, _vp]),
+    "gpmi_unimodal_logpdf_sums": (C.c_int, [_vp, _vp, _i64, C.c_int, _dp, _dp]),
     "gpmi_timer_start": (C.c_int, [_vp]),
     "gpmi_timer_stop": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "gpmi_profile_enable": (C.c_int, [_vp, C.c_int]),

@@ -1,9 +1,9 @@
 """Device side of the density estimators: one lazily created `_lib.Handle` per device for the whole module (thousands
-of KDEs from a tempering run share its stream and workspaces), the density objects of csrc/kde.hip and csrc/kde2d.hip
-and the leave-one-out log-probability.  No CPU fallback: without the library or a GPU, `GpmiUnavailable` is raised.
+of KDEs from a tempering run share its stream and workspaces), the density objects of csrc/kde.hip, csrc/kde2d.hip
+and csrc/unimodal.hip and the leave-one-out log-probability.  No CPU fallback: without the library or a GPU, `GpmiUnavailable` is raised.
 
 The library expects the calls on one handle to be serialised (include/gpmi.h), and ctypes releases the GIL during a
-call, so every gpmi_kde_* / gpmi_kde2d_* call - with the read of its error text - holds the handle's lock: KDEs built
+call, so every gpmi_kde_* / gpmi_kde2d_* / gpmi_unimodal_* call - with the read of its error text - holds the handle's lock: KDEs built
 and evaluated on several threads at once share the handle safely.  The lock is re-entrant, because a density object's finaliser
 (which releases it on the device) can run inside a locked region of the same thread."""
 import ctypes as C
@@ -134,6 +134,37 @@ class DeviceDensity2D:
         with h.kde_lock:
             if h.ctx and self.ptr:
                 h.lib.gpmi_kde2d_destroy(h.ctx, self.ptr)
+            self.ptr = C.c_void_p()
+
+
+class DeviceUnimodal:
+    """A sample on the device in the order given (gpmi_unimodal_create, csrc/unimodal.hip), for the sums of the
+    UnimodalPdf model's log-density over it."""
+
+    def __init__(self, sample, device=None):
+        self.h = handle(device)
+        s = np.ascontiguousarray(sample, dtype=np.float64).ravel()
+        self.n = s.size
+        self.ptr = C.c_void_p()
+        _call(self.h, "gpmi_unimodal_create", self.h.ctx, s.size, _lib.dptr(s), C.byref(self.ptr))
+
+    def sums(self, thetas, stride=1):
+        """Sum of log_pdf_model(sample[::stride], theta) for every row theta of `thetas` (T x 6), in one call."""
+        th = np.ascontiguousarray(thetas, dtype=np.float64).reshape(-1, 6)
+        out = np.empty(th.shape[0])
+        _call(self.h, "gpmi_unimodal_logpdf_sums", self.h.ctx, self.ptr, int(stride), th.shape[0], _lib.dptr(th),
+              _lib.dptr(out))
+        return out
+
+    def __del__(self):
+        if sys.is_finalizing():
+            return
+        h = getattr(self, "h", None)
+        if h is None or not getattr(self, "ptr", None):
+            return
+        with h.kde_lock:
+            if h.ctx and self.ptr:
+                h.lib.gpmi_unimodal_destroy(h.ctx, self.ptr)
             self.ptr = C.c_void_p()
 
 

@@ -51,8 +51,9 @@ def hdi_inaccurate() -> str:
 
 
 def marginal_unimodal() -> str:
-    return ("\n\n[ GibbsChain error ]\n>> unimodal=True asks for a UnimodalPdf, which inference_amd does not provide:"
-            "\n>> use the default GaussianKDE marginal (unimodal=False).\n")
+    return ("\n\n[ GibbsChain error ]\n>> unimodal=True asks for a UnimodalPdf, which get_marginal does not build here:"
+            "\n>> use inference_amd.pdf.UnimodalPdf(chain.get_parameter(index, burn, thin)),"
+            "\n>> or the default GaussianKDE marginal (unimodal=False).\n")
 
 
 def kde2d_bad_samples(x_shape, y_shape) -> str:
