@@ -480,6 +480,29 @@ int gpmi_unimodal_destroy(gpmi_ctx* ctx, gpmi_unimodal* pdf);
 int gpmi_unimodal_logpdf_sums(gpmi_ctx* ctx, gpmi_unimodal* pdf, int64_t stride, int n_theta,
                               const double* theta_host, double* out_host);
 
+/* ---- highest-density intervals of the columns of a sample (inference/pdf/hdi.py:6-105) ----
+ * Replaces sample_hdi's sort, window widths and argmin (hdi.py:94-104) for m columns of n rows and n_frac window lengths
+ * at once.  For column c sorted ascending into s and window length L = L_host[f]:
+ *   L <  n : i* = the lowest i in [0, n - L) that attains min (s[i + L] - s[i]);
+ *            hdi_host[(2 f) m + c] = s[i*], hdi_host[(2 f + 1) m + c] = s[i* + L]      (L = 0 gives (s[0], s[0]))
+ *   L >= n : (s[0], s[n - 1])
+ * The caller computes L = int(fraction * n) itself.  A finite column gives exactly the reference's doubles (comparisons
+ * and one fp64 subtraction), whatever the other columns, fractions, layout or workspace cap of the call, and repeated
+ * calls are bit-identical.  flag_host[c] is 1 if column c holds a NaN or an infinity, else 0: the numbers of a flagged
+ * column are unspecified (the kernels stay in bounds and terminate on it), and the caller recomputes it.
+ * sample_host is read in place, element (r, c) at sample_host[r * row_stride + c * col_stride] (strides in elements),
+ * in one of two dense layouts: (ld, 1) with ld >= m (C order), transposed on the device, or (1, ld) with ld >= n
+ * (column-contiguous); m = 1 with row_stride = 1 is one contiguous run.  Anything else is GPMI_ERR_ARG, as are n < 2,
+ * m < 1, n_frac < 1 or > 65535 and a negative L.
+ * Device memory: the columns are walked in blocks of at most 65535 that fit ws_bytes (0: 4 GiB); the workspace belongs to
+ * the handle and is kept for later calls.  A column costs 8 n bytes, twice that in C order and 8 n more for n > 8192,
+ * plus 16 n_frac (1 + ceil(n / 4096)) + 4; about 2 KiB + 8 n_frac are fixed.  If one column does not fit the cap the
+ * call is GPMI_ERR_ARG and the error text says so.  n <= 2^30 (which needs ws_bytes of 32 GiB or more).
+ * Synchronous on the stream of the density entry points above, and serialised by the caller in the same way. */
+int gpmi_hdi_columns(gpmi_ctx* ctx, int64_t n, int64_t m, int64_t row_stride, int64_t col_stride,
+                     const double* sample_host, int n_frac, const int64_t* L_host, int64_t ws_bytes,
+                     double* hdi_host /* n_frac x 2 x m */, int32_t* flag_host /* m */);
+
 /* ---- instrumentation ---------------------------------------------------------------
  * HIP-event timing on the handle's own stream (torch.cuda.Event would not see it). */
 int gpmi_timer_start(gpmi_ctx* ctx);

@@ -118,6 +118,8 @@ SIGNATURES = {
     "gpmi_unimodal_create": (C.c_int, [_vp, _i64, _dp, C.POINTER(_vp)]),
     "gpmi_unimodal_destroy": (C.c_int, [_vp, _vp]),
     "gpmi_unimodal_logpdf_sums": (C.c_int, [_vp, _vp, _i64, C.c_int, _dp, _dp]),
+    "gpmi_hdi_columns": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _dp, C.c_int, C.POINTER(_i64), _i64, _dp,
+                                   C.POINTER(C.c_int32)]),
     "gpmi_timer_start": (C.c_int, [_vp]),
     "gpmi_timer_stop": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "gpmi_profile_enable": (C.c_int, [_vp, C.c_int]),

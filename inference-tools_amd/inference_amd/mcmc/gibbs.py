@@ -9,8 +9,8 @@ with proposal widths tuned towards a 50 % acceptance rate.
 Provided: what `ParallelTempering` needs (`inv_temp`, `take_step`, `get_last`,
 `replace_last`, `probs`, sample access, boundaries) and the reference's read-out
 of results (base.py:75-160, gibbs.py:370-377): `get_marginal` (a device
-`GaussianKDE` of one parameter), `get_interval`, `mode` and `matrix_plot`
-(base.py:162-189, over `inference_amd.plotting`).  The other plots,
+`GaussianKDE` of one parameter), `get_interval`, `mode`, `matrix_plot` and
+`trace_plot` (base.py:162-216, over `inference_amd.plotting`).  The other plots,
 `UnimodalPdf` marginals and save / load of the reference are out of scope.
 
 MI355X-specific addition: `advance_lockstep` advances MANY chains together so
@@ -259,6 +259,17 @@ class GibbsChain:
         params = params if params is not None else range(self.n_parameters)
         samples = [self.get_parameter(i, burn=burn, thin=thin) for i in params]
         return matrix_plot(samples, **kwargs)
+
+    def trace_plot(self, params=None, burn: int = 0, thin: int = 1, **kwargs):
+        """The trace plot of the parameters (or of those whose indices `params` lists): the value of each as a function
+        of the step number, for the samples left after `burn` and `thin` (base.py:191-216).  The other keyword arguments
+        are those of `inference_amd.plotting.trace_plot`, whose figure is returned (the reference returns None)."""
+        from inference_amd.plotting import trace_plot
+
+        self._plot_checks(burn, thin, "trace")
+        params = params if params is not None else range(self.n_parameters)
+        samples = [self.get_parameter(i, burn=burn, thin=thin) for i in params]
+        return trace_plot(samples, **kwargs)
 
     def _plot_checks(self, burn: int, thin: int, plot_type: str):
         """base.py:218-237."""

@@ -168,6 +168,34 @@ class DeviceUnimodal:
             self.ptr = C.c_void_p()
 
 
+def hdi_columns(sample2d, Ls, device=None, ws_bytes=0):
+    """The narrowest windows of the columns of `sample2d` (n x m, float64) for every window length of `Ls`
+    (gpmi_hdi_columns, csrc/hdi.hip): `hdi` of shape (len(Ls), 2, m) and `flags` (m, bool), set for the columns that
+    hold a NaN or an infinity, whose numbers in `hdi` mean nothing.  The array is read in place through its own strides
+    when it is dense in either order (C order, also a view of some of its columns, or the transpose of such an array);
+    any other view is made C-contiguous first.  `ws_bytes` caps the device workspace (0: the library's default)."""
+    s = np.asarray(sample2d, dtype=np.float64)
+    if s.ndim != 2:
+        raise ValueError("hdi_columns takes a two-dimensional sample")
+    n, m = s.shape
+    item = s.itemsize
+    rs, cs = s.strides
+
+    def dense(a, b, count):  # strides (ld, 1) in elements with ld >= count
+        return b == item and a % item == 0 and a // item >= count
+
+    if not s.flags.aligned or not (dense(rs, cs, m) or dense(cs, rs, n) or (m == 1 and rs == item)):
+        s = np.ascontiguousarray(s)
+        rs, cs = s.strides
+    L = np.ascontiguousarray(Ls, dtype=np.int64).ravel()
+    hdi = np.empty((L.size, 2, m))
+    flags = np.zeros(m, dtype=np.int32)
+    h = handle(device)
+    _call(h, "gpmi_hdi_columns", h.ctx, n, m, rs // item, cs // item, s.ctypes.data_as(C.POINTER(C.c_double)), L.size, _i64(L), int(ws_bytes),
+          _lib.dptr(hdi), flags.ctypes.data_as(C.POINTER(C.c_int32)))
+    return hdi, flags.astype(bool)
+
+
 def cv_logprob(samples, widths, c=0.99, device=None):
     """Leave-one-out log-probabilities of `samples` for every width (gpmi_kde_cv_logprob, one call).  A width that is
     not finite and positive gives NaN without a device call, as the reference's arithmetic does for width = inf."""

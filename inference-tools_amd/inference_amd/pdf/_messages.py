@@ -1,6 +1,6 @@
 """Error / warning texts of the density estimators, of the matrix plot and of the chains' plot checks.  The wording, line
 breaks and indentation follow the reference (pdf/kde.py:53-60, pdf/base.py:41-48, pdf/hdi.py:27-91, plotting.py:91-135,
-mcmc/base.py:218-237) so that callers that match on messages keep working; the KDE2D texts are this package's own (the
+plotting.py:331-333, plotting.py:416-434, mcmc/base.py:218-237) so that callers that match on messages keep working; the KDE2D texts are this package's own (the
 reference has none)."""
 
 
@@ -92,6 +92,18 @@ def matrix_plot_style() -> str:
 
 def matrix_plot_colormap(colormap) -> str:
     return f"'{colormap}' is not a valid colormap from matplotlib.colormaps"
+
+
+def hdi_plot_intervals() -> str:
+    return "All intervals must be greater than 0 and less than 1"
+
+
+def hdi_plot_dimensions() -> str:
+    return '"x" and "sample" have incompatible dimensions'
+
+
+def trace_plot_labels() -> str:
+    return "number of labels must match the number of plotted parameters"
 
 
 def plot_no_samples(owner: str, plot_type: str, chain_length) -> str:

@@ -3,16 +3,22 @@ The matrix plot of a set of variables: every 1D and 2D marginal distribution (re
 
 `matrix_plot_data` computes everything the plot shows - axis limits and arrays, the 1D estimates, the 2D densities and
 the highest-density levels - as plain arrays; that is where the device works (`GaussianKDE`, `KDE2D.grid` and
-`KDE2D.at_samples`).  `matrix_plot` is the renderer over those arrays.  matplotlib is imported inside `matrix_plot`
+`KDE2D.at_samples`).  `matrix_plot` is the renderer over those arrays.
+
+The highest-density bands of a set of model realisations and the trace plot (reference: plotting.py:306-454) are split
+the same way: `hdi_plot_data` and `trace_plot_data` ask the device for every interval of every column in one call
+(`sample_hdi_batch`), and `hdi_plot` and `trace_plot` draw the arrays.  matplotlib is imported inside the renderers
 only: importing this module, or the package, never needs it.
 """
+from itertools import cycle, product
+from math import ceil, sqrt
 from warnings import warn
 
 import numpy as np
 from numpy import array, linspace, percentile
 
 from inference_amd.pdf import _messages as msg
-from inference_amd.pdf.hdi import sample_hdi
+from inference_amd.pdf.hdi import sample_hdi, sample_hdi_batch
 from inference_amd.pdf.kde import GaussianKDE
 from inference_amd.pdf.kde2d import KDE2D
 
@@ -185,6 +191,141 @@ def matrix_plot(samples, labels=None, show=True, reference=None, filename=None, 
     fig.subplots_adjust(wspace=0.0, hspace=0.0)
     if filename is not None:
         fig.savefig(filename)
+    if show:
+        plt.show()
+    return fig
+
+
+def hdi_plot_data(x, sample, intervals=(0.65, 0.95), *, device=None):
+    """
+    Everything `hdi_plot` draws, as a dict of plain arrays: "x", "intervals" (the fractions, highest first), and "lower"
+    and "upper", both of shape ``(len(intervals), len(x))``: the bounds of the highest-density interval of the sample at
+    each x, one row per fraction.  `sample` has shape ``(n, len(x))``; one of shape ``(len(x), n)`` is transposed (as a
+    view: the device reads either layout in place).  All the intervals of all the columns come from one device call.
+    """
+    # order the intervals from highest to lowest
+    intervals = array(intervals)
+    intervals.sort()
+    intervals = intervals[::-1]
+    if not all((intervals > 0.0) & (intervals < 1.0)):
+        raise ValueError(msg.hdi_plot_intervals())
+    s = np.asarray(sample)
+    if s.shape[1] != len(x):
+        if s.shape[0] == len(x):
+            s = s.T
+        else:
+            raise ValueError(msg.hdi_plot_dimensions())
+    bands = sample_hdi_batch(s, [float(f) for f in intervals], device=device)
+    return {"x": x, "intervals": intervals, "lower": bands[:, 0, :], "upper": bands[:, 1, :]}
+
+
+def hdi_plot(x, sample, intervals=(0.65, 0.95), colormap="Blues", axis=None, label_intervals=True, color_levels=None, *,
+             device=None):
+    """
+    Plot highest-density intervals for a given sample of model realisations, and return the axis.
+
+    :param x: The x-axis locations of the sample data as a ``numpy.ndarray``.
+    :param sample: A ``numpy.ndarray`` containing the sample data, which has shape ``(n, len(x))`` where ``n`` is the
+        number of samples.
+    :param intervals: A tuple containing the fractions of the total probability for each interval.
+    :param str colormap: The colormap to be used for plotting the intervals: the name of a colormap present in
+        ``matplotlib.colormaps``.
+    :param axis: A ``matplotlib.pyplot`` axis object which will be used to plot the intervals.
+    :param bool label_intervals: If ``True``, labels are assigned to each interval plot such that they appear in the
+        legend when using ``matplotlib.pyplot.legend``.
+    :param color_levels: A list of integers in the range [0,255] which specify the color value within the chosen color
+        map to be used for each of the intervals.
+    :param device: (not in the reference) device index of the interval computation.
+    """
+    data = hdi_plot_data(x, sample, intervals, device=device)
+    intervals = data["intervals"]
+
+    import matplotlib.pyplot as plt
+    from matplotlib import colormaps
+
+    if colormap in colormaps:
+        cmap = colormaps[colormap]
+    else:
+        cmap = colormaps["Blues"]
+        warn(msg.matrix_plot_colormap(colormap))
+    if color_levels is None:  # the colors of the intervals
+        lwr = 0.20
+        upr = 1.0
+        color_levels = 255 * ((upr - lwr) * (1 - intervals) + lwr)
+    colors = [cmap(int(c)) for c in color_levels]
+    if axis is None:
+        _, axis = plt.subplots()
+    for frac, col, lower, upper in zip(intervals, colors, data["lower"], data["upper"]):
+        lab = f"{int(100 * frac)}% HDI" if label_intervals else None
+        axis.fill_between(x, lower, upper, color=col, label=lab)
+    return axis
+
+
+def trace_plot_data(samples, *, device=None):
+    """
+    The y-limits and y-ticks `trace_plot` gives each parameter of `samples` (a list of 1D arrays), as a dict of the
+    arrays "limits" (N, 2) and "ticks" (N, 3): with (lwr, upr) the 99 % highest-density interval and mid the centre of
+    the 10 % one, the limits are lwr - 0.7 (mid - lwr) and upr + 0.7 (upr - mid), the ticks lwr - 0.5 (mid - lwr), mid and
+    upr + 0.5 (upr - mid).  Samples of equal length are answered by one device call with both fractions; a ragged list
+    takes one call per sample.
+    """
+    samples = [np.asarray(s, dtype=np.float64) for s in samples]
+    fractions = (0.99, 0.10)
+    if samples and all(s.ndim == 1 for s in samples) and len({s.size for s in samples}) == 1:
+        hdis = sample_hdi_batch(array(samples).T, fractions, device=device)  # one column per parameter
+    else:
+        hdis = np.stack([sample_hdi_batch(s, fractions, device=device) for s in samples], axis=-1) if samples \
+            else np.empty((2, 2, 0))
+    lwr, upr = hdis[0]
+    mid = 0.5 * (0 + hdis[1, 0] + hdis[1, 1])
+    limits = np.stack([lwr - (mid - lwr) * 0.7, upr + (upr - mid) * 0.7], axis=-1)
+    ticks = np.stack([lwr - (mid - lwr) * 0.5, mid, upr + (upr - mid) * 0.5], axis=-1)
+    return {"limits": limits, "ticks": ticks}
+
+
+def trace_plot(samples, labels=None, show=True, filename=None, *, device=None):
+    """
+    Construct a 'trace plot' for a set of variables which displays the value of the variables as a function of step
+    number in the chain, and return the figure.
+
+    :param samples: A list of array-like objects containing the samples for each variable.
+    :param labels: A list of strings to be used as axis labels for each parameter being plotted.
+    :param bool show: Sets whether the plot is displayed.
+    :param str filename: File path to which the plot will be saved (if specified).
+    :param device: (not in the reference) device index of the interval computation.
+    """
+    N_par = len(samples)
+    if labels is None:
+        labels = [f"p{i}" for i in range(N_par)] if N_par >= 10 else [f"param {i}" for i in range(N_par)]
+    elif len(labels) != N_par:
+        raise ValueError(msg.trace_plot_labels())
+    data = trace_plot_data(samples, device=device)
+
+    import matplotlib.pyplot as plt
+
+    # if for 'n' columns we allow up to m = 2*n rows, set 'n' to be as small as possible given the number of
+    # parameters, then make m as small as we can
+    n = int(ceil(sqrt(0.5 * N_par)))
+    m = int(ceil(float(N_par) / float(n)))
+
+    fig = plt.figure(figsize=(12, 8))
+    grid_inds = product(range(m), range(n))
+    colors = cycle(["C0", "C1", "C2", "C3", "C4"])
+    axes = {}
+    for k, (s, label, (i, j), col) in enumerate(zip(samples, labels, grid_inds, colors)):
+        share = {} if (i == 0 and j == 0) else {"sharex": axes[(0, 0)]}
+        ax = axes[(i, j)] = plt.subplot2grid((m, n), (i, j), **share)
+        ax.plot(s, ".", markersize=4, alpha=0.15, c=col)
+        ax.set_ylabel(label)
+        ax.set_ylim(list(data["limits"][k]))
+        ax.set_yticks(list(data["ticks"][k]))
+        if i < m - 1:
+            plt.setp(ax.get_xticklabels(), visible=False)
+        else:
+            ax.set_xlabel("chain step #")
+    fig.tight_layout()
+    if filename is not None:
+        plt.savefig(filename)
     if show:
         plt.show()
     return fig
