@@ -503,6 +503,38 @@ int gpmi_hdi_columns(gpmi_ctx* ctx, int64_t n, int64_t m, int64_t row_stride, in
                      const double* sample_host, int n_frac, const int64_t* L_host, int64_t ws_bytes,
                      double* hdi_host /* n_frac x 2 x m */, int32_t* flag_host /* m */);
 
+/* ---- autocorrelation sums of the columns of a sample (inference/mcmc/utilities.py:83-95) ----
+ * Replaces the FFT autocorrelation, the cut at the first negative lag and the sum of effective_sample_size for m columns
+ * of n rows at once.  For column c, with y = x - mean(x) in fp64:
+ *   f[k] = sum over t < n of y[t] y[(t + k) mod n]        (the circular autocorrelation of length n, for every n)
+ *   cut_host[c] = the lowest k in [1, n / 2) with f[k] < 0,   f0_host[c] = f[0],   sum_host[c] = sum over k < cut of f[k]
+ * and the caller finishes the effective sample size as int(n / (sum / f0)).  For even n this is what the reference's
+ * irfft(|rfft(y)|^2) holds, to rounding; for odd n the reference's irfft returns n - 1 points, which is not an
+ * autocorrelation of the sample, and this entry point does not reproduce it.
+ * flag_host[c] is 0 for an answered column, 1 if the column holds a NaN or an infinity, 2 if no such k exists (which
+ * includes n < 4 and f[0] == 0, a constant column): the numbers of a flagged column are unspecified (the kernels stay in
+ * bounds and terminate on it).
+ * Every sum is reduced in an order that depends on n alone, without atomics: a column alone and the same column inside a
+ * batch give the same bits, whatever the layout or the workspace cap, and repeated calls are bit-identical.  The mean is
+ * a fixed-order fp64 sum over n: integer-valued data has an exact mean, so a constant column gives y = 0.
+ * The lags are summed in rounds, one block of lags per round (gpmi_acf_lag_blocks), for the columns that have not met
+ * a negative lag yet: the work of a column is n (cut rounded up to the end of its block) products.
+ * Layouts and strides are those of gpmi_hdi_columns: (ld, 1) with ld >= m (C order), transposed on the device, or
+ * (1, ld) with ld >= n; m = 1 with row_stride = 1 is one contiguous run.  Anything else is GPMI_ERR_ARG, as are n < 2
+ * and m < 1.
+ * Device memory: the columns are walked in blocks of at most 65535 that fit ws_bytes (0: 4 GiB); the workspace belongs to
+ * the handle and is kept for later calls.  A column costs 8 (n + n / 2) bytes, 8 n more in C order, 8 ceil(n / 2048) B
+ * for the partial sums (B the largest block of gpmi_acf_lag_blocks(n): 256 .. 2048 lags) and 36; 2304 bytes are fixed.
+ * If one column does not fit the cap the call is GPMI_ERR_ARG and the error text says so.  n <= 2^30.
+ * Synchronous on the stream of the density entry points above, and serialised by the caller in the same way. */
+int gpmi_acf_columns(gpmi_ctx* ctx, int64_t n, int64_t m, int64_t row_stride, int64_t col_stride,
+                     const double* sample_host, int64_t ws_bytes, double* f0_host /* m */, double* sum_host /* m */,
+                     int64_t* cut_host /* m */, int32_t* flag_host /* m */);
+/* Host-only (no device call): the first lags of the blocks that gpmi_acf_columns walks for n >= 2 rows, ascending from 0
+ * and below n / 2 (256, 256, 512, 1024 and then 2048 lags each).  *count receives their number; starts_host, if not
+ * NULL, the first `cap` of them (fewer than *count: GPMI_ERR_ARG). */
+int gpmi_acf_lag_blocks(int64_t n, int64_t cap, int64_t* starts_host, int64_t* count);
+
 /* ---- instrumentation ---------------------------------------------------------------
  * HIP-event timing on the handle's own stream (torch.cuda.Event would not see it). */
 int gpmi_timer_start(gpmi_ctx* ctx);

@@ -6,7 +6,7 @@
 //
 // A block of columns (as many as the workspace cap allows) is copied to the device as it lies in host memory (a pitched
 // copy) and brought to one contiguous run of n doubles per column: a C-order block is transposed through a 32 x 33 LDS
-// tile (hdi_transpose, both sides coalesced), a column-contiguous one lands there directly.  Then
+// tile (col_transpose of col_transpose.h, both sides coalesced), a column-contiguous one lands there directly.  Then
 //   n <= HDI_C  hdi_small: a workgroup loads one column (or, below 2048 rows, 2048 / P columns of P = max(64, 2^ceil(log2
 //               n)) slots each) into LDS, pads with +inf, sorts with a direction-free bitonic network and scans every
 //               window length straight from LDS.
@@ -26,6 +26,7 @@
 // clamped to the runs, and the serial merge checks both cursors - so such a column costs what any other does, stays
 // in bounds and terminates.
 #include "api_internal.h"
+#include "col_transpose.h"
 #include "kde_state.h"
 
 #pragma clang fp contract(off)
@@ -87,23 +88,6 @@ __device__ __forceinline__ void bitonic_blocks(double* sh, int T, int P) {
 // (w, i) < (bw, bi) in the order by w, then i
 __device__ __forceinline__ bool win_less(double w, long long i, double bw, long long bi) {
   return w < bw || (w == bw && i < bi);
-}
-
-// raw (n x mb, row-major) -> cols (mb runs of n): 32 x 32 tiles, rows of tiles on grid.x
-__global__ __launch_bounds__(256) void hdi_transpose(const double* __restrict__ raw, double* __restrict__ cols, int64_t n,
-                                                     int64_t mb) {
-  __shared__ double tile[32][33];
-  const int64_t r0 = (int64_t)blockIdx.x * 32, c0 = (int64_t)blockIdx.y * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  for (int u = ty; u < 32; u += 8) {
-    const int64_t r = r0 + u, c = c0 + tx;
-    if (r < n && c < mb) tile[u][tx] = raw[r * mb + c];
-  }
-  __syncthreads();
-  for (int u = ty; u < 32; u += 8) {
-    const int64_t c = c0 + u, r = r0 + tx;
-    if (r < n && c < mb) cols[c * n + r] = tile[tx][u];
-  }
 }
 
 // n <= HDI_C: cpw columns of P slots per workgroup (cpw * P = T <= HDI_C), sort and window scan in LDS.
@@ -423,8 +407,8 @@ int gpmi_hdi_columns(gpmi_ctx* c, int64_t n, int64_t m, int64_t row_stride, int6
       HIPCHK(c, hipMemcpy2DAsync(dst, width, src, 8 * (size_t)ld, width, height, hipMemcpyHostToDevice, st->stream));
     }
     if (by_row) {
-      hipLaunchKernelGGL(hdi_transpose, dim3((unsigned)((n + 31) / 32), (unsigned)((mb + 31) / 32)), dim3(256), 0, st->stream,
-                         d_raw, d_a, n, mb);
+      hipLaunchKernelGGL(col_transpose, dim3((unsigned)((n + 31) / 32), (unsigned)((mb + 31) / 32)), dim3(256), 0, st->stream,
+                         d_raw, d_a, n, mb, n);
       HIPCHK(c, hipGetLastError());
     }
     if (!large) {

@@ -120,6 +120,9 @@ SIGNATURES = {
     "gpmi_unimodal_logpdf_sums": (C.c_int, [_vp, _vp, _i64, C.c_int, _dp, _dp]),
     "gpmi_hdi_columns": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _dp, C.c_int, C.POINTER(_i64), _i64, _dp,
                                    C.POINTER(C.c_int32)]),
+    "gpmi_acf_columns": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _dp, _i64, _dp, _dp, C.POINTER(_i64),
+                                   C.POINTER(C.c_int32)]),
+    "gpmi_acf_lag_blocks": (C.c_int, [_i64, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
     "gpmi_timer_start": (C.c_int, [_vp]),
     "gpmi_timer_stop": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "gpmi_profile_enable": (C.c_int, [_vp, C.c_int]),

@@ -10,8 +10,10 @@ Provided: what `ParallelTempering` needs (`inv_temp`, `take_step`, `get_last`,
 `replace_last`, `probs`, sample access, boundaries) and the reference's read-out
 of results (base.py:75-160, gibbs.py:370-377): `get_marginal` (a device
 `GaussianKDE` of one parameter), `get_interval`, `mode`, `matrix_plot` and
-`trace_plot` (base.py:162-216, over `inference_amd.plotting`).  The other plots,
-`UnimodalPdf` marginals and save / load of the reference are out of scope.
+`trace_plot` (base.py:162-216, over `inference_amd.plotting`), and the check that
+comes before them (gibbs.py:405-519, :577-592): `estimate_burn_in`, `diagnostics_data`
+(with the effective sample size of every parameter from one device call) and
+`plot_diagnostics`.  `UnimodalPdf` marginals and save / load of the reference are out of scope.
 
 MI355X-specific addition: `advance_lockstep` advances MANY chains together so
 that each round of proposals is ONE batched posterior evaluation on the device
@@ -270,6 +272,101 @@ class GibbsChain:
         params = params if params is not None else range(self.n_parameters)
         samples = [self.get_parameter(i, burn=burn, thin=thin) for i in params]
         return trace_plot(samples, **kwargs)
+
+    # -- diagnostics (reference: gibbs.py:405-519, :577-592) -----------------------------------
+    def estimate_burn_in(self) -> int:
+        """An estimate of the burn-in: the later of the step at which the chain first enters the top 1 % of its
+        log-probabilities and the mean, over the parameters, of the last step at which the proposal width was reviewed
+        and found more than 15 % away from its final value.  (As in the reference, a parameter whose width never was
+        that far away contributes its LAST review, the 0 that argmax gives for no match on the reversed log.)"""
+        probs = array(self.probs)
+        prob_estimate = argmax(probs > np.percentile(probs, 99))
+        width_estimates = []
+        for p in self.params:
+            latest_first = array(p.sigma_values)[::-1]
+            checks = array(p.sigma_checks)[::-1]
+            far = abs(latest_first / p.sigma - 1.0) > 0.15
+            width_estimates.append(checks[argmax(far)])
+        return int(max(prob_estimate, np.mean(width_estimates)))
+
+    def diagnostics_data(self, burn=None, *, device=None) -> dict:
+        """The arrays that `plot_diagnostics` draws.  `burn` defaults to `estimate_burn_in()`; `ess` holds the effective
+        sample size of every parameter over `get_sample(burn=burn)`, from ONE device call for all of them
+        (`effective_sample_size_batch`), and `ess_mean` / `ess_min` the integers of the text panel."""
+        from inference_amd.mcmc.utilities import effective_sample_size_batch
+
+        if burn is None:
+            burn = self.estimate_burn_in()
+        ess = effective_sample_size_batch(self.get_sample(burn=burn), device=device)
+        probs = array(self.probs)
+        floor = probs[self.chain_length // 2:].min()
+        widths = [array(p.sigma_values) for p in self.params]
+        return {
+            "burn": burn,
+            "ess": ess,
+            "ess_mean": int(np.mean(ess)),
+            "ess_min": int(ess.min()),
+            "step_axis": np.arange(probs.size) * 1e-3,
+            "probs": probs,
+            "prob_ylims": [floor, probs.max() * 1.1 - 0.1 * floor],
+            "width_steps": [array(p.sigma_checks[1:]) * 1e-3 for p in self.params],
+            "width_percent_change": [1e2 * np.diff(w) / w[:-1] for w in widths],
+        }
+
+    def plot_diagnostics(self, show=True, filename=None, *, device=None):
+        """Plot diagnostic traces that show how the chain is progressing: the log-probability against the step number
+        with the estimated burn-in marked, the history of the changes to every parameter's proposal width (which
+        should die away), the effective sample size of every parameter after the burn-in, and a summary of the
+        three.  Returns the figure (the reference returns None)."""
+        data = self.diagnostics_data(device=device)
+
+        import matplotlib.pyplot as plt
+
+        fig = plt.figure(figsize=(12, 9))
+        burn_mark = data["burn"] * 1e-3
+        length_mark = self.chain_length * 1e-3
+
+        ax1 = fig.add_subplot(221)
+        ax1.plot(data["step_axis"], data["probs"], marker=".", ls="none", markersize=3)
+        ax1.plot([burn_mark, burn_mark], data["prob_ylims"], c="red", ls="dashed", lw=2)
+        ax1.set_xlabel("chain step number ($10^3$)", fontsize=12)
+        ax1.set_ylabel("posterior log-probability", fontsize=12)
+        ax1.set_title("Chain log-probability history")
+        ax1.set_ylim(data["prob_ylims"])
+        ax1.grid()
+
+        ax2 = fig.add_subplot(222)
+        for steps, change in zip(data["width_steps"], data["width_percent_change"]):
+            ax2.plot(steps, change, marker="D", markersize=3)
+        for level in (5, -5):
+            ax2.plot([0, length_mark], [level, level], ls="dashed", lw=2, color="black")
+        ax2.set_xlabel("chain step number ($10^3$)", fontsize=12)
+        ax2.set_ylabel("% change in proposal widths", fontsize=12)
+        ax2.set_title("Parameter proposal widths adjustment summary")
+        ax2.set_ylim([-50, 50])
+        ax2.grid()
+
+        ax3 = fig.add_subplot(223)
+        ax3.bar(range(self.n_parameters), data["ess"], color=["C0", "C1", "C2", "C3", "C4"])
+        ax3.set_xlabel("parameter", fontsize=12)
+        ax3.set_ylabel("effective sample size", fontsize=12)
+        ax3.set_title("Parameter effective sample size estimate")
+        ax3.set_xticks(range(self.n_parameters))
+
+        ax4 = fig.add_subplot(224)
+        rows = (("Estimated burn-in:", data["burn"]), ("Average ESS:", data["ess_mean"]), ("Lowest ESS:", data["ess_min"]))
+        for k, (name, value) in enumerate(rows):
+            height = 0.85 - 0.1 * k
+            ax4.text(0.5, height, name, horizontalalignment="right", fontsize=14)
+            ax4.text(0.55, height, "{:.5G}".format(value), horizontalalignment="left", fontsize=14)
+        ax4.axis("off")
+
+        fig.tight_layout()
+        if filename is not None:
+            fig.savefig(filename)
+        if show:
+            plt.show()
+        return fig
 
     def _plot_checks(self, burn: int, thin: int, plot_type: str):
         """base.py:218-237."""

@@ -14,7 +14,8 @@ in lockstep so that each proposal round of the whole ladder is one batched
 log-marginal-likelihood evaluation on the GPU.  Several ladders are advanced
 together by `advance_ladders`; ladders are the unit sharded over GPUs (every swap
 stays GPU-local, nothing but the final samples is gathered).
-`swap_diagnostics` (matplotlib) is out of scope.
+`swap_diagnostics` draws the swap counters (parallel.py:328-362) and returns the figure; `swap_diagnostics_data` is
+the arrays it draws.
 """
 import os
 import sys
@@ -23,7 +24,7 @@ from random import choice
 from time import time
 from warnings import warn
 
-from numpy import arange, array, exp, identity, zeros
+from numpy import arange, array, exp, identity, triu, zeros
 from numpy.random import default_rng
 
 from inference_amd.mcmc.gibbs import advance_lockstep
@@ -166,6 +167,43 @@ class ParallelTempering:
         while time() < end_time:
             self.take_steps(swap_interval)
             self.swap()
+
+    def swap_diagnostics_data(self):
+        """What `swap_diagnostics` draws: `rate_matrix`, the accepted fraction of the swaps proposed between every
+        pair of chains (pairs never proposed count one attempt, so their rate is zero), and `total_swaps`, the number
+        of accepted swaps every chain took part in."""
+        rate_matrix = self.successful_swaps / self.attempted_swaps.clip(min=1)
+        above = triu(self.successful_swaps, k=1)
+        total_swaps = above.sum(axis=1) + above.sum(axis=0)
+        return rate_matrix, total_swaps
+
+    def swap_diagnostics(self, show=True):
+        """Plot the acceptance rates of the proposed position swaps between the chains, and the number of successful
+        swaps of every chain (parallel.py:328-362): useful in selecting the temperatures.  Returns the figure (the
+        reference returns None)."""
+        from inference_amd.plotting import transition_matrix_plot
+
+        rate_matrix, total_swaps = self.swap_diagnostics_data()
+
+        import matplotlib.pyplot as plt
+
+        fig = plt.figure(figsize=(10, 5))
+        ax1 = fig.add_subplot(121)
+        transition_matrix_plot(axis=ax1, matrix=rate_matrix, exclude_diagonal=True, upper_triangular=True)
+        ax1.set_xlabel("chain number")
+        ax1.set_ylabel("chain number")
+        ax1.set_title("acceptance rate of chain position swaps")
+
+        ax2 = fig.add_subplot(122)
+        ax2.bar(list(range(1, self.N_chains + 1)), total_swaps)
+        ax2.set_ylim([0, None])
+        ax2.set_xlabel("chain number")
+        ax2.set_ylabel("total successful position swaps")
+
+        fig.tight_layout()
+        if show:
+            plt.show()
+        return fig
 
     def return_chains(self):
         return self.chains

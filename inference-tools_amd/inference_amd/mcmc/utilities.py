@@ -1,0 +1,59 @@
+"""Chain diagnostics (reference: mcmc/utilities.py:83-95).  `effective_sample_size` is the host function with the
+reference's exact semantics; `effective_sample_size_batch` answers every column of a sample in one device call
+(csrc/acf.hip)."""
+from numpy import asarray, empty, float64, int64, ndarray
+from numpy.fft import irfft, rfft
+
+from inference_amd.pdf import _device
+from inference_amd.pdf import _messages as msg
+
+
+def effective_sample_size(x: ndarray) -> int:
+    """
+    Estimate of the effective sample size of a 1D sample: its length over the sum of the normalised autocorrelation
+    up to the first negative lag.
+
+    The autocorrelation is the inverse real FFT of the power spectrum, of which the first half is kept.  For an odd
+    length the inverse transform returns one point fewer than the sample has (numpy's default output length), as in
+    the reference, and that is kept: the integer is the reference's for every length.  A sample without a negative
+    lag in that half (two points, a constant sample, one holding a NaN) raises the reference's ``IndexError``.
+    """
+    x = asarray(x)
+    power = abs(rfft(x - x.mean())) ** 2
+    acf = irfft(power)
+    acf = acf[: acf.size // 2]
+    if acf[0] < 0.0:
+        raise ValueError(msg.ess_negative_first())
+    cut = (acf < 0.0).argmax()  # 0 when no lag is negative: nothing is left, and acf[0] below raises IndexError
+    acf = acf[:cut]
+    return int(x.size / (acf.sum() / acf[0]))
+
+
+def effective_sample_size_batch(sample, *, device=None, details=False):
+    """
+    The effective sample size of every column of `sample`, in one device call.  A 2D sample of shape ``(n, p)`` gives an
+    int64 array of shape ``(p,)``, a 1D sample one of shape ``(1,)``.  With ``details=True`` the return value is
+    ``(ess, f0, sum, cut)``: the zero-lag autocorrelation, its sum up to the first negative lag and that lag, per column.
+
+    The device sums the circular autocorrelation of length n directly, lag by lag, until a column meets its first
+    negative lag, and the integer is finished here as ``int(n / (sum / f0))``.  For even n that is the number
+    `effective_sample_size` gives; for odd n the host function follows the reference's shorter inverse transform and
+    this one does not (the two can differ by one or so for short samples).  The sample is converted to float64 (a
+    float32 sample is widened).  A column without an answer - one that holds a NaN or an infinity, or has no negative
+    lag below ``n // 2`` - is handed to `effective_sample_size`, which raises what the reference raises for it.  There
+    is no host route by size: without a GPU the call raises `GpmiUnavailable`.
+    """
+    s = asarray(sample, dtype=float64)
+    if s.ndim == 1:
+        s = s.reshape(s.size, 1)
+    if s.ndim != 2:
+        raise ValueError("effective_sample_size_batch takes a one- or two-dimensional sample")
+    n, p = s.shape
+    f0, total, cut, flags = _device.acf_columns(s, device=device)
+    ess = empty(p, dtype=int64)
+    for c in range(p):
+        if flags[c]:
+            ess[c] = effective_sample_size(s[:, c])
+        else:
+            ess[c] = int(n / (total[c] / f0[c]))
+    return (ess, f0, total, cut) if details else ess

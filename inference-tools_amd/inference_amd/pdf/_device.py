@@ -168,15 +168,13 @@ class DeviceUnimodal:
             self.ptr = C.c_void_p()
 
 
-def hdi_columns(sample2d, Ls, device=None, ws_bytes=0):
-    """The narrowest windows of the columns of `sample2d` (n x m, float64) for every window length of `Ls`
-    (gpmi_hdi_columns, csrc/hdi.hip): `hdi` of shape (len(Ls), 2, m) and `flags` (m, bool), set for the columns that
-    hold a NaN or an infinity, whose numbers in `hdi` mean nothing.  The array is read in place through its own strides
-    when it is dense in either order (C order, also a view of some of its columns, or the transpose of such an array);
-    any other view is made C-contiguous first.  `ws_bytes` caps the device workspace (0: the library's default)."""
+def _dense_columns(sample2d, who):
+    """`sample2d` as a float64 array the column entry points can read in place - dense in C order (also a view of some
+    of its columns) or as the transpose of such an array; any other view is made C-contiguous first - with its shape and
+    its strides in elements."""
     s = np.asarray(sample2d, dtype=np.float64)
     if s.ndim != 2:
-        raise ValueError("hdi_columns takes a two-dimensional sample")
+        raise ValueError(f"{who} takes a two-dimensional sample")
     n, m = s.shape
     item = s.itemsize
     rs, cs = s.strides
@@ -187,13 +185,51 @@ def hdi_columns(sample2d, Ls, device=None, ws_bytes=0):
     if not s.flags.aligned or not (dense(rs, cs, m) or dense(cs, rs, n) or (m == 1 and rs == item)):
         s = np.ascontiguousarray(s)
         rs, cs = s.strides
+    return s, n, m, rs // item, cs // item
+
+
+def hdi_columns(sample2d, Ls, device=None, ws_bytes=0):
+    """The narrowest windows of the columns of `sample2d` (n x m, float64) for every window length of `Ls`
+    (gpmi_hdi_columns, csrc/hdi.hip): `hdi` of shape (len(Ls), 2, m) and `flags` (m, bool), set for the columns that
+    hold a NaN or an infinity, whose numbers in `hdi` mean nothing.  The array is read in place through its own strides
+    when it is dense in either order (C order, also a view of some of its columns, or the transpose of such an array);
+    any other view is made C-contiguous first.  `ws_bytes` caps the device workspace (0: the library's default)."""
+    s, n, m, rs, cs = _dense_columns(sample2d, "hdi_columns")
     L = np.ascontiguousarray(Ls, dtype=np.int64).ravel()
     hdi = np.empty((L.size, 2, m))
     flags = np.zeros(m, dtype=np.int32)
     h = handle(device)
-    _call(h, "gpmi_hdi_columns", h.ctx, n, m, rs // item, cs // item, s.ctypes.data_as(C.POINTER(C.c_double)), L.size, _i64(L), int(ws_bytes),
+    _call(h, "gpmi_hdi_columns", h.ctx, n, m, rs, cs, s.ctypes.data_as(C.POINTER(C.c_double)), L.size, _i64(L), int(ws_bytes),
           _lib.dptr(hdi), flags.ctypes.data_as(C.POINTER(C.c_int32)))
     return hdi, flags.astype(bool)
+
+
+def acf_columns(sample2d, device=None, ws_bytes=0):
+    """The autocorrelation sums of the columns of `sample2d` (n x m, float64) up to their first negative lag
+    (gpmi_acf_columns, csrc/acf.hip): `f0`, `sum` (m, float64), `cut` (m, int64) and `flags` (m, int32): 0 for an
+    answered column, 1 for one that holds a NaN or an infinity, 2 for one without a negative lag below n // 2; the
+    numbers of a flagged column mean nothing.  The array is read in place under the rules of `hdi_columns`."""
+    s, n, m, rs, cs = _dense_columns(sample2d, "acf_columns")
+    f0 = np.zeros(m)
+    total = np.zeros(m)
+    cut = np.zeros(m, dtype=np.int64)
+    flags = np.zeros(m, dtype=np.int32)
+    h = handle(device)
+    _call(h, "gpmi_acf_columns", h.ctx, n, m, rs, cs, s.ctypes.data_as(C.POINTER(C.c_double)), int(ws_bytes),
+          _lib.dptr(f0), _lib.dptr(total), _i64(cut), flags.ctypes.data_as(C.POINTER(C.c_int32)))
+    return f0, total, cut, flags
+
+
+def acf_lag_blocks(n):
+    """The first lags of the blocks in which gpmi_acf_columns walks the lags of a column of n rows (host-only)."""
+    lib = _lib.load()
+    count = C.c_int64(0)
+    if lib.gpmi_acf_lag_blocks(int(n), 0, None, C.byref(count)) != 0:
+        raise ValueError("acf_lag_blocks takes n >= 2")
+    starts = np.zeros(count.value, dtype=np.int64)
+    if lib.gpmi_acf_lag_blocks(int(n), starts.size, _i64(starts), C.byref(count)) != 0:
+        raise _lib.GpmiError("gpmi_acf_lag_blocks failed")
+    return [int(k) for k in starts]
 
 
 def cv_logprob(samples, widths, c=0.99, device=None):

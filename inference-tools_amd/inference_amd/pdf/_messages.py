@@ -1,6 +1,6 @@
 """Error / warning texts of the density estimators, of the matrix plot and of the chains' plot checks.  The wording, line
 breaks and indentation follow the reference (pdf/kde.py:53-60, pdf/base.py:41-48, pdf/hdi.py:27-91, plotting.py:91-135,
-plotting.py:331-333, plotting.py:416-434, mcmc/base.py:218-237) so that callers that match on messages keep working; the KDE2D texts are this package's own (the
+plotting.py:331-333, plotting.py:416-434, plotting.py:481-518, mcmc/base.py:218-237, mcmc/utilities.py:90) so that callers that match on messages keep working; the KDE2D texts are this package's own (the
 reference has none)."""
 
 
@@ -114,3 +114,23 @@ def plot_no_samples(owner: str, plot_type: str, chain_length) -> str:
 def plot_burn_thin(owner: str, plot_type: str, reduced_length) -> str:
     return _framed(16, owner, "error", "The given values of 'burn' and 'thin' leave insufficient",
                    f"samples to generate the {plot_type} plot.", f"Number of samples after burn / thin is {reduced_length}.")
+
+
+def ess_negative_first() -> str:
+    return "First element of the autocorrelation is negative"
+
+
+def transition_matrix_type() -> str:
+    return "given matrix must be a numpy.ndarray"
+
+
+def transition_matrix_ndim() -> str:
+    return "given matrix must have exactly two dimensions"
+
+
+def transition_matrix_square() -> str:
+    return "given matrix must be square (i.e. both dimensions are of the same length)"
+
+
+def transition_matrix_size() -> str:
+    return "given matrix must be at least of size 2x2"

@@ -9,6 +9,9 @@ The highest-density bands of a set of model realisations and the trace plot (ref
 the same way: `hdi_plot_data` and `trace_plot_data` ask the device for every interval of every column in one call
 (`sample_hdi_batch`), and `hdi_plot` and `trace_plot` draw the arrays.  matplotlib is imported inside the renderers
 only: importing this module, or the package, never needs it.
+
+`transition_matrix_plot` (reference: plotting.py:457-554) draws a matrix of transition rates as coloured, labelled
+squares; `ParallelTempering.swap_diagnostics` uses it for the acceptance rates of the swaps.
 """
 from itertools import cycle, product
 from math import ceil, sqrt
@@ -329,3 +332,59 @@ def trace_plot(samples, labels=None, show=True, filename=None, *, device=None):
     if show:
         plt.show()
     return fig
+
+
+def transition_matrix_plot(axis=None, matrix=None, colormap="viridis", exclude_diagonal=False, upper_triangular=False):
+    """
+    Plot the transition matrix of a Markov chain, one unit square per element centred on ``(i + 1, j + 1)``, and return
+    the axis.
+
+    :param axis: A ``matplotlib.pyplot`` axis object on which the matrix will be plotted.  If not specified, a new
+        axis is created for the plot.
+    :param matrix: A 2D ``numpy.ndarray`` of the transition probabilities, which should be in the range [0, 1].
+    :param str colormap: The name of a colormap in ``matplotlib.colormaps``; any other name warns and draws viridis.
+    :param bool exclude_diagonal: If ``True`` the diagonal of the matrix is not plotted.
+    :param bool upper_triangular: If ``True`` only the elements with ``i <= j`` are plotted.
+    """
+    if type(matrix) is not np.ndarray:
+        raise TypeError(msg.transition_matrix_type())
+    if len(matrix.shape) != 2:
+        raise ValueError(msg.transition_matrix_ndim())
+    if matrix.shape[0] != matrix.shape[1]:
+        raise ValueError(msg.transition_matrix_square())
+    if matrix.shape[0] == 1:
+        raise ValueError(msg.transition_matrix_size())
+
+    import matplotlib.pyplot as plt
+    from matplotlib import colormaps, patheffects
+    from matplotlib.collections import PatchCollection
+    from matplotlib.patches import Rectangle
+
+    N = matrix.shape[0]
+    cells = [(i, j) for i in range(N) for j in range(N)
+             if (i <= j or not upper_triangular) and (i != j or not exclude_diagonal)]
+    first = [i for i, _ in cells]
+    second = [j for _, j in cells]
+
+    if colormap in colormaps:
+        cmap = colormaps[colormap]
+    else:
+        cmap = colormaps["viridis"]
+        warn(msg.matrix_plot_colormap(colormap))
+
+    top = matrix.max()
+    squares = PatchCollection([Rectangle((i + 0.5, j + 0.5), 1, 1) for i, j in cells],
+                              facecolors=[cmap(matrix[i, j] / top) for i, j in cells], edgecolors=["black"] * N)
+    if axis is None:
+        _, axis = plt.subplots()
+    axis.add_collection(squares)
+    axis.set_xlim([min(first) + 0.5, max(first) + 1.5])
+    axis.set_ylim([min(second) + 0.5, max(second) + 1.5])
+
+    if N < 11:  # the rates as text, white with a black outline, while they are still legible
+        outline = [patheffects.Stroke(linewidth=1.5, foreground="black"), patheffects.Normal()]
+        for i, j in cells:
+            label = axis.text(i + 1, j + 1, "{}%".format(int(matrix[i, j] * 100)), horizontalalignment="center",
+                              verticalalignment="center", color="white", fontsize=20 - N)
+            label.set_path_effects(outline)
+    return axis
