@@ -673,18 +673,29 @@ class GpRegressor:
         grad[self.cov_slice] = g_cov
         return lml, grad
 
-    def marginal_likelihood_gradient_batch(self, thetas: ndarray):
+    def marginal_likelihood_gradient_batch(self, thetas: ndarray, failed: str = "raise"):
         """(extension) `marginal_likelihood_gradient` for T hyper-parameter vectors in one device call
         (gpmi_lml_grad_batch: for N <= 4096 the evaluations advance in lockstep, every launch carrying all of them):
-        returns (lml (T,), grad (T, P)).  What the lockstep multi-start search evaluates per round."""
+        returns (lml (T,), grad (T, P)).  What the lockstep multi-start search and `advance_lockstep_hmc` evaluate per
+        round.  A vector whose matrix is not positive definite raises LinAlgError for the whole batch, as the single
+        evaluation does; with `failed="sentinel"` such a row gets the -1e50 of `marginal_likelihood` and a zero gradient
+        instead (one warning per call), and the other rows keep their values."""
+        if failed not in ("raise", "sentinel"):
+            raise ValueError("'failed' must be \"raise\" or \"sentinel\"")
         thetas = np.atleast_2d(np.asarray(thetas, dtype=float))
         if self._mix is not None and not self._generic and self._het_slice is None:
-            return self._mixture_gradient_batch(thetas)  # (round 4: gpmi_lml_grad_batch_mix; any number of regions: round 5)
+            # (round 4: gpmi_lml_grad_batch_mix; any number of regions: round 5)
+            return self._failed_rows(*self._mixture_gradient_batch(thetas), failed)
         # a mixture with per-point noise on top, or per-point noise beside a dense y_cov (gpmi_lml_grad_batch_noise
         # carries diagonals only - the condition of _lockstep_search): one at a time
         if self._generic or self._mix is not None or (self._het_slice is not None and self._y_cov is not None):
-            res = [self.marginal_likelihood_gradient(t) for t in thetas]
-            return np.array([r[0] for r in res]), np.array([r[1] for r in res])
+            lml, grads, info = np.zeros(len(thetas)), zeros((len(thetas), self.n_hyperpars)), np.zeros(len(thetas), dtype=int)
+            for t, theta in enumerate(thetas):
+                try:
+                    lml[t], grads[t] = self.marginal_likelihood_gradient(theta)
+                except LinAlgError:
+                    info[t] = 1
+            return self._failed_rows(lml, grads, info, failed)
         th = np.array([np.ascontiguousarray(t[self.cov_slice][self._stat_slice]) for t in thetas])
         ex = np.array([float(np.exp(2 * t[self.cov_slice][self._wn_index])) if self._wn_index is not None else 0.0
                        for t in thetas])
@@ -699,7 +710,7 @@ class GpRegressor:
                                                                                         **mean_kw)
         else:
             lml, g_stat, trace_q, alpha, info = self.engine.lml_grad_batch(self._kernel_id, th, ex, **mean_kw)
-        if (info != 0).any():
+        if failed == "raise" and (info != 0).any():
             raise LinAlgError("Matrix is not positive definite")  # regression.py:555 has no guard
         grads = zeros((len(thetas), self.n_hyperpars))
         for t in range(len(thetas)):
@@ -711,6 +722,20 @@ class GpRegressor:
             if qdiag is not None:  # dK/d ln sigma_i = 2 sigma_i^2 e_i e_i^T (covariance.py:682-686)
                 g_cov[self._het_slice] = np.exp(2 * thetas[t][self.cov_slice][self._het_slice]) * qdiag[t]
             grads[t, self.cov_slice] = g_cov
+        return self._failed_rows(lml, grads, info, failed)
+
+    @staticmethod
+    def _failed_rows(lml, grads, info, failed):
+        """The result of a gradient batch whose rows with info != 0 did not factorise: LinAlgError, or
+        (`failed="sentinel"`) -1e50 and a zero gradient in those rows and one warning."""
+        bad = np.asarray(info) != 0
+        if bad.any():
+            if failed == "raise":
+                raise LinAlgError("Matrix is not positive definite")  # regression.py:555 has no guard
+            warn("Cholesky decomposition failure in marginal_likelihood_gradient_batch")
+            lml, grads = np.array(lml, dtype=float), np.array(grads, dtype=float)
+            lml[bad] = -1e50
+            grads[bad] = 0.0
         return lml, grads
 
     def _mixture_gradient(self, theta_cp, extra, mu):
@@ -749,8 +774,6 @@ class GpRegressor:
             kernels, [a[1] for a in args], np.array([a[2] for a in args]), ex, want_qdiag=self._wn_index is not None,
             row_weights=np.array([w_[0] for w_ in win]), **mean_kw)
         self._mix_fit_stale = True
-        if (info != 0).any():
-            raise LinAlgError("Matrix is not positive definite")  # regression.py:555 has no guard
         grads = zeros((T, self.n_hyperpars))
         for t in range(T):
             g_cp = zeros(cp.n_params)
@@ -762,7 +785,7 @@ class GpRegressor:
             if self._wn_index is not None:
                 g_cov[self._wn_index] = ex[t] * float(qdiag[t].sum())
             grads[t, self.cov_slice] = g_cov
-        return lml, grads
+        return lml, grads, info
 
     def _mixture_loo_gradient_batch(self, thetas):
         """`loo_likelihood_gradient` of a ChangePoint model (any number of regions) for T hyper-parameter vectors in one device call

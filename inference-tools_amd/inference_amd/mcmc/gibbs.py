@@ -8,7 +8,7 @@ with proposal widths tuned towards a 50 % acceptance rate.
 
 Provided: what `ParallelTempering` needs (`inv_temp`, `take_step`, `get_last`,
 `replace_last`, `probs`, sample access, boundaries) and the reference's read-out
-of results (base.py:75-160, gibbs.py:370-377): `get_marginal` (a device
+of results (base.py:75-160, gibbs.py:370-377; shared with `HamiltonianChain` through `MarkovChain`): `get_marginal` (a device
 `GaussianKDE` of one parameter), `get_interval`, `mode`, `matrix_plot` and
 `trace_plot` (base.py:162-216, over `inference_amd.plotting`), and the check that
 comes before them (gibbs.py:405-519, :577-592): `estimate_burn_in`, `diagnostics_data`
@@ -24,8 +24,10 @@ and one-by-one execution produce identical trajectories.
 from copy import copy
 
 import numpy as np
-from numpy import argmax, array, exp, float64, isfinite, log, sqrt
-from numpy.random import default_rng, permutation
+from numpy import argmax, array, exp, float64, log, sqrt
+from numpy.random import default_rng
+
+from inference_amd.mcmc.base import MarkovChain
 
 
 class Parameter:
@@ -115,7 +117,7 @@ class Parameter:
         self.try_count = 0
 
 
-class GibbsChain:
+class GibbsChain(MarkovChain):
     """
     :param posterior: callable `theta (ndarray) -> float` log-probability
         (e.g. `GpRegressor.marginal_likelihood`).
@@ -138,23 +140,6 @@ class GibbsChain:
         self.n_parameters = len(start)
         self.probs = [self.posterior(self.get_last()) * self.inv_temp]
         self.display_progress = display_progress
-
-    def _validate_posterior(self, posterior, start):
-        """base.py:266-296."""
-        name = self.__class__.__name__
-        if not callable(posterior):
-            raise ValueError(f"\n[ {name} error ]\n>> The given 'posterior' is not a callable object.")
-        prob = posterior(start)
-        if not isinstance(prob, float):
-            raise ValueError(
-                f"\n[ {name} error ]\n>> The given 'posterior' must return a float or a type which derives "
-                f"from float, however the returned value has type:\n>> {type(prob)}"
-            )
-        if not isfinite(prob):
-            raise ValueError(
-                f"\n[ {name} error ]\n>> The given 'posterior' must return a finite value for the given "
-                f"'start' parameter values, but instead returns a value of:\n>> {prob}"
-            )
 
     # -- stepping ----------------------------------------------------------------------
     def take_step(self):
@@ -206,72 +191,11 @@ class GibbsChain:
     def get_sample(self, burn: int = 1, thin: int = 1):
         return array([self.get_parameter(i, burn=burn, thin=thin) for i in range(self.n_parameters)]).T
 
-    # -- results (reference: base.py:75-160, gibbs.py:370-377) ------------------------------
-    def get_marginal(self, index: int, burn: int = 1, thin: int = 1, unimodal=False):
-        """Estimate of the 1D marginal distribution of parameter `index`: a `GaussianKDE` of
-        `get_parameter(index, burn, thin)`.  `unimodal=True` (a `UnimodalPdf` in the reference) is not provided."""
-        from inference_amd.pdf import GaussianKDE
-        from inference_amd.pdf._messages import marginal_unimodal
-
-        if unimodal:
-            raise NotImplementedError(marginal_unimodal())
-        return GaussianKDE(self.get_parameter(index, burn=burn, thin=thin))
-
-    def get_interval(self, interval: float = 0.95, burn: int = 1, thin: int = 1, samples: int = None):
-        """The samples in the highest-probability fraction `interval` of the chain, ordered by increasing
-        log-probability, and their log-probabilities.  `samples` overrides `thin`.  As in the reference, the trim to
-        `samples` draws `numpy.random.permutation` and then indexes with the None that `ndarray.sort()` returns: no
-        sample is removed and both arrays gain a leading axis of length 1."""
-        probs = self.get_probabilities(burn=burn)
-        if samples is not None:
-            thin = max(probs.size // samples, 1)
-
-        sample = self.get_sample(burn=burn, thin=thin)
-        probs = probs[::thin]
-
-        sorter = probs.argsort()
-        sample = sample[sorter, :]
-        probs = probs[sorter]
-        # trim the lowest-probability samples
-        cutoff = int(probs.size * (1 - interval))
-        sample = sample[cutoff:, :]
-        probs = probs[cutoff:]
-
-        if samples is not None:
-            n_trim = probs.size - samples
-            if n_trim > 0:
-                subsample = permutation(probs.size)[n_trim:].sort()
-                sample = sample[subsample, :]
-                probs = probs[subsample]
-
-        return sample, probs
-
+    # -- results: `get_marginal`, `get_interval`, `matrix_plot` and `trace_plot` come from `MarkovChain` ------------------
     def mode(self):
         """The sample with the highest log-probability so far."""
         ind = argmax(self.probs)
         return array([p.samples[ind] for p in self.params])
-
-    def matrix_plot(self, params=None, burn: int = 0, thin: int = 1, **kwargs):
-        """The matrix plot of the parameters (or of those whose indices `params` lists): all 1D and 2D marginal
-        distributions of the samples left after `burn` and `thin`.  The other keyword arguments are those of
-        `inference_amd.plotting.matrix_plot`, whose figure is returned (the reference returns None)."""
-        from inference_amd.plotting import matrix_plot
-
-        self._plot_checks(burn, thin, "matrix")
-        params = params if params is not None else range(self.n_parameters)
-        samples = [self.get_parameter(i, burn=burn, thin=thin) for i in params]
-        return matrix_plot(samples, **kwargs)
-
-    def trace_plot(self, params=None, burn: int = 0, thin: int = 1, **kwargs):
-        """The trace plot of the parameters (or of those whose indices `params` lists): the value of each as a function
-        of the step number, for the samples left after `burn` and `thin` (base.py:191-216).  The other keyword arguments
-        are those of `inference_amd.plotting.trace_plot`, whose figure is returned (the reference returns None)."""
-        from inference_amd.plotting import trace_plot
-
-        self._plot_checks(burn, thin, "trace")
-        params = params if params is not None else range(self.n_parameters)
-        samples = [self.get_parameter(i, burn=burn, thin=thin) for i in params]
-        return trace_plot(samples, **kwargs)
 
     # -- diagnostics (reference: gibbs.py:405-519, :577-592) -----------------------------------
     def estimate_burn_in(self) -> int:
@@ -367,17 +291,6 @@ class GibbsChain:
         if show:
             plt.show()
         return fig
-
-    def _plot_checks(self, burn: int, thin: int, plot_type: str):
-        """base.py:218-237."""
-        from inference_amd.pdf._messages import plot_burn_thin, plot_no_samples
-
-        name = self.__class__.__name__
-        if self.chain_length < 2:
-            raise ValueError(plot_no_samples(name, plot_type, self.chain_length))
-        reduced_length = max(self.chain_length - burn - 1, 0) // thin + 1
-        if reduced_length < 2:
-            raise ValueError(plot_burn_thin(name, plot_type, reduced_length))
 
     def set_non_negative(self, parameter: int, flag=True):
         self.params[parameter].non_negative = flag

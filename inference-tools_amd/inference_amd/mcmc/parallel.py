@@ -28,6 +28,8 @@ from numpy import arange, array, exp, identity, triu, zeros
 from numpy.random import default_rng
 
 from inference_amd.mcmc.gibbs import advance_lockstep
+from inference_amd.mcmc.hmc import HamiltonianChain, advance_lockstep_hmc
+from inference_amd.pdf._messages import ladders_are_gibbs
 
 
 def _common_batch_posterior(chains):
@@ -54,9 +56,12 @@ class ParallelTempering:
     :param chains: chain objects (e.g. `GibbsChain`) sorted by increasing temperature.
     :param batch_posterior: optional `thetas (B, P) -> (B,)` batched form of the chains'
         posterior; detected automatically for `GpRegressor.marginal_likelihood`.
+    :param batch_value_and_grad: optional `thetas (B, P) -> (values (B,), grads (B, P))`, the un-tempered posterior
+        and its gradient (e.g. `GpRegressor.marginal_likelihood_gradient_batch`): a ladder of `HamiltonianChain`
+        objects then advances through `advance_lockstep_hmc`, one batched evaluation per leapfrog round.
     """
 
-    def __init__(self, chains, batch_posterior=None):
+    def __init__(self, chains, batch_posterior=None, batch_value_and_grad=None):
         self.rng = default_rng()
         # pairing uses the stdlib generator (the module-level `random.choice`, parallel.py:172); a ladder that must
         # not share that global stream with other ladders (sharded runs) gets its own `random.Random(seed).choice`
@@ -67,7 +72,10 @@ class ParallelTempering:
         self.N_chains = len(self.chains)
         self.attempted_swaps = identity(self.N_chains)
         self.successful_swaps = zeros([self.N_chains, self.N_chains])
-        self.batch_posterior = batch_posterior or _common_batch_posterior(self.chains)
+        hmc = [isinstance(chain, HamiltonianChain) for chain in self.chains]
+        # (the batched LML alone serves Gibbs proposals; a HamiltonianChain needs values AND gradients)
+        self.batch_posterior = None if any(hmc) else batch_posterior or _common_batch_posterior(self.chains)
+        self.batch_value_and_grad = batch_value_and_grad if all(hmc) else None
         self.posterior_evaluations = 0
         if sorted(self.temperatures) != self.temperatures:
             warn(
@@ -79,7 +87,9 @@ class ParallelTempering:
 
     def take_steps(self, n: int):
         """Advance all the chains `n` steps without performing any swaps."""
-        if self.batch_posterior is not None:
+        if self.batch_value_and_grad is not None:
+            self.posterior_evaluations += advance_lockstep_hmc(self.chains, n, self.batch_value_and_grad)
+        elif self.batch_posterior is not None:
             self.posterior_evaluations += advance_lockstep(self.chains, n, self.batch_posterior)
         else:
             for chain in self.chains:
@@ -231,6 +241,8 @@ def advance_ladders(ladders, n: int, swap_interval=10, batch_posterior=None):
     parallel.py:172 share ONE stream; for those every swap point stays a common one and the swaps are made in ladder
     order, as before.)
     Returns the number of posterior evaluations made."""
+    if any(isinstance(c, HamiltonianChain) for lad in ladders for c in lad.chains):
+        raise TypeError(ladders_are_gibbs())
     bp = batch_posterior or ladders[0].batch_posterior
     if bp is None:
         raise ValueError("advance_ladders needs a batched posterior")

@@ -1,7 +1,7 @@
-"""Chain diagnostics (reference: mcmc/utilities.py:83-95).  `effective_sample_size` is the host function with the
-reference's exact semantics; `effective_sample_size_batch` answers every column of a sample in one device call
-(csrc/acf.hip)."""
-from numpy import asarray, empty, float64, int64, ndarray
+"""Chain diagnostics (reference: mcmc/utilities.py:83-95) and parameter bounds (:98-162).  `effective_sample_size` is
+the host function with the reference's exact semantics; `effective_sample_size_batch` answers every column of a sample
+in one device call (csrc/acf.hip).  `Bounds` holds the box a `HamiltonianChain` is reflected into."""
+from numpy import array, asarray, divmod as np_divmod, empty, float64, int64, ndarray
 from numpy.fft import irfft, rfft
 
 from inference_amd.pdf import _device
@@ -57,3 +57,48 @@ def effective_sample_size_batch(sample, *, device=None, details=False):
         else:
             ess[c] = int(n / (total[c] / f0[c]))
     return (ess, f0, total, cut) if details else ess
+
+
+class Bounds:
+    """
+    Lower and upper limits of every parameter, and the reflection of points that left them.
+
+    :param lower: one-dimensional array of lower limits.
+    :param upper: one-dimensional array of upper limits, each above its lower limit.
+    :param error_source: the name that the error messages carry.
+    """
+
+    def __init__(self, lower, upper, error_source="Bounds"):
+        self.lower = lower if isinstance(lower, ndarray) else array(lower).squeeze()
+        self.upper = upper if isinstance(upper, ndarray) else array(upper).squeeze()
+        if self.lower.ndim > 1 or self.upper.ndim > 1:
+            raise ValueError(msg.bounds_not_1d(error_source, self.lower.ndim, self.upper.ndim))
+        if self.lower.size != self.upper.size:
+            raise ValueError(msg.bounds_sizes(error_source, self.lower.size, self.upper.size))
+        if (self.lower >= self.upper).any():
+            raise ValueError(msg.bounds_order(error_source))
+        self.width = self.upper - self.lower
+        self.n_bounds = self.width.size
+
+    def validate_start_point(self, start: ndarray, error_source="Bounds"):
+        if self.n_bounds != start.size:
+            raise ValueError(msg.bounds_start_size(error_source, start.size, self.n_bounds))
+        if not self.inside(start):
+            raise ValueError(msg.bounds_start_outside(error_source))
+
+    def _fold(self, theta):
+        """A triangle wave of period 2 width: the point after as many reflections as it takes, and the sign (+1 or -1)
+        that the reflections leave on the velocity along each axis."""
+        bounces, inside = np_divmod(theta - self.lower, self.width)
+        odd = bounces % 2
+        sign = 1 - 2 * odd
+        return self.lower + sign * inside + odd * self.width, sign
+
+    def reflect(self, theta: ndarray) -> ndarray:
+        return self._fold(theta)[0]
+
+    def reflect_momenta(self, theta: ndarray):
+        return self._fold(theta)
+
+    def inside(self, theta: ndarray) -> bool:
+        return ((theta >= self.lower) & (theta <= self.upper)).all()

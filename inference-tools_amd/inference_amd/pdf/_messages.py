@@ -1,6 +1,6 @@
 """Error / warning texts of the density estimators, of the matrix plot and of the chains' plot checks.  The wording, line
 breaks and indentation follow the reference (pdf/kde.py:53-60, pdf/base.py:41-48, pdf/hdi.py:27-91, plotting.py:91-135,
-plotting.py:331-333, plotting.py:416-434, plotting.py:481-518, mcmc/base.py:218-237, mcmc/utilities.py:90) so that callers that match on messages keep working; the KDE2D texts are this package's own (the
+plotting.py:331-333, plotting.py:416-434, plotting.py:481-518, mcmc/base.py:218-237, mcmc/utilities.py:90, :98-148, mcmc/hmc/mass.py, mcmc/hmc/__init__.py:152-157) so that callers that match on messages keep working; the KDE2D texts are this package's own (the
 reference has none)."""
 
 
@@ -50,8 +50,8 @@ def hdi_inaccurate() -> str:
                    "n_samples * (1 - fraction) is small - calculated interval may be inaccurate.")
 
 
-def marginal_unimodal() -> str:
-    return ("\n\n[ GibbsChain error ]\n>> unimodal=True asks for a UnimodalPdf, which get_marginal does not build here:"
+def marginal_unimodal(owner: str = "GibbsChain") -> str:
+    return (f"\n\n[ {owner} error ]\n>> unimodal=True asks for a UnimodalPdf, which get_marginal does not build here:"
             "\n>> use inference_amd.pdf.UnimodalPdf(chain.get_parameter(index, burn, thin)),"
             "\n>> or the default GaussianKDE marginal (unimodal=False).\n")
 
@@ -134,3 +134,60 @@ def transition_matrix_square() -> str:
 
 def transition_matrix_size() -> str:
     return "given matrix must be at least of size 2x2"
+
+
+def bounds_not_1d(owner: str, lower_ndim, upper_ndim) -> str:
+    return _framed(16, owner, "error", "Lower and upper bounds must be one-dimensional arrays, but",
+                   f"instead have dimensions {lower_ndim} and {upper_ndim} respectively.")
+
+
+def bounds_sizes(owner: str, lower_size, upper_size) -> str:
+    return _framed(16, owner, "error", "Lower and upper bounds must be arrays of equal size, but",
+                   f"instead have sizes {lower_size} and {upper_size} respectively.")
+
+
+def bounds_order(owner: str) -> str:
+    return _framed(16, owner, "error", "All given upper bounds must be larger than the corresponding lower bounds.")
+
+
+def bounds_start_size(owner: str, start_size, n_bounds) -> str:
+    return _framed(16, owner, "error", f"The number of parameters ({start_size}) does not",
+                   f"match the given number of bounds ({n_bounds}).")
+
+
+def bounds_start_outside(owner: str) -> str:
+    return _framed(16, owner, "error", "Starting location for the chain is outside specified bounds.")
+
+
+def vector_mass(n_parameters) -> str:
+    return _framed(16, "VectorMass", "error", "The inverse-mass vector must be a 1D array and have size",
+                   f"equal to the given number of model parameters ({n_parameters})", "and contain only positive values.")
+
+
+def matrix_mass_covariance() -> str:
+    return _framed(16, "MatrixMass", "error", "The given inverse-mass matrix must be a valid covariance matrix,",
+                   "i.e. 2 dimensional, square and symmetric.")
+
+
+def matrix_mass_size(shape, n_parameters) -> str:
+    return _framed(16, "MatrixMass", "error", f"The dimensions of the given inverse-mass matrix {shape}",
+                   f"do not match the given number of model parameters ({n_parameters}).")
+
+
+def inverse_mass_type(kind) -> str:
+    return _framed(12, "HamiltonianChain", "error", "The value given to the 'inverse_mass' keyword argument must be either",
+                   "a scalar type (e.g. int or float), or a numpy.ndarray.", "Instead, the given value has type:", f"{kind}")
+
+
+def hmc_attempts(max_attempts) -> str:
+    return _framed(16, "HamiltonianChain", "error", f"Failed to take step within maximum allowed attempts of {max_attempts}")
+
+
+def lockstep_needs_gradient() -> str:
+    return ("advance_lockstep_hmc needs chains that were given an analytic 'grad': a chain that estimates its gradient by "
+            "finite differences (grad=None) makes P + 1 posterior calls per gradient and is advanced with take_step")
+
+
+def ladders_are_gibbs() -> str:
+    return ("advance_ladders drives GibbsChain ladders; advance a ladder of HamiltonianChain objects with "
+            "ParallelTempering(chains, batch_value_and_grad=...), which uses advance_lockstep_hmc")
