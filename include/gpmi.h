@@ -572,14 +572,22 @@ int gpmi_profile_reset(gpmi_ctx* ctx);
 int gpmi_profile_clock(gpmi_ctx* ctx, double* ghz);
 
 /* ---- device-pointer entry points (kernel tests / micro-benchmarks) -------------------
- * Matrices are row-major with leading dimension ld (multiple of 128); n multiple of 128. */
+ * Matrices are row-major with a leading dimension ld of at least the row length and a multiple of 32 (the library's own
+ * matrices have ld = n + 32, off a power-of-two pitch); m, n multiples of 128.  tests/test_kernels_gpu.py holds both entry
+ * points to exact results on integer data, in the whole buffer. */
 int gpmi_dev_alloc(gpmi_ctx* ctx, int64_t bytes, void** ptr_dev);
 int gpmi_dev_free(gpmi_ctx* ctx, void* ptr_dev);
 int gpmi_dev_upload(gpmi_ctx* ctx, void* dst_dev, const void* src_host, int64_t bytes);
 int gpmi_dev_download(gpmi_ctx* ctx, void* dst_host, const void* src_dev, int64_t bytes);
-/* in-place lower Cholesky of the n x n matrix at A_dev (upper triangle untouched) */
+/* in-place lower Cholesky of the n x n matrix at A_dev, of which only the tiles on and below the diagonal are read.  Untouched: the
+ * columns from n on, every 128 x 128 tile strictly above the diagonal, and the part of tile (0, 0) above the diagonal.
+ * The part above the diagonal inside the other diagonal tiles is workspace: the trailing updates write whole diagonal
+ * tiles (or their two diagonal 64 x 64 quarters), so it returns holding intermediate values of theirs. */
 int gpmi_dev_potrf(gpmi_ctx* ctx, double* A_dev, int64_t n, int64_t ld, int* info);
-/* C (m x n, lower tiles only if lower != 0) -= A (m x k) * B (n x k)^T */
+/* C (m x n, lower tiles only if lower != 0) -= A (m x k) * B (n x k)^T; k a multiple of 16, A and B may be one buffer.
+ * lower != 0 (m >= n): every element on or below the diagonal is updated and no 128 x 128 tile strictly above it is
+ * touched; above the diagonal inside a diagonal tile an element is either updated or left as it was (the 128 x 128
+ * kernels update the whole tile, the 64 x 64 kernels its two diagonal quarters). */
 int gpmi_dev_gemm_nt(gpmi_ctx* ctx, double* C_dev, int64_t ldc, const double* A_dev, int64_t lda,
                      const double* B_dev, int64_t ldb, int64_t m, int64_t n, int64_t k, int lower);
 
