@@ -177,6 +177,25 @@ int gpmi_lml_grad_batch(gpmi_ctx* ctx, int kernel, int64_t T, const double* thet
  */
 int gpmi_predict(gpmi_ctx* ctx, const double* pts_host, int64_t m, double* mu_host,
                  double* var_host);
+/* Prediction under T hyper-parameter vectors at once, and its mixture (an addition: the reference predicts under one
+ * fitted theta).  For row t of thetas, gpmi_predict's values after a gpmi_fit at that row:
+ *   mean_t[t][q] = k_t(q, x) . alpha_t + mu_q[t][q]   (mu_q NULL: + mu_const[t])
+ *   var_t[t][q]  = | a_t^2 - |L_t^-1 k_t(x, q)|^2 |   (the square of the reference's sqrt(abs(.)), regression.py:216)
+ * and over the rows that factorised, with weights w_t (weights_host NULL: equal), in two passes (law of total variance):
+ *   mix_mean[q] = sum_t w_t mean_t[t][q],   mix_var[q] = sum_t w_t (var_t[t][q] + (mean_t[t][q] - mix_mean[q])^2).
+ * thetas / extra / mus | mu_const as gpmi_lml_grad_batch; pts: m x d; weights: T finite values >= 0 with a positive sum.
+ * mean_t, var_t (T x m) and mix_mean, mix_var (m) may each be NULL; with var_t and mix_var both NULL no variance is
+ * computed.  A row that does not factorise gets info[t] != 0 and NaN in mean_t / var_t and is left out of the mixture:
+ * the other rows' weights are divided by their sum (equal weights: 1 / number of good rows); no good row: NaN mixtures,
+ * GPMI_OK.  Lockstep sizes only (padded n <= 4096, diagonal data errors; SE, RQ, GPMI_KERNEL_SUM): every launch carries
+ * a chunk of rows, also for T = 1, so a row's values do not depend on the batch it is in; the sums over t run as a
+ * pairwise tree over the good rows in order, so they depend on T and the failures alone.  The points are processed in
+ * panels of GPMI_PREDICT_PANEL rows.  The fitted state of gpmi_fit is not touched. */
+#define GPMI_PREDICT_PANEL 256
+int gpmi_predict_batch(gpmi_ctx* ctx, int kernel, int64_t T, const double* thetas_host, int n_theta,
+                       const double* extra_diag_host, const double* mus_host, const double* mu_const_host,
+                       const double* pts_host, int64_t m, const double* mu_q_host, const double* weights_host,
+                       double* mean_t_host, double* var_t_host, double* mix_mean_host, double* mix_var_host, int* info);
 /* Replaces GpRegressor.build_posterior (regression.py:421-449): mu (m) and
  * Sigma = K_qq - Q^T Q (m x m), Q = L^-1 K_qx^T.  cov_host may be NULL (mean_only). */
 int gpmi_posterior(gpmi_ctx* ctx, const double* pts_host, int64_t m, double* mu_host,

@@ -222,6 +222,8 @@ void free_data(gpmi_ctx* c) {
   fr(c->bGws);  //  another size kept using the first one's)
   fr(c->bGout);
   fr(c->bLoo);
+  fr(c->bQ);
+  c->bQ_cap = 0;
   fr(c->bNoise);
   fr(c->bMixG);
   fr(c->bMixH);
@@ -488,6 +490,8 @@ int ensure_batch_ws(gpmi_ctx* c, int want) {
   fr(c->bGws);
   fr(c->bGout);
   fr(c->bLoo);
+  fr(c->bQ);
+  c->bQ_cap = 0;
   fr(c->bNoise);
   fr(c->bMixG);
   fr(c->bMixH);

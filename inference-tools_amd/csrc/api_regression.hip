@@ -677,6 +677,216 @@ int gpmi_predict(gpmi_ctx* c, const double* pts, int64_t m, double* mu_out, doub
   return GPMI_OK;
 }
 
+extern "C++" {
+namespace {
+// device memory of one call
+struct DevBuf {
+  void* p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+  template <class T>
+  T* as() const {
+    return static_cast<T*>(p);
+  }
+};
+
+// sum of v[0 .. n) as the pairwise tree of predict_batch.hip (halves split at the largest power of two below n)
+double tree_sum_host(const double* v, int64_t n) {
+  if (n <= 0) return 0.0;
+  if (n == 1) return v[0];
+  int64_t h = 1;
+  while (2 * h < n) h *= 2;
+  return tree_sum_host(v, h) + tree_sum_host(v + h, n - h);
+}
+}  // namespace
+}  // extern "C++"
+
+// Prediction under T hyper-parameter vectors and its mixture (include/gpmi.h).  Per chunk of rows, in lockstep on the two
+// half-batch streams (as gpmi_lml_batch; chunks capped as the gradient batches): K(theta_z), factor, both sweeps -> alpha_z;
+// with a variance L_z^-T by forward substitution on the identity (bB2).  Then per panel of GPMI_PREDICT_PANEL points: the
+// batched cross-covariance K*_z, its row dots with alpha_z, V_z = K*_z L_z^-T by the batched k-major GEMM (contraction
+// ending with the tile column: L^-T is upper triangular; ring_order_only - a value does not depend on the batch it shares)
+// and its row sums of squares; the store kernel files both under the row's place in the T x m arrays of the call.  The
+// mixture runs once, behind the last chunk.  Lanes 1 and 2 carry the streams; lane 0 - the fit - is not touched.
+int gpmi_predict_batch(gpmi_ctx* c, int kernel, int64_t T, const double* thetas, int n_theta, const double* extra,
+                       const double* mus, const double* mu_const, const double* pts, int64_t m, const double* mu_q,
+                       const double* weights, double* mean_t, double* var_t, double* mix_mean, double* mix_var, int* info) {
+  if (!c) return GPMI_ERR_ARG;
+  ARGCHK(c, T >= 1 && T <= RED_SLOTS, "T out of range");
+  ARGCHK(c, thetas && pts && m > 0, "thetas / pts is NULL or m <= 0");
+  ARGCHK(c, mus || mu_const, "one of mus / mu_const is required");
+  ARGCHK(c, mu_q || mu_const, "one of mu_q / mu_const is required");
+  ARGCHK(c, mean_t || var_t || mix_mean, "no output requested");
+  ARGCHK(c, mix_mean || !mix_var, "mix_var needs mix_mean");
+  ARGCHK(c, c->n > 0, "gpmi_set_data has not been called");
+  ARGCHK(c, c->np <= 4096 && !c->ycov, "gpmi_predict_batch: lockstep sizes only (n <= 4096, diagonal data errors)");
+  ARGCHK(c, T * m <= ((int64_t)1 << 31), "T x m too large");
+  if (weights) {
+    double wsum = 0.0;
+    for (int64_t t = 0; t < T; ++t) {
+      ARGCHK(c, std::isfinite(weights[t]) && weights[t] >= 0.0, "weights must be finite and non-negative");
+      wsum += weights[t];
+    }
+    ARGCHK(c, wsum > 0.0, "weights must have a positive sum");
+  }
+  if (int rc = set_device(c)) return rc;
+  std::vector<KParams> ps;
+  std::vector<CovParams> sps;  // (a sum: its parameters, ps stays empty)
+  if (int rc = make_batch_params(c, kernel, T, thetas, n_theta, extra, ps, sps)) return rc;
+  ARGCHK(c, c->bpend[0] == 0 && c->bpend[1] == 0,
+         "gpmi_predict_batch: an asynchronous batch is pending on this handle (gpmi_lml_batch_wait first)");
+  if (int rc = ensure_lanes(c, 2)) return rc;
+  if (int rc = ensure_batch_ws(c, (int)(T < 64 ? (T < 2 ? 2 : T) : 64))) return rc;
+  if (int rc = ensure_batch_grad_ws(c, c->bcap, n_theta)) return rc;
+  const bool want_var = var_t || mix_var;
+  const int64_t P = GPMI_PREDICT_PANEL;
+  const int64_t sQ = 2 * P * c->ld;  // per problem: the panel K* and, behind it, V = K* L^-T
+  if (c->bQ_cap < c->bgrad_cap) {
+    if (c->bQ) (void)hipFree(c->bQ);
+    c->bQ = nullptr;
+    c->bQ_cap = 0;
+    HIPCHK(c, hipMalloc(&c->bQ, sizeof(double) * sQ * c->bgrad_cap));
+    c->bQ_cap = c->bgrad_cap;
+  }
+  static const bool split_ok = [] {
+    const char* e = std::getenv("GPMI_BATCH_SPLIT");
+    return !e || std::atoi(e) != 0;
+  }();
+  const bool two = split_ok && T >= 16 && ensure_lanes(c, 3) == GPMI_OK;
+  const int cap = c->bgrad_cap;
+  // the call's own device arrays: points, prior means at the points, the T x m results, the mixture's row list
+  DevBuf dPts, dPrior, dMean, dVar, dSq, dIdx, dW, dMix;
+  HIPCHK(c, hipMalloc(&dPts.p, sizeof(double) * m * c->d));
+  HIPCHK(c, hipMalloc(&dPrior.p, sizeof(double) * (mu_q ? T * m : T)));
+  HIPCHK(c, hipMalloc(&dMean.p, sizeof(double) * T * m));
+  if (want_var) {
+    HIPCHK(c, hipMalloc(&dVar.p, sizeof(double) * T * m));
+    HIPCHK(c, hipMalloc(&dSq.p, sizeof(double) * P * cap));
+  }
+  HIPCHK(c, hipMemcpy(dPts.p, pts, sizeof(double) * m * c->d, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dPrior.p, mu_q ? mu_q : mu_const, sizeof(double) * (mu_q ? T * m : T), hipMemcpyHostToDevice));
+  HIPCHK(c, hipStreamSynchronize(nullptr));  // (the lanes' streams do not wait for the null stream)
+  const int nt = (int)(c->np / GPMI_NB);
+  const BatchShape shape0{1, c->np * c->ld, (c->np / GPMI_NB) * GPMI_NB * GPMI_NB, 4 * c->np};
+  const bool sum = !sps.empty();
+  auto enqueue = [&](hipStream_t s, int64_t t_first, int off, int B) -> int {
+    BatchShape bs = shape0;
+    bs.count = B;
+    double* A = c->bA + (int64_t)off * bs.sMat;
+    double* Inv = c->bInv + (int64_t)off * bs.sInv;
+    double* Vec = c->bVec + (int64_t)off * bs.sVec;
+    double* Mu = c->bMu + (int64_t)off * (mus ? c->n : 1);
+    double* B2 = c->bB2 + (int64_t)off * bs.sMat;
+    double* Q = c->bQ + (int64_t)off * sQ;
+    double* V = Q + P * c->ld;
+    if (sum)
+      HIPCHK(c, hipMemcpyAsync(c->bSum + off, sps.data() + t_first, sizeof(CovParams) * B, hipMemcpyHostToDevice, s));
+    else
+      HIPCHK(c, hipMemcpyAsync(c->bParams + off, ps.data() + t_first, sizeof(KParams) * B, hipMemcpyHostToDevice, s));
+    if (mus)
+      HIPCHK(c, hipMemcpyAsync(Mu, mus + t_first * c->n, sizeof(double) * B * c->n, hipMemcpyHostToDevice, s));
+    else
+      HIPCHK(c, hipMemcpyAsync(Mu, mu_const + t_first, sizeof(double) * B, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(c->bInfo + off, 0, sizeof(int) * B, s));
+    if (sum)
+      launch_kbuild_square_batched(s, c->bSum + off, B, c->x, c->n, c->np, c->noise, A, c->ld, bs.sMat, (int)c->d);
+    else
+      launch_kbuild_square_batched(s, kernel, c->bParams + off, B, c->x, c->n, c->np, c->noise, A, c->ld, bs.sMat,
+                                   (int)c->d);
+    potrf_lower_batched(c, s, A, c->np, c->ld, Inv, c->bInfo + off, bs);
+    launch_residual_batched(s, c->y, mus ? Mu : nullptr, mus ? nullptr : Mu, Vec + 2 * c->np, c->n, c->np, bs);
+    trsv_forward(c, s, A, c->np, c->ld, Inv, Vec + 2 * c->np, Vec, c->bInfo + off, bs);
+    double* alpha_dev = Vec + c->np;  // slot 1 of every problem's four work vectors
+    trsv_backward(c, s, A, c->np, c->ld, Inv, Vec, alpha_dev, c->bInfo + off, bs);
+    if (want_var) trsm_identity_batched(s, A, c->np, c->ld, Inv, B2, bs);
+    // slots 2 and 3 (2 np >= GPMI_PREDICT_PANEL doubles; the residual is spent) take a panel's row dots: launch_rows_dot
+    // strides its output like alpha
+    double* dot_dev = Vec + 2 * c->np;
+    double* sq_dev = want_var ? dSq.as<double>() + (int64_t)off * P : nullptr;
+    GemmBatch gb{B, sQ, sQ, bs.sMat};
+    gb.ring_order_only = true;
+    for (int64_t m0 = 0; m0 < m; m0 += P) {
+      const int64_t mc = (m - m0 < P) ? m - m0 : P;
+      const int64_t mp = round_up(mc, GPMI_NB);
+      const double* U = dPts.as<double>() + m0 * c->d;
+      if (sum)
+        launch_kbuild_cross_batched(s, c->bSum + off, B, U, mc, mp, c->x, c->n, c->np, Q, c->ld, sQ, (int)c->d);
+      else
+        launch_kbuild_cross_batched(s, kernel, c->bParams + off, B, U, mc, mp, c->x, c->n, c->np, Q, c->ld, sQ, (int)c->d);
+      launch_rows_dot(s, Q, c->ld, mc, c->np, alpha_dev, dot_dev, B, sQ, bs.sVec);
+      if (want_var) {
+        launch_gemm(s, TILES_RECT, OP_ASSIGN, true, 2, V, c->ld, Q, c->ld, B2, c->ld, (int)(mp / GPMI_NB), nt, (int)c->np,
+                    nullptr, gb);
+        launch_rows_sumsq(s, V, c->ld, mc, c->np, 0.0, sq_dev, B, sQ, P, -1.0);  // (-(0 - sum): the sum itself)
+      }
+      launch_predict_store(s, B, t_first, m0, mc, m, dot_dev, sq_dev, bs.sVec, P,
+                           sum ? static_cast<const void*>(c->bSum + off) : static_cast<const void*>(c->bParams + off),
+                           (int64_t)(sum ? sizeof(CovParams) : sizeof(KParams)), c->bInfo + off,
+                           mu_q ? dPrior.as<double>() : nullptr, mu_q ? nullptr : dPrior.as<double>(), dMean.as<double>(),
+                           dVar.as<double>());
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->h_bInfo + off, c->bInfo + off, sizeof(int) * B, hipMemcpyDeviceToHost, s));
+    return GPMI_OK;
+  };
+  std::vector<int> inf_all((size_t)T, 0);
+  for (int64_t t0 = 0; t0 < T; t0 += cap) {
+    const int B = (int)((T - t0 < cap) ? T - t0 : cap);
+    const int B1 = (two && B >= 16) ? B / 2 : B;
+    if (int rc = enqueue(c->lanes[1].stream, t0, 0, B1)) return rc;
+    if (B1 < B)
+      if (int rc = enqueue(c->lanes[2].stream, t0 + B1, B1, B - B1)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->lanes[1].stream));
+    if (B1 < B) HIPCHK(c, hipStreamSynchronize(c->lanes[2].stream));
+    for (int b = 0; b < B; ++b) {
+      const int inf = c->h_bInfo[b];
+      INFOCHK(c, inf);
+      inf_all[(size_t)(t0 + b)] = inf;
+      if (info) info[t0 + b] = inf;
+    }
+  }
+  hipStream_t s = c->lanes[1].stream;
+  if (mix_mean) {
+    // the rows that factorised, in order, and their weights divided by their sum (equal weights: 1 / their number)
+    std::vector<int> idx;
+    std::vector<double> w;
+    for (int64_t t = 0; t < T; ++t)
+      if (inf_all[(size_t)t] == 0) {
+        idx.push_back((int)t);
+        w.push_back(weights ? weights[t] : 1.0);
+      }
+    const int64_t G = (int64_t)idx.size();
+    const double wsum = weights ? tree_sum_host(w.data(), G) : (double)G;
+    if (G == 0 || !(wsum > 0.0)) {
+      for (int64_t q = 0; q < m; ++q) {
+        mix_mean[q] = std::nan("");
+        if (mix_var) mix_var[q] = std::nan("");
+      }
+    } else {
+      for (double& v : w) v = weights ? v / wsum : 1.0 / (double)G;
+      HIPCHK(c, hipMalloc(&dIdx.p, sizeof(int) * G));
+      HIPCHK(c, hipMalloc(&dW.p, sizeof(double) * G));
+      HIPCHK(c, hipMalloc(&dMix.p, sizeof(double) * 2 * m));
+      HIPCHK(c, hipMemcpyAsync(dIdx.p, idx.data(), sizeof(int) * G, hipMemcpyHostToDevice, s));
+      HIPCHK(c, hipMemcpyAsync(dW.p, w.data(), sizeof(double) * G, hipMemcpyHostToDevice, s));
+      launch_predict_mix(s, G, dIdx.as<int>(), dW.as<double>(), m, dMean.as<double>(), dVar.as<double>(), dMix.as<double>(),
+                         mix_var ? dMix.as<double>() + m : nullptr);
+      HIPCHK(c, hipGetLastError());
+      HIPCHK(c, hipMemcpyAsync(mix_mean, dMix.p, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+      if (mix_var)
+        HIPCHK(c, hipMemcpyAsync(mix_var, dMix.as<double>() + m, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+    }
+  }
+  if (mean_t) HIPCHK(c, hipMemcpyAsync(mean_t, dMean.p, sizeof(double) * T * m, hipMemcpyDeviceToHost, s));
+  if (var_t) HIPCHK(c, hipMemcpyAsync(var_t, dVar.p, sizeof(double) * T * m, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  return GPMI_OK;
+}
+
 int gpmi_posterior(gpmi_ctx* c, const double* pts, int64_t m, double* mu_out, double* cov_out) {
   if (!c) return GPMI_ERR_ARG;
   ARGCHK(c, c->fitted, "gpmi_posterior needs a successful gpmi_fit");

@@ -175,6 +175,8 @@ struct gpmi_ctx {
   KParams* bMixP = nullptr;
   double* bMixExtra = nullptr;
   int bMix_cap = 0;
+  double* bQ = nullptr;      // gpmi_predict_batch: per problem two panels of GPMI_PREDICT_PANEL x ld (K*, K* L^-T)
+  int bQ_cap = 0;
   double* bLoo = nullptr;    // gpmi_loo_grad_batch: 4 vectors per problem (diag K^-1, c1, sqrt c2, p)
   int bLoo_cap = 0;
   double* bGout = nullptr;   // (n_theta + 1) results per problem
@@ -262,6 +264,27 @@ void launch_kbuild_cross(hipStream_t s, const CovParams& p, const double* U, int
 // launch_kbuild_square_batched
 void launch_kbuild_square_batched(hipStream_t s, const CovParams* pdev, int batch, const double* x, int64_t n,
                                   int64_t np, const double* noise, double* A, int64_t ld, int64_t stride, int d);
+
+// lockstep batch of cross covariances: problem z builds K*_z (mp x ld: the mu valid rows of U against the n valid rows of
+// V, zeros in the padding) from pdev[z] into out + z * stride - element for element launch_kbuild_cross for that problem
+void launch_kbuild_cross_batched(hipStream_t s, int kernel, const KParams* pdev, int batch, const double* U, int64_t mu,
+                                 int64_t mp, const double* V, int64_t n, int64_t np, double* out, int64_t ld,
+                                 int64_t stride, int d);
+void launch_kbuild_cross_batched(hipStream_t s, const CovParams* pdev, int batch, const double* U, int64_t mu, int64_t mp,
+                                 const double* V, int64_t n, int64_t np, double* out, int64_t ld, int64_t stride, int d);
+
+// predict_batch.hip: the per-row results of a panel of gpmi_predict_batch and their mixture
+// rows [m0, m0 + rows) of problems [t_first, t_first + batch): mean = dot + prior mean, var = |a_z^2 - sumsq|, NaN where
+// info[z] != 0.  dot / sumsq: the panel's row sums at dot + z * sDot, sumsq + z * sSq (sumsq == nullptr: means only); a2 of
+// problem z at params + z * pstride bytes (the KParams base of either parameter struct); mu_q (T x m) or mu_const (T), device
+void launch_predict_store(hipStream_t s, int batch, int64_t t_first, int64_t m0, int64_t rows, int64_t m,
+                          const double* dot, const double* sumsq, int64_t sDot, int64_t sSq, const void* params,
+                          int64_t pstride, const int* info, const double* mu_q, const double* mu_const, double* mean_t,
+                          double* var_t);
+// mix_mean[q] = sum_g w[g] mean_t[idx[g]][q], mix_var[q] = sum_g w[g] (var_t[idx[g]][q] + (mean_t[idx[g]][q] - mix_mean[q])^2)
+// over the G listed rows, each sum a pairwise tree in list order (var_t / mix_var == nullptr: the mean alone)
+void launch_predict_mix(hipStream_t s, int64_t G, const int* idx, const double* w, int64_t m, const double* mean_t,
+                        const double* var_t, double* mix_mean, double* mix_var);
 
 // grad.hip: fused contraction 1/2 sum (alpha alpha^T - K^-1) o dK/dtheta_j with dK recomputed from x.
 // out[0..n_theta) = gradient, out[n_theta] = sum_i (alpha_i^2 - K^-1_ii).  iK holds K^-1 (lower tiles).

@@ -64,6 +64,17 @@ __global__ __launch_bounds__(256) void kbuild_batched_kernel(const KParams* __re
                             out + (int64_t)blockIdx.z * stride, ld, 2);
 }
 
+// batched cross build: problem z builds its own K*_z (the rows of U against the rows of V) from pdev[z] into
+// out + z * stride; tile (blockIdx.y, blockIdx.x) as in the single cross build, so an element has the value
+// launch_kbuild_cross gives for those parameters
+template <int KERNEL>
+__global__ __launch_bounds__(256) void kbuild_cross_batched_kernel(const KParams* __restrict__ pdev,
+                                                                   const double* __restrict__ U, int64_t nu,
+                                                                   const double* __restrict__ V, int64_t nv,
+                                                                   double* __restrict__ out, int64_t ld, int64_t stride) {
+  kbuild_body<false, KERNEL>(pdev[blockIdx.z], U, nu, V, nv, nullptr, out + (int64_t)blockIdx.z * stride, ld, 0);
+}
+
 template <bool SQUARE, int KERNEL>
 __device__ inline void kbuild_body(const KParams& p, const double* __restrict__ U, int64_t nu,
                                    const double* __restrict__ V, int64_t nv,
@@ -306,6 +317,14 @@ __global__ __launch_bounds__(256) void ksum_batched_kernel(const CovParams* __re
   ksum_body<true>(pdev[blockIdx.z], x, n, x, n, noise, out + (int64_t)blockIdx.z * stride, ld, 2);
 }
 
+// batched cross build of sums (kbuild_cross_batched_kernel for GPMI_KERNEL_SUM)
+__global__ __launch_bounds__(256) void ksum_cross_batched_kernel(const CovParams* __restrict__ pdev,
+                                                                 const double* __restrict__ U, int64_t nu,
+                                                                 const double* __restrict__ V, int64_t nv,
+                                                                 double* __restrict__ out, int64_t ld, int64_t stride) {
+  ksum_body<false>(pdev[blockIdx.z], U, nu, V, nv, nullptr, out + (int64_t)blockIdx.z * stride, ld, 0);
+}
+
 }  // namespace
 
 static size_t kb_lds_bytes(int d) { return sizeof(double) * 2 * (size_t)d * KT; }
@@ -413,6 +432,26 @@ void launch_kbuild_cross(hipStream_t s, const KParams& p, const double* U, int64
 void launch_kbuild_cross(hipStream_t s, const CovParams& p, const double* U, int64_t mu, int64_t mp,
                          const double* V, int64_t n, int64_t np, double* out, int64_t ld) {
   kbuild_cross(s, p, U, mu, mp, V, n, np, out, ld);
+}
+
+// lockstep batch: K*_z (mp x ld, mu valid rows against the n valid rows of V) for problem z of `batch`, `stride` doubles
+// apart; one panel of query points per launch (the caller bounds mp: gpmi_predict_batch)
+void launch_kbuild_cross_batched(hipStream_t s, int kernel, const KParams* pdev, int batch, const double* U, int64_t mu,
+                                 int64_t mp, const double* V, int64_t n, int64_t np, double* out, int64_t ld,
+                                 int64_t stride, int d) {
+  assert((kernel == GPMI_KERNEL_SE || kernel == GPMI_KERNEL_RQ) && "a batch of sums is an array of CovParams");
+  dim3 grid((unsigned)(np / KT), (unsigned)(mp / KT), (unsigned)batch);
+  if (kernel == GPMI_KERNEL_SE)
+    hipLaunchKernelGGL(kbuild_cross_batched_kernel<GPMI_KERNEL_SE>, grid, dim3(256), kb_lds_bytes(d), s, pdev, U, mu, V, n,
+                       out, ld, stride);
+  else
+    hipLaunchKernelGGL(kbuild_cross_batched_kernel<GPMI_KERNEL_RQ>, grid, dim3(256), kb_lds_bytes(d), s, pdev, U, mu, V, n,
+                       out, ld, stride);
+}
+void launch_kbuild_cross_batched(hipStream_t s, const CovParams* pdev, int batch, const double* U, int64_t mu, int64_t mp,
+                                 const double* V, int64_t n, int64_t np, double* out, int64_t ld, int64_t stride, int d) {
+  dim3 grid((unsigned)(np / KT), (unsigned)(mp / KT), (unsigned)batch);
+  hipLaunchKernelGGL(ksum_cross_batched_kernel, grid, dim3(256), kb_lds_bytes(d), s, pdev, U, mu, V, n, out, ld, stride);
 }
 
 void launch_add_full(hipStream_t s, double* A, int64_t ld, const double* Y, int64_t n) {

@@ -371,6 +371,32 @@ class GpEngine(_DeviceCommMixin):
         self.h.call("gpmi_predict", dptr(p), m, dptr(mu), dptr(var))
         return mu, var
 
+    def predict_batch(self, kernel, thetas_cov, extra_diag, pts, mus=None, mu_const=None, mu_q=None, weights=None,
+                      want_var=True, want_samples=True, want_mix=True):
+        """gpmi_predict_batch: prediction at `pts` under the T rows of `thetas_cov` in lockstep, and its mixture.
+        mus (T, n) with mu_q (T, m) - the prior means at the data and at the points -, or mu_const (T,).
+        Returns (mean_t (T, m) | None, var_t (T, m) | None, mix_mean (m,) | None, mix_var (m,) | None, info (T,));
+        var_t is |a^2 - |L^-1 k|^2|, rows with info != 0 are NaN and left out of the mixture."""
+        th = as_f64(np.atleast_2d(thetas_cov))
+        T, nth = th.shape
+        p = as_f64(pts)
+        m = p.shape[0]
+        ex = as_f64(np.broadcast_to(np.asarray(extra_diag, dtype=float), (T,)))
+        if mus is not None:
+            mus_a, muq_a, muc_a = as_f64(mus).reshape(T, self.n), as_f64(mu_q).reshape(T, m), None
+        else:
+            mus_a, muq_a, muc_a = None, None, as_f64(np.broadcast_to(np.asarray(mu_const, dtype=float), (T,)))
+        w = None if weights is None else as_f64(weights).reshape(T)
+        mean_t = np.empty((T, m)) if want_samples else None
+        var_t = np.empty((T, m)) if want_samples and want_var else None
+        mix_mean = np.empty(m) if want_mix else None
+        mix_var = np.empty(m) if want_mix and want_var else None
+        info = np.zeros(T, dtype=np.int32)
+        self.h.call("gpmi_predict_batch", kernel, T, dptr(th), nth, dptr(ex), dptr(mus_a), dptr(muc_a), dptr(p), m,
+                    dptr(muq_a), dptr(w), dptr(mean_t), dptr(var_t), dptr(mix_mean), dptr(mix_var),
+                    info.ctypes.data_as(C.POINTER(C.c_int)))
+        return mean_t, var_t, mix_mean, mix_var, info
+
     def posterior(self, pts, mean_only=False):
         p = as_f64(pts)
         m = p.shape[0]

@@ -23,6 +23,7 @@ KERNEL_RQ = 1
 KERNEL_SUM = 2  # GPMI_KERNEL_SUM: a sum of SE / RQ kernels declared by gpmi_set_sum
 PROF_KBUILD, PROF_SYRK, PROF_PANEL, PROF_SOLVE, PROF_SYRK_REST, PROF_TRSM, PROF_SYRK_SLICE, PROF_FLOW = 0, 1, 2, 3, 4, 5, 6, 7
 OPT_LOCKSTEP_ALWAYS, OPT_RESERVE_POINTS, OPT_NO_FLOW = 1, 2, 3
+PREDICT_PANEL = 256  # GPMI_PREDICT_PANEL: query points per panel of gpmi_predict_batch
 _TRACE_MS = float(os.environ["GPMI_TRACE_CALLS"]) if os.environ.get("GPMI_TRACE_CALLS") else None
 ERR_INTERNAL = -5  # GPMI_ERR_INTERNAL
 
@@ -62,6 +63,8 @@ SIGNATURES = {
     "gpmi_lml_grad_batch": (C.c_int, [_vp, C.c_int, C.c_int64, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
     "gpmi_lml_grad_batch_noise": (C.c_int, [_vp, C.c_int, C.c_int64, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
     "gpmi_predict": (C.c_int, [_vp, _dp, _i64, _dp, _dp]),
+    "gpmi_predict_batch": (C.c_int, [_vp, C.c_int, _i64, _dp, C.c_int, _dp, _dp, _dp, _dp, _i64, _dp, _dp, _dp, _dp, _dp, _dp,
+                                     _ip]),
     "gpmi_posterior": (C.c_int, [_vp, _dp, _i64, _dp, _dp]),
     "gpmi_spatial_derivatives": (C.c_int, [_vp, _dp, _i64, _dp, _dp]),
     "gpmi_gradient": (C.c_int, [_vp, _dp, _i64, _dp, _dp]),
@@ -231,7 +234,7 @@ class Handle:
                              "gpmi_linv_lml", "gpmi_linv_lml_grad", "gpmi_linv_posterior", "gpmi_linv_lml_dense",
                              "gpmi_linv_lml_grad_dense", "gpmi_linv_posterior_dense", "gpmi_loo_terms", "gpmi_loo_grad",
                              "gpmi_loo_terms_mix", "gpmi_dev_potrf", "gpmi_loo_grad_batch", "gpmi_loo_grad_batch_noise", "gpmi_lml_grad_batch_noise",
-                             "gpmi_lml_grad_batch_mix", "gpmi_loo_grad_batch_mix"))
+                             "gpmi_lml_grad_batch_mix", "gpmi_loo_grad_batch_mix", "gpmi_predict_batch"))
 
     def call(self, name, *args):
         if _TRACE_MS is not None:  # GPMI_TRACE_CALLS=<ms>: report every entry-point call that takes longer (debugging aid)

@@ -190,12 +190,14 @@ class GpRegressor:
         base = np.zeros(self.n_points) if self._noise_var is None else self._noise_var
         return base + np.exp(2 * np.asarray(theta_cov, dtype=float)[self._het_slice])
 
-    def _mean_at(self, pts):
+    def _mean_at(self, pts, theta_mean=None):
         """Prior mean at the rows of `pts`: vectorised for the built-in means, point by point (as the reference
-        does, regression.py:211) for user-defined ones."""
+        does, regression.py:211) for user-defined ones.  `theta_mean`: the mean's parameters (default: the fitted ones)."""
+        if theta_mean is None:
+            theta_mean = self.mean_hyperpars
         if hasattr(self.mean, "at_points"):
-            return self.mean.at_points(pts, self.mean_hyperpars)
-        return array([self.mean(q, self.mean_hyperpars) for q in pts[:, None, :]])
+            return self.mean.at_points(pts, theta_mean)
+        return array([self.mean(q, theta_mean) for q in pts[:, None, :]])
 
     def _mix_args(self, theta_cp):
         """(kernel ids, sub-kernel parameter vectors, training-point weights) of a ChangePoint block."""
@@ -281,6 +283,142 @@ class GpRegressor:
         else:
             mu, var = self.engine.predict(p)
         return mu + self._mean_at(p), sqrt(abs(var))
+
+    # ---------------------------------------------------------------------------------
+    # (extension) prediction under a sample of hyper-parameters
+    # ---------------------------------------------------------------------------------
+    def _lockstep_predict_ok(self):
+        """The model gpmi_predict_batch serves: SquaredExponential / RationalQuadratic / sums of them (+ WhiteNoise),
+        diagonal data errors, lockstep sizes."""
+        return (not self._generic and self._mix is None and self._het_slice is None and self._y_cov is None
+                and self.engine.capacity() <= 4096)
+
+    def _check_thetas(self, thetas):
+        thetas = np.atleast_2d(np.asarray(thetas, dtype=float))
+        if thetas.ndim != 2 or thetas.shape[1] != self.n_hyperpars:
+            raise ValueError(msg.wrong_hyperpar_count(self.n_hyperpars, thetas.shape[-1]))
+        return np.ascontiguousarray(thetas)
+
+    @staticmethod
+    def _check_failed(failed):
+        if failed not in ("raise", "skip"):
+            raise ValueError("'failed' must be \"raise\" or \"skip\"")
+
+    @staticmethod
+    def _mixture_weights(weights, T):
+        """The weights of a mixture over T hyper-parameter vectors, normalised: equal by default, else finite,
+        non-negative, of length T and with a positive sum."""
+        if weights is None:
+            w = np.full(T, 1.0 / T)
+        else:
+            w = np.asarray(weights, dtype=float)
+            if w.ndim != 1 or w.size != T:
+                raise ValueError(f"weights must be a vector of one weight per hyper-parameter vector ({T}), got shape {w.shape}")
+            if not np.isfinite(w).all() or (w < 0).any():
+                raise ValueError("weights must be finite and non-negative")
+            if not w.sum() > 0:
+                raise ValueError("weights must have a positive sum")
+        return w / w.sum()
+
+    @staticmethod
+    def _host_mixture(means, variances, w, good):
+        """Two-pass mixture of the rows `good` (law of total variance, no E[x^2] - E[x]^2 cancellation); the weights of
+        those rows are divided by their sum.  NaN without a good row."""
+        m = means.shape[1]
+        if not good.any() or not w[good].sum() > 0:
+            return np.full(m, np.nan), (None if variances is None else np.full(m, np.nan))
+        wg = (w[good] / w[good].sum())[:, None]
+        mean = (wg * means[good]).sum(axis=0)
+        if variances is None:
+            return mean, None
+        return mean, (wg * (variances[good] + (means[good] - mean) ** 2)).sum(axis=0)
+
+    def _predict_thetas(self, points, thetas, weights, failed, want_var, want_samples, want_mix):
+        """Per-theta predictions and / or their mixture: (means (T, m), variances (T, m), mean (m,), variance (m,)),
+        None for what was not asked for.  One lockstep device call (gpmi_predict_batch) where the model allows it,
+        else one fit + predict per row with the fitted state restored at the end."""
+        self._check_failed(failed)
+        p = self.process_points(points)
+        thetas = self._check_thetas(thetas)
+        T = len(thetas)
+        w = self._mixture_weights(weights, T) if want_mix else None
+        if self._lockstep_predict_ok():
+            th = np.array([np.ascontiguousarray(t[self.cov_slice][self._stat_slice]) for t in thetas])
+            ex = np.array([float(np.exp(2 * t[self.cov_slice][self._wn_index])) if self._wn_index is not None else 0.0
+                           for t in thetas])
+            if isinstance(self.mean, ConstantMean):
+                mean_kw = dict(mu_const=thetas[:, 0])
+            else:  # Linear / Quadratic / user means: the prior mean at the data and at the points, per theta
+                mean_kw = dict(mus=np.array([self.mean.build_mean(t[self.mean_slice]) for t in thetas]),
+                               mu_q=np.array([self._mean_at(p, t[self.mean_slice]) for t in thetas]))
+            means, variances, mean, var, info = self.engine.predict_batch(
+                self._kernel_id, th, ex, p, weights=w, want_var=want_var, want_samples=want_samples, want_mix=want_mix,
+                **mean_kw)
+            bad = info != 0
+        else:
+            saved = self.hyperpars
+            m = len(p)
+            means = np.full((T, m), np.nan)
+            variances = np.full((T, m), np.nan) if want_var else None
+            bad = np.zeros(T, dtype=bool)
+            try:
+                for t, theta in enumerate(thetas):
+                    try:
+                        self.set_hyperparameters(theta)
+                    except LinAlgError:
+                        bad[t] = True
+                        continue
+                    mu_t, sd_t = self(p)
+                    means[t] = mu_t
+                    if want_var:
+                        variances[t] = sd_t**2
+            finally:
+                self.set_hyperparameters(saved)
+            mean, var = self._host_mixture(means, variances, w, ~bad) if want_mix else (None, None)
+        if bad.any():
+            if failed == "raise":
+                raise LinAlgError("Matrix is not positive definite")
+            warn("Cholesky decomposition failure in %d of %d hyper-parameter vectors: left out" % (int(bad.sum()), T))
+        return means, variances, mean, var
+
+    def predict_samples(self, points: ndarray, thetas: ndarray, failed: str = "raise", mean_only: bool = False):
+        """(extension) Mean and standard deviation of the regression estimate at `points` under each of the T
+        hyper-parameter vectors in the rows of `thetas` (full vectors, as `set_hyperparameters` takes them): what
+        `set_hyperparameters(theta_t)` followed by `__call__(points)` returns, as two (T, M) arrays - the band of model
+        realisations `plotting.hdi_plot` draws.  The fitted state (`hyperpars`, `alpha`, `L`, later predictions) is what
+        it was before the call.
+
+        SquaredExponential / RationalQuadratic kernels, sums of them and ``+ WhiteNoise()`` with diagonal data errors
+        and up to 4096 (padded) points are evaluated in lockstep batches on the device (gpmi_predict_batch), without
+        touching the fit.  Every other model (larger N, dense ``y_cov``, ``HeteroscedasticNoise``, ``ChangePoint``,
+        plugin kernels) is fitted and evaluated one vector at a time and re-fitted at its original hyper-parameters at
+        the end: that costs T + 1 fits.
+
+        A vector whose covariance matrix is not positive definite raises LinAlgError; with ``failed="skip"`` its rows
+        are NaN (one warning per call).  ``mean_only=True`` returns the means alone and computes no variance."""
+        means, variances, _, _ = self._predict_thetas(points, thetas, None, failed, not mean_only, True, False)
+        if mean_only:
+            return means
+        return means, sqrt(variances)
+
+    def predict_marginalised(self, points: ndarray, thetas: ndarray, weights: ndarray = None,
+                             return_samples: bool = False, failed: str = "raise", mean_only: bool = False):
+        """(extension) Prediction at `points` with the hyper-parameters marginalised over the sample in the rows of
+        `thetas` (e.g. ``chain.get_sample(burn, thin)``): mean and standard deviation (M,) of the mixture of the T
+        Gaussian predictions with `weights` (default 1 / T; finite, non-negative, positive sum; normalised here),
+
+            mean = sum_t w_t mu_t,    std^2 = sum_t w_t (sigma_t^2 + (mu_t - mean)^2)
+
+        (law of total variance, evaluated in two passes).  With ``return_samples=True`` also the (T, M) means and
+        standard deviations of `predict_samples`.  Where and at what cost it runs, and ``failed``, as `predict_samples`
+        (T + 1 fits outside the lockstep route); a vector skipped with ``failed="skip"`` is left out of the mixture and
+        the remaining weights are renormalised.  ``mean_only=True``: no variances are computed or returned."""
+        means, variances, mean, var = self._predict_thetas(points, thetas, weights, failed, not mean_only,
+                                                           return_samples, True)
+        out = (mean,) if mean_only else (mean, sqrt(var))
+        if return_samples:
+            out += (means,) if mean_only else (means, sqrt(variances))
+        return out[0] if len(out) == 1 else out
 
     def set_hyperparameters(self, hyperpars: ndarray):
         """Update the hyper-parameters and re-fit (regression.py:218-244)."""
