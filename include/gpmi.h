@@ -38,7 +38,11 @@ extern "C" {
 /* covariance kernels (covariance.py:181-279 SquaredExponential, 282-368 RationalQuadratic) */
 #define GPMI_KERNEL_SE 0 /* theta = [ln a, ln l_1..ln l_d]            n_theta = d+1 */
 #define GPMI_KERNEL_RQ 1 /* theta = [ln a, ln kappa, ln l_1..ln l_d]  n_theta = d+2 */
-/* sum of 2..4 SE / RQ kernels (CompositeCovariance, covariance.py:33-36,47-105) declared per handle by gpmi_set_sum:
+/* Matern kernels of order 3/2 and 5/2 (no counterpart in the reference), theta laid out as for SE.  With
+ * t = sqrt(2 nu sum_k ((u_k - v_k) / l_k)^2):  K = a^2 (1 + t) e^-t  and  K = a^2 (1 + t + t^2 / 3) e^-t. */
+#define GPMI_KERNEL_M32 3 /* theta = [ln a, ln l_1..ln l_d]            n_theta = d+1 */
+#define GPMI_KERNEL_M52 4 /* theta = [ln a, ln l_1..ln l_d]            n_theta = d+1 */
+/* sum of 2..4 SE / RQ / Matern kernels (CompositeCovariance, covariance.py:33-36,47-105) declared per handle by gpmi_set_sum:
  * theta = the components' own parameter vectors back to back, in component order; n_theta = the sum of theirs.
  * Accepted by gpmi_fit, gpmi_lml, gpmi_lml_batch(_submit), gpmi_lml_grad(_batch), gpmi_loo_terms, gpmi_loo_grad(_batch),
  * gpmi_covariance, gpmi_cross_covariance; a sum fit serves gpmi_predict, gpmi_posterior, gpmi_get_K, gpmi_get_L and
@@ -187,7 +191,7 @@ int gpmi_predict(gpmi_ctx* ctx, const double* pts_host, int64_t m, double* mu_ho
  * mean_t, var_t (T x m) and mix_mean, mix_var (m) may each be NULL; with var_t and mix_var both NULL no variance is
  * computed.  A row that does not factorise gets info[t] != 0 and NaN in mean_t / var_t and is left out of the mixture:
  * the other rows' weights are divided by their sum (equal weights: 1 / number of good rows); no good row: NaN mixtures,
- * GPMI_OK.  Lockstep sizes only (padded n <= 4096, diagonal data errors; SE, RQ, GPMI_KERNEL_SUM): every launch carries
+ * GPMI_OK.  Lockstep sizes only (padded n <= 4096, diagonal data errors; SE, RQ, Matern, GPMI_KERNEL_SUM): every launch carries
  * a chunk of rows, also for T = 1, so a row's values do not depend on the batch it is in; the sums over t run as a
  * pairwise tree over the good rows in order, so they depend on T and the failures alone.  The points are processed in
  * panels of GPMI_PREDICT_PANEL rows.  The fitted state of gpmi_fit is not touched. */
@@ -200,11 +204,11 @@ int gpmi_predict_batch(gpmi_ctx* ctx, int kernel, int64_t T, const double* theta
  * Sigma = K_qq - Q^T Q (m x m), Q = L^-1 K_qx^T.  cov_host may be NULL (mean_only). */
 int gpmi_posterior(gpmi_ctx* ctx, const double* pts_host, int64_t m, double* mu_host,
                    double* cov_host);
-/* Replaces GpRegressor.spatial_derivatives (regression.py:387-419), SE kernel only
- * (RationalQuadratic has no gradient_terms: covariance.py:38-44): dmu (m x d), dvar (m x d). */
+/* Replaces GpRegressor.spatial_derivatives (regression.py:387-419), SE and the Matern kernels only
+ * (RationalQuadratic has no gradient_terms: covariance.py:38-44; sums and mixtures are refused): dmu (m x d), dvar (m x d). */
 int gpmi_spatial_derivatives(gpmi_ctx* ctx, const double* pts_host, int64_t m, double* dmu_host,
                              double* dvar_host);
-/* Replaces GpRegressor.gradient (regression.py:351-385), SE only: mean (m x d) and covariance
+/* Replaces GpRegressor.gradient (regression.py:351-385), SE and the Matern kernels only: mean (m x d) and covariance
  * (m x d x d) of the gradient of the regression estimate. */
 int gpmi_gradient(gpmi_ctx* ctx, const double* pts_host, int64_t m, double* gmu_host,
                   double* gcov_host);
@@ -273,7 +277,7 @@ int gpmi_loo_terms(gpmi_ctx* ctx, int kernel, const double* theta_host, int n_th
 int gpmi_set_noise(gpmi_ctx* ctx, const double* noise_var_host);
 
 /* ---- sums of stationary kernels (GPMI_KERNEL_SUM) ------------------------------------
- * Declares the components of the handle's sum: nk in 2..4, kernels[m] GPMI_KERNEL_SE or GPMI_KERNEL_RQ in the order of
+ * Declares the components of the handle's sum: nk in 2..4, kernels[m] GPMI_KERNEL_SE, _RQ, _M32 or _M52 in the order of
  * the sum.  K = sum_m a_m^2 (C_m + 1e-12 I) + extra_diag I + data errors (every component carries its own jitter,
  * covariance.py:254-255,348); a query point's prior variance is sum_m a_m^2. */
 int gpmi_set_sum(gpmi_ctx* ctx, int nk, const int* kernels);
@@ -396,7 +400,7 @@ int gpmi_comm_destroy(gpmi_ctx* ctx);
 /* Append ONE training point to the fitted model at unchanged hyper-parameters in O(n^2): the new row of the Cholesky
  * factor is l = L^-1 k(X, x_new), l_nn = sqrt(k_nn - l.l) (one triangular sweep), alpha is re-solved (two sweeps).
  * The reference has no counterpart: GpOptimiser.add_evaluation re-fits from scratch (optimisation.py:177-186,
- * O(n^3) per added point even when the hyper-parameters are kept).  Needs a fit by gpmi_fit (SE / RQ, diagonal
+ * O(n^3) per added point even when the hyper-parameters are kept).  Needs a fit by gpmi_fit (one stationary kernel or a sum of them, diagonal
  * data errors) and free capacity (GPMI_OPT_RESERVE_POINTS).
  *   x_new_host : d values    mu_host : n + 1 prior means (the old points' first)    alpha_host : n + 1 out
  *   info : 0, or n + 1 if the enlarged matrix is not positive definite (the model is then left unchanged) */

@@ -260,8 +260,8 @@ int make_params(gpmi_ctx* c, int kernel, const double* theta, int n_theta, doubl
                 KParams& p) {
   ARGCHK(c, c->n > 0, "gpmi_set_data has not been called");
   ARGCHK(c, kernel != GPMI_KERNEL_SUM, "this entry point does not take sums of kernels (GPMI_KERNEL_SUM)");
-  ARGCHK(c, kernel == GPMI_KERNEL_SE || kernel == GPMI_KERNEL_RQ, "unknown kernel id");
-  const int off = (kernel == GPMI_KERNEL_SE) ? 1 : 2;
+  ARGCHK(c, kernel_is_stationary(kernel), "unknown kernel id");
+  const int off = kernel_theta_offset(kernel);  // SE, Matern: 1; RQ: 2
   ARGCHK(c, n_theta == c->d + off, "n_theta does not match the kernel and the data dimension");
   ARGCHK(c, theta != nullptr, "theta is NULL");
   std::memset(&p, 0, sizeof(p));
@@ -285,7 +285,7 @@ int make_cov(gpmi_ctx* c, int kernel, const double* theta, int n_theta, double e
   ARGCHK(c, c->sum_nk >= 2, "GPMI_KERNEL_SUM: declare the components of the sum with gpmi_set_sum first");
   ARGCHK(c, theta != nullptr, "theta is NULL");
   int need = 0;
-  for (int m = 0; m < c->sum_nk; ++m) need += (c->sum_kinds[m] == GPMI_KERNEL_SE ? 1 : 2) + (int)c->d;
+  for (int m = 0; m < c->sum_nk; ++m) need += kernel_theta_offset(c->sum_kinds[m]) + (int)c->d;
   ARGCHK(c, n_theta == need, "n_theta does not match the sum declared by gpmi_set_sum and the data dimension");
   p.kernel = GPMI_KERNEL_SUM;
   p.d = (int)c->d;
@@ -295,7 +295,7 @@ int make_cov(gpmi_ctx* c, int kernel, const double* theta, int n_theta, double e
   int off = 0;
   double a2 = 0.0;
   for (int m = 0; m < p.nk; ++m) {
-    const int nt = (c->sum_kinds[m] == GPMI_KERNEL_SE ? 1 : 2) + (int)c->d;
+    const int nt = kernel_theta_offset(c->sum_kinds[m]) + (int)c->d;
     if (int rc = make_params(c, c->sum_kinds[m], theta + off, nt, 0.0, p.comp[m])) return rc;
     a2 += p.comp[m].a2;  // K_qq = sum_m a_m^2 in component order (regression.py:210 through covariance.py:87-90)
     off += nt;
@@ -801,8 +801,8 @@ int gpmi_set_sum(gpmi_ctx* c, int nk, const int* kernels) {
   ARGCHK(c, nk >= 2 && nk <= GPMI_MAX_SUM, "gpmi_set_sum: a sum has 2 to 4 components");
   ARGCHK(c, kernels != nullptr, "kernels is NULL");
   for (int m = 0; m < nk; ++m)
-    ARGCHK(c, kernels[m] == GPMI_KERNEL_SE || kernels[m] == GPMI_KERNEL_RQ,
-           "gpmi_set_sum: every component is GPMI_KERNEL_SE or GPMI_KERNEL_RQ");
+    ARGCHK(c, kernel_is_stationary(kernels[m]),
+           "gpmi_set_sum: every component is GPMI_KERNEL_SE, GPMI_KERNEL_RQ, GPMI_KERNEL_M32 or GPMI_KERNEL_M52");
   c->sum_nk = nk;
   for (int m = 0; m < GPMI_MAX_SUM; ++m) c->sum_kinds[m] = (m < nk) ? kernels[m] : 0;
   return GPMI_OK;

@@ -365,8 +365,8 @@ int gpmi_lml_grad_batch_mix(gpmi_ctx* c, int nk, const int* kernels, int64_t T, 
       // 1/2 sum (D_m Q D_m) o dK_m: the fused contraction on the weight-scaled inverse with u = v = g_m o alpha
       launch_scale_add(s, c->bB2, c->ld, c->bA, c->ld, gm, gm, c->np, c->np, false, B, bs.sMat, bs.sMat, sG);
       launch_vec_mul(s, gm, alpha_dev, ua_dev, c->np, B, sG, bs.sVec, bs.sVec);
-      launch_lml_grad_batched(s, pm, B, n_thetas[m], c->x, c->n, c->np, c->bB2, c->ld, bs.sMat, ua_dev, ua_dev, bs.sVec,
-                              c->bGws, c->bGout + (int64_t)m * cap * W);
+      launch_lml_grad_batched(s, kernels[m], pm, B, n_thetas[m], c->x, c->n, c->np, c->bB2, c->ld, bs.sMat, ua_dev, ua_dev,
+                              bs.sVec, c->bGws, c->bGout + (int64_t)m * cap * W);
       // window parameters: h_m(i) = sum_j Q_ij K_m,ij g_m(j) on the full K_m (lower tiles built, then mirrored)
       launch_kbuild_square_batched(s, kernels[m], pm, B, c->x, c->n, c->np, c->mix_zero, c->bB2, c->ld, bs.sMat,
                                    (int)c->d, 0);
@@ -585,8 +585,8 @@ int gpmi_loo_grad_batch_mix(gpmi_ctx* c, int nk, const int* kernels, int64_t T, 
       launch_scale_add(s, c->bB2, c->ld, c->bA, c->ld, gm, gm, c->np, c->np, false, B, bs.sMat, bs.sMat, sG);
       launch_vec_mul(s, gm, p_dev, ua_dev, c->np, B, sG, sLoo, bs.sVec);
       launch_vec_mul(s, gm, alpha_dev, va_dev, c->np, B, sG, bs.sVec, bs.sVec);
-      launch_lml_grad_batched(s, pm, B, n_thetas[m], c->x, c->n, c->np, c->bB2, c->ld, bs.sMat, ua_dev, va_dev, bs.sVec,
-                              c->bGws, c->bGout + (int64_t)m * cap * W);
+      launch_lml_grad_batched(s, kernels[m], pm, B, n_thetas[m], c->x, c->n, c->np, c->bB2, c->ld, bs.sMat, ua_dev, va_dev,
+                              bs.sVec, c->bGws, c->bGout + (int64_t)m * cap * W);
       // window parameters: h_m(i) = sum_j Q_ij K_m,ij g_m(j) on the full K_m (lower tiles built, then mirrored)
       launch_kbuild_square_batched(s, kernels[m], pm, B, c->x, c->n, c->np, c->mix_zero, c->bB2, c->ld, bs.sMat,
                                    (int)c->d, 0);

@@ -431,7 +431,7 @@ static int lml_grad_batch_impl(gpmi_ctx* c, int kernel, int64_t T, const double*
     launch_gemm(s, TILES_LOWER, OP_ASSIGN, false, 1, c->bA, c->ld, c->bB2, c->ld, c->bB2, c->ld, nt, nt, (int)c->np,
                 nullptr, syrk);
     if (sps.empty())
-      launch_lml_grad_batched(s, c->bParams, B, n_theta, c->x, c->n, c->np, c->bA, c->ld, bs.sMat, alpha_dev, alpha_dev,
+      launch_lml_grad_batched(s, kernel, c->bParams, B, n_theta, c->x, c->n, c->np, c->bA, c->ld, bs.sMat, alpha_dev, alpha_dev,
                               bs.sVec, c->bGws, c->bGout);
     else
       launch_lml_grad_batched(s, c->bSum, B, n_theta, c->x, c->n, c->np, c->bA, c->ld, bs.sMat, alpha_dev, alpha_dev,
@@ -591,7 +591,7 @@ static int loo_grad_batch_impl(gpmi_ctx* c, int kernel, int64_t T, const double*
     launch_gemm(s, TILES_LOWER, OP_ASSIGN, false, 0, c->bA, c->ld, c->bB2, c->ld, c->bB2, c->ld, nt, nt, (int)c->np,
                 nullptr, syrk);
     if (sps.empty())
-      launch_lml_grad_batched(s, c->bParams, B, n_theta, c->x, c->n, c->np, c->bA, c->ld, bs.sMat, p_dev, alpha_dev, sLoo,
+      launch_lml_grad_batched(s, kernel, c->bParams, B, n_theta, c->x, c->n, c->np, c->bA, c->ld, bs.sMat, p_dev, alpha_dev, sLoo,
                               c->bGws, c->bGout);
     else
       launch_lml_grad_batched(s, c->bSum, B, n_theta, c->x, c->n, c->np, c->bA, c->ld, bs.sMat, p_dev, alpha_dev, sLoo,
@@ -933,7 +933,8 @@ int gpmi_spatial_derivatives(gpmi_ctx* c, const double* pts, int64_t m, double* 
   ARGCHK(c, c->fitted, "gpmi_spatial_derivatives needs a successful gpmi_fit");
   ARGCHK(c, c->fit_params.kernel >= 0 || c->mix_nk > 0,
          "gpmi_spatial_derivatives: the model was fitted with a caller-built covariance (gpmi_fit_dense) - use gpmi_predict_dense / gpmi_solve_rows");
-  ARGCHK(c, c->fit_params.kernel == GPMI_KERNEL_SE, "spatial derivatives: SquaredExponential only (not sums of kernels)");
+  ARGCHK(c, c->fit_params.kernel == GPMI_KERNEL_SE || kernel_is_matern(c->fit_params.kernel),
+         "spatial derivatives: SquaredExponential, Matern32 and Matern52 only (not sums of kernels)");
   ARGCHK(c, pts && m > 0 && dmu_out && dvar_out, "NULL argument or m <= 0");
   if (int rc = set_device(c)) return rc;
   Lane& L = c->lanes[0];
@@ -947,6 +948,9 @@ int gpmi_spatial_derivatives(gpmi_ctx* c, const double* pts, int64_t m, double* 
     HIPCHK(c, hipMemcpyAsync(c->pts, pts + m0 * d, sizeof(double) * mc * d, hipMemcpyHostToDevice, s));
     launch_kbuild_cross(s, p, c->pts, mc, mp, c->x, c->n, c->np, c->Q, c->ld);
     launch_copy(s, c->Q, c->Q2, mp * c->ld);
+    // Matern: the multiplier of the reductions is the derivative profile a^2 g, not K* (predgrad.hip); K* has been
+    // copied for the solves, so c->Q is free to be rebuilt
+    if (kernel_is_matern(p.kernel)) launch_kbuild_cross_dprofile(s, p, c->pts, mc, mp, c->x, c->n, c->np, c->Q, c->ld);
     // Z = K^-1 k per row: forward then backward solve (regression.py:410)
     if (int rc = ensure_inv2(c, L, s)) return rc;
     if (int rc = ensure_trsm_panel(c, mp)) return rc;
@@ -969,7 +973,8 @@ int gpmi_gradient(gpmi_ctx* c, const double* pts, int64_t m, double* gmu_out, do
   ARGCHK(c, c->fitted, "gpmi_gradient needs a successful gpmi_fit");
   ARGCHK(c, c->fit_params.kernel >= 0 || c->mix_nk > 0,
          "gpmi_gradient: the model was fitted with a caller-built covariance (gpmi_fit_dense) - use gpmi_predict_dense / gpmi_solve_rows");
-  ARGCHK(c, c->fit_params.kernel == GPMI_KERNEL_SE, "gradient: SquaredExponential only (not sums of kernels)");
+  ARGCHK(c, c->fit_params.kernel == GPMI_KERNEL_SE || kernel_is_matern(c->fit_params.kernel),
+         "gradient: SquaredExponential, Matern32 and Matern52 only (not sums of kernels)");
   ARGCHK(c, pts && m > 0 && gmu_out && gcov_out, "NULL argument or m <= 0");
   if (int rc = set_device(c)) return rc;
   Lane& L = c->lanes[0];
@@ -983,7 +988,11 @@ int gpmi_gradient(gpmi_ctx* c, const double* pts, int64_t m, double* gmu_out, do
     const int64_t rp = round_up(mc * d, GPMI_NB);
     if (int rc = ensure_query_ws(c, rp)) return rc;
     HIPCHK(c, hipMemcpyAsync(c->pts, pts + m0 * d, sizeof(double) * mc * d, hipMemcpyHostToDevice, s));
-    launch_kbuild_cross(s, p, c->pts, mc, round_up(mc, GPMI_NB), c->x, c->n, c->np, c->Q, c->ld);
+    // c->Q is only ever the multiplier of the two kernels below: K* for SE, the derivative profile a^2 g for Matern
+    if (kernel_is_matern(p.kernel))
+      launch_kbuild_cross_dprofile(s, p, c->pts, mc, round_up(mc, GPMI_NB), c->x, c->n, c->np, c->Q, c->ld);
+    else
+      launch_kbuild_cross(s, p, c->pts, mc, round_up(mc, GPMI_NB), c->x, c->n, c->np, c->Q, c->ld);
     double* gmu_dev = c->pvec;
     double* gcov_dev = c->pvec + rp;
     launch_sd_reduce(s, p, c->x, c->n, c->pts, mc, c->Q, c->ld, c->alpha, 0, 1.0, gmu_dev);

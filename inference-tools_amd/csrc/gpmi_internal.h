@@ -20,7 +20,7 @@ static inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * 
 
 // Hyper-parameters of one covariance evaluation, passed by value as a kernel argument.
 struct KParams {
-  int kernel;                 // GPMI_KERNEL_SE / GPMI_KERNEL_RQ
+  int kernel;                 // GPMI_KERNEL_SE / _RQ / _M32 / _M52
   int d;                      // spatial dimensions
   double a2;                  // exp(theta0)^2
   double kappa;               // RQ: exp(theta1)
@@ -28,11 +28,27 @@ struct KParams {
   double inv_l2[GPMI_MAX_D];  // 1 / l_k^2
 };
 
-// A covariance evaluation the entry points hold: one SE / RQ kernel (the KParams base, nk = 0), or a sum of nk = 2..4 of
+// The stationary kernels one KParams can describe, and the number of parameters each has in front of its length scales
+// (ln a; RQ: ln a, ln kappa).  One explicit decision per id: "not SE" does not mean RQ.  -1: not such a kernel.
+__host__ __device__ inline int kernel_theta_offset(int kernel) {
+  switch (kernel) {
+    case GPMI_KERNEL_SE: return 1;
+    case GPMI_KERNEL_RQ: return 2;
+    case GPMI_KERNEL_M32: return 1;
+    case GPMI_KERNEL_M52: return 1;
+    default: return -1;
+  }
+}
+__host__ __device__ inline bool kernel_is_stationary(int kernel) { return kernel_theta_offset(kernel) > 0; }
+__host__ __device__ inline bool kernel_is_matern(int kernel) {
+  return kernel == GPMI_KERNEL_M32 || kernel == GPMI_KERNEL_M52;
+}
+
+// A covariance evaluation the entry points hold: one stationary kernel (the KParams base, nk = 0), or a sum of nk = 2..4 of
 // them (GPMI_KERNEL_SUM, gpmi_set_sum).  For a sum the base carries kernel = GPMI_KERNEL_SUM, d, a2 = sum_m a_m^2 (the
 // prior variance of a query point, regression.py:210) and the WhiteNoise variance; comp[m] are the components' own
 // parameters (extra_diag 0).  The launchers of kbuild.hip / grad.hip have CovParams overloads, which launch the fused
-// sum kernels for GPMI_KERNEL_SUM, and KParams forms, which take one SE / RQ kernel and assert so (a sum copied into a
+// sum kernels for GPMI_KERNEL_SUM, and KParams forms, which take one stationary kernel and assert so (a sum copied into a
 // KParams would lose its components).  KParams itself keeps its layout: it is the kernarg of every single-kernel launch.
 constexpr int GPMI_MAX_SUM = 4;
 struct CovParams : KParams {
@@ -251,6 +267,10 @@ void launch_kbuild_square_part(hipStream_t s, const KParams& p, const double* x,
 // cross covariance U (mp x d, mu valid rows) vs V (np x d, n valid rows): out mp x ld, zeros in padding
 void launch_kbuild_cross(hipStream_t s, const KParams& p, const double* U, int64_t mu, int64_t mp,
                          const double* V, int64_t n, int64_t np, double* out, int64_t ld);
+// the same cross build of the Matern DERIVATIVE profile a^2 g (kmath.h: matern_profile) in the place of K = a^2 C: the
+// rows the predictive-gradient kernels multiply by (predgrad.hip).  Matern kernels only.
+void launch_kbuild_cross_dprofile(hipStream_t s, const KParams& p, const double* U, int64_t mu, int64_t mp,
+                                  const double* V, int64_t n, int64_t np, double* out, int64_t ld);
 void launch_add_full(hipStream_t s, double* A, int64_t ld, const double* Y, int64_t n);
 // The same builders for a CovParams: the fused sum build when p.kernel == GPMI_KERNEL_SUM, else its base's build.  (The
 // KParams forms take SE / RQ only: a sum is never passed as its base.)
@@ -293,9 +313,10 @@ int64_t grad_ws_doubles(int64_t np, int n_theta);
 void launch_lml_grad(hipStream_t s, const KParams& p, int n_theta, const double* x, int64_t n,
                      int64_t np, const double* iK, int64_t ld, const double* u, const double* v,
                      double* ws, double* out);
-void launch_lml_grad_batched(hipStream_t s, const KParams* pdev, int batch, int n_theta, const double* x, int64_t n,
-                             int64_t np, const double* iK, int64_t ld, int64_t sK, const double* u, const double* v,
-                             int64_t sV, double* ws, double* out);
+// (kernel: the kind of every pdev[z], which selects the instantiation)
+void launch_lml_grad_batched(hipStream_t s, int kernel, const KParams* pdev, int batch, int n_theta, const double* x,
+                             int64_t n, int64_t np, const double* iK, int64_t ld, int64_t sK, const double* u,
+                             const double* v, int64_t sV, double* ws, double* out);
 // the same for a CovParams (the fused contraction of a sum: partials [component 1, ..., component nk, trace]) and for a
 // lockstep batch of sums
 void launch_lml_grad(hipStream_t s, const CovParams& p, int n_theta, const double* x, int64_t n,

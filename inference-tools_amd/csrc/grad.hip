@@ -32,22 +32,37 @@ __device__ inline double block_sum(double v, double* red) {
   return red[0] + red[1] + red[2] + red[3];
 }
 
+// Matern value and derivative profiles of one element (kmath.h: matern_profile has the formulas): C and g at
+// s = 1/2 sum_k dx_k^2 / l_k^2, with the library's exp as in the SE / RQ branches of the contraction
+__device__ __forceinline__ void matern_cg(bool m32, double s, double& C, double& g) {
+  double t = sqrt((m32 ? 6.0 : 10.0) * s);
+  t = t > 1000.0 ? 1000.0 : t;  // beyond the underflow of exp: 0 x finite, never inf x 0
+  const double e = exp(-t);
+  C = m32 ? (1.0 + t) * e : fma(t, fma(t, 1.0 / 3.0, 1.0), 1.0) * e;
+  g = m32 ? 3.0 * e : (5.0 / 3.0) * ((1.0 + t) * e);
+}
+
+// MATERN: the Matern kernels have an instantiation of their own, so that SE / RQ run the code they ran before these
+// were added.
 // batch (blockIdx.z, lockstep evaluations of gpmi_lml_grad_batch): problem z takes pdev[z], iK + z sK, u / v + z sV,
 // ws + z sW
+template <bool MATERN>
 __device__ __forceinline__ void lml_grad_body(const KParams& p, int n_theta, const double* __restrict__ x, int64_t n,
                                               const double* __restrict__ iK, int64_t ld,
                                               const double* __restrict__ uvec, const double* __restrict__ vvec,
                                               double* __restrict__ ws);
 
+template <bool MATERN>
 __global__ __launch_bounds__(256) void lml_grad_kernel(KParams p, int n_theta,
                                                        const double* __restrict__ x, int64_t n,
                                                        const double* __restrict__ iK, int64_t ld,
                                                        const double* __restrict__ uvec,
                                                        const double* __restrict__ vvec,
                                                        double* __restrict__ ws) {
-  lml_grad_body(p, n_theta, x, n, iK, ld, uvec, vvec, ws);
+  lml_grad_body<MATERN>(p, n_theta, x, n, iK, ld, uvec, vvec, ws);
 }
 
+template <bool MATERN>
 __global__ __launch_bounds__(256) void lml_grad_batched_kernel(const KParams* __restrict__ pdev, int n_theta,
                                                                const double* __restrict__ x, int64_t n,
                                                                const double* __restrict__ iK, int64_t ld,
@@ -55,9 +70,10 @@ __global__ __launch_bounds__(256) void lml_grad_batched_kernel(const KParams* __
                                                                const double* __restrict__ vvec, double* __restrict__ ws,
                                                                int64_t sK, int64_t sV, int64_t sW) {
   const int64_t z = blockIdx.z;
-  lml_grad_body(pdev[z], n_theta, x, n, iK + z * sK, ld, uvec + z * sV, vvec + z * sV, ws + z * sW);
+  lml_grad_body<MATERN>(pdev[z], n_theta, x, n, iK + z * sK, ld, uvec + z * sV, vvec + z * sV, ws + z * sW);
 }
 
+template <bool MATERN>
 __device__ __forceinline__ void lml_grad_body(const KParams& p, int n_theta, const double* __restrict__ x, int64_t n,
                                               const double* __restrict__ iK, int64_t ld,
                                               const double* __restrict__ uvec, const double* __restrict__ vvec,
@@ -110,12 +126,19 @@ __device__ __forceinline__ void lml_grad_body(const KParams& p, int n_theta, con
         if (ga == gb) tq += q;
       }
       const double z = s[r][c];
-      if (p.kernel == GPMI_KERNEL_SE) {
+      if (MATERN) {
+        double C, g;
+        matern_cg(p.kernel == GPMI_KERNEL_M32, z, C, g);
+        double K = p.a2 * C;
+        if (ga == gb) K = p.a2 * (C + 1e-12);
+        g_amp = fma(w, 2.0 * K, g_amp);   // dK/d ln a = 2 K
+        wk[r][c] = w * (p.a2 * g);        // dK/d ln l_k = a^2 g dx_k^2 / l_k^2; no shape parameter
+      } else if (p.kernel == GPMI_KERNEL_SE) {
         double K = p.a2 * exp(-z);
         if (ga == gb) K = p.a2 * (exp(-z) + 1e-12);
         g_amp = fma(w, 2.0 * K, g_amp);   // dK/d ln a = 2 K            (covariance.py:273)
         wk[r][c] = w * K;                 // dK/d ln l_k = (dx_k^2 / l_k^2) K   (covariance.py:275)
-      } else {
+      } else {  // GPMI_KERNEL_RQ (launch_lml_grad sends the Matern kinds to the other instantiation)
         const double F = 1.0 + z / p.kappa;
         const double lnF = log(F);
         double K = p.a2 * exp(-p.kappa * lnF);  // covariance.py:356-360
@@ -128,7 +151,7 @@ __device__ __forceinline__ void lml_grad_body(const KParams& p, int n_theta, con
   }
   const int64_t tile = (int64_t)ti * (ti + 1) / 2 + tj;
   double* out = ws + tile * (n_theta + 1);
-  const int off = (p.kernel == GPMI_KERNEL_SE) ? 1 : 2;
+  const int off = MATERN ? 1 : (p.kernel == GPMI_KERNEL_SE) ? 1 : 2;  // SE, Matern: [ln a, ln l]; RQ: [ln a, ln kappa, ln l]
   double v = block_sum(g_amp, red);
   if (tid == 0) out[0] = v;
   if (off == 2) {
@@ -269,7 +292,10 @@ __device__ __forceinline__ void sum_grad_body(const CovParams& p, int n_theta, c
   const int nk = __builtin_amdgcn_readfirstlane(p.nk);
   for (int m = 0; m < nk; ++m) {
     const KParams& q = p.comp[m];
-    const bool rq = (__builtin_amdgcn_readfirstlane(q.kernel) == GPMI_KERNEL_RQ);
+    // (make_cov admits four kinds: SE, RQ, Matern32, Matern52; only RQ has a shape parameter)
+    const int kind = __builtin_amdgcn_readfirstlane(q.kernel);
+    const bool rq = (kind == GPMI_KERNEL_RQ);
+    const bool matern = (kind == GPMI_KERNEL_M32 || kind == GPMI_KERNEL_M52);
     double s[4][4];
 #pragma unroll
     for (int r = 0; r < 4; ++r)
@@ -294,12 +320,19 @@ __device__ __forceinline__ void sum_grad_body(const CovParams& p, int n_theta, c
         const int64_t gb = j0 + tx * 4 + c;
         const double z = s[r][c];
         const double wv = w[r][c];
-        if (!rq) {
+        if (matern) {
+          double C, g;
+          matern_cg(kind == GPMI_KERNEL_M32, z, C, g);
+          double K = q.a2 * C;
+          if (ga == gb) K = q.a2 * (C + 1e-12);
+          g_amp = fma(wv, 2.0 * K, g_amp);  // dK_m/d ln a_m = 2 K_m
+          s[r][c] = wv * (q.a2 * g);        // dK_m/d ln l_k = a_m^2 g dx_k^2 / l_k^2
+        } else if (!rq) {  // GPMI_KERNEL_SE
           double K = q.a2 * exp(-z);
           if (ga == gb) K = q.a2 * (exp(-z) + 1e-12);
           g_amp = fma(wv, 2.0 * K, g_amp);  // dK_m/d ln a_m = 2 K_m             (covariance.py:273)
           s[r][c] = wv * K;                 // dK_m/d ln l_k = (dx_k^2 / l_k^2) K_m (covariance.py:275)
-        } else {
+        } else {  // GPMI_KERNEL_RQ
           const double F = 1.0 + z / q.kappa;
           const double lnF = log(F);
           double K = q.a2 * exp(-q.kappa * lnF);  // covariance.py:356-360
@@ -380,10 +413,13 @@ int64_t grad_ws_doubles(int64_t np, int n_theta) {
 void launch_lml_grad(hipStream_t s, const KParams& p, int n_theta, const double* x, int64_t n,
                      int64_t np, const double* iK, int64_t ld, const double* u, const double* v,
                      double* ws, double* out) {
-  assert((p.kernel == GPMI_KERNEL_SE || p.kernel == GPMI_KERNEL_RQ) && "a sum of kernels must be passed as a CovParams");
+  assert(kernel_is_stationary(p.kernel) && "a sum of kernels must be passed as a CovParams");
   const int64_t t = np / KT;
   dim3 grid((unsigned)t, (unsigned)t);
-  hipLaunchKernelGGL(lml_grad_kernel, grid, dim3(256), 0, s, p, n_theta, x, n, iK, ld, u, v, ws);
+  if (kernel_is_matern(p.kernel))
+    hipLaunchKernelGGL(lml_grad_kernel<true>, grid, dim3(256), 0, s, p, n_theta, x, n, iK, ld, u, v, ws);
+  else
+    hipLaunchKernelGGL(lml_grad_kernel<false>, grid, dim3(256), 0, s, p, n_theta, x, n, iK, ld, u, v, ws);
   hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)(n_theta + 1)), dim3(256), 0, s, ws,
                      t * (t + 1) / 2, n_theta + 1, out, (int64_t)0);
 }
@@ -405,13 +441,19 @@ void launch_lml_grad(hipStream_t s, const CovParams& p, int n_theta, const doubl
 
 // B lockstep evaluations: out[z * (n_theta + 1) ..] = gradient and trace of problem z (likelihood gradient: u = v =
 // alpha_z; leave-one-out gradient: u = p_z, v = alpha_z, both with stride sV)
-void launch_lml_grad_batched(hipStream_t s, const KParams* pdev, int batch, int n_theta, const double* x, int64_t n,
-                             int64_t np, const double* iK, int64_t ld, int64_t sK, const double* u, const double* v,
-                             int64_t sV, double* ws, double* out) {
+void launch_lml_grad_batched(hipStream_t s, int kernel, const KParams* pdev, int batch, int n_theta, const double* x,
+                             int64_t n, int64_t np, const double* iK, int64_t ld, int64_t sK, const double* u,
+                             const double* v, int64_t sV, double* ws, double* out) {
+  assert(kernel_is_stationary(kernel) && "a batch of sums is an array of CovParams");
   const int64_t t = np / KT;
   const int64_t sW = grad_ws_doubles(np, n_theta);
   dim3 grid((unsigned)t, (unsigned)t, (unsigned)batch);
-  hipLaunchKernelGGL(lml_grad_batched_kernel, grid, dim3(256), 0, s, pdev, n_theta, x, n, iK, ld, u, v, ws, sK, sV, sW);
+  if (kernel_is_matern(kernel))
+    hipLaunchKernelGGL(lml_grad_batched_kernel<true>, grid, dim3(256), 0, s, pdev, n_theta, x, n, iK, ld, u, v, ws, sK, sV,
+                       sW);
+  else
+    hipLaunchKernelGGL(lml_grad_batched_kernel<false>, grid, dim3(256), 0, s, pdev, n_theta, x, n, iK, ld, u, v, ws, sK, sV,
+                       sW);
   hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)(n_theta + 1), 1, (unsigned)batch), dim3(256), 0, s, ws,
                      t * (t + 1) / 2, n_theta + 1, out, sW);
 }

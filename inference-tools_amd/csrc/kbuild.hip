@@ -1,4 +1,4 @@
-// Covariance-matrix build for SquaredExponential / RationalQuadratic on gfx950.
+// Covariance-matrix build for SquaredExponential / RationalQuadratic / Matern32 / Matern52 on gfx950.
 //
 // Replaces the reference's N x N x d broadcast tensors (covariance.py:218-219, 254, 315-316, 347)
 // by a tiled kernel: a workgroup stages the two 64-point panels in LDS (transposed, [dim][point]) and
@@ -13,6 +13,11 @@ namespace {
 
 constexpr int KT = 64;  // output tile edge
 
+// kinds of kfun beyond the public kernel ids: the Matern derivative profiles g (kmath.h: matern_profile; the cross build
+// of a^2 g for the predictive-gradient kernels, launch_kbuild_cross_dprofile)
+constexpr int KFUN_M32_G = 0x100 | GPMI_KERNEL_M32;
+constexpr int KFUN_M52_G = 0x100 | GPMI_KERNEL_M52;
+
 // Covariance function of N elements at once (kmath.h: a thread's elements go through exp / log1p in lockstep, so a
 // polynomial coefficient is fetched once per N FMAs; the library's exp() inlined per element re-materialised its
 // constants at every use - as many v_mov_b32 as arithmetic - and its pow() is ~300 instructions per element).
@@ -20,11 +25,24 @@ constexpr int KT = 64;  // output tile edge
 // instruction cache two CUs share.   s = sum_k 0.5 * dx_k^2 / l_k^2  (>= 0)
 template <int KERNEL, int N>
 __device__ inline void kfun(const KParams& p, const double (&s)[N], double (&out)[N]) {
+  static_assert(KERNEL == GPMI_KERNEL_SE || KERNEL == GPMI_KERNEL_RQ || KERNEL == GPMI_KERNEL_M32 ||
+                    KERNEL == GPMI_KERNEL_M52 || KERNEL == KFUN_M32_G || KERNEL == KFUN_M52_G,
+                "kfun: no covariance function of this kind");
+  if (KERNEL == GPMI_KERNEL_M32 || KERNEL == GPMI_KERNEL_M52 || KERNEL == KFUN_M32_G || KERNEL == KFUN_M52_G) {
+    // Matern 3/2, 5/2: (1 + t) e^-t, (1 + t + t^2 / 3) e^-t with t = sqrt(4 nu s) - or their derivative profiles
+    constexpr int TWO_NU = (KERNEL == GPMI_KERNEL_M32 || KERNEL == KFUN_M32_G) ? 3 : 5;
+    double other[N];
+    if (KERNEL == KFUN_M32_G || KERNEL == KFUN_M52_G)
+      kmath::matern_profile<TWO_NU>(s, other, out);
+    else
+      kmath::matern_profile<TWO_NU>(s, out, other);
+    return;
+  }
   double e[N];
   if (KERNEL == GPMI_KERNEL_SE) {  // exp(-s)  (covariance.py:254)
 #pragma unroll
     for (int i = 0; i < N; ++i) e[i] = -s[i];
-  } else {  // (1 + s / kappa)^-kappa = exp(-kappa log1p(s / kappa))  (covariance.py:348)
+  } else {  // GPMI_KERNEL_RQ: (1 + s / kappa)^-kappa = exp(-kappa log1p(s / kappa))  (covariance.py:348)
     const double ik = 1.0 / p.kappa;
     double z[N], l[N];
 #pragma unroll
@@ -189,8 +207,8 @@ __global__ void add_full_kernel(double* __restrict__ A, int64_t ld, const double
 // accumulates s_m = sum_k 1/2 dx_k^2 / l_{m,k}^2 with that component's length scales and applies its covariance function
 // (kfun, the same lockstep exp / log1p as the single-kernel build), summing in component order - the order of the
 // reference's sum(...) (covariance.py:94-98).  The component's kind is a uniform run-time branch (one per component and
-// half-block), not a template parameter: one kernel serves all 28 combinations of two to four SE / RQ components instead
-// of 28 instantiations competing for the instruction cache.  The choice rests on that code size: a per-combination
+// half-block), not a template parameter: one kernel serves every combination of two to four SE / RQ / Matern components instead
+// of one instantiation each competing for the instruction cache.  The choice rests on that code size: a per-combination
 // instantiation was not built or timed.  Timings of this form: DESIGN.md (kernel table) and tools/sum_time.py.
 // ksum_body is force-inlined: used by two kernels, the compiler otherwise made it a called function, and the batched
 // kernel then took 248 VGPRs and a scratch spill behind the call (inlined: 130 VGPRs, no scratch, as ksum_kernel).
@@ -260,10 +278,12 @@ __device__ __forceinline__ void ksum_body(const CovParams& p, const double* __re
             sv8[4 * r + c] = fma(0.5 * dx * dx, il2, sv8[4 * r + c]);
           }
       }
-      if (__builtin_amdgcn_readfirstlane(q.kernel) == GPMI_KERNEL_RQ)
-        kfun<GPMI_KERNEL_RQ>(q, sv8, cf8);
-      else
-        kfun<GPMI_KERNEL_SE>(q, sv8, cf8);
+      switch (__builtin_amdgcn_readfirstlane(q.kernel)) {  // (make_cov admits these four kinds only)
+        case GPMI_KERNEL_RQ: kfun<GPMI_KERNEL_RQ>(q, sv8, cf8); break;
+        case GPMI_KERNEL_M32: kfun<GPMI_KERNEL_M32>(q, sv8, cf8); break;
+        case GPMI_KERNEL_M52: kfun<GPMI_KERNEL_M52>(q, sv8, cf8); break;
+        default: kfun<GPMI_KERNEL_SE>(q, sv8, cf8); break;
+      }
       const double a2 = q.a2;
 #pragma unroll
       for (int r = 0; r < 2; ++r)
@@ -329,19 +349,32 @@ __global__ __launch_bounds__(256) void ksum_cross_batched_kernel(const CovParams
 
 static size_t kb_lds_bytes(int d) { return sizeof(double) * 2 * (size_t)d * KT; }
 
-// dispatch on the covariance function (a template parameter of the kernels).  A KParams is one SE / RQ kernel: a sum
+// dispatch on the covariance function (a template parameter of the kernels).  A KParams is one stationary kernel: a sum
 // reaches the builders only as a CovParams (the overloads below), so a KParams whose kind is GPMI_KERNEL_SUM is a sliced
 // copy - a bug of the caller.
 template <bool SQUARE>
 static void launch_kb(dim3 grid, hipStream_t s, const KParams& p, const double* U, int64_t nu, const double* V,
                       int64_t nv, const double* noise, double* out, int64_t ld, int lower_only) {
-  assert((p.kernel == GPMI_KERNEL_SE || p.kernel == GPMI_KERNEL_RQ) && "a sum of kernels must be passed as a CovParams");
-  if (p.kernel == GPMI_KERNEL_SE)
-    hipLaunchKernelGGL((kbuild_kernel<SQUARE, GPMI_KERNEL_SE>), grid, dim3(256), kb_lds_bytes(p.d), s, p, U, nu, V, nv,
-                       noise, out, ld, lower_only);
-  else
-    hipLaunchKernelGGL((kbuild_kernel<SQUARE, GPMI_KERNEL_RQ>), grid, dim3(256), kb_lds_bytes(p.d), s, p, U, nu, V, nv,
-                       noise, out, ld, lower_only);
+  assert(kernel_is_stationary(p.kernel) && "a sum of kernels must be passed as a CovParams");
+  switch (p.kernel) {
+    case GPMI_KERNEL_SE:
+      hipLaunchKernelGGL((kbuild_kernel<SQUARE, GPMI_KERNEL_SE>), grid, dim3(256), kb_lds_bytes(p.d), s, p, U, nu, V, nv,
+                         noise, out, ld, lower_only);
+      break;
+    case GPMI_KERNEL_RQ:
+      hipLaunchKernelGGL((kbuild_kernel<SQUARE, GPMI_KERNEL_RQ>), grid, dim3(256), kb_lds_bytes(p.d), s, p, U, nu, V, nv,
+                         noise, out, ld, lower_only);
+      break;
+    case GPMI_KERNEL_M32:
+      hipLaunchKernelGGL((kbuild_kernel<SQUARE, GPMI_KERNEL_M32>), grid, dim3(256), kb_lds_bytes(p.d), s, p, U, nu, V, nv,
+                         noise, out, ld, lower_only);
+      break;
+    case GPMI_KERNEL_M52:
+      hipLaunchKernelGGL((kbuild_kernel<SQUARE, GPMI_KERNEL_M52>), grid, dim3(256), kb_lds_bytes(p.d), s, p, U, nu, V, nv,
+                         noise, out, ld, lower_only);
+      break;
+    default: break;  // (make_params admits no other kind)
+  }
 }
 
 // a CovParams: the fused build of its sum, or the single-kernel build of its base
@@ -406,15 +439,28 @@ void launch_kbuild_square_part(hipStream_t s, const CovParams& p, const double* 
 void launch_kbuild_square_batched(hipStream_t s, int kernel, const KParams* pdev, int batch, const double* x,
                                   int64_t n, int64_t np, const double* noise, double* A, int64_t ld,
                                   int64_t stride, int d, int64_t noise_stride) {
-  assert((kernel == GPMI_KERNEL_SE || kernel == GPMI_KERNEL_RQ) && "a batch of sums is an array of CovParams");
+  assert(kernel_is_stationary(kernel) && "a batch of sums is an array of CovParams");
   const unsigned nt = (unsigned)(np / KT);
   dim3 grid(nt * (nt + 1) / 2, 1, (unsigned)batch);  // lower tiles only, one-dimensional (kbuild_body, mode 2)
-  if (kernel == GPMI_KERNEL_SE)
-    hipLaunchKernelGGL(kbuild_batched_kernel<GPMI_KERNEL_SE>, grid, dim3(256), kb_lds_bytes(d), s, pdev, x, n, noise, A,
-                       ld, stride, noise_stride);
-  else
-    hipLaunchKernelGGL(kbuild_batched_kernel<GPMI_KERNEL_RQ>, grid, dim3(256), kb_lds_bytes(d), s, pdev, x, n, noise, A,
-                       ld, stride, noise_stride);
+  switch (kernel) {
+    case GPMI_KERNEL_SE:
+      hipLaunchKernelGGL(kbuild_batched_kernel<GPMI_KERNEL_SE>, grid, dim3(256), kb_lds_bytes(d), s, pdev, x, n, noise, A,
+                         ld, stride, noise_stride);
+      break;
+    case GPMI_KERNEL_RQ:
+      hipLaunchKernelGGL(kbuild_batched_kernel<GPMI_KERNEL_RQ>, grid, dim3(256), kb_lds_bytes(d), s, pdev, x, n, noise, A,
+                         ld, stride, noise_stride);
+      break;
+    case GPMI_KERNEL_M32:
+      hipLaunchKernelGGL(kbuild_batched_kernel<GPMI_KERNEL_M32>, grid, dim3(256), kb_lds_bytes(d), s, pdev, x, n, noise, A,
+                         ld, stride, noise_stride);
+      break;
+    case GPMI_KERNEL_M52:
+      hipLaunchKernelGGL(kbuild_batched_kernel<GPMI_KERNEL_M52>, grid, dim3(256), kb_lds_bytes(d), s, pdev, x, n, noise, A,
+                         ld, stride, noise_stride);
+      break;
+    default: break;
+  }
 }
 
 // a batch of sums (every pdev[z] of kind GPMI_KERNEL_SUM; the data variances are shared)
@@ -434,19 +480,45 @@ void launch_kbuild_cross(hipStream_t s, const CovParams& p, const double* U, int
   kbuild_cross(s, p, U, mu, mp, V, n, np, out, ld);
 }
 
+// a^2 g in the place of K = a^2 C: kbuild_body with the derivative profile as its covariance function
+void launch_kbuild_cross_dprofile(hipStream_t s, const KParams& p, const double* U, int64_t mu, int64_t mp,
+                                  const double* V, int64_t n, int64_t np, double* out, int64_t ld) {
+  assert(kernel_is_matern(p.kernel) && "derivative-profile rows exist for the Matern kernels only");
+  dim3 grid((unsigned)(np / KT), (unsigned)(mp / KT));
+  if (p.kernel == GPMI_KERNEL_M32)
+    hipLaunchKernelGGL((kbuild_kernel<false, KFUN_M32_G>), grid, dim3(256), kb_lds_bytes(p.d), s, p, U, mu, V, n, nullptr,
+                       out, ld, 0);
+  else if (p.kernel == GPMI_KERNEL_M52)
+    hipLaunchKernelGGL((kbuild_kernel<false, KFUN_M52_G>), grid, dim3(256), kb_lds_bytes(p.d), s, p, U, mu, V, n, nullptr,
+                       out, ld, 0);
+}
+
 // lockstep batch: K*_z (mp x ld, mu valid rows against the n valid rows of V) for problem z of `batch`, `stride` doubles
 // apart; one panel of query points per launch (the caller bounds mp: gpmi_predict_batch)
 void launch_kbuild_cross_batched(hipStream_t s, int kernel, const KParams* pdev, int batch, const double* U, int64_t mu,
                                  int64_t mp, const double* V, int64_t n, int64_t np, double* out, int64_t ld,
                                  int64_t stride, int d) {
-  assert((kernel == GPMI_KERNEL_SE || kernel == GPMI_KERNEL_RQ) && "a batch of sums is an array of CovParams");
+  assert(kernel_is_stationary(kernel) && "a batch of sums is an array of CovParams");
   dim3 grid((unsigned)(np / KT), (unsigned)(mp / KT), (unsigned)batch);
-  if (kernel == GPMI_KERNEL_SE)
-    hipLaunchKernelGGL(kbuild_cross_batched_kernel<GPMI_KERNEL_SE>, grid, dim3(256), kb_lds_bytes(d), s, pdev, U, mu, V, n,
-                       out, ld, stride);
-  else
-    hipLaunchKernelGGL(kbuild_cross_batched_kernel<GPMI_KERNEL_RQ>, grid, dim3(256), kb_lds_bytes(d), s, pdev, U, mu, V, n,
-                       out, ld, stride);
+  switch (kernel) {
+    case GPMI_KERNEL_SE:
+      hipLaunchKernelGGL(kbuild_cross_batched_kernel<GPMI_KERNEL_SE>, grid, dim3(256), kb_lds_bytes(d), s, pdev, U, mu, V,
+                         n, out, ld, stride);
+      break;
+    case GPMI_KERNEL_RQ:
+      hipLaunchKernelGGL(kbuild_cross_batched_kernel<GPMI_KERNEL_RQ>, grid, dim3(256), kb_lds_bytes(d), s, pdev, U, mu, V,
+                         n, out, ld, stride);
+      break;
+    case GPMI_KERNEL_M32:
+      hipLaunchKernelGGL(kbuild_cross_batched_kernel<GPMI_KERNEL_M32>, grid, dim3(256), kb_lds_bytes(d), s, pdev, U, mu, V,
+                         n, out, ld, stride);
+      break;
+    case GPMI_KERNEL_M52:
+      hipLaunchKernelGGL(kbuild_cross_batched_kernel<GPMI_KERNEL_M52>, grid, dim3(256), kb_lds_bytes(d), s, pdev, U, mu, V,
+                         n, out, ld, stride);
+      break;
+    default: break;
+  }
 }
 void launch_kbuild_cross_batched(hipStream_t s, const CovParams* pdev, int batch, const double* U, int64_t mu, int64_t mp,
                                  const double* V, int64_t n, int64_t np, double* out, int64_t ld, int64_t stride, int d) {

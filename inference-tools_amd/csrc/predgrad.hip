@@ -1,11 +1,14 @@
-// Spatial-gradient kernels of the GP predictor (SquaredExponential only, as in the reference:
-// RationalQuadratic has no gradient_terms, covariance.py:38-44).
+// Spatial-gradient kernels of the GP predictor (SquaredExponential as in the reference - RationalQuadratic has no
+// gradient_terms, covariance.py:38-44 - and the Matern kernels).
 //
 // Replace the per-point loops of GpRegressor.gradient (regression.py:351-385) and
 // GpRegressor.spatial_derivatives (regression.py:387-419) by batched kernels over M query points:
 //   A_in = (x_n,i - q_i) / l_i^2         (gradient_terms, covariance.py:257-266)
 //   dmu_i   = sum_n A_in k_n alpha_n                       dvar_i = -2 sum_n A_in k_n (K^-1 k)_n
 //   cov_ij  = R_j - sum_n Q_in Q_jn,  Q = L^-1 (A o k)^T,  R_j = (a / l_j)^2
+// Matern: dK(q, x_n) / dq_i = a^2 g (x_n - q)_i / l_i^2 - SE's expression with the derivative profile a^2 g (kmath.h:
+// matern_profile) in the place of k_n.  The kernels are the same: the caller hands them rows of a^2 g as Kq
+// (launch_kbuild_cross_dprofile), and R_j = g(0) (a / l_j)^2 with g(0) = 3 and 5/3 (launch_grad_cov).
 #include "gpmi_internal.h"
 
 namespace {
@@ -100,5 +103,10 @@ void launch_grad_rhs(hipStream_t s, const KParams& p, const double* x, int64_t n
 
 void launch_grad_cov(hipStream_t s, const KParams& p, const double* G, int64_t ld, int64_t np,
                      int64_t m, double* cov) {
-  hipLaunchKernelGGL(grad_cov_kernel, dim3((unsigned)m), dim3(256), 0, s, p, G, ld, np, cov);
+  // R_j = g(0) a^2 / l_j^2, the prior variance of the derivative along axis j: the kernel forms a2 * inv_l2[j], so g(0)
+  // goes into its copy of a2 (SE: g = K / a^2, g(0) = 1 - the parameters as they are)
+  KParams pr = p;
+  if (p.kernel == GPMI_KERNEL_M32) pr.a2 = 3.0 * p.a2;
+  if (p.kernel == GPMI_KERNEL_M52) pr.a2 = (5.0 / 3.0) * p.a2;
+  hipLaunchKernelGGL(grad_cov_kernel, dim3((unsigned)m), dim3(256), 0, s, pr, G, ld, np, cov);
 }

@@ -20,7 +20,9 @@ LIB_PATH = os.environ.get("GPMI_LIB") or os.path.join(_HERE, "lib", "libgpmi.so"
 
 KERNEL_SE = 0
 KERNEL_RQ = 1
-KERNEL_SUM = 2  # GPMI_KERNEL_SUM: a sum of SE / RQ kernels declared by gpmi_set_sum
+KERNEL_SUM = 2  # GPMI_KERNEL_SUM: a sum of stationary kernels declared by gpmi_set_sum
+KERNEL_M32 = 3  # GPMI_KERNEL_M32 / _M52: Matern 3/2 and 5/2, theta laid out as for SE
+KERNEL_M52 = 4
 PROF_KBUILD, PROF_SYRK, PROF_PANEL, PROF_SOLVE, PROF_SYRK_REST, PROF_TRSM, PROF_SYRK_SLICE, PROF_FLOW = 0, 1, 2, 3, 4, 5, 6, 7
 OPT_LOCKSTEP_ALWAYS, OPT_RESERVE_POINTS, OPT_NO_FLOW = 1, 2, 3
 PREDICT_PANEL = 256  # GPMI_PREDICT_PANEL: query points per panel of gpmi_predict_batch

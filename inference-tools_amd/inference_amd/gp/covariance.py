@@ -82,7 +82,7 @@ def _pairwise_abs_mean_and_range(col: ndarray):
 
 
 class _StationaryDeviceKernel(CovarianceFunction):
-    """Shared machinery of the two device-resident stationary kernels."""
+    """Shared machinery of the device-resident stationary kernels."""
 
     _gpmi_kernel = None  # GPMI_KERNEL_* id
     _n_shape_params = 0  # parameters between the amplitude and the length-scales
@@ -224,6 +224,97 @@ class RationalQuadratic(_StationaryDeviceKernel):
         return K, grads
 
 
+class _Matern(_StationaryDeviceKernel):
+    r"""Matern kernels of half-integer order (no counterpart in the reference).  With
+    t = sqrt(2 nu) r, r^2 = sum_i ((u_i - v_i) / l_i)^2 and theta = [ln A, ln l_1 .. ln l_n] as for SquaredExponential:
+
+       K = A^2 C(t),   dK/d ln A = 2 K,   dK/d ln l_k = A^2 g(t) ((u_k - v_k) / l_k)^2,
+       dK(q, x)/dq_k = A^2 g(t) (x - q)_k / l_k^2
+
+    with the value profile C and the derivative profile g of the subclass - no division by r anywhere, so the
+    expressions are finite and correct at coincident points."""
+
+    _n_shape_params = 0
+    _two_nu = None
+    _name = None
+
+    def _labels(self, d):
+        return [f"{self._name} log-amplitude"] + [f"{self._name} log-scale {i}" for i in range(d)]
+
+    def estimate_hyperpar_bounds(self, y: ndarray):
+        s = log(y.std())
+        self.bounds = [(s - 4, s + 4)] + self._scale_bounds()
+
+    @staticmethod
+    def _profiles(t):
+        """(C, g) at t."""
+        raise NotImplementedError
+
+    def gradient_terms(self, v: ndarray, x: ndarray, theta: ndarray):
+        """(A, R) of the predictive-gradient expressions in SquaredExponential's shapes: A (d, N) with
+        A_kn k_n = dK(v, x_n)/dv_k, i.e. A = ((x - v) / l^2)^T rho(t), rho = g / C, and R = g(0) (a / l)^2, the prior
+        variance of the derivative along each axis."""
+        a = exp(theta[0])
+        scales = exp(theta[1:])
+        diff = x - v[None, :]
+        t = np.sqrt(self._two_nu * ((diff / scales[None, :]) ** 2).sum(axis=1))
+        t = np.minimum(t, 700.0)  # rho is algebraic in t; beyond this k_n is 0 and the term with it
+        C, g = self._profiles(t)
+        A = (diff / scales[None, :] ** 2) * (g / C)[:, None]
+        return A.T, self._profiles(0.0)[1] * (a / scales) ** 2
+
+    def covariance_and_gradients(self, theta: ndarray):
+        """K and dK/dtheta_j as dense matrices.  The regressor never calls this (its LML gradient contracts dK on the
+        fly on the device); it is provided for plugin users and is O(N^2 d) in memory."""
+        K = self.build_covariance(theta)
+        a2 = exp(2.0 * theta[0])
+        scales = exp(theta[1:])
+        u2 = [((self.x[:, None, i] - self.x[None, :, i]) / l) ** 2 for i, l in enumerate(scales)]
+        G = a2 * self._profiles(np.sqrt(self._two_nu * sum(u2)))[1]
+        return K, [2.0 * K] + [G * u for u in u2]
+
+
+class Matern32(_Matern):
+    r"""
+    Matern covariance of order 3/2 (once differentiable sample paths)
+
+       K(u, v) = A^2 (1 + t) exp(-t),   t = sqrt(3 sum_i ((u_i - v_i) / l_i)^2),   theta = [ln A, ln l_1 .. ln l_n]
+
+    :param hyperpar_bounds: optional list of (lower, upper) tuples, one per parameter;
+        estimated from the data when omitted.
+    """
+
+    _gpmi_kernel = _lib.KERNEL_M32
+    _two_nu = 3
+    _name = "Matern32"
+
+    @staticmethod
+    def _profiles(t):
+        e = exp(-t)
+        return (1.0 + t) * e, 3.0 * e
+
+
+class Matern52(_Matern):
+    r"""
+    Matern covariance of order 5/2 (twice differentiable sample paths; the usual choice for Bayesian optimisation)
+
+       K(u, v) = A^2 (1 + t + t^2 / 3) exp(-t),   t = sqrt(5 sum_i ((u_i - v_i) / l_i)^2),
+       theta = [ln A, ln l_1 .. ln l_n]
+
+    :param hyperpar_bounds: optional list of (lower, upper) tuples, one per parameter;
+        estimated from the data when omitted.
+    """
+
+    _gpmi_kernel = _lib.KERNEL_M52
+    _two_nu = 5
+    _name = "Matern52"
+
+    @staticmethod
+    def _profiles(t):
+        e = exp(-t)
+        return (1.0 + t + t * t / 3.0) * e, (5.0 / 3.0) * (1.0 + t) * e
+
+
 class WhiteNoise(CovarianceFunction):
     r"""
     Independent Gaussian noise, K = delta_ij sigma_n^2 with theta = [ln sigma_n]
@@ -355,7 +446,7 @@ class ChangePoint(CovarianceFunction):
     `gpmi_lml_grad_mix`, `gpmi_predict_mix`); the weights cost O(N) and are formed here.
 
     :param kernels: the kernels of the regions, instances or classes (device path: SquaredExponential /
-        RationalQuadratic, at most four).
+        RationalQuadratic / Matern32 / Matern52, at most four).
     :param axis: the spatial axis along which the regions follow each other.
     :param location_bounds, width_bounds: optional (lower, upper) pairs, one per change-point.
     """
@@ -479,7 +570,7 @@ def device_plan(cov):
     """How `GpRegressor` maps a covariance object onto the device kernels:
     returns (kernel_id, main_component, slice_of_its_theta, white_noise_index or None)
     or None when the object is not a supported combination: one stationary kernel (SquaredExponential /
-    RationalQuadratic) or one ChangePoint over such kernels (kernel_id -1), optionally plus one WhiteNoise
+    RationalQuadratic / Matern32 / Matern52) or one ChangePoint over such kernels (kernel_id -1), optionally plus one WhiteNoise
     and / or one HeteroscedasticNoise (see `heteroscedastic_slice`); or a sum of 2 to 4 stationary kernels with at
     most one WhiteNoise, in any order (kernel_id `_lib.KERNEL_SUM`: the main component is the CompositeCovariance
     itself, the "slice" an index array that gathers the stationary components' parameters in component order, and

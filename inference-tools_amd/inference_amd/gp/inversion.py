@@ -72,12 +72,12 @@ class GpLinearInverter:
         self.cov_slice = slice(self.mean.n_params, self.n_hyperpars)
         self.hyperpar_labels = [*self.mean.hyperpar_labels, *self.cov.hyperpar_labels]
 
-        # SquaredExponential / RationalQuadratic (+ WhiteNoise) priors are built on the device; for any other
+        # SquaredExponential / RationalQuadratic / Matern32 / Matern52 (+ WhiteNoise) priors are built on the device; for any other
         # CovarianceFunction object (the reference takes any, inversion.py:117-127) the host evaluates the object's
         # own build_covariance / covariance_and_gradients and the device does every O(n^3) step (gpmi_linv_*_dense)
         plan = device_plan(self.cov)
         # (-1: ChangePoint mixture, _lib.KERNEL_SUM: a sum of stationary kernels - both through the dense path)
-        self._dense = (plan is None or plan[0] not in (_lib.KERNEL_SE, _lib.KERNEL_RQ)
+        self._dense = (plan is None or plan[0] not in (_lib.KERNEL_SE, _lib.KERNEL_RQ, _lib.KERNEL_M32, _lib.KERNEL_M52)
                        or heteroscedastic_slice(self.cov) is not None)
         if not self._dense:
             self._kernel_id, self._stat, self._stat_slice, self._wn_index = plan

@@ -550,8 +550,9 @@ class GpRegressor:
             return
         if self._mix is not None:
             self._mix.gradient_terms(None, None, None)  # ChangePoint has none either (covariance.py:38-44)
-        if self._kernel_id != 0:
-            # RationalQuadratic has no gradient_terms (covariance.py:38-44): same error as the reference
+        if self._kernel_id not in (_lib.KERNEL_SE, _lib.KERNEL_M32, _lib.KERNEL_M52):
+            # the device has predictive-gradient kernels for these three; RationalQuadratic and sums have no
+            # gradient_terms (covariance.py:38-44): same error as the reference
             self._stat.gradient_terms(None, None, None)
 
     def gradient(self, points: ndarray):
