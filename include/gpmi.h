@@ -81,6 +81,10 @@ int gpmi_sync(gpmi_ctx* ctx);
  * reference are never formed.
  *   noise_var_host : n values y_err**2 (regression.py:320) or NULL for zeros (regression.py:322)
  *   y_cov_host     : dense n x n y-covariance (regression.py:262-293) or NULL; replaces noise_var
+ * Limit: 1 <= d <= 64 spatial dimensions (the reference has no such limit).  The covariance kernels stage two
+ * [d][64] point panels in LDS - 64 KiB at d = 64 - and carry the d length scales by value.  A larger d returns
+ * GPMI_ERR_ARG with a message that names the limit, before anything is released: the handle keeps the data set and
+ * the fit it had and takes the next gpmi_set_data.
  */
 int gpmi_set_data(gpmi_ctx* ctx, const double* x_host, const double* y_host,
                   const double* noise_var_host, const double* y_cov_host, int64_t n, int64_t d);

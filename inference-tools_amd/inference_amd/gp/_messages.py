@@ -68,6 +68,15 @@ def points_wrong_width(n_dim, shape):
                   f"The input data have {n_dim} dimensions but 'points' has shape {shape}.")
 
 
+MAX_DIMENSIONS = 64  # GPMI_MAX_D (csrc/gpmi_internal.h): gpmi_set_data refuses more
+
+
+def too_many_dimensions(owner, d):
+    """An extension of this package: the reference has no such limit.  Raised before any device context exists."""
+    return framed(owner, "error", f"The input data have {d} spatial dimensions, but the device kernels",
+                  f"handle at most {MAX_DIMENSIONS} (GPMI_MAX_D).")
+
+
 def no_device_kernel(cov_type):
     return framed("GpRegressor", "error", f"The covariance function {cov_type} has no MI355X device kernel.",
                   "Supported: SquaredExponential, RationalQuadratic, each optionally + WhiteNoise().")

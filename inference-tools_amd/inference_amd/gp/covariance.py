@@ -24,6 +24,7 @@ import numpy as np
 from numpy import exp, log, ndarray
 
 from inference_amd import _lib
+from inference_amd.gp import _messages as msg
 
 
 class CovarianceFunction(ABC):
@@ -93,6 +94,8 @@ class _StationaryDeviceKernel(CovarianceFunction):
         self._engine = None
 
     def pass_spatial_data(self, x: ndarray):
+        if np.ndim(x) == 2 and np.shape(x)[1] > msg.MAX_DIMENSIONS:
+            raise ValueError(msg.too_many_dimensions(type(self).__name__, np.shape(x)[1]))
         self.x = np.ascontiguousarray(x, dtype=float)
         if self._engine is not None:
             self._engine.close()

@@ -79,6 +79,8 @@ class GpRegressor:
         self._diffev_batched = bool(diffev_batched)
         self.n_points = self.y.size
         self.n_dimensions = self.x.shape[1]
+        if self.n_dimensions > msg.MAX_DIMENSIONS:  # gpmi_set_data would refuse the upload (also a plugin kernel's)
+            raise ValueError(msg.too_many_dimensions("GpRegressor", self.n_dimensions))
 
         # data-error covariance: kept as a variance vector or the dense matrix the user gave
         self._noise_var, self._y_cov = self.check_error_data(y_err, y_cov)
