@@ -562,6 +562,34 @@ int gpmi_acf_columns(gpmi_ctx* ctx, int64_t n, int64_t m, int64_t row_stride, in
  * NULL, the first `cap` of them (fewer than *count: GPMI_ERR_ARG). */
 int gpmi_acf_lag_blocks(int64_t n, int64_t cap, int64_t* starts_host, int64_t* count);
 
+/* ---- covariance matrix of the columns of a sample (inference/mcmc/pca.py:98-108: numpy.cov) ----
+ * What numpy.cov(sample.T) computes for m columns of n rows, in two passes on the device:
+ *   mean_host[c] = fl(sum over t of x[t][c] / n),   y = x - mean in fp64,   S = y^T y on the fp64 matrix cores,
+ *   cov_host[i * m + j] = S[i][j] * fl(1.0 / (n - 1))           (a product with the rounded reciprocal, as NumPy's)
+ * The rows are cut into chunks of GPMI_COV_CHUNK_ROWS.  A column's sum is reduced in a fixed order (inside a chunk four
+ * interleaved partial sums over ascending rows, added in order; then the chunks in ascending order), and S[i][j] is one
+ * chain of 16 x 16 x 4 matrix-core accumulations over the rows of a chunk, from its first row on, and one chain of
+ * additions over the chunks in ascending order, without atomics.  Both orders are fixed by n alone, so
+ *   - cov[i][j] depends on columns i and j and on n alone: it has the same bits when the two columns are passed alone,
+ *     inside any batch, at any column position, in either layout, under any ws_bytes and on repeated calls;
+ *   - cov is symmetric bit for bit (the upper triangle is computed and mirrored);
+ *   - integer-valued data whose column sums are multiples of n (and stay below 2^53) has an exact mean, and with
+ *     |S| < 2^53 the whole result is NumPy's bit for bit.
+ * flag_host[c] is 1 if column c holds a NaN or an infinity, else 0: the rows and columns of cov that involve a flagged
+ * column are unspecified (the kernels stay in bounds and terminate on it); the others are not affected.
+ * Layouts and strides are those of gpmi_hdi_columns: (ld, 1) with ld >= m (C order) or (1, ld) with ld >= n, both read
+ * by the kernels as they lie; m = 1 with row_stride = 1 is one contiguous run.  2 <= n <= 2^30 and 1 <= m <= 512;
+ * anything else is GPMI_ERR_ARG with an error text, and the handle stays usable.
+ * Device memory: the sample (8 n m bytes), 12 ceil(n / GPMI_COV_CHUNK_ROWS) mp for the chunk sums (mp = m rounded up to
+ * 64) and a few tiles belong to the handle's workspace and are kept for later calls.  ws_bytes (0: 1 GiB) caps the
+ * partial tiles alone: a chunk costs 32768 T (T + 1) / 2 bytes (T = mp / 64), and the chunks are walked in groups that
+ * fit the cap - the bits do not change.  If one chunk does not fit the cap the call is GPMI_ERR_ARG and the text says so.
+ * Synchronous on the stream of the density entry points above, and serialised by the caller in the same way. */
+#define GPMI_COV_CHUNK_ROWS 2048
+int gpmi_cov_columns(gpmi_ctx* ctx, int64_t n, int64_t m, int64_t row_stride, int64_t col_stride,
+                     const double* sample_host, int64_t ws_bytes, double* mean_host /* m */,
+                     double* cov_host /* m x m, row-major */, int32_t* flag_host /* m */);
+
 /* ---- instrumentation ---------------------------------------------------------------
  * HIP-event timing on the handle's own stream (torch.cuda.Event would not see it). */
 int gpmi_timer_start(gpmi_ctx* ctx);
@@ -587,7 +615,9 @@ int gpmi_flow_task_lists(int m, int nwg, int64_t cap, int32_t* out, int64_t* nta
 #define GPMI_PROF_FLOW 7    /* the flag-ordered tile-task launch of the chain-bound part of a factorisation (potrf_flow.hip):
                                FLOPs of its update tasks over the launch's whole duration - it waits for the panel
                                chain most of the time, so this is the overlap achieved, not a kernel rate */
-#define GPMI_PROF_NCLASS 8
+#define GPMI_PROF_COV 8     /* the kernels of gpmi_cov_columns, from the column sums to the scaled covariance, without the
+                               copies to and from the device (HBM-read bound: the sample is read twice) */
+#define GPMI_PROF_NCLASS 9
 /* on = 0: off; 1: every class; otherwise a class bitmask shifted left by one (2 << klass) */
 int gpmi_profile_enable(gpmi_ctx* ctx, int on);
 /* accumulated since the last reset: launches, total ms, algorithmic flops and bytes */

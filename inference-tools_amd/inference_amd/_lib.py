@@ -24,10 +24,13 @@ KERNEL_SUM = 2  # GPMI_KERNEL_SUM: a sum of stationary kernels declared by gpmi_
 KERNEL_M32 = 3  # GPMI_KERNEL_M32 / _M52: Matern 3/2 and 5/2, theta laid out as for SE
 KERNEL_M52 = 4
 PROF_KBUILD, PROF_SYRK, PROF_PANEL, PROF_SOLVE, PROF_SYRK_REST, PROF_TRSM, PROF_SYRK_SLICE, PROF_FLOW = 0, 1, 2, 3, 4, 5, 6, 7
+PROF_COV = 8  # GPMI_PROF_COV: the kernels of gpmi_cov_columns without the copies
 OPT_LOCKSTEP_ALWAYS, OPT_RESERVE_POINTS, OPT_NO_FLOW = 1, 2, 3
 PREDICT_PANEL = 256  # GPMI_PREDICT_PANEL: query points per panel of gpmi_predict_batch
 _TRACE_MS = float(os.environ["GPMI_TRACE_CALLS"]) if os.environ.get("GPMI_TRACE_CALLS") else None
 ERR_INTERNAL = -5  # GPMI_ERR_INTERNAL
+COV_CHUNK_ROWS = 2048  # GPMI_COV_CHUNK_ROWS: rows per chunk of gpmi_cov_columns
+COV_MAX_COLUMNS = 512  # the most columns gpmi_cov_columns takes
 
 
 class GpmiUnavailable(RuntimeError):
@@ -127,6 +130,7 @@ SIGNATURES = {
                                    C.POINTER(C.c_int32)]),
     "gpmi_acf_columns": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _dp, _i64, _dp, _dp, C.POINTER(_i64),
                                    C.POINTER(C.c_int32)]),
+    "gpmi_cov_columns": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _dp, _i64, _dp, _dp, C.POINTER(C.c_int32)]),
     "gpmi_acf_lag_blocks": (C.c_int, [_i64, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
     "gpmi_timer_start": (C.c_int, [_vp]),
     "gpmi_timer_stop": (C.c_int, [_vp, C.POINTER(C.c_float)]),

@@ -149,12 +149,19 @@ class GibbsChain(MarkovChain):
         p_new = p_old
         for i, par in enumerate(self.params):
             while True:
-                prop[i] = par.proposal()
+                prop = self._propose(prop, i)
                 p_new = self.posterior(prop) * self.inv_temp
                 if self._mh_test(par, p_new, p_old):
                     break
             p_old = p_new
         self._commit(prop, p_new)
+
+    def _propose(self, prop, par: int):
+        """The next proposal of the step in progress, for the update of parameter `par`: `prop`, the point the step has
+        reached, with a new value of that parameter.  The seam through which the lockstep drivers ask a chain for its
+        proposals (`PcaChain` proposes a whole vector along a direction instead)."""
+        prop[par] = self.params[par].proposal()
+        return prop
 
     def _mh_test(self, par, p_new, p_old) -> bool:
         if p_new > p_old:
@@ -307,7 +314,7 @@ def advance_lockstep(chains, n: int, batch_posterior):
 
     `batch_posterior(thetas (B, P)) -> (B,)` must agree element-wise with each chain's own
     `posterior`.  Every round, every chain that still has work proposes a value for ITS current
-    parameter and all proposals are evaluated in one call; a chain whose proposal is accepted moves
+    parameter (`chain._propose`: `GibbsChain`s and `PcaChain`s may be mixed) and all proposals are evaluated in one call; a chain whose proposal is accepted moves
     on to its next parameter (and its next step) at once, one whose proposal is rejected retries
     (the retry-until-accept loop of gibbs.py:635-648).  Chains therefore drift apart inside a call
     and only meet again at its end - a chain draws from its own generators only and never sees the
@@ -326,7 +333,7 @@ def advance_lockstep(chains, n: int, batch_posterior):
     active = list(range(len(chains)))
     while active:
         for c in active:
-            prop[c][par[c]] = chains[c].params[par[c]].proposal()
+            prop[c] = chains[c]._propose(prop[c], par[c])
         vals = batch_posterior(array([prop[c] for c in active]))
         evals += len(active)
         still = []

@@ -361,7 +361,7 @@ def advance_ladders(ladders, n: int, swap_interval=10, batch_posterior=None):
                 held = []
                 continue
             for c in active:
-                prop[c][par[c]] = chains[c].params[par[c]].proposal()
+                prop[c] = chains[c]._propose(prop[c], par[c])
             vals = bp(array([prop[c] for c in active]))
             evals += len(active)
             active, ended = _settle(active, vals)
@@ -403,7 +403,7 @@ def advance_ladders(ladders, n: int, swap_interval=10, batch_posterior=None):
                 while ready and free:
                     g = ready.popleft()
                     for c in act[g]:
-                        prop[c][par[c]] = chains[c].params[par[c]].proposal()
+                        prop[c] = chains[c]._propose(prop[c], par[c])
                     slot = free.pop(0)
                     model.marginal_likelihood_batch_submit(array([prop[c] for c in act[g]]), slot)
                     flying.append((slot, g))
@@ -428,7 +428,7 @@ def advance_ladders(ladders, n: int, swap_interval=10, batch_posterior=None):
         return evals
     while active:
         for c in active:
-            prop[c][par[c]] = chains[c].params[par[c]].proposal()
+            prop[c] = chains[c]._propose(prop[c], par[c])
         vals = bp(array([prop[c] for c in active]))
         evals += len(active)
         active, _ = _settle(active, vals)

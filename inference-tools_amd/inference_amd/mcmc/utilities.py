@@ -1,7 +1,8 @@
 """Chain diagnostics (reference: mcmc/utilities.py:83-95) and parameter bounds (:98-162).  `effective_sample_size` is
 the host function with the reference's exact semantics; `effective_sample_size_batch` answers every column of a sample
-in one device call (csrc/acf.hip).  `Bounds` holds the box a `HamiltonianChain` is reflected into."""
-from numpy import array, asarray, divmod as np_divmod, empty, float64, int64, ndarray
+in one device call (csrc/acf.hip); `sample_covariance` is numpy.cov of a tall sample on the device (csrc/cov.hip), the
+covariance that `PcaChain` takes its directions from.  `Bounds` holds the box a `HamiltonianChain` is reflected into."""
+from numpy import array, asarray, cov as np_cov, divmod as np_divmod, empty, float64, int64, ndarray
 from numpy.fft import irfft, rfft
 
 from inference_amd.pdf import _device
@@ -57,6 +58,36 @@ def effective_sample_size_batch(sample, *, device=None, details=False):
         else:
             ess[c] = int(n / (total[c] / f0[c]))
     return (ess, f0, total, cut) if details else ess
+
+
+def sample_covariance(sample, *, device=None, return_mean=False):
+    """
+    The covariance matrix of the columns of `sample`, ``numpy.cov(sample.T)``, in one device call.  A 2D sample of shape
+    ``(n, p)`` gives a float64 array of shape ``(p, p)``, a 1D sample (one column) one of shape ``(1, 1)``; with
+    ``return_mean=True`` the return value is ``(cov, mean)`` with the column means, shape ``(p,)``.
+
+    The device takes the means first and then the products of the centred columns on the fp64 matrix cores, in an order
+    of summation that depends on n alone: the entry of two columns has the same bits whatever else is in the sample, the
+    matrix is symmetric bit for bit, and integer-valued data with an exact mean and sums below 2^53 gives NumPy's bits.
+    The sample is converted to float64 (a float32 sample is widened) and read in place when it is dense in either order.
+    It takes at least two rows and at most 512 columns.  If any column holds a NaN or an infinity the whole answer is
+    NumPy's, computed on the host.  There is no host route by size: without a GPU the call raises `GpmiUnavailable`.
+    """
+    s = asarray(sample, dtype=float64)
+    if s.ndim == 1:
+        s = s.reshape(s.size, 1)
+    if s.ndim != 2:
+        raise ValueError("sample_covariance takes a one- or two-dimensional sample")
+    n, p = s.shape
+    if n < 2:
+        raise ValueError(f"sample_covariance needs at least two rows, the sample has {n}")
+    if p < 1 or p > _device.COV_MAX_COLUMNS:
+        raise ValueError(f"sample_covariance takes 1 to {_device.COV_MAX_COLUMNS} columns, the sample has {p}")
+    mean, cov, flags = _device.cov_columns(s, device=device)
+    if flags.any():
+        cov = np_cov(s.T).reshape(p, p)
+        mean = s.mean(axis=0)
+    return (cov, mean) if return_mean else cov
 
 
 class Bounds:

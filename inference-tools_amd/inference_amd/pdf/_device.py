@@ -14,6 +14,9 @@ import numpy as np
 
 from inference_amd import _lib
 
+COV_CHUNK_ROWS = _lib.COV_CHUNK_ROWS
+COV_MAX_COLUMNS = _lib.COV_MAX_COLUMNS
+
 _handles = {}
 _handles_lock = threading.Lock()
 
@@ -218,6 +221,21 @@ def acf_columns(sample2d, device=None, ws_bytes=0):
     _call(h, "gpmi_acf_columns", h.ctx, n, m, rs, cs, s.ctypes.data_as(C.POINTER(C.c_double)), int(ws_bytes),
           _lib.dptr(f0), _lib.dptr(total), _i64(cut), flags.ctypes.data_as(C.POINTER(C.c_int32)))
     return f0, total, cut, flags
+
+
+def cov_columns(sample2d, device=None, ws_bytes=0):
+    """The column means and the covariance matrix of the columns of `sample2d` (n x m, float64, m <= 512), as
+    numpy.cov(sample2d.T) defines it (gpmi_cov_columns, csrc/cov.hip): `mean` (m), `cov` (m, m) and `flags` (m, int32),
+    1 for a column that holds a NaN or an infinity, whose rows and columns of `cov` mean nothing.  The array is read in
+    place under the rules of `hdi_columns`; `ws_bytes` caps the partial tiles on the device (0: the library's default)."""
+    s, n, m, rs, cs = _dense_columns(sample2d, "cov_columns")
+    mean = np.zeros(m)
+    cov = np.zeros((m, m))
+    flags = np.zeros(m, dtype=np.int32)
+    h = handle(device)
+    _call(h, "gpmi_cov_columns", h.ctx, n, m, rs, cs, s.ctypes.data_as(C.POINTER(C.c_double)), int(ws_bytes),
+          _lib.dptr(mean), _lib.dptr(cov), flags.ctypes.data_as(C.POINTER(C.c_int32)))
+    return mean, cov, flags
 
 
 def acf_lag_blocks(n):
