@@ -190,6 +190,28 @@ int ensure_lanes(gpmi_ctx* c, size_t count) {
 
 void linv_free(LinvState& S);
 
+// the lockstep workspace: everything ensure_batch_ws, ensure_batch_grad_ws and the batch entry points allocate per problem
+// (the gradient batches' buffers were left behind at a new data set until round 4: a handle given a second data set of
+// another size kept using the first one's)
+void free_batch_ws(gpmi_ctx* c) {
+  for (double** q : {&c->bA, &c->bInv, &c->bVec, &c->bRed, &c->bMu, &c->bB2, &c->bGws, &c->bGout, &c->bLoo, &c->bQ, &c->bNoise,
+                     &c->bMixG, &c->bMixH, &c->bMixW, &c->bMixExtra}) {
+    if (*q) (void)hipFree(*q);
+    *q = nullptr;
+  }
+  for (void* q : {(void*)c->bMixP, (void*)c->bInfo, (void*)c->bParams, (void*)c->bSum})
+    if (q) (void)hipFree(q);
+  c->bMixP = nullptr;
+  c->bInfo = nullptr;
+  c->bParams = nullptr;
+  c->bSum = nullptr;
+  for (void* q : {(void*)c->h_bGout, (void*)c->h_bRed, (void*)c->h_bInfo})
+    if (q) (void)hipHostFree(q);
+  c->h_bGout = c->h_bRed = nullptr;
+  c->h_bInfo = nullptr;
+  c->bcap = c->bgrad_cap = c->bgrad_ntheta = c->bLoo_cap = c->bNoise_cap = c->bMix_cap = c->bQ_cap = 0;
+}
+
 void free_data(gpmi_ctx* c) {
   linv_free(c->linv);
   for (double** q : {&c->mix_g, &c->mix_scratch, &c->mix_zero, &c->Q3}) {
@@ -213,44 +235,13 @@ void free_data(gpmi_ctx* c) {
   fr(c->Q2);
   fr(c->pts);
   fr(c->pvec);
-  fr(c->bA);
-  fr(c->bInv);
-  fr(c->bVec);
-  fr(c->bRed);
-  fr(c->bMu);
-  fr(c->bB2);  // (the gradient batches' buffers were left behind here until round 4: a handle given a second data set of
-  fr(c->bGws);  //  another size kept using the first one's)
-  fr(c->bGout);
-  fr(c->bLoo);
-  fr(c->bQ);
-  c->bQ_cap = 0;
-  fr(c->bNoise);
-  fr(c->bMixG);
-  fr(c->bMixH);
-  fr(c->bMixW);
-  fr(c->bMixExtra);
-  if (c->bMixP) (void)hipFree(c->bMixP);
-  c->bMixP = nullptr;
-  if (c->h_bGout) (void)hipHostFree(c->h_bGout);
-  c->h_bGout = nullptr;
-  c->bgrad_cap = c->bgrad_ntheta = c->bLoo_cap = c->bNoise_cap = c->bMix_cap = 0;
-  if (c->bInfo) (void)hipFree(c->bInfo);
-  c->bInfo = nullptr;
-  if (c->bParams) (void)hipFree(c->bParams);
-  c->bParams = nullptr;
-  if (c->bSum) (void)hipFree(c->bSum);
-  c->bSum = nullptr;
-  if (c->h_bRed) (void)hipHostFree(c->h_bRed);
-  c->h_bRed = nullptr;
-  if (c->h_bInfo) (void)hipHostFree(c->h_bInfo);
-  c->h_bInfo = nullptr;
+  free_batch_ws(c);
   for (int k = 0; k < 2; ++k) {
     if (c->h_bStage[k]) (void)hipHostFree(c->h_bStage[k]);
     c->h_bStage[k] = nullptr;
     c->h_bStage_bytes[k] = 0;
     c->bpend[k] = 0;
   }
-  c->bcap = 0;
   c->mq_cap = 0;
   c->fitted = false;
   c->n = c->d = c->np = c->ld = 0;
@@ -477,43 +468,7 @@ int ensure_batch_ws(gpmi_ctx* c, int want) {
   if (want <= c->bcap) return GPMI_OK;
   ARGCHK(c, c->bpend[0] == 0 && c->bpend[1] == 0,
          "the batch workspace cannot grow while an asynchronous batch is pending (gpmi_lml_batch_wait first)");
-  auto fr = [](double*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-  };
-  fr(c->bA);
-  fr(c->bInv);
-  fr(c->bVec);
-  fr(c->bRed);
-  fr(c->bMu);
-  fr(c->bB2);
-  fr(c->bGws);
-  fr(c->bGout);
-  fr(c->bLoo);
-  fr(c->bQ);
-  c->bQ_cap = 0;
-  fr(c->bNoise);
-  fr(c->bMixG);
-  fr(c->bMixH);
-  fr(c->bMixW);
-  fr(c->bMixExtra);
-  if (c->bMixP) (void)hipFree(c->bMixP);
-  c->bMixP = nullptr;
-  c->bLoo_cap = c->bNoise_cap = c->bMix_cap = 0;
-  if (c->h_bGout) (void)hipHostFree(c->h_bGout);
-  c->h_bGout = nullptr;
-  c->bgrad_cap = c->bgrad_ntheta = 0;
-  if (c->bInfo) (void)hipFree(c->bInfo);
-  if (c->bParams) (void)hipFree(c->bParams);
-  if (c->bSum) (void)hipFree(c->bSum);
-  if (c->h_bRed) (void)hipHostFree(c->h_bRed);
-  if (c->h_bInfo) (void)hipHostFree(c->h_bInfo);
-  c->bInfo = nullptr;
-  c->bParams = nullptr;
-  c->bSum = nullptr;
-  c->h_bRed = nullptr;
-  c->h_bInfo = nullptr;
-  c->bcap = 0;
+  free_batch_ws(c);
   const int64_t nt = c->np / GPMI_NB;
   HIPCHK(c, hipMalloc(&c->bA, sizeof(double) * want * c->np * c->ld));
   HIPCHK(c, hipMalloc(&c->bInv, sizeof(double) * want * nt * GPMI_NB * GPMI_NB));

@@ -1,7 +1,9 @@
 // Shared by the translation units of the C-ABI (api.hip: handle, lanes, workspaces, lifecycle, instrumentation;
-// api_regression.hip: the GpRegressor entry points; api_mix.hip: ChangePoint mixtures and per-point noise; api_linv.hip:
-// GpLinearInverter; api_dense.hip: plugin covariance functions and the rank-one append): error macros and the helpers
-// every entry point is built from.  Internal - the public interface is include/gpmi.h.
+// api_regression.hip: the GpRegressor entry points; api_mix.hip: ChangePoint mixtures and per-point noise; api_lockstep.hip:
+// the chunk pipeline every lockstep batch entry point of those two runs - Chunk, BatchParams, lockstep_stages, the
+// leave-one-out middle part, the mixture batches' workspace and staging; api_linv.hip: GpLinearInverter; api_dense.hip:
+// plugin covariance functions and the rank-one append): error macros and the helpers every entry point is built from.
+// Internal - the public interface is include/gpmi.h.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -140,7 +142,6 @@ struct RowStage {
     items.push_back({static_cast<char*>(dst), dpitch, off, width, height});
     return GPMI_OK;
   }
-  int flush() { return GPMI_OK; }
   // after the stream has been synchronised
   void finish() {
     const char* base = reinterpret_cast<const char*>(c->h_stage);
@@ -174,6 +175,7 @@ int ensure_second_matrix(gpmi_ctx* c, Lane& L);
 int ensure_inv2(gpmi_ctx* c, Lane& F, hipStream_t s);
 int ensure_trsm_panel(gpmi_ctx* c, int64_t rows);
 int enqueue_inverse_factor(gpmi_ctx* c, Lane& L, Lane& F);
+void free_batch_ws(gpmi_ctx* c);  // every lockstep buffer, caps to 0
 int ensure_batch_ws(gpmi_ctx* c, int want);
 int ensure_batch_grad_ws(gpmi_ctx* c, int want, int n_theta);
 int ensure_query_ws(gpmi_ctx* c, int64_t mp);
@@ -183,3 +185,126 @@ void launch_negate(hipStream_t s, double* v, int64_t n);
 void launch_qdiag(hipStream_t s, const double* iK, int64_t ld, const double* alpha, double* out, int64_t n);
 void launch_qdiag_batched(hipStream_t s, int batch, const double* iK, int64_t ld, const double* alpha, double* out, int64_t n,
                           int64_t sMat, int64_t sVec, int64_t sOut);
+
+// A device buffer of at least `want` elements of `bytes_each`: freed and allocated anew when it is smaller (contents
+// lost).  On failure the pointer is null and the capacity 0.
+template <class P, class N>
+int grow(gpmi_ctx* c, P*& ptr, N& cap, int64_t want, size_t bytes_each) {
+  if (cap >= want) return GPMI_OK;
+  if (ptr) (void)hipFree(ptr);
+  ptr = nullptr;
+  cap = 0;
+  HIPCHK(c, hipMalloc(&ptr, bytes_each * (size_t)want));
+  cap = (N)want;
+  return GPMI_OK;
+}
+
+// T evaluations one at a time (beyond the lockstep sizes): row(t, mu_t) with the mean of evaluation t as n values
+template <class F>
+int one_at_a_time(gpmi_ctx* c, int64_t T, const double* mus, const double* mu_const, F&& row) {
+  std::vector<double> mu_row(mus ? 0 : (size_t)c->n);
+  for (int64_t t = 0; t < T; ++t) {
+    if (!mus) std::fill(mu_row.begin(), mu_row.end(), mu_const[t]);
+    if (int rc = row(t, mus ? mus + t * c->n : mu_row.data())) return rc;
+  }
+  return GPMI_OK;
+}
+
+// ---- api_lockstep.hip: the lockstep batches (np <= 4096; every launch carries a chunk of problems in blockIdx.z) ----
+bool batch_split_enabled();  // GPMI_BATCH_SPLIT=0: a chunk of gpmi_lml_batch / gpmi_predict_batch on one stream (A/B)
+
+// The per-problem parameters of a batch on the host: single kernels (k) or sums (sum, GPMI_KERNEL_SUM), whichever is
+// set.  On the device they live in bParams / bSum, at the chunk's offset.
+struct BatchParams {
+  int kernel;
+  const KParams* k;
+  const CovParams* sum;
+  BatchParams(int kern, const KParams* kp, const CovParams* sp) : kernel(kern), k(sp ? nullptr : kp), sum(sp) {}
+  BatchParams(int kern, const std::vector<KParams>& ps, const std::vector<CovParams>& sps)  // (of make_batch_params)
+      : BatchParams(kern, ps.data(), sps.empty() ? nullptr : sps.data()) {}
+  size_t bytes_each() const { return sum ? sizeof(CovParams) : sizeof(KParams); }
+  const void* host(int64_t t) const { return sum ? static_cast<const void*>(sum + t) : static_cast<const void*>(k + t); }
+  void* device(const gpmi_ctx* c, int off) const {
+    return sum ? static_cast<void*>(c->bSum + off) : static_cast<void*>(c->bParams + off);
+  }
+};
+
+// B problems of the lockstep workspace from problem `off` on, on one stream: off = 0 for the gradient batches, B1 for the
+// second half-batch of gpmi_lml_batch / gpmi_predict_batch, slot * (bcap / 2) for the asynchronous slots.
+struct Chunk {
+  gpmi_ctx* c;
+  hipStream_t stream;
+  int off, B;
+  bool mu_rows;  // Mu holds n prior means per problem (else one constant)
+  BatchShape bs;
+  double *A, *Inv, *Vec, *Mu, *B2, *red;  // B2: with the gradient workspace (ensure_batch_grad_ws)
+  int* info;
+  Chunk(gpmi_ctx* ctx, hipStream_t s, int first, int count, bool mean_rows);
+  // the four work vectors of every problem (bs.sVec apart)
+  double* v() const { return Vec; }                  // L^-1 (y - mu)
+  double* alpha() const { return Vec + c->np; }      // K^-1 (y - mu)
+  double* resid() const { return Vec + 2 * c->np; }  // y - mu: spent after the forward sweep
+  double* slot3() const { return Vec + 3 * c->np; }
+  int clear_info() const;
+  // A <- B2 B2^T, lower tiles (kskip: launch_gemm)
+  void syrk(int kskip) const;
+};
+
+// mixture batches (ChangePoint): K_z = sum_m D_zm K_zm D_zm + noise + extra_z from bMixP / bMixG / bMixExtra.  Those
+// buffers, bMixH / bMixW and the mixture's slots of bGout are indexed from problem 0: a mixture chunk has off == 0.
+struct MixBatch {
+  int nk;
+  const int* kernels;
+  const int* n_thetas;
+  int nrow;  // row sums per sub-kernel: 1 with the sub-kernel's own window weights, 2 with the caller's (hw)
+  int tot_nt = 0, max_nt = 0;
+  MixBatch(int n, const int* kern, const int* nts, bool hw) : nk(n), kernels(kern), n_thetas(nts), nrow(hw ? 2 : 1) {
+    for (int m = 0; m < nk; ++m) {
+      tot_nt += n_thetas[m];
+      max_nt = n_thetas[m] > max_nt ? n_thetas[m] : max_nt;
+    }
+  }
+  int W() const { return max_nt + 1; }  // values per sub-kernel and problem from the contraction
+  int64_t sG(const gpmi_ctx* c) const { return (int64_t)GPMI_MAX_MIX * c->np; }         // between the problems' weight sets
+  int64_t sW(const gpmi_ctx* c) const { return (int64_t)nrow * GPMI_MAX_MIX * c->np; }  // ... row-sum (weight) sets
+};
+
+// what fills A before the factorisation: the batch's single / sum kernels with the data's noise or - `noise` - with
+// per-problem noise vectors (np apart), or the mixture
+struct ChunkBuild {
+  const BatchParams* p;
+  const double* noise;
+  const MixBatch* mix;
+  static ChunkBuild kernels(const BatchParams& bp, const double* noise_rows = nullptr) { return {&bp, noise_rows, nullptr}; }
+  static ChunkBuild mixture(const MixBatch& mx) { return {nullptr, nullptr, &mx}; }  // (chunks at problem 0 only)
+};
+
+// The stages every lockstep entry point shares, behind its uploads: [clear info], build, potrf_lower_batched, residual,
+// forward sweep, [lml_reduce], [backward sweep -> alpha()], [L^-T -> B2].  The bracketed ones as `steps` says.
+enum : unsigned { LS_CLEAR_INFO = 1, LS_REDUCE = 2, LS_BACKWARD = 4, LS_INVERSE = 8 };
+int lockstep_stages(const Chunk& k, const ChunkBuild& b, unsigned steps);
+void launch_kbuild_cross_batched(const Chunk& k, const BatchParams& p, const double* U, int64_t mu, int64_t mp, double* out,
+                                 int64_t stride);
+void launch_lml_grad_batched(const Chunk& k, const BatchParams& p, int n_theta, const double* u, const double* v, int64_t sV);
+// params + means of chunk rows [t0, t0 + k.B) through the pinned staging (gradient batches)
+int stage_batch_inputs(RowStage& stage, const Chunk& k, const BatchParams& p, int64_t t0, const double* mus,
+                       const double* mu_const);
+// the four leave-one-out vectors of every problem in bLoo (sLoo = 4 np apart)
+struct LooVectors {
+  double *diag, *c1, *sc2, *p;  // diag K^-1, c1, sqrt c2 - later diag M -, p = K^-1 c1
+  int64_t sLoo;
+  explicit LooVectors(const gpmi_ctx* c) : diag(c->bLoo), c1(c->bLoo + c->np), sc2(c->bLoo + 2 * c->np), p(c->bLoo + 3 * c->np), sLoo(4 * c->np) {}
+};
+// behind lockstep_stages(.., LS_BACKWARD | LS_INVERSE): diag K^-1, K^-1 in full, the leave-one-out vectors, p, and
+// M = K^-1 diag(c2) K^-1 into A (lower tiles; both triangles with mirror_m); diag M where sc2 was if want_mdiag
+void loo_middle(const Chunk& k, const LooVectors& lv, bool want_mdiag, bool mirror_m);
+int ensure_batch_mix_ws(gpmi_ctx* c);
+int make_mix_batch_params(gpmi_ctx* c, const MixBatch& mx, int64_t T, const double* thetas, std::vector<KParams>& ps);
+int stage_mix_inputs(RowStage& stage, const Chunk& k, const MixBatch& mx, int64_t t0, int64_t T, const std::vector<KParams>& ps,
+                     const double* g_host, const double* hw_host, const double* extra, const double* mus,
+                     const double* mu_const);
+// per sub-kernel, on Q in A (both triangles): the weight-scaled contraction into bGout and the window row sums into
+// bMixH; p == nullptr: the likelihood form (u = v = g_m o alpha), else u = g_m o p, v = g_m o alpha
+void mix_sub_kernel_terms(const Chunk& k, const MixBatch& mx, const double* p, int64_t sP);
+// grad_thetas row of problem b of the chunk from h_bGout, times `factor`
+void unpack_mix_gradient(const gpmi_ctx* c, const MixBatch& mx, int b, double factor, double* out);

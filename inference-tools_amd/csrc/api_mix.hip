@@ -120,19 +120,9 @@ int gpmi_lml_grad_mix(gpmi_ctx* c, int nk, const int* kernels, const double* the
   c->fitted = false;
   Lane& L = c->lanes[1];
   if (int rc = ensure_second_matrix(c, L)) return rc;
-  int max_nt = 0, tot_nt = 0;
-  for (int m = 0; m < nk; ++m) {
-    max_nt = n_thetas[m] > max_nt ? n_thetas[m] : max_nt;
-    tot_nt += n_thetas[m];
-  }
-  const int64_t need = grad_ws_doubles(c->np, max_nt);
-  if (L.gws_doubles < need) {
-    if (L.gws) (void)hipFree(L.gws);
-    L.gws = nullptr;
-    L.gws_doubles = 0;
-    HIPCHK(c, hipMalloc(&L.gws, sizeof(double) * need));
-    L.gws_doubles = need;
-  }
+  int max_nt = 0;
+  for (int m = 0; m < nk; ++m) max_nt = n_thetas[m] > max_nt ? n_thetas[m] : max_nt;
+  if (int rc = grow(c, L.gws, L.gws_doubles, grad_ws_doubles(c->np, max_nt), sizeof(double))) return rc;
   hipStream_t s = L.stream;
   double* mu_dev = L.vec + 3 * c->np;
   double* alpha_dev = L.vec + c->np;
@@ -193,7 +183,6 @@ int gpmi_lml_grad_mix(gpmi_ctx* c, int nk, const int* kernels, const double* the
     for (int j = 0; j < n_thetas[m]; ++j) grad_thetas[o++] = L.h_red[16 + goff + j];
     goff += n_thetas[m] + 1;
   }
-  (void)tot_nt;
   INFOCHK(c, L.h_info[0]);
   if (info) *info = L.h_info[0];
   return GPMI_OK;
@@ -214,87 +203,33 @@ int gpmi_lml_grad_batch_mix(gpmi_ctx* c, int nk, const int* kernels, int64_t T, 
   ARGCHK(c, nk >= 1 && nk <= GPMI_MAX_MIX, "number of sub-kernels out of range (1..4)");
   ARGCHK(c, kernels && thetas && n_thetas && g_host && lml && grad_thetas && hrows, "NULL argument");
   ARGCHK(c, mus || mu_const, "one of mus / mu_const is required");
-  int tot_nt = 0, max_nt = 0;
-  for (int m = 0; m < nk; ++m) {
-    tot_nt += n_thetas[m];
-    max_nt = n_thetas[m] > max_nt ? n_thetas[m] : max_nt;
-  }
+  const MixBatch mx(nk, kernels, n_thetas, hw_host != nullptr);
   if (int rc = set_device(c)) return rc;
   const bool lockstep = (T >= 2 || c->lockstep_always) && c->np <= 4096 && !c->ycov;
-  if (!lockstep) {
-    std::vector<double> mu_row((size_t)c->n);
-    for (int64_t t = 0; t < T; ++t) {
-      const double* mu_t = mus ? mus + t * c->n : mu_row.data();
-      if (!mus) std::fill(mu_row.begin(), mu_row.end(), mu_const[t]);
+  if (!lockstep)
+    return one_at_a_time(c, T, mus, mu_const, [&](int64_t t, const double* mu_t) -> int {
       int inf = 0;
-      const int nrow1 = hw_host ? 2 : 1;
-      const int rc = gpmi_lml_grad_mix(c, nk, kernels, thetas + t * tot_nt, n_thetas, g_host + t * nk * c->n,
+      const int rc = gpmi_lml_grad_mix(c, nk, kernels, thetas + t * mx.tot_nt, n_thetas, g_host + t * nk * c->n,
                                        hw_host ? hw_host + t * nk * 2 * c->n : nullptr, extra ? extra[t] : 0.0, mu_t,
-                                       lml + t, grad_thetas + t * tot_nt, hrows + t * nk * nrow1 * c->n,
+                                       lml + t, grad_thetas + t * mx.tot_nt, hrows + t * nk * mx.nrow * c->n,
                                        alpha_out ? alpha_out + t * c->n : nullptr, &inf);
       if (info) info[t] = inf;
       if (rc != GPMI_OK) return rc;
-      if (qdiag_out)
-        if (int rc2 = gpmi_lml_grad_qdiag(c, qdiag_out + t * c->n)) return rc2;
-    }
-    return GPMI_OK;
-  }
+      return qdiag_out ? gpmi_lml_grad_qdiag(c, qdiag_out + t * c->n) : GPMI_OK;
+    });
   if (c->lanes.size() < 2)
     if (int rc = ensure_lanes(c, 2)) return rc;
-  // parameters: ps[m][t]
-  std::vector<KParams> ps((size_t)nk * T);
-  for (int64_t t = 0; t < T; ++t) {
-    int off = 0;
-    for (int m = 0; m < nk; ++m) {
-      if (int rc = make_params(c, kernels[m], thetas + t * tot_nt + off, n_thetas[m], 0.0, ps[(size_t)m * T + t])) return rc;
-      off += n_thetas[m];
-    }
-  }
+  std::vector<KParams> ps;
+  if (int rc = make_mix_batch_params(c, mx, T, thetas, ps)) return rc;
   ARGCHK(c, c->bpend[0] == 0 && c->bpend[1] == 0,
          "gpmi_lml_grad_batch_mix: an asynchronous batch is pending on this handle (gpmi_lml_batch_wait first)");
   if (int rc = ensure_batch_ws(c, (int)(T < 64 ? (T < 2 ? 2 : T) : 64))) return rc;
-  const int W = max_nt + 1;  // values per sub-kernel and problem from the contraction
-  if (int rc = ensure_batch_grad_ws(c, c->bcap, nk * W - 1)) return rc;
-  if (!c->mix_zero) {
-    HIPCHK(c, hipMalloc(&c->mix_zero, sizeof(double) * c->np));
-    ZERO_SYNC(c, c->mix_zero, sizeof(double) * c->np);
-  }
+  if (int rc = ensure_batch_grad_ws(c, c->bcap, nk * mx.W() - 1)) return rc;
+  if (int rc = ensure_batch_mix_ws(c)) return rc;
   const int cap = c->bgrad_cap;
-  if (c->bMix_cap < cap) {
-    auto fr = [](double*& p) {
-      if (p) (void)hipFree(p);
-      p = nullptr;
-    };
-    fr(c->bMixG);
-    fr(c->bMixH);
-    fr(c->bMixW);
-    fr(c->bMixExtra);
-    if (c->bMixP) (void)hipFree(c->bMixP);
-    c->bMixP = nullptr;
-    c->bMix_cap = 0;
-    HIPCHK(c, hipMalloc(&c->bMixG, sizeof(double) * cap * GPMI_MAX_MIX * c->np));
-    // (row sums and the caller's row-sum weights: up to two per sub-kernel)
-    HIPCHK(c, hipMalloc(&c->bMixH, sizeof(double) * cap * 2 * GPMI_MAX_MIX * c->np));
-    HIPCHK(c, hipMalloc(&c->bMixW, sizeof(double) * cap * 2 * GPMI_MAX_MIX * c->np));
-    HIPCHK(c, hipMalloc(&c->bMixExtra, sizeof(double) * cap));
-    HIPCHK(c, hipMalloc(&c->bMixP, sizeof(KParams) * cap * GPMI_MAX_MIX));
-    c->bMix_cap = cap;
-  }
-  if (qdiag_out && c->bNoise_cap < cap) {
-    if (c->bNoise) (void)hipFree(c->bNoise);
-    c->bNoise = nullptr;
-    c->bNoise_cap = 0;
-    HIPCHK(c, hipMalloc(&c->bNoise, sizeof(double) * c->np * cap));
-    c->bNoise_cap = cap;
-  }
+  if (qdiag_out)
+    if (int rc = grow(c, c->bNoise, c->bNoise_cap, cap, sizeof(double) * c->np)) return rc;
   hipStream_t s = c->lanes[1].stream;
-  const int nt = (int)(c->np / GPMI_NB);
-  const BatchShape shape0{1, c->np * c->ld, (c->np / GPMI_NB) * GPMI_NB * GPMI_NB, 4 * c->np};
-  const int64_t sG = (int64_t)GPMI_MAX_MIX * c->np;  // between the problems' weight sets
-  // row sums per sub-kernel: one with the sub-kernel's own weights, or two with the caller's (hw); stride between the
-  // problems' row-sum (and row-sum weight) sets
-  const int nrow = hw_host ? 2 : 1;
-  const int64_t sW = (int64_t)nrow * GPMI_MAX_MIX * c->np;
   static const bool stage_times = std::getenv("GPMI_DEBUG_STAGES") != nullptr;  // debugging aid: host time per stage
   RowStage stage(c, s);  // strided outputs reach the caller's arrays through pinned memory (api_internal.h)
   if (int rc = stage.reserve((size_t)cap * (sizeof(double) * (3 * GPMI_MAX_MIX * c->np + c->n) + GPMI_MAX_MIX * sizeof(KParams) + 4096) +
@@ -303,99 +238,29 @@ int gpmi_lml_grad_batch_mix(gpmi_ctx* c, int nk, const int* kernels, int64_t T, 
   for (int64_t t0 = 0; t0 < T; t0 += cap) {
     const auto h0 = std::chrono::steady_clock::now();
     const int B = (int)((T - t0 < cap) ? T - t0 : cap);
-    BatchShape bs = shape0;
-    bs.count = B;
-    // weights, padded like mix_prepare does (the identity in the padding belongs to sub-kernel 0); every input of the
-    // chunk is laid out in the pinned staging buffer and leaves from there (RowStage, api_internal.h)
-    double* gpad = stage.host(sizeof(double) * B * sG);
-    std::fill(gpad, gpad + (size_t)B * sG, 0.0);
-    for (int b = 0; b < B; ++b)
-      for (int m = 0; m < nk; ++m) {
-        double* dst = gpad + (size_t)b * sG + (size_t)m * c->np;
-        const double* src = g_host + ((t0 + b) * nk + m) * c->n;
-        for (int64_t i = 0; i < c->np; ++i) dst[i] = i < c->n ? src[i] : (m == 0 ? 1.0 : 0.0);
-      }
-    if (int rc = stage.put(c->bMixG, gpad, sizeof(double) * B * sG)) return rc;
-    if (hw_host) {
-      double* wpad = stage.host(sizeof(double) * B * sW);
-      std::fill(wpad, wpad + (size_t)B * sW, 0.0);
-      for (int b = 0; b < B; ++b)
-        for (int row = 0; row < 2 * nk; ++row)
-          std::copy(hw_host + ((t0 + b) * 2 * nk + row) * c->n, hw_host + ((t0 + b) * 2 * nk + row + 1) * c->n,
-                    wpad + (size_t)b * sW + (size_t)row * c->np);
-      if (int rc = stage.put(c->bMixW, wpad, sizeof(double) * B * sW)) return rc;
-    }
-    double* ex = stage.host(sizeof(double) * B);
-    for (int b = 0; b < B; ++b) ex[b] = extra ? extra[t0 + b] : 0.0;
-    if (int rc = stage.put(c->bMixExtra, ex, sizeof(double) * B)) return rc;
-    for (int m = 0; m < nk; ++m)
-      if (int rc = stage.put_copy(c->bMixP + (int64_t)m * cap, ps.data() + (size_t)m * T + t0, sizeof(KParams) * B)) return rc;
-    if (mus) {
-      if (int rc = stage.put_copy(c->bMu, mus + t0 * c->n, sizeof(double) * B * c->n)) return rc;
-    } else {
-      if (int rc = stage.put_copy(c->bMu, mu_const + t0, sizeof(double) * B)) return rc;
-    }
-    HIPCHK(c, hipMemsetAsync(c->bInfo, 0, sizeof(int) * B, s));
-    // K = sum_m D_m K_m D_m + noise + extra: the sub-kernels' lower tiles into the second matrix, folded into the first
-    // (the upper triangle of the sum is never read before the mirror below)
-    for (int m = 0; m < nk; ++m) {
-      launch_kbuild_square_batched(s, kernels[m], c->bMixP + (int64_t)m * cap, B, c->x, c->n, c->np, c->mix_zero, c->bB2,
-                                   c->ld, bs.sMat, (int)c->d, 0);
-      launch_scale_add(s, c->bA, c->ld, c->bB2, c->ld, c->bMixG + (int64_t)m * c->np, c->bMixG + (int64_t)m * c->np,
-                       c->np, c->np, m > 0, B, bs.sMat, bs.sMat, sG);
-    }
-    launch_add_diag_vec(s, c->bA, c->ld, c->noise, 0.0, c->n, B, bs.sMat, c->bMixExtra);
-    potrf_lower_batched(c, s, c->bA, c->np, c->ld, c->bInv, c->bInfo, bs);
-    launch_residual_batched(s, c->y, mus ? c->bMu : nullptr, mus ? nullptr : c->bMu, c->bVec + 2 * c->np, c->n, c->np,
-                            bs);
-    trsv_forward(c, s, c->bA, c->np, c->ld, c->bInv, c->bVec + 2 * c->np, c->bVec, c->bInfo, bs);
-    launch_lml_reduce(s, c->bVec, c->bA, c->ld, c->np, c->bRed, bs);
-    double* alpha_dev = c->bVec + c->np;   // slot 1 of every problem's four work vectors
-    double* ua_dev = c->bVec + 2 * c->np;  // slot 2 (the residual is spent): g_m o alpha
-    trsv_backward(c, s, c->bA, c->np, c->ld, c->bInv, c->bVec, alpha_dev, c->bInfo, bs);
-    trsm_identity_batched(s, c->bA, c->np, c->ld, c->bInv, c->bB2, bs);
-    const GemmBatch syrk{B, bs.sMat, bs.sMat, bs.sMat};
-    launch_gemm(s, TILES_LOWER, OP_ASSIGN, false, 1, c->bA, c->ld, c->bB2, c->ld, c->bB2, c->ld, nt, nt, (int)c->np,
-                nullptr, syrk);
-    launch_mirror_lower(s, c->bA, c->ld, c->np, B, bs.sMat);
-    if (qdiag_out) launch_qdiag_batched(s, B, c->bA, c->ld, alpha_dev, c->bNoise, c->n, bs.sMat, bs.sVec, c->np);
-    for (int m = 0; m < nk; ++m) {
-      const double* gm = c->bMixG + (int64_t)m * c->np;
-      const KParams* pm = c->bMixP + (int64_t)m * cap;
-      // 1/2 sum (D_m Q D_m) o dK_m: the fused contraction on the weight-scaled inverse with u = v = g_m o alpha
-      launch_scale_add(s, c->bB2, c->ld, c->bA, c->ld, gm, gm, c->np, c->np, false, B, bs.sMat, bs.sMat, sG);
-      launch_vec_mul(s, gm, alpha_dev, ua_dev, c->np, B, sG, bs.sVec, bs.sVec);
-      launch_lml_grad_batched(s, kernels[m], pm, B, n_thetas[m], c->x, c->n, c->np, c->bB2, c->ld, bs.sMat, ua_dev, ua_dev,
-                              bs.sVec, c->bGws, c->bGout + (int64_t)m * cap * W);
-      // window parameters: h_m(i) = sum_j Q_ij K_m,ij g_m(j) on the full K_m (lower tiles built, then mirrored)
-      launch_kbuild_square_batched(s, kernels[m], pm, B, c->x, c->n, c->np, c->mix_zero, c->bB2, c->ld, bs.sMat,
-                                   (int)c->d, 0);
-      launch_mirror_lower(s, c->bB2, c->ld, c->np, B, bs.sMat);
-      if (!hw_host) {
-        launch_mix_rowsum(s, c->bA, c->bB2, c->ld, alpha_dev, gm, c->bMixH + (int64_t)m * c->np, c->n, B, bs.sMat,
-                          bs.sVec, sG);
-      } else {
-        // (weights and rows share the stride, bMixG's differs; the sub-kernel's two window factors in one pass)
-        launch_mix_rowsum(s, c->bA, c->bB2, c->ld, alpha_dev, c->bMixW + (int64_t)(2 * m) * c->np,
-                          c->bMixH + (int64_t)(2 * m) * c->np, c->n, B, bs.sMat, bs.sVec, sW, nullptr, 0, c->np);
-      }
-    }
+    const Chunk k(c, s, 0, B, mus != nullptr);
+    if (int rc = stage_mix_inputs(stage, k, mx, t0, T, ps, g_host, hw_host, extra, mus, mu_const)) return rc;
+    if (int rc = lockstep_stages(k, ChunkBuild::mixture(mx), LS_CLEAR_INFO | LS_REDUCE | LS_BACKWARD | LS_INVERSE)) return rc;
+    // K^-1 = L^-T L^-1 in full (it is read row-wise below)
+    k.syrk(1);
+    launch_mirror_lower(s, k.A, c->ld, c->np, B, k.bs.sMat);
+    if (qdiag_out) launch_qdiag_batched(s, B, k.A, c->ld, k.alpha(), c->bNoise, c->n, k.bs.sMat, k.bs.sVec, c->np);
+    mix_sub_kernel_terms(k, mx, nullptr, 0);
     HIPCHK(c, hipGetLastError());
     const auto h1 = std::chrono::steady_clock::now();
-    HIPCHK(c, hipMemcpyAsync(c->h_bRed, c->bRed, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(c->h_bGout, c->bGout, sizeof(double) * nk * cap * W, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(c->h_bInfo, c->bInfo, sizeof(int) * B, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(c->h_bRed, k.red, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(c->h_bGout, c->bGout, sizeof(double) * nk * cap * mx.W(), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(c->h_bInfo, k.info, sizeof(int) * B, hipMemcpyDeviceToHost, s));
     const size_t rowb = sizeof(double) * c->n;
-    for (int row = 0; row < nk * nrow; ++row)
-      if (int rc = stage.down(hrows + (t0 * nk * nrow + row) * c->n, rowb * nk * nrow, c->bMixH + (int64_t)row * c->np,
-                              sizeof(double) * sW, rowb, B))
+    for (int row = 0; row < nk * mx.nrow; ++row)
+      if (int rc = stage.down(hrows + (t0 * nk * mx.nrow + row) * c->n, rowb * nk * mx.nrow, c->bMixH + (int64_t)row * c->np,
+                              sizeof(double) * mx.sW(c), rowb, B))
         return rc;
     if (alpha_out)
-      if (int rc = stage.down(alpha_out + t0 * c->n, rowb, alpha_dev, sizeof(double) * bs.sVec, rowb, B)) return rc;
+      if (int rc = stage.down(alpha_out + t0 * c->n, rowb, k.alpha(), sizeof(double) * k.bs.sVec, rowb, B)) return rc;
     if (qdiag_out)
       if (int rc = stage.down(qdiag_out + t0 * c->n, rowb, c->bNoise, sizeof(double) * c->np, rowb, B)) return rc;
     const auto h2 = std::chrono::steady_clock::now();
-    if (int rc = stage.flush()) return rc;
     HIPCHK(c, hipStreamSynchronize(s));
     stage.finish();
     if (stage_times) {
@@ -408,10 +273,7 @@ int gpmi_lml_grad_batch_mix(gpmi_ctx* c, int nk, const int* kernels, int64_t T, 
       const int inf = c->h_bInfo[b];
       INFOCHK(c, inf);
       lml[t0 + b] = -0.5 * c->h_bRed[2 * b] - c->h_bRed[2 * b + 1];
-      int o = 0;
-      for (int m = 0; m < nk; ++m)
-        for (int j = 0; j < n_thetas[m]; ++j)
-          grad_thetas[(t0 + b) * tot_nt + o++] = c->h_bGout[(int64_t)m * cap * W + (int64_t)b * (n_thetas[m] + 1) + j];
+      unpack_mix_gradient(c, mx, b, 1.0, grad_thetas + (t0 + b) * mx.tot_nt);
       if (info) info[t0 + b] = inf;
     }
   }
@@ -435,192 +297,55 @@ int gpmi_loo_grad_batch_mix(gpmi_ctx* c, int nk, const int* kernels, int64_t T, 
   ARGCHK(c, kernels && thetas && n_thetas && g_host && alpha_out && ikdiag_out && p_out && mdiag_out && grad_thetas && hrows,
          "NULL argument");
   ARGCHK(c, mus || mu_const, "one of mus / mu_const is required");
-  int tot_nt = 0, max_nt = 0;
-  for (int m = 0; m < nk; ++m) {
-    tot_nt += n_thetas[m];
-    max_nt = n_thetas[m] > max_nt ? n_thetas[m] : max_nt;
-  }
+  const MixBatch mx(nk, kernels, n_thetas, hw_host != nullptr);
   if (int rc = set_device(c)) return rc;
   ARGCHK(c, c->np <= 4096 && !c->ycov, "lockstep sizes only (n <= 4096, diagonal data errors)");
   if (c->lanes.size() < 2)
     if (int rc = ensure_lanes(c, 2)) return rc;
-  // parameters: ps[m][t]
-  std::vector<KParams> ps((size_t)nk * T);
-  for (int64_t t = 0; t < T; ++t) {
-    int off = 0;
-    for (int m = 0; m < nk; ++m) {
-      if (int rc = make_params(c, kernels[m], thetas + t * tot_nt + off, n_thetas[m], 0.0, ps[(size_t)m * T + t])) return rc;
-      off += n_thetas[m];
-    }
-  }
+  std::vector<KParams> ps;
+  if (int rc = make_mix_batch_params(c, mx, T, thetas, ps)) return rc;
   ARGCHK(c, c->bpend[0] == 0 && c->bpend[1] == 0,
          "gpmi_loo_grad_batch_mix: an asynchronous batch is pending on this handle (gpmi_lml_batch_wait first)");
   if (int rc = ensure_batch_ws(c, (int)(T < 64 ? (T < 2 ? 2 : T) : 64))) return rc;
-  const int W = max_nt + 1;  // values per sub-kernel and problem from the contraction
-  if (int rc = ensure_batch_grad_ws(c, c->bcap, nk * W - 1)) return rc;
-  if (!c->mix_zero) {
-    HIPCHK(c, hipMalloc(&c->mix_zero, sizeof(double) * c->np));
-    ZERO_SYNC(c, c->mix_zero, sizeof(double) * c->np);
-  }
+  if (int rc = ensure_batch_grad_ws(c, c->bcap, nk * mx.W() - 1)) return rc;
+  if (int rc = ensure_batch_mix_ws(c)) return rc;
   const int cap = c->bgrad_cap;
-  if (c->bMix_cap < cap) {
-    auto fr = [](double*& p) {
-      if (p) (void)hipFree(p);
-      p = nullptr;
-    };
-    fr(c->bMixG);
-    fr(c->bMixH);
-    fr(c->bMixW);
-    fr(c->bMixExtra);
-    if (c->bMixP) (void)hipFree(c->bMixP);
-    c->bMixP = nullptr;
-    c->bMix_cap = 0;
-    HIPCHK(c, hipMalloc(&c->bMixG, sizeof(double) * cap * GPMI_MAX_MIX * c->np));
-    // (row sums and the caller's row-sum weights: up to two per sub-kernel)
-    HIPCHK(c, hipMalloc(&c->bMixH, sizeof(double) * cap * 2 * GPMI_MAX_MIX * c->np));
-    HIPCHK(c, hipMalloc(&c->bMixW, sizeof(double) * cap * 2 * GPMI_MAX_MIX * c->np));
-    HIPCHK(c, hipMalloc(&c->bMixExtra, sizeof(double) * cap));
-    HIPCHK(c, hipMalloc(&c->bMixP, sizeof(KParams) * cap * GPMI_MAX_MIX));
-    c->bMix_cap = cap;
-  }
   // four more vectors per problem: diag(K^-1), c1, sqrt(c2) - later diag(M) -, p = K^-1 c1 (regression.py:505-513).
   // (the same stride as the work vectors': the fused contraction takes u = p and v = alpha with ONE stride)
-  const int64_t sLoo = 4 * c->np;
-  if (c->bLoo_cap < cap) {
-    if (c->bLoo) (void)hipFree(c->bLoo);
-    c->bLoo = nullptr;
-    c->bLoo_cap = 0;
-    HIPCHK(c, hipMalloc(&c->bLoo, sizeof(double) * sLoo * cap));
-    c->bLoo_cap = cap;
-  }
+  if (int rc = grow(c, c->bLoo, c->bLoo_cap, cap, sizeof(double) * 4 * c->np)) return rc;
+  const LooVectors lv(c);
   hipStream_t s = c->lanes[1].stream;
-  const int nt = (int)(c->np / GPMI_NB);
-  const BatchShape shape0{1, c->np * c->ld, (c->np / GPMI_NB) * GPMI_NB * GPMI_NB, 4 * c->np};
-  const int64_t sG = (int64_t)GPMI_MAX_MIX * c->np;  // between the problems' weight sets
-  // row sums per sub-kernel: one with the sub-kernel's own weights, or two with the caller's (hw); stride between the
-  // problems' row-sum (and row-sum weight) sets
-  const int nrow = hw_host ? 2 : 1;
-  const int64_t sW = (int64_t)nrow * GPMI_MAX_MIX * c->np;
   RowStage stage(c, s);  // strided outputs reach the caller's arrays through pinned memory (api_internal.h)
   if (int rc = stage.reserve((size_t)cap * (sizeof(double) * (3 * GPMI_MAX_MIX * c->np + c->n) + GPMI_MAX_MIX * sizeof(KParams) + 4096) +
                              (size_t)(2 * GPMI_MAX_MIX + 4) * cap * (sizeof(double) * c->n + 256)))
     return rc;
   for (int64_t t0 = 0; t0 < T; t0 += cap) {
     const int B = (int)((T - t0 < cap) ? T - t0 : cap);
-    BatchShape bs = shape0;
-    bs.count = B;
-    // weights, padded like mix_prepare does (the identity in the padding belongs to sub-kernel 0); every input of the
-    // chunk is laid out in the pinned staging buffer and leaves from there (RowStage, api_internal.h)
-    double* gpad = stage.host(sizeof(double) * B * sG);
-    std::fill(gpad, gpad + (size_t)B * sG, 0.0);
-    for (int b = 0; b < B; ++b)
-      for (int m = 0; m < nk; ++m) {
-        double* dst = gpad + (size_t)b * sG + (size_t)m * c->np;
-        const double* src = g_host + ((t0 + b) * nk + m) * c->n;
-        for (int64_t i = 0; i < c->np; ++i) dst[i] = i < c->n ? src[i] : (m == 0 ? 1.0 : 0.0);
-      }
-    if (int rc = stage.put(c->bMixG, gpad, sizeof(double) * B * sG)) return rc;
-    if (hw_host) {
-      double* wpad = stage.host(sizeof(double) * B * sW);
-      std::fill(wpad, wpad + (size_t)B * sW, 0.0);
-      for (int b = 0; b < B; ++b)
-        for (int row = 0; row < 2 * nk; ++row)
-          std::copy(hw_host + ((t0 + b) * 2 * nk + row) * c->n, hw_host + ((t0 + b) * 2 * nk + row + 1) * c->n,
-                    wpad + (size_t)b * sW + (size_t)row * c->np);
-      if (int rc = stage.put(c->bMixW, wpad, sizeof(double) * B * sW)) return rc;
-    }
-    double* ex = stage.host(sizeof(double) * B);
-    for (int b = 0; b < B; ++b) ex[b] = extra ? extra[t0 + b] : 0.0;
-    if (int rc = stage.put(c->bMixExtra, ex, sizeof(double) * B)) return rc;
-    for (int m = 0; m < nk; ++m)
-      if (int rc = stage.put_copy(c->bMixP + (int64_t)m * cap, ps.data() + (size_t)m * T + t0, sizeof(KParams) * B)) return rc;
-    if (mus) {
-      if (int rc = stage.put_copy(c->bMu, mus + t0 * c->n, sizeof(double) * B * c->n)) return rc;
-    } else {
-      if (int rc = stage.put_copy(c->bMu, mu_const + t0, sizeof(double) * B)) return rc;
-    }
-    HIPCHK(c, hipMemsetAsync(c->bInfo, 0, sizeof(int) * B, s));
-    // K = sum_m D_m K_m D_m + noise + extra: the sub-kernels' lower tiles into the second matrix, folded into the first
-    // (the upper triangle of the sum is never read before the mirror below)
-    for (int m = 0; m < nk; ++m) {
-      launch_kbuild_square_batched(s, kernels[m], c->bMixP + (int64_t)m * cap, B, c->x, c->n, c->np, c->mix_zero, c->bB2,
-                                   c->ld, bs.sMat, (int)c->d, 0);
-      launch_scale_add(s, c->bA, c->ld, c->bB2, c->ld, c->bMixG + (int64_t)m * c->np, c->bMixG + (int64_t)m * c->np,
-                       c->np, c->np, m > 0, B, bs.sMat, bs.sMat, sG);
-    }
-    launch_add_diag_vec(s, c->bA, c->ld, c->noise, 0.0, c->n, B, bs.sMat, c->bMixExtra);
-    potrf_lower_batched(c, s, c->bA, c->np, c->ld, c->bInv, c->bInfo, bs);
-    launch_residual_batched(s, c->y, mus ? c->bMu : nullptr, mus ? nullptr : c->bMu, c->bVec + 2 * c->np, c->n, c->np,
-                            bs);
-    trsv_forward(c, s, c->bA, c->np, c->ld, c->bInv, c->bVec + 2 * c->np, c->bVec, c->bInfo, bs);
-    double* alpha_dev = c->bVec + c->np;   // slot 1 of every problem's four work vectors
-    double* ua_dev = c->bVec + 2 * c->np;  // slot 2 (the residual is spent): g_m o alpha
-    trsv_backward(c, s, c->bA, c->np, c->ld, c->bInv, c->bVec, alpha_dev, c->bInfo, bs);
-    double* va_dev = c->bVec + 3 * c->np;  // slot 3: g_m o alpha (slot 2: g_m o p)
-    double* diag_dev = c->bLoo;
-    double* c1_dev = c->bLoo + c->np;
-    double* sc2_dev = c->bLoo + 2 * c->np;
-    double* p_dev = c->bLoo + 3 * c->np;
-    double* mdiag_dev = sc2_dev;  // (sqrt(c2) is spent once G = K^-1 diag(sqrt c2) exists)
-    // L^-T, its row sums of squares = diag(K^-1), K^-1 in full, the leave-one-out vectors, p = K^-1 c1, then
-    // M = K^-1 diag(c2) K^-1 = G G^T with G = K^-1 diag(sqrt c2), in full as well (it is read row-wise below)
-    trsm_identity_batched(s, c->bA, c->np, c->ld, c->bInv, c->bB2, bs);
-    launch_rows_sumsq(s, c->bB2, c->ld, c->np, c->np, 0.0, diag_dev, B, bs.sMat, sLoo, -1.0);
-    const GemmBatch syrk{B, bs.sMat, bs.sMat, bs.sMat};
-    launch_gemm(s, TILES_LOWER, OP_ASSIGN, false, 1, c->bA, c->ld, c->bB2, c->ld, c->bB2, c->ld, nt, nt, (int)c->np,
-                nullptr, syrk);
-    launch_mirror_lower(s, c->bA, c->ld, c->np, B, bs.sMat);
-    launch_loo_vectors(s, alpha_dev, diag_dev, c1_dev, sc2_dev, c->n, c->np, B, bs.sVec, sLoo);
-    launch_rows_dot(s, c->bA, c->ld, c->np, c->np, c1_dev, p_dev, B, bs.sMat, sLoo);
-    launch_scale_columns(s, c->bA, sc2_dev, c->bB2, c->ld, c->np, B, bs.sMat, sLoo);
-    launch_rows_sumsq(s, c->bB2, c->ld, c->np, c->np, 0.0, mdiag_dev, B, bs.sMat, sLoo, -1.0);  // M_ii = |row i of G|^2
-    launch_gemm(s, TILES_LOWER, OP_ASSIGN, false, 0, c->bA, c->ld, c->bB2, c->ld, c->bB2, c->ld, nt, nt, (int)c->np,
-                nullptr, syrk);
-    launch_mirror_lower(s, c->bA, c->ld, c->np, B, bs.sMat);
-    for (int m = 0; m < nk; ++m) {
-      const double* gm = c->bMixG + (int64_t)m * c->np;
-      const KParams* pm = c->bMixP + (int64_t)m * cap;
-      // sum (D_m Q D_m) o dK_m with Q = sym(p alpha^T) - M: the fused contraction on the weight-scaled M with
-      // u = g_m o p, v = g_m o alpha (it returns 1/2 of the sum; the leave-one-out gradient has no 1/2: doubled below)
-      launch_scale_add(s, c->bB2, c->ld, c->bA, c->ld, gm, gm, c->np, c->np, false, B, bs.sMat, bs.sMat, sG);
-      launch_vec_mul(s, gm, p_dev, ua_dev, c->np, B, sG, sLoo, bs.sVec);
-      launch_vec_mul(s, gm, alpha_dev, va_dev, c->np, B, sG, bs.sVec, bs.sVec);
-      launch_lml_grad_batched(s, kernels[m], pm, B, n_thetas[m], c->x, c->n, c->np, c->bB2, c->ld, bs.sMat, ua_dev, va_dev,
-                              bs.sVec, c->bGws, c->bGout + (int64_t)m * cap * W);
-      // window parameters: h_m(i) = sum_j Q_ij K_m,ij g_m(j) on the full K_m (lower tiles built, then mirrored)
-      launch_kbuild_square_batched(s, kernels[m], pm, B, c->x, c->n, c->np, c->mix_zero, c->bB2, c->ld, bs.sMat,
-                                   (int)c->d, 0);
-      launch_mirror_lower(s, c->bB2, c->ld, c->np, B, bs.sMat);
-      if (!hw_host) {
-        launch_mix_rowsum(s, c->bA, c->bB2, c->ld, alpha_dev, gm, c->bMixH + (int64_t)m * c->np, c->n, B, bs.sMat,
-                          bs.sVec, sG, p_dev, sLoo);
-      } else {
-        launch_mix_rowsum(s, c->bA, c->bB2, c->ld, alpha_dev, c->bMixW + (int64_t)(2 * m) * c->np,
-                          c->bMixH + (int64_t)(2 * m) * c->np, c->n, B, bs.sMat, bs.sVec, sW, p_dev, sLoo, c->np);
-      }
-    }
+    const Chunk k(c, s, 0, B, mus != nullptr);
+    if (int rc = stage_mix_inputs(stage, k, mx, t0, T, ps, g_host, hw_host, extra, mus, mu_const)) return rc;
+    if (int rc = lockstep_stages(k, ChunkBuild::mixture(mx), LS_CLEAR_INFO | LS_BACKWARD | LS_INVERSE)) return rc;
+    // M in full as well: it is read row-wise below
+    loo_middle(k, lv, true, true);
+    // Q = sym(p alpha^T) - M (the contraction returns 1/2 of the sum; the leave-one-out gradient has no 1/2: doubled below)
+    mix_sub_kernel_terms(k, mx, lv.p, lv.sLoo);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->h_bGout, c->bGout, sizeof(double) * nk * cap * W, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(c->h_bInfo, c->bInfo, sizeof(int) * B, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(c->h_bGout, c->bGout, sizeof(double) * nk * cap * mx.W(), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(c->h_bInfo, k.info, sizeof(int) * B, hipMemcpyDeviceToHost, s));
     const size_t rowb = sizeof(double) * c->n;
-    for (int row = 0; row < nk * nrow; ++row)
-      if (int rc = stage.down(hrows + (t0 * nk * nrow + row) * c->n, rowb * nk * nrow, c->bMixH + (int64_t)row * c->np,
-                              sizeof(double) * sW, rowb, B))
+    for (int row = 0; row < nk * mx.nrow; ++row)
+      if (int rc = stage.down(hrows + (t0 * nk * mx.nrow + row) * c->n, rowb * nk * mx.nrow, c->bMixH + (int64_t)row * c->np,
+                              sizeof(double) * mx.sW(c), rowb, B))
         return rc;
-    if (int rc = stage.down(alpha_out + t0 * c->n, rowb, alpha_dev, sizeof(double) * bs.sVec, rowb, B)) return rc;
-    if (int rc = stage.down(ikdiag_out + t0 * c->n, rowb, diag_dev, sizeof(double) * sLoo, rowb, B)) return rc;
-    if (int rc = stage.down(p_out + t0 * c->n, rowb, p_dev, sizeof(double) * sLoo, rowb, B)) return rc;
-    if (int rc = stage.down(mdiag_out + t0 * c->n, rowb, mdiag_dev, sizeof(double) * sLoo, rowb, B)) return rc;
-    if (int rc = stage.flush()) return rc;
+    if (int rc = stage.down(alpha_out + t0 * c->n, rowb, k.alpha(), sizeof(double) * k.bs.sVec, rowb, B)) return rc;
+    if (int rc = stage.down(ikdiag_out + t0 * c->n, rowb, lv.diag, sizeof(double) * lv.sLoo, rowb, B)) return rc;
+    if (int rc = stage.down(p_out + t0 * c->n, rowb, lv.p, sizeof(double) * lv.sLoo, rowb, B)) return rc;
+    if (int rc = stage.down(mdiag_out + t0 * c->n, rowb, lv.sc2, sizeof(double) * lv.sLoo, rowb, B)) return rc;
     HIPCHK(c, hipStreamSynchronize(s));
     stage.finish();
     for (int b = 0; b < B; ++b) {
       const int inf = c->h_bInfo[b];
       INFOCHK(c, inf);
-      int o = 0;
-      for (int m = 0; m < nk; ++m)
-        for (int j = 0; j < n_thetas[m]; ++j)
-          grad_thetas[(t0 + b) * tot_nt + o++] = 2.0 * c->h_bGout[(int64_t)m * cap * W + (int64_t)b * (n_thetas[m] + 1) + j];
+      unpack_mix_gradient(c, mx, b, 2.0, grad_thetas + (t0 + b) * mx.tot_nt);
       if (info) info[t0 + b] = inf;
     }
   }

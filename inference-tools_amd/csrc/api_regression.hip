@@ -78,40 +78,17 @@ int gpmi_lml_batch(gpmi_ctx* c, int kernel, int64_t T, const double* thetas, int
     // a latency-bound step - potrf_diag: one workgroup per matrix, 32 of 256 CUs for a half of 32 - the other half's
     // GEMM launches fill the chip.  A value does not depend on the batch it is evaluated in (§4.3), so the split is
     // invisible in the results.  GPMI_BATCH_SPLIT=0: one stream (A/B).
-    static const bool split_ok = [] {
-      const char* e = std::getenv("GPMI_BATCH_SPLIT");
-      return !e || std::atoi(e) != 0;
-    }();
-    const bool two = split_ok && T >= 16 && ensure_lanes(c, 3) == GPMI_OK;
-    const BatchShape shape0{1, c->np * c->ld, (c->np / GPMI_NB) * GPMI_NB * GPMI_NB, 4 * c->np};
+    const bool two = batch_split_enabled() && T >= 16 && ensure_lanes(c, 3) == GPMI_OK;
+    const BatchParams bp(kernel, ps, sps);
     auto enqueue = [&](hipStream_t s, int64_t t_first, int off, int B) -> int {
-      BatchShape bs = shape0;
-      bs.count = B;
-      double* A = c->bA + (int64_t)off * bs.sMat;
-      double* Inv = c->bInv + (int64_t)off * bs.sInv;
-      double* Vec = c->bVec + (int64_t)off * bs.sVec;
-      double* Mu = c->bMu + (int64_t)off * (mus ? c->n : 1);
-      if (sps.empty())
-        HIPCHK(c, hipMemcpyAsync(c->bParams + off, ps.data() + t_first, sizeof(KParams) * B, hipMemcpyHostToDevice, s));
-      else
-        HIPCHK(c, hipMemcpyAsync(c->bSum + off, sps.data() + t_first, sizeof(CovParams) * B, hipMemcpyHostToDevice, s));
-      if (mus)
-        HIPCHK(c, hipMemcpyAsync(Mu, mus + t_first * c->n, sizeof(double) * B * c->n, hipMemcpyHostToDevice, s));
-      else
-        HIPCHK(c, hipMemcpyAsync(Mu, mu_const + t_first, sizeof(double) * B, hipMemcpyHostToDevice, s));
-      HIPCHK(c, hipMemsetAsync(c->bInfo + off, 0, sizeof(int) * B, s));
-      if (sps.empty())
-        launch_kbuild_square_batched(s, kernel, c->bParams + off, B, c->x, c->n, c->np, c->noise, A, c->ld, bs.sMat,
-                                     (int)c->d);
-      else
-        launch_kbuild_square_batched(s, c->bSum + off, B, c->x, c->n, c->np, c->noise, A, c->ld, bs.sMat, (int)c->d);
-      potrf_lower_batched(c, s, A, c->np, c->ld, Inv, c->bInfo + off, bs);
-      launch_residual_batched(s, c->y, mus ? Mu : nullptr, mus ? nullptr : Mu, Vec + 2 * c->np, c->n, c->np, bs);
-      trsv_forward(c, s, A, c->np, c->ld, Inv, Vec + 2 * c->np, Vec, c->bInfo + off, bs);
-      launch_lml_reduce(s, Vec, A, c->ld, c->np, c->bRed + 2 * off, bs);
+      const Chunk k(c, s, off, B, mus != nullptr);
+      HIPCHK(c, hipMemcpyAsync(bp.device(c, off), bp.host(t_first), bp.bytes_each() * B, hipMemcpyHostToDevice, s));
+      HIPCHK(c, hipMemcpyAsync(k.Mu, mus ? mus + t_first * c->n : mu_const + t_first, sizeof(double) * B * (mus ? c->n : 1),
+                               hipMemcpyHostToDevice, s));
+      if (int rc = lockstep_stages(k, ChunkBuild::kernels(bp), LS_CLEAR_INFO | LS_REDUCE)) return rc;
       HIPCHK(c, hipGetLastError());
-      HIPCHK(c, hipMemcpyAsync(c->h_bRed + 2 * off, c->bRed + 2 * off, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, s));
-      HIPCHK(c, hipMemcpyAsync(c->h_bInfo + off, c->bInfo + off, sizeof(int) * B, hipMemcpyDeviceToHost, s));
+      HIPCHK(c, hipMemcpyAsync(c->h_bRed + 2 * off, k.red, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, s));
+      HIPCHK(c, hipMemcpyAsync(c->h_bInfo + off, k.info, sizeof(int) * B, hipMemcpyDeviceToHost, s));
       return GPMI_OK;
     };
     for (int64_t t0 = 0; t0 < T; t0 += c->bcap) {
@@ -228,30 +205,16 @@ int gpmi_lml_batch_submit(gpmi_ctx* c, int kernel, int64_t T, const double* thet
   }
   std::memcpy(mu_stage, mus ? mus : mu_const, sizeof(double) * mu_doubles);
   hipStream_t s = c->lanes[1 + slot].stream;
-  BatchShape bs{(int)T, c->np * c->ld, (c->np / GPMI_NB) * GPMI_NB * GPMI_NB, 4 * c->np};
-  double* A = c->bA + (int64_t)off * bs.sMat;
-  double* Inv = c->bInv + (int64_t)off * bs.sInv;
-  double* Vec = c->bVec + (int64_t)off * bs.sVec;
-  double* Mu = c->bMu + (int64_t)off * (mus ? c->n : 1);
   const bool sum = (kernel == GPMI_KERNEL_SUM);
-  if (sum)
-    HIPCHK(c, hipMemcpyAsync(c->bSum + off, c->h_bStage[slot], sizeof(CovParams) * T, hipMemcpyHostToDevice, s));
-  else
-    HIPCHK(c, hipMemcpyAsync(c->bParams + off, c->h_bStage[slot], sizeof(KParams) * T, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(Mu, mu_stage, sizeof(double) * mu_doubles, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemsetAsync(c->bInfo + off, 0, sizeof(int) * T, s));
-  if (sum)
-    launch_kbuild_square_batched(s, c->bSum + off, (int)T, c->x, c->n, c->np, c->noise, A, c->ld, bs.sMat, (int)c->d);
-  else
-    launch_kbuild_square_batched(s, kernel, c->bParams + off, (int)T, c->x, c->n, c->np, c->noise, A, c->ld, bs.sMat,
-                                 (int)c->d);
-  potrf_lower_batched(c, s, A, c->np, c->ld, Inv, c->bInfo + off, bs);
-  launch_residual_batched(s, c->y, mus ? Mu : nullptr, mus ? nullptr : Mu, Vec + 2 * c->np, c->n, c->np, bs);
-  trsv_forward(c, s, A, c->np, c->ld, Inv, Vec + 2 * c->np, Vec, c->bInfo + off, bs);
-  launch_lml_reduce(s, Vec, A, c->ld, c->np, c->bRed + 2 * off, bs);
+  const BatchParams bp = sum ? BatchParams(kernel, nullptr, reinterpret_cast<const CovParams*>(c->h_bStage[slot]))
+                             : BatchParams(kernel, reinterpret_cast<const KParams*>(c->h_bStage[slot]), nullptr);
+  const Chunk k(c, s, off, (int)T, mus != nullptr);
+  HIPCHK(c, hipMemcpyAsync(bp.device(c, off), c->h_bStage[slot], bp.bytes_each() * T, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(k.Mu, mu_stage, sizeof(double) * mu_doubles, hipMemcpyHostToDevice, s));
+  if (int rc = lockstep_stages(k, ChunkBuild::kernels(bp), LS_CLEAR_INFO | LS_REDUCE)) return rc;
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(c->h_bRed + 2 * off, c->bRed + 2 * off, sizeof(double) * 2 * T, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(c->h_bInfo + off, c->bInfo + off, sizeof(int) * T, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(c->h_bRed + 2 * off, k.red, sizeof(double) * 2 * T, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(c->h_bInfo + off, k.info, sizeof(int) * T, hipMemcpyDeviceToHost, s));
   c->bpend[slot] = (int)T;
   return GPMI_OK;
 }
@@ -282,15 +245,7 @@ static int ensure_gradient_lane(gpmi_ctx* c, int n_theta) {
   if (int rc = ensure_lanes(c, 2)) return rc;
   Lane& L = c->lanes[1];
   if (int rc = ensure_second_matrix(c, L)) return rc;
-  const int64_t need = grad_ws_doubles(c->np, n_theta);
-  if (L.gws_doubles < need) {
-    if (L.gws) (void)hipFree(L.gws);
-    L.gws = nullptr;
-    L.gws_doubles = 0;
-    HIPCHK(c, hipMalloc(&L.gws, sizeof(double) * need));
-    L.gws_doubles = need;
-  }
-  return GPMI_OK;
+  return grow(c, L.gws, L.gws_doubles, grad_ws_doubles(c->np, n_theta), sizeof(double));
 }
 
 int gpmi_prepare_gradient(gpmi_ctx* c, int n_theta) {
@@ -353,12 +308,9 @@ static int lml_grad_batch_impl(gpmi_ctx* c, int kernel, int64_t T, const double*
   ARGCHK(c, mus || mu_const, "one of mus / mu_const is required");
   if (int rc = set_device(c)) return rc;
   const bool lockstep = (T >= 2 || c->lockstep_always) && c->np <= 4096 && !c->ycov;
-  if (!lockstep) {
+  if (!lockstep)
     // large problems are throughput-bound one at a time: the single-evaluation path, one after another
-    std::vector<double> mu_row((size_t)c->n);
-    for (int64_t t = 0; t < T; ++t) {
-      const double* mu_t = mus ? mus + t * c->n : mu_row.data();
-      if (!mus) std::fill(mu_row.begin(), mu_row.end(), mu_const[t]);
+    return one_at_a_time(c, T, mus, mu_const, [&](int64_t t, const double* mu_t) -> int {
       int inf = 0;
       if (noise_batch)
         if (int rc = gpmi_set_noise(c, noise_batch + t * c->n)) return rc;
@@ -367,86 +319,48 @@ static int lml_grad_batch_impl(gpmi_ctx* c, int kernel, int64_t T, const double*
                                    alpha_out ? alpha_out + t * c->n : nullptr, &inf);
       if (info) info[t] = inf;
       if (rc != GPMI_OK) return rc;
-      if (qdiag_out)
-        if (int rc2 = gpmi_lml_grad_qdiag(c, qdiag_out + t * c->n)) return rc2;
-    }
-    return GPMI_OK;
-  }
+      return qdiag_out ? gpmi_lml_grad_qdiag(c, qdiag_out + t * c->n) : GPMI_OK;
+    });
   if (c->lanes.size() < 2)
     if (int rc = ensure_lanes(c, 2)) return rc;
   std::vector<KParams> ps;
   std::vector<CovParams> sps;  // (a sum: its parameters, ps stays empty)
   if (int rc = make_batch_params(c, kernel, T, thetas, n_theta, extra, ps, sps)) return rc;
+  const BatchParams bp(kernel, ps, sps);
   // lockstep: every launch carries the chunk in blockIdx.z - K-build, factorisation, both sweeps, L^-T by forward
   // substitution on the identity, the k-skipped SYRK K^-1 = L^-T L^-1 (regression.py:556-557) and the fused contraction
   ARGCHK(c, c->bpend[0] == 0 && c->bpend[1] == 0,
          "gpmi_lml_grad_batch: an asynchronous batch is pending on this handle (gpmi_lml_batch_wait first)");
   if (int rc = ensure_batch_ws(c, (int)(T < 64 ? (T < 2 ? 2 : T) : 64))) return rc;
   if (int rc = ensure_batch_grad_ws(c, c->bcap, n_theta)) return rc;
-  if ((noise_batch || qdiag_out) && c->bNoise_cap < c->bgrad_cap) {
-    if (c->bNoise) (void)hipFree(c->bNoise);
-    c->bNoise = nullptr;
-    c->bNoise_cap = 0;
-    HIPCHK(c, hipMalloc(&c->bNoise, sizeof(double) * c->np * c->bgrad_cap));
-    c->bNoise_cap = c->bgrad_cap;
-  }
+  if (noise_batch || qdiag_out)
+    if (int rc = grow(c, c->bNoise, c->bNoise_cap, c->bgrad_cap, sizeof(double) * c->np)) return rc;
   hipStream_t s = c->lanes[1].stream;
-  const int nt = (int)(c->np / GPMI_NB);
-  const BatchShape shape0{1, c->np * c->ld, (c->np / GPMI_NB) * GPMI_NB * GPMI_NB, 4 * c->np};
   const int W = n_theta + 1;
   const size_t rowb = sizeof(double) * c->n;
   RowStage stage(c, s);  // strided rows travel between the caller's arrays and the device through pinned memory (api_internal.h)
   if (int rc = stage.reserve((size_t)c->bgrad_cap * (7 * (rowb + 256) + sizeof(CovParams) + 512))) return rc;
   for (int64_t t0 = 0; t0 < T; t0 += c->bgrad_cap) {
     const int B = (int)((T - t0 < c->bgrad_cap) ? T - t0 : c->bgrad_cap);
-    BatchShape bs = shape0;
-    bs.count = B;
-    if (sps.empty()) {
-      if (int rc = stage.put_copy(c->bParams, ps.data() + t0, sizeof(KParams) * B)) return rc;  // (inputs leave from pinned memory)
-    } else {
-      if (int rc = stage.put_copy(c->bSum, sps.data() + t0, sizeof(CovParams) * B)) return rc;
-    }
-    if (mus) {
-      if (int rc = stage.put_copy(c->bMu, mus + t0 * c->n, sizeof(double) * B * c->n)) return rc;
-    } else {
-      if (int rc = stage.put_copy(c->bMu, mu_const + t0, sizeof(double) * B)) return rc;
-    }
-    HIPCHK(c, hipMemsetAsync(c->bInfo, 0, sizeof(int) * B, s));
+    const Chunk k(c, s, 0, B, mus != nullptr);
+    if (int rc = stage_batch_inputs(stage, k, bp, t0, mus, mu_const)) return rc;
+    if (int rc = k.clear_info()) return rc;
     if (noise_batch)
       if (int rc = stage.up(c->bNoise, sizeof(double) * c->np, noise_batch + t0 * c->n, rowb, rowb, B)) return rc;
-    if (sps.empty())
-      launch_kbuild_square_batched(s, kernel, c->bParams, B, c->x, c->n, c->np, noise_batch ? c->bNoise : c->noise,
-                                   c->bA, c->ld, bs.sMat, (int)c->d, noise_batch ? c->np : 0);
-    else  // (sums take no per-problem noise: the *_noise entry points refuse them)
-      launch_kbuild_square_batched(s, c->bSum, B, c->x, c->n, c->np, c->noise, c->bA, c->ld, bs.sMat, (int)c->d);
-    potrf_lower_batched(c, s, c->bA, c->np, c->ld, c->bInv, c->bInfo, bs);
-    launch_residual_batched(s, c->y, mus ? c->bMu : nullptr, mus ? nullptr : c->bMu, c->bVec + 2 * c->np, c->n, c->np,
-                            bs);
-    trsv_forward(c, s, c->bA, c->np, c->ld, c->bInv, c->bVec + 2 * c->np, c->bVec, c->bInfo, bs);
-    launch_lml_reduce(s, c->bVec, c->bA, c->ld, c->np, c->bRed, bs);
-    double* alpha_dev = c->bVec + c->np;  // slot 1 of every problem's four work vectors
-    trsv_backward(c, s, c->bA, c->np, c->ld, c->bInv, c->bVec, alpha_dev, c->bInfo, bs);
-    trsm_identity_batched(s, c->bA, c->np, c->ld, c->bInv, c->bB2, bs);
-    const GemmBatch syrk{B, bs.sMat, bs.sMat, bs.sMat};
-    launch_gemm(s, TILES_LOWER, OP_ASSIGN, false, 1, c->bA, c->ld, c->bB2, c->ld, c->bB2, c->ld, nt, nt, (int)c->np,
-                nullptr, syrk);
-    if (sps.empty())
-      launch_lml_grad_batched(s, kernel, c->bParams, B, n_theta, c->x, c->n, c->np, c->bA, c->ld, bs.sMat, alpha_dev, alpha_dev,
-                              bs.sVec, c->bGws, c->bGout);
-    else
-      launch_lml_grad_batched(s, c->bSum, B, n_theta, c->x, c->n, c->np, c->bA, c->ld, bs.sMat, alpha_dev, alpha_dev,
-                              bs.sVec, c->bGws, c->bGout, (int)c->d);
+    if (int rc = lockstep_stages(k, ChunkBuild::kernels(bp, noise_batch ? c->bNoise : nullptr), LS_REDUCE | LS_BACKWARD | LS_INVERSE))
+      return rc;
+    k.syrk(1);
+    launch_lml_grad_batched(k, bp, n_theta, k.alpha(), k.alpha(), k.bs.sVec);
     if (qdiag_out) {  // diag(alpha alpha^T - K^-1) per problem, into the noise buffer (consumed by the build above)
-      launch_qdiag_batched(s, B, c->bA, c->ld, alpha_dev, c->bNoise, c->n, bs.sMat, bs.sVec, c->np);
+      launch_qdiag_batched(s, B, k.A, c->ld, k.alpha(), c->bNoise, c->n, k.bs.sMat, k.bs.sVec, c->np);
       if (int rc = stage.down(qdiag_out + t0 * c->n, rowb, c->bNoise, sizeof(double) * c->np, rowb, B)) return rc;
     }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->h_bRed, c->bRed, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(c->h_bRed, k.red, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(c->h_bGout, c->bGout, sizeof(double) * W * B, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(c->h_bInfo, c->bInfo, sizeof(int) * B, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(c->h_bInfo, k.info, sizeof(int) * B, hipMemcpyDeviceToHost, s));
     if (alpha_out)
-      if (int rc = stage.down(alpha_out + t0 * c->n, rowb, alpha_dev, sizeof(double) * bs.sVec, rowb, B)) return rc;
-    if (int rc = stage.flush()) return rc;
+      if (int rc = stage.down(alpha_out + t0 * c->n, rowb, k.alpha(), sizeof(double) * k.bs.sVec, rowb, B)) return rc;
     HIPCHK(c, hipStreamSynchronize(s));
     stage.finish();
     for (int b = 0; b < B; ++b) {
@@ -496,115 +410,54 @@ static int loo_grad_batch_impl(gpmi_ctx* c, int kernel, int64_t T, const double*
   if (int rc = set_device(c)) return rc;
   const bool lockstep = (T >= 2 || c->lockstep_always || noise_batch) && c->np <= 4096 && !c->ycov;
   ARGCHK(c, lockstep || !noise_batch, "per-point noise in the batch: lockstep sizes only (n <= 4096, diagonal data errors)");
-  if (!lockstep) {
-    std::vector<double> mu_row((size_t)c->n);
-    for (int64_t t = 0; t < T; ++t) {
-      const double* mu_t = mus ? mus + t * c->n : mu_row.data();
-      if (!mus) std::fill(mu_row.begin(), mu_row.end(), mu_const[t]);
+  if (!lockstep)
+    return one_at_a_time(c, T, mus, mu_const, [&](int64_t t, const double* mu_t) -> int {
       int inf = 0;
       const int rc = gpmi_loo_grad(c, kernel, thetas + t * n_theta, n_theta, extra ? extra[t] : 0.0, mu_t,
                                    alpha_out + t * c->n, ikdiag_out + t * c->n, p_out + t * c->n,
                                    grad_theta + t * n_theta, trace_q ? trace_q + t : nullptr, &inf);
       if (info) info[t] = inf;
-      if (rc != GPMI_OK) return rc;
-    }
-    return GPMI_OK;
-  }
+      return rc;
+    });
   if (c->lanes.size() < 2)
     if (int rc = ensure_lanes(c, 2)) return rc;
   std::vector<KParams> ps;
   std::vector<CovParams> sps;  // (a sum: its parameters, ps stays empty)
   if (int rc = make_batch_params(c, kernel, T, thetas, n_theta, extra, ps, sps)) return rc;
+  const BatchParams bp(kernel, ps, sps);
   ARGCHK(c, c->bpend[0] == 0 && c->bpend[1] == 0,
          "gpmi_loo_grad_batch: an asynchronous batch is pending on this handle (gpmi_lml_batch_wait first)");
   if (int rc = ensure_batch_ws(c, (int)(T < 64 ? (T < 2 ? 2 : T) : 64))) return rc;
   if (int rc = ensure_batch_grad_ws(c, c->bcap, n_theta)) return rc;
+  if (noise_batch)
+    if (int rc = grow(c, c->bNoise, c->bNoise_cap, c->bgrad_cap, sizeof(double) * c->np)) return rc;
   // four more vectors per problem: diag(K^-1), c1, sqrt(c2) - later diag(M) -, p = K^-1 c1 (regression.py:505-513).
   // (the same stride as the work vectors': the fused contraction takes u = p and v = alpha with ONE stride)
-  const int64_t sLoo = 4 * c->np;
-  if (noise_batch && c->bNoise_cap < c->bgrad_cap) {
-    if (c->bNoise) (void)hipFree(c->bNoise);
-    c->bNoise = nullptr;
-    c->bNoise_cap = 0;
-    HIPCHK(c, hipMalloc(&c->bNoise, sizeof(double) * c->np * c->bgrad_cap));
-    c->bNoise_cap = c->bgrad_cap;
-  }
-  if (c->bLoo_cap < c->bgrad_cap) {
-    if (c->bLoo) (void)hipFree(c->bLoo);
-    c->bLoo = nullptr;
-    c->bLoo_cap = 0;
-    HIPCHK(c, hipMalloc(&c->bLoo, sizeof(double) * sLoo * c->bgrad_cap));
-    c->bLoo_cap = c->bgrad_cap;
-  }
+  if (int rc = grow(c, c->bLoo, c->bLoo_cap, c->bgrad_cap, sizeof(double) * 4 * c->np)) return rc;
+  const LooVectors lv(c);
   hipStream_t s = c->lanes[1].stream;
-  const int nt = (int)(c->np / GPMI_NB);
-  const BatchShape shape0{1, c->np * c->ld, (c->np / GPMI_NB) * GPMI_NB * GPMI_NB, 4 * c->np};
   const int W = n_theta + 1;
   const size_t rowb = sizeof(double) * c->n;
   RowStage stage(c, s);  // strided rows travel between the caller's arrays and the device through pinned memory (api_internal.h)
   if (int rc = stage.reserve((size_t)c->bgrad_cap * (7 * (rowb + 256) + sizeof(CovParams) + 512))) return rc;
   for (int64_t t0 = 0; t0 < T; t0 += c->bgrad_cap) {
     const int B = (int)((T - t0 < c->bgrad_cap) ? T - t0 : c->bgrad_cap);
-    BatchShape bs = shape0;
-    bs.count = B;
-    if (sps.empty()) {
-      if (int rc = stage.put_copy(c->bParams, ps.data() + t0, sizeof(KParams) * B)) return rc;  // (inputs leave from pinned memory)
-    } else {
-      if (int rc = stage.put_copy(c->bSum, sps.data() + t0, sizeof(CovParams) * B)) return rc;
-    }
-    if (mus) {
-      if (int rc = stage.put_copy(c->bMu, mus + t0 * c->n, sizeof(double) * B * c->n)) return rc;
-    } else {
-      if (int rc = stage.put_copy(c->bMu, mu_const + t0, sizeof(double) * B)) return rc;
-    }
-    HIPCHK(c, hipMemsetAsync(c->bInfo, 0, sizeof(int) * B, s));
+    const Chunk k(c, s, 0, B, mus != nullptr);
+    if (int rc = stage_batch_inputs(stage, k, bp, t0, mus, mu_const)) return rc;
+    if (int rc = k.clear_info()) return rc;
     if (noise_batch)
       if (int rc = stage.up(c->bNoise, sizeof(double) * c->np, noise_batch + t0 * c->n, rowb, rowb, B)) return rc;
-    if (sps.empty())
-      launch_kbuild_square_batched(s, kernel, c->bParams, B, c->x, c->n, c->np, noise_batch ? c->bNoise : c->noise,
-                                   c->bA, c->ld, bs.sMat, (int)c->d, noise_batch ? c->np : 0);
-    else  // (sums take no per-problem noise: the *_noise entry points refuse them)
-      launch_kbuild_square_batched(s, c->bSum, B, c->x, c->n, c->np, c->noise, c->bA, c->ld, bs.sMat, (int)c->d);
-    potrf_lower_batched(c, s, c->bA, c->np, c->ld, c->bInv, c->bInfo, bs);
-    launch_residual_batched(s, c->y, mus ? c->bMu : nullptr, mus ? nullptr : c->bMu, c->bVec + 2 * c->np, c->n, c->np,
-                            bs);
-    trsv_forward(c, s, c->bA, c->np, c->ld, c->bInv, c->bVec + 2 * c->np, c->bVec, c->bInfo, bs);
-    double* alpha_dev = c->bVec + c->np;  // slot 1 of every problem's four work vectors
-    trsv_backward(c, s, c->bA, c->np, c->ld, c->bInv, c->bVec, alpha_dev, c->bInfo, bs);
-    double* diag_dev = c->bLoo;
-    double* c1_dev = c->bLoo + c->np;
-    double* sc2_dev = c->bLoo + 2 * c->np;
-    double* p_dev = c->bLoo + 3 * c->np;
-    // L^-T, its row sums of squares = diag(K^-1), then K^-1 in full (both triangles)
-    trsm_identity_batched(s, c->bA, c->np, c->ld, c->bInv, c->bB2, bs);
-    launch_rows_sumsq(s, c->bB2, c->ld, c->np, c->np, 0.0, diag_dev, B, bs.sMat, sLoo, -1.0);
-    const GemmBatch syrk{B, bs.sMat, bs.sMat, bs.sMat};
-    launch_gemm(s, TILES_LOWER, OP_ASSIGN, false, 1, c->bA, c->ld, c->bB2, c->ld, c->bB2, c->ld, nt, nt, (int)c->np,
-                nullptr, syrk);
-    launch_mirror_lower(s, c->bA, c->ld, c->np, B, bs.sMat);
-    launch_loo_vectors(s, alpha_dev, diag_dev, c1_dev, sc2_dev, c->n, c->np, B, bs.sVec, sLoo);
-    launch_rows_dot(s, c->bA, c->ld, c->np, c->np, c1_dev, p_dev, B, bs.sMat, sLoo);
-    // M = K^-1 diag(c2) K^-1 = G G^T with G = K^-1 diag(sqrt c2); lower tiles, overwriting K^-1
-    launch_scale_columns(s, c->bA, sc2_dev, c->bB2, c->ld, c->np, B, bs.sMat, sLoo);
-    double* mdiag_dev = sc2_dev;  // (sqrt(c2) is spent once G = K^-1 diag(sqrt c2) exists)
-    if (mdiag_out) launch_rows_sumsq(s, c->bB2, c->ld, c->np, c->np, 0.0, mdiag_dev, B, bs.sMat, sLoo, -1.0);  // M_ii = |row i of G|^2
-    launch_gemm(s, TILES_LOWER, OP_ASSIGN, false, 0, c->bA, c->ld, c->bB2, c->ld, c->bB2, c->ld, nt, nt, (int)c->np,
-                nullptr, syrk);
-    if (sps.empty())
-      launch_lml_grad_batched(s, kernel, c->bParams, B, n_theta, c->x, c->n, c->np, c->bA, c->ld, bs.sMat, p_dev, alpha_dev, sLoo,
-                              c->bGws, c->bGout);
-    else
-      launch_lml_grad_batched(s, c->bSum, B, n_theta, c->x, c->n, c->np, c->bA, c->ld, bs.sMat, p_dev, alpha_dev, sLoo,
-                              c->bGws, c->bGout, (int)c->d);
+    if (int rc = lockstep_stages(k, ChunkBuild::kernels(bp, noise_batch ? c->bNoise : nullptr), LS_BACKWARD | LS_INVERSE)) return rc;
+    loo_middle(k, lv, mdiag_out != nullptr, false);
+    launch_lml_grad_batched(k, bp, n_theta, lv.p, k.alpha(), lv.sLoo);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(c->h_bGout, c->bGout, sizeof(double) * W * B, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(c->h_bInfo, c->bInfo, sizeof(int) * B, hipMemcpyDeviceToHost, s));
-    if (int rc = stage.down(alpha_out + t0 * c->n, rowb, alpha_dev, sizeof(double) * bs.sVec, rowb, B)) return rc;
-    if (int rc = stage.down(ikdiag_out + t0 * c->n, rowb, diag_dev, sizeof(double) * sLoo, rowb, B)) return rc;
-    if (int rc = stage.down(p_out + t0 * c->n, rowb, p_dev, sizeof(double) * sLoo, rowb, B)) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->h_bInfo, k.info, sizeof(int) * B, hipMemcpyDeviceToHost, s));
+    if (int rc = stage.down(alpha_out + t0 * c->n, rowb, k.alpha(), sizeof(double) * k.bs.sVec, rowb, B)) return rc;
+    if (int rc = stage.down(ikdiag_out + t0 * c->n, rowb, lv.diag, sizeof(double) * lv.sLoo, rowb, B)) return rc;
+    if (int rc = stage.down(p_out + t0 * c->n, rowb, lv.p, sizeof(double) * lv.sLoo, rowb, B)) return rc;
     if (mdiag_out)
-      if (int rc = stage.down(mdiag_out + t0 * c->n, rowb, mdiag_dev, sizeof(double) * sLoo, rowb, B)) return rc;
-    if (int rc = stage.flush()) return rc;
+      if (int rc = stage.down(mdiag_out + t0 * c->n, rowb, lv.sc2, sizeof(double) * lv.sLoo, rowb, B)) return rc;
     HIPCHK(c, hipStreamSynchronize(s));
     stage.finish();
     for (int b = 0; b < B; ++b) {
@@ -737,6 +590,7 @@ int gpmi_predict_batch(gpmi_ctx* c, int kernel, int64_t T, const double* thetas,
   std::vector<KParams> ps;
   std::vector<CovParams> sps;  // (a sum: its parameters, ps stays empty)
   if (int rc = make_batch_params(c, kernel, T, thetas, n_theta, extra, ps, sps)) return rc;
+  const BatchParams bp(kernel, ps, sps);
   ARGCHK(c, c->bpend[0] == 0 && c->bpend[1] == 0,
          "gpmi_predict_batch: an asynchronous batch is pending on this handle (gpmi_lml_batch_wait first)");
   if (int rc = ensure_lanes(c, 2)) return rc;
@@ -745,18 +599,8 @@ int gpmi_predict_batch(gpmi_ctx* c, int kernel, int64_t T, const double* thetas,
   const bool want_var = var_t || mix_var;
   const int64_t P = GPMI_PREDICT_PANEL;
   const int64_t sQ = 2 * P * c->ld;  // per problem: the panel K* and, behind it, V = K* L^-T
-  if (c->bQ_cap < c->bgrad_cap) {
-    if (c->bQ) (void)hipFree(c->bQ);
-    c->bQ = nullptr;
-    c->bQ_cap = 0;
-    HIPCHK(c, hipMalloc(&c->bQ, sizeof(double) * sQ * c->bgrad_cap));
-    c->bQ_cap = c->bgrad_cap;
-  }
-  static const bool split_ok = [] {
-    const char* e = std::getenv("GPMI_BATCH_SPLIT");
-    return !e || std::atoi(e) != 0;
-  }();
-  const bool two = split_ok && T >= 16 && ensure_lanes(c, 3) == GPMI_OK;
+  if (int rc = grow(c, c->bQ, c->bQ_cap, c->bgrad_cap, sizeof(double) * sQ)) return rc;
+  const bool two = batch_split_enabled() && T >= 16 && ensure_lanes(c, 3) == GPMI_OK;
   const int cap = c->bgrad_cap;
   // the call's own device arrays: points, prior means at the points, the T x m results, the mixture's row list
   DevBuf dPts, dPrior, dMean, dVar, dSq, dIdx, dW, dMix;
@@ -771,66 +615,36 @@ int gpmi_predict_batch(gpmi_ctx* c, int kernel, int64_t T, const double* thetas,
   HIPCHK(c, hipMemcpy(dPrior.p, mu_q ? mu_q : mu_const, sizeof(double) * (mu_q ? T * m : T), hipMemcpyHostToDevice));
   HIPCHK(c, hipStreamSynchronize(nullptr));  // (the lanes' streams do not wait for the null stream)
   const int nt = (int)(c->np / GPMI_NB);
-  const BatchShape shape0{1, c->np * c->ld, (c->np / GPMI_NB) * GPMI_NB * GPMI_NB, 4 * c->np};
-  const bool sum = !sps.empty();
   auto enqueue = [&](hipStream_t s, int64_t t_first, int off, int B) -> int {
-    BatchShape bs = shape0;
-    bs.count = B;
-    double* A = c->bA + (int64_t)off * bs.sMat;
-    double* Inv = c->bInv + (int64_t)off * bs.sInv;
-    double* Vec = c->bVec + (int64_t)off * bs.sVec;
-    double* Mu = c->bMu + (int64_t)off * (mus ? c->n : 1);
-    double* B2 = c->bB2 + (int64_t)off * bs.sMat;
+    const Chunk k(c, s, off, B, mus != nullptr);
     double* Q = c->bQ + (int64_t)off * sQ;
     double* V = Q + P * c->ld;
-    if (sum)
-      HIPCHK(c, hipMemcpyAsync(c->bSum + off, sps.data() + t_first, sizeof(CovParams) * B, hipMemcpyHostToDevice, s));
-    else
-      HIPCHK(c, hipMemcpyAsync(c->bParams + off, ps.data() + t_first, sizeof(KParams) * B, hipMemcpyHostToDevice, s));
-    if (mus)
-      HIPCHK(c, hipMemcpyAsync(Mu, mus + t_first * c->n, sizeof(double) * B * c->n, hipMemcpyHostToDevice, s));
-    else
-      HIPCHK(c, hipMemcpyAsync(Mu, mu_const + t_first, sizeof(double) * B, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemsetAsync(c->bInfo + off, 0, sizeof(int) * B, s));
-    if (sum)
-      launch_kbuild_square_batched(s, c->bSum + off, B, c->x, c->n, c->np, c->noise, A, c->ld, bs.sMat, (int)c->d);
-    else
-      launch_kbuild_square_batched(s, kernel, c->bParams + off, B, c->x, c->n, c->np, c->noise, A, c->ld, bs.sMat,
-                                   (int)c->d);
-    potrf_lower_batched(c, s, A, c->np, c->ld, Inv, c->bInfo + off, bs);
-    launch_residual_batched(s, c->y, mus ? Mu : nullptr, mus ? nullptr : Mu, Vec + 2 * c->np, c->n, c->np, bs);
-    trsv_forward(c, s, A, c->np, c->ld, Inv, Vec + 2 * c->np, Vec, c->bInfo + off, bs);
-    double* alpha_dev = Vec + c->np;  // slot 1 of every problem's four work vectors
-    trsv_backward(c, s, A, c->np, c->ld, Inv, Vec, alpha_dev, c->bInfo + off, bs);
-    if (want_var) trsm_identity_batched(s, A, c->np, c->ld, Inv, B2, bs);
+    HIPCHK(c, hipMemcpyAsync(bp.device(c, off), bp.host(t_first), bp.bytes_each() * B, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(k.Mu, mus ? mus + t_first * c->n : mu_const + t_first, sizeof(double) * B * (mus ? c->n : 1),
+                             hipMemcpyHostToDevice, s));
+    if (int rc = lockstep_stages(k, ChunkBuild::kernels(bp), LS_CLEAR_INFO | LS_BACKWARD | (want_var ? LS_INVERSE : 0u))) return rc;
     // slots 2 and 3 (2 np >= GPMI_PREDICT_PANEL doubles; the residual is spent) take a panel's row dots: launch_rows_dot
     // strides its output like alpha
-    double* dot_dev = Vec + 2 * c->np;
+    double* dot_dev = k.resid();
     double* sq_dev = want_var ? dSq.as<double>() + (int64_t)off * P : nullptr;
-    GemmBatch gb{B, sQ, sQ, bs.sMat};
+    GemmBatch gb{B, sQ, sQ, k.bs.sMat};
     gb.ring_order_only = true;
     for (int64_t m0 = 0; m0 < m; m0 += P) {
       const int64_t mc = (m - m0 < P) ? m - m0 : P;
       const int64_t mp = round_up(mc, GPMI_NB);
-      const double* U = dPts.as<double>() + m0 * c->d;
-      if (sum)
-        launch_kbuild_cross_batched(s, c->bSum + off, B, U, mc, mp, c->x, c->n, c->np, Q, c->ld, sQ, (int)c->d);
-      else
-        launch_kbuild_cross_batched(s, kernel, c->bParams + off, B, U, mc, mp, c->x, c->n, c->np, Q, c->ld, sQ, (int)c->d);
-      launch_rows_dot(s, Q, c->ld, mc, c->np, alpha_dev, dot_dev, B, sQ, bs.sVec);
+      launch_kbuild_cross_batched(k, bp, dPts.as<double>() + m0 * c->d, mc, mp, Q, sQ);
+      launch_rows_dot(s, Q, c->ld, mc, c->np, k.alpha(), dot_dev, B, sQ, k.bs.sVec);
       if (want_var) {
-        launch_gemm(s, TILES_RECT, OP_ASSIGN, true, 2, V, c->ld, Q, c->ld, B2, c->ld, (int)(mp / GPMI_NB), nt, (int)c->np,
+        launch_gemm(s, TILES_RECT, OP_ASSIGN, true, 2, V, c->ld, Q, c->ld, k.B2, c->ld, (int)(mp / GPMI_NB), nt, (int)c->np,
                     nullptr, gb);
         launch_rows_sumsq(s, V, c->ld, mc, c->np, 0.0, sq_dev, B, sQ, P, -1.0);  // (-(0 - sum): the sum itself)
       }
-      launch_predict_store(s, B, t_first, m0, mc, m, dot_dev, sq_dev, bs.sVec, P,
-                           sum ? static_cast<const void*>(c->bSum + off) : static_cast<const void*>(c->bParams + off),
-                           (int64_t)(sum ? sizeof(CovParams) : sizeof(KParams)), c->bInfo + off,
-                           mu_q ? dPrior.as<double>() : nullptr, mu_q ? nullptr : dPrior.as<double>(), dMean.as<double>(),
-                           dVar.as<double>());
+      launch_predict_store(s, B, t_first, m0, mc, m, dot_dev, sq_dev, k.bs.sVec, P, bp.device(c, off), (int64_t)bp.bytes_each(),
+                           k.info, mu_q ? dPrior.as<double>() : nullptr, mu_q ? nullptr : dPrior.as<double>(),
+                           dMean.as<double>(), dVar.as<double>());
     }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->h_bInfo + off, c->bInfo + off, sizeof(int) * B, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(c->h_bInfo + off, k.info, sizeof(int) * B, hipMemcpyDeviceToHost, s));
     return GPMI_OK;
   };
   std::vector<int> inf_all((size_t)T, 0);
@@ -1069,14 +883,7 @@ int gpmi_loo_grad(gpmi_ctx* c, int kernel, const double* theta, int n_theta, dou
   if (int rc = ensure_lanes(c, 2)) return rc;
   Lane& L = c->lanes[1];
   if (int rc = ensure_second_matrix(c, L)) return rc;
-  const int64_t need = grad_ws_doubles(c->np, n_theta) + 4 * c->np;
-  if (L.gws_doubles < need) {
-    if (L.gws) (void)hipFree(L.gws);
-    L.gws = nullptr;
-    L.gws_doubles = 0;
-    HIPCHK(c, hipMalloc(&L.gws, sizeof(double) * need));
-    L.gws_doubles = need;
-  }
+  if (int rc = grow(c, L.gws, L.gws_doubles, grad_ws_doubles(c->np, n_theta) + 4 * c->np, sizeof(double))) return rc;
   hipStream_t s = L.stream;
   const int nt = (int)(c->np / GPMI_NB);
   double* mu_dev = L.vec + 3 * c->np;

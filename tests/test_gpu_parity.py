@@ -524,7 +524,6 @@ def test_batched_gradient_equals_single_evaluations(gp_mod, kid, wn, mean):
     kw = dict(kernel=cov)
     if mean == "linear":
         kw["mean"] = gp_mod.LinearMean
-    base = gp_mod.GpRegressor(x, y, y_err=e, hyperpars=None, n_starts=1, **kw) if False else None
     thetas = wl.theta_set(kid, y, d, 9)
     if wn:
         thetas = np.hstack([thetas, np.linspace(-3.0, -1.0, len(thetas))[:, None]])
