@@ -590,6 +590,48 @@ int gpmi_cov_columns(gpmi_ctx* ctx, int64_t n, int64_t m, int64_t row_stride, in
                      const double* sample_host, int64_t ws_bytes, double* mean_host /* m */,
                      double* cov_host /* m x m, row-major */, int32_t* flag_host /* m */);
 
+/* ---- joint draws from a Gaussian posterior (an addition: the reference's demos call numpy.random.multivariate_normal on
+ * the output of build_posterior, regression.py:421-449) ----
+ * D = mu + Z L^T with L L^T = Sigma + eps I, eps = jitter_rel * max_j Sigma[j][j], all on the device: neither Sigma nor Z
+ * visits the host.  Z is the caller's (z_host) or the library's own counter-based stream of standard normals:
+ *   element (s, j) of the stream of `seed` depends on (seed, s, j) alone.  With p = j / 2, one Philox4x32-10 block
+ *   (Random123: multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85; ten rounds) with the key
+ *   (seed & 0xffffffff, seed >> 32) of the seed's 64-bit pattern and the counter (p, s & 0xffffffff, s >> 32, 0) gives
+ *   the words r0..r3,  u1 = ((r0 >> 5) 2^26 + (r1 >> 6) + 1) 2^-53 in (0, 1],  u2 = ((r2 >> 5) 2^26 + (r3 >> 6)) 2^-53 in
+ *   [0, 1), and with r = sqrt(-2 ln u1), a = fl(2 pi) u2:  Z[s][2 p] = r cos a,  Z[s][2 p + 1] = r sin a (Box-Muller; for
+ *   odd m the last sine is dropped).  Row s of a call is draw first_draw + s of the stream.
+ * Invariants: the fitted state of gpmi_fit is not touched; row s of the result depends on (model, points, jitter_rel,
+ * seed or z row, first_draw + s) alone - not on n_draws, not on the panels the draws are processed in (at most
+ * GPMI_DRAWS_PANEL rows at a time, so n_draws is unbounded while the workspace is not), not on where first_draw starts -
+ * and repeated calls are bit-identical: the product runs on the tile kernels whose order of summation does not depend on
+ * the number of row tiles, and nothing is reduced with atomics.
+ * Numerical failure is not an error status: if the largest diagonal entry of Sigma is not finite and positive, info = 1; if
+ * the factorisation fails, info = k > 0, the order of the leading minor (within the first m rows) that is not positive
+ * definite.  In both cases draws_host is left untouched, the call returns GPMI_OK and the handle stays usable.
+ * GPMI_ERR_ARG: m < 1 or m > GPMI_DRAWS_MAX_M, n_draws < 1, first_draw < 0, jitter_rel negative or not finite, a NULL
+ * pts_host / mean_host / cov_host / draws_host.
+ * Device memory, owned by the call: Sigma (mp (mp + 32) doubles, mp = m rounded up to 128; factorised in place), the
+ * inverses of its diagonal blocks (128 mp), one panel of Z and one of D (rows (mp + 32) each, rows = min(n_draws rounded
+ * up to 128, GPMI_DRAWS_PANEL)); gpmi_posterior_draws also uses the handle's query workspace, as gpmi_posterior does. */
+#define GPMI_DRAWS_MAX_M 16384
+#define GPMI_DRAWS_PANEL 4096
+/* S joint draws of the latent function at m points from the model of gpmi_fit (one stationary kernel or a sum,
+ * any noise model gpmi_posterior serves):  D[s][j] = mu[j] + sum_{k<=j} L[j][k] Z[s][k],  L L^T = Sigma + eps I,
+ * Sigma = K_qq - Q^T Q as gpmi_posterior, eps = jitter_rel * max_j Sigma[j][j].  (No data noise in K_qq; the host adds
+ * the mean function at the points.)  Without a fit, or after gpmi_fit_dense / gpmi_fit_mix: GPMI_ERR_ARG - such a caller
+ * passes its own mean and covariance to gpmi_mvn_draws. */
+int gpmi_posterior_draws(gpmi_ctx*, const double* pts_host, int64_t m, double jitter_rel, int64_t n_draws,
+                         const double* z_host /* n_draws x m, or NULL: generated */, int64_t seed, int64_t first_draw,
+                         double* mu_host /* m, may be NULL */, double* draws_host /* n_draws x m */,
+                         double* eps_host /* 1, may be NULL */, int* info);
+/* the same tail for a caller's mean (m) and covariance (m x m row-major, lower triangle read); needs no data set */
+int gpmi_mvn_draws(gpmi_ctx*, int64_t m, const double* mean_host, const double* cov_host, double jitter_rel,
+                   int64_t n_draws, const double* z_host, int64_t seed, int64_t first_draw,
+                   double* draws_host, double* eps_host, int* info);
+/* host-only, no device call: rows first_draw .. first_draw + n_draws - 1 of the generator's stream (n_draws x m), from the
+ * same integer code with the host's libm: within a few units in the last place of the device's */
+int gpmi_draws_normals(int64_t seed, int64_t first_draw, int64_t n_draws, int64_t m, double* z_host);
+
 /* ---- instrumentation ---------------------------------------------------------------
  * HIP-event timing on the handle's own stream (torch.cuda.Event would not see it). */
 int gpmi_timer_start(gpmi_ctx* ctx);
@@ -617,7 +659,12 @@ int gpmi_flow_task_lists(int m, int nwg, int64_t cap, int32_t* out, int64_t* nta
                                chain most of the time, so this is the overlap achieved, not a kernel rate */
 #define GPMI_PROF_COV 8     /* the kernels of gpmi_cov_columns, from the column sums to the scaled covariance, without the
                                copies to and from the device (HBM-read bound: the sample is read twice) */
-#define GPMI_PROF_NCLASS 9
+/* the four stages of gpmi_posterior_draws / gpmi_mvn_draws (tools/draws_bench.py), each bracketed as a whole */
+#define GPMI_PROF_DRAWS_SIGMA 9    /* Sigma: cross-covariances, the many-right-hand-side solve, K_qq - Q^T Q (or the upload) */
+#define GPMI_PROF_DRAWS_FACTOR 10  /* max diag, + eps I, the factorisation, the zeroing of the upper triangle */
+#define GPMI_PROF_DRAWS_NORMALS 11 /* the normal generator (or the upload of the caller's Z) */
+#define GPMI_PROF_DRAWS_PRODUCT 12 /* D = Z L^T + mu */
+#define GPMI_PROF_NCLASS 13
 /* on = 0: off; 1: every class; otherwise a class bitmask shifted left by one (2 << klass) */
 int gpmi_profile_enable(gpmi_ctx* ctx, int on);
 /* accumulated since the last reset: launches, total ms, algorithmic flops and bytes */

@@ -576,7 +576,7 @@ unsigned long long* prof_stamp_slot(gpmi_ctx* c, double flops, double bytes, int
 }
 
 ProfScope::ProfScope(gpmi_ctx* ctx, hipStream_t st, int klass, double flops, double bytes)
-    : c(ctx), s(st), slot(nullptr) {
+    : c(ctx), s(st), slot(-1) {
   if (!((c->prof_mask >> klass) & 1) || klass == GPMI_PROF_SYRK || klass == GPMI_PROF_SYRK_REST ||
       klass == GPMI_PROF_SYRK_SLICE || klass == GPMI_PROF_FLOW)
     return;
@@ -585,14 +585,15 @@ ProfScope::ProfScope(gpmi_ctx* ctx, hipStream_t st, int klass, double flops, dou
     if (hipEventCreate(&ns.e0) != hipSuccess || hipEventCreate(&ns.e1) != hipSuccess) return;
     c->prof_slots.push_back(ns);
   }
-  slot = &c->prof_slots[c->prof_used++];
-  slot->klass = klass;
-  slot->flops = flops;
-  slot->bytes = bytes;
-  (void)hipEventRecord(slot->e0, s);
+  slot = (int64_t)c->prof_used++;
+  ProfSlot& sl = c->prof_slots[(size_t)slot];
+  sl.klass = klass;
+  sl.flops = flops;
+  sl.bytes = bytes;
+  (void)hipEventRecord(sl.e0, s);
 }
 ProfScope::~ProfScope() {
-  if (slot) (void)hipEventRecord(slot->e1, s);
+  if (slot >= 0) (void)hipEventRecord(c->prof_slots[(size_t)slot].e1, s);
 }
 extern "C" {
 

@@ -199,6 +199,21 @@ int grow(gpmi_ctx* c, P*& ptr, N& cap, int64_t want, size_t bytes_each) {
   return GPMI_OK;
 }
 
+// device memory of one call
+struct DevBuf {
+  void* p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+  template <class T>
+  T* as() const {
+    return static_cast<T*>(p);
+  }
+};
+
 // T evaluations one at a time (beyond the lockstep sizes): row(t, mu_t) with the mean of evaluation t as n values
 template <class F>
 int one_at_a_time(gpmi_ctx* c, int64_t T, const double* mus, const double* mu_const, F&& row) {

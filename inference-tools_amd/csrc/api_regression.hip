@@ -532,21 +532,6 @@ int gpmi_predict(gpmi_ctx* c, const double* pts, int64_t m, double* mu_out, doub
 
 extern "C++" {
 namespace {
-// device memory of one call
-struct DevBuf {
-  void* p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  template <class T>
-  T* as() const {
-    return static_cast<T*>(p);
-  }
-};
-
 // sum of v[0 .. n) as the pairwise tree of predict_batch.hip (halves split at the largest power of two below n)
 double tree_sum_host(const double* v, int64_t n) {
   if (n <= 0) return 0.0;

@@ -8,7 +8,7 @@ ASAN_FLAGS := --offload-arch=$(ARCH) -O1 -g -std=c++17 -fPIC -fsanitize=address,
               -fno-omit-frame-pointer -fno-sanitize-recover=undefined $(INC)
 ASAN_OBJS  := $(patsubst %.hip,$(ROOT)/build_asan/%.o,$(SRCS))
 
-$(ROOT)/build_asan/%.o: $(ROOT)/%.hip $(ROOT)/gpmi_internal.h $(ROOT)/gemm_tiles.h $(ROOT)/kmath.h $(ROOT)/factor16_steps.h $(ROOT)/potrf_diag.h $(ROOT)/api_internal.h $(ROOT)/kde_state.h $(ROOT)/col_transpose.h $(ROOT)/../../include/gpmi.h
+$(ROOT)/build_asan/%.o: $(ROOT)/%.hip $(ROOT)/gpmi_internal.h $(ROOT)/gemm_tiles.h $(ROOT)/kmath.h $(ROOT)/factor16_steps.h $(ROOT)/potrf_diag.h $(ROOT)/api_internal.h $(ROOT)/kde_state.h $(ROOT)/col_transpose.h $(ROOT)/philox.h $(ROOT)/../../include/gpmi.h
 	@mkdir -p $(ROOT)/build_asan
 	$(HIPCC) $(ASAN_FLAGS) -c $< -o $@
 

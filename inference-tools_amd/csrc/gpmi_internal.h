@@ -252,7 +252,7 @@ unsigned long long* prof_stamp_slot(gpmi_ctx* c, double flops, double bytes, int
 struct ProfScope {
   gpmi_ctx* c;
   hipStream_t s;
-  ProfSlot* slot;
+  int64_t slot;  // index into gpmi_ctx::prof_slots (-1: not timed) - not a pointer: a scope opened inside this one may grow the vector
   ProfScope(gpmi_ctx* ctx, hipStream_t st, int klass, double flops, double bytes);
   ~ProfScope();
 };

@@ -70,6 +70,30 @@ class _DeviceCommMixin:
         self.comm_world = 0
 
 
+def _seed_i64(seed):
+    """The 64-bit pattern of `seed` as the signed integer the C-ABI takes."""
+    return ((int(seed) + (1 << 63)) % (1 << 64)) - (1 << 63)
+
+
+class _DrawsMixin:
+    """gpmi_mvn_draws on the handle `self.h`: joint normal draws from a mean vector and a covariance matrix."""
+
+    def mvn_draws(self, mean, cov, n_draws=1, seed=0, z=None, jitter=1e-9, first_draw=0):
+        """`n_draws` rows mean + z_s L^T with L L^T = cov + eps I, eps = jitter * max diag(cov) (the lower triangle of
+        `cov` is read).  z: (n_draws, m) normals of the caller, or None: rows first_draw .. of the stream of `seed`.
+        Returns (draws (n_draws, m) - None if info != 0 -, eps, info)."""
+        mean, cov = as_f64(mean), as_f64(cov)
+        m = mean.size
+        if cov.shape != (m, m):
+            raise ValueError(f"cov must be ({m}, {m}), got {cov.shape}")
+        z = None if z is None else as_f64(z).reshape(int(n_draws), m)
+        draws = np.empty((int(n_draws), m))
+        eps, info = C.c_double(0.0), C.c_int(0)
+        self.h.call("gpmi_mvn_draws", m, dptr(mean), dptr(cov), float(jitter), int(n_draws), dptr(z), _seed_i64(seed),
+                    int(first_draw), dptr(draws), C.byref(eps), C.byref(info))
+        return (draws if info.value == 0 else None), eps.value, info.value
+
+
 class DeviceComm(_DeviceCommMixin):
     """A communicator on a handle of its own, for what happens before a rank has any data: rank 0 broadcasts x, y,
     y_err (sharding.broadcast_dataset; the reference pickles the whole regressor into its worker processes,
@@ -83,7 +107,7 @@ class DeviceComm(_DeviceCommMixin):
         self.h.close()
 
 
-class GpEngine(_DeviceCommMixin):
+class GpEngine(_DeviceCommMixin, _DrawsMixin):
     def __init__(self, x, y, noise_var=None, y_cov=None, device=None, reserve=0):
         self.h = _lib.Handle(device)
         self.x = as_f64(x)
@@ -405,6 +429,18 @@ class GpEngine(_DeviceCommMixin):
         self.h.call("gpmi_posterior", dptr(p), m, dptr(mu), dptr(cov))
         return mu, cov
 
+    def posterior_draws(self, pts, n_draws=1, seed=0, z=None, jitter=1e-9, first_draw=0):
+        """gpmi_posterior_draws: `n_draws` joint draws of the latent function at `pts` from the fitted model, without the
+        mean function.  Arguments as `mvn_draws`.  Returns (draws | None, mu (m,), eps, info)."""
+        p = as_f64(pts)
+        m = p.shape[0]
+        z = None if z is None else as_f64(z).reshape(int(n_draws), m)
+        mu, draws = np.empty(m), np.empty((int(n_draws), m))
+        eps, info = C.c_double(0.0), C.c_int(0)
+        self.h.call("gpmi_posterior_draws", dptr(p), m, float(jitter), int(n_draws), dptr(z), _seed_i64(seed),
+                    int(first_draw), dptr(mu), dptr(draws), C.byref(eps), C.byref(info))
+        return (draws if info.value == 0 else None), mu, eps.value, info.value
+
     def spatial_derivatives(self, pts):
         p = as_f64(pts)
         m = p.shape[0]
@@ -573,7 +609,7 @@ class GpEngine(_DeviceCommMixin):
         self.h.close()
 
 
-class LinvEngine:
+class LinvEngine(_DrawsMixin):
     """Device side of `GpLinearInverter` (gpmi_linv_*): parameter positions, model matrix and data are
     uploaded once; every call evaluates one hyper-parameter vector."""
 

@@ -31,6 +31,9 @@ _TRACE_MS = float(os.environ["GPMI_TRACE_CALLS"]) if os.environ.get("GPMI_TRACE_
 ERR_INTERNAL = -5  # GPMI_ERR_INTERNAL
 COV_CHUNK_ROWS = 2048  # GPMI_COV_CHUNK_ROWS: rows per chunk of gpmi_cov_columns
 COV_MAX_COLUMNS = 512  # the most columns gpmi_cov_columns takes
+PROF_DRAWS_SIGMA, PROF_DRAWS_FACTOR, PROF_DRAWS_NORMALS, PROF_DRAWS_PRODUCT = 9, 10, 11, 12  # GPMI_PROF_DRAWS_*
+DRAWS_MAX_M = 16384  # GPMI_DRAWS_MAX_M: the most points gpmi_posterior_draws / gpmi_mvn_draws take
+DRAWS_PANEL = 4096  # GPMI_DRAWS_PANEL: draws per panel of those two
 
 
 class GpmiUnavailable(RuntimeError):
@@ -132,6 +135,9 @@ SIGNATURES = {
                                    C.POINTER(C.c_int32)]),
     "gpmi_cov_columns": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _dp, _i64, _dp, _dp, C.POINTER(C.c_int32)]),
     "gpmi_acf_lag_blocks": (C.c_int, [_i64, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
+    "gpmi_posterior_draws": (C.c_int, [_vp, _dp, _i64, C.c_double, _i64, _dp, _i64, _i64, _dp, _dp, _dp, _ip]),
+    "gpmi_mvn_draws": (C.c_int, [_vp, _i64, _dp, _dp, C.c_double, _i64, _dp, _i64, _i64, _dp, _dp, _ip]),
+    "gpmi_draws_normals": (C.c_int, [_i64, _i64, _i64, _i64, _dp]),
     "gpmi_timer_start": (C.c_int, [_vp]),
     "gpmi_timer_stop": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "gpmi_profile_enable": (C.c_int, [_vp, C.c_int]),
@@ -240,7 +246,8 @@ class Handle:
                              "gpmi_linv_lml", "gpmi_linv_lml_grad", "gpmi_linv_posterior", "gpmi_linv_lml_dense",
                              "gpmi_linv_lml_grad_dense", "gpmi_linv_posterior_dense", "gpmi_loo_terms", "gpmi_loo_grad",
                              "gpmi_loo_terms_mix", "gpmi_dev_potrf", "gpmi_loo_grad_batch", "gpmi_loo_grad_batch_noise", "gpmi_lml_grad_batch_noise",
-                             "gpmi_lml_grad_batch_mix", "gpmi_loo_grad_batch_mix", "gpmi_predict_batch"))
+                             "gpmi_lml_grad_batch_mix", "gpmi_loo_grad_batch_mix", "gpmi_predict_batch", "gpmi_posterior_draws",
+                             "gpmi_mvn_draws"))
 
     def call(self, name, *args):
         if _TRACE_MS is not None:  # GPMI_TRACE_CALLS=<ms>: report every entry-point call that takes longer (debugging aid)

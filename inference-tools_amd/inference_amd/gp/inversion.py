@@ -23,6 +23,7 @@ from scipy.optimize import minimize
 from inference_amd import _lib
 from inference_amd._engine import LinvEngine
 from inference_amd.gp import _messages as msg
+from inference_amd.gp._draws import draw_arguments, raise_if_not_positive_definite
 from inference_amd.gp.covariance import CovarianceFunction, SquaredExponential, device_plan, heteroscedastic_slice
 from inference_amd.gp.mean import ConstantMean, MeanFunction
 
@@ -132,6 +133,21 @@ class GpLinearInverter:
             mean, _, info = self.engine.posterior(self._kernel_id, theta_stat, extra, prior_mean, with_cov=False)
         self._check(info)
         return mean
+
+    def sample_posterior(self, theta: ndarray, n_draws: int = 1, *, seed=None, z=None, jitter: float = 1e-9,
+                         first_draw: int = 0):
+        """(extension) `n_draws` joint draws of the model parameters from the posterior of `calculate_posterior(theta)`,
+        shape (n_draws, parameters): mean + z_s L^T with L L^T = cov + eps I, eps = jitter * max diag(cov), factorised
+        and multiplied on the device.  `seed`, `z`, `first_draw` and the error as `GpRegressor.sample_posterior`; the seed
+        used is kept in `last_sample_seed`."""
+        mean, cov = self.calculate_posterior(theta)
+        n_draws, seed, z, jitter, first_draw = draw_arguments("GpLinearInverter", mean.size, n_draws, seed, z, jitter,
+                                                              first_draw)
+        draws, eps, info = self.engine.mvn_draws(mean, cov, n_draws=n_draws, seed=0 if seed is None else seed, z=z,
+                                                 jitter=jitter, first_draw=first_draw)
+        self.last_sample_seed = seed
+        raise_if_not_positive_definite("GpLinearInverter", info, jitter, eps)
+        return draws
 
     def marginal_likelihood(self, theta: ndarray) -> float:
         """Log-marginal likelihood without the 2 pi constant (inversion.py:177-191)."""

@@ -26,6 +26,7 @@ from scipy.optimize import differential_evolution, fmin_l_bfgs_b
 from inference_amd import _lib
 from inference_amd._engine import GpEngine
 from inference_amd.gp import _messages as msg
+from inference_amd.gp._draws import draw_arguments, raise_if_not_positive_definite
 from inference_amd.gp.covariance import heteroscedastic_slice, CovarianceFunction, SquaredExponential, device_plan, sum_kernels
 from inference_amd.gp.mean import ConstantMean, MeanFunction
 
@@ -600,6 +601,35 @@ class GpRegressor:
         if mean_only:
             return mu
         return mu, sigma
+
+    def sample_posterior(self, points: ndarray, n_draws: int = 1, *, seed=None, z=None, jitter: float = 1e-9,
+                         first_draw: int = 0):
+        """(extension) `n_draws` joint draws of the latent function at the M `points` from the fitted posterior, shape
+        (n_draws, M): mu + z_s L^T with L L^T = Sigma + eps I for the mean and covariance of `build_posterior` (no data
+        noise) and eps = jitter * max diag(Sigma), evaluated on the device without bringing Sigma or the normals to the
+        host.  The reference has no counterpart (its demos pass `build_posterior`'s output to
+        numpy.random.multivariate_normal).
+
+        seed: the draws are rows first_draw .. first_draw + n_draws - 1 of the counter-based stream of that seed
+        (include/gpmi.h), so a row depends on (model, points, jitter, seed, its index) alone; None takes 64 bits from
+        numpy.random.SeedSequence() - not reproducible.  The seed used is kept in `last_sample_seed`.
+        z: (n_draws, M) standard normals of the caller instead (common random numbers, quasi-random inputs); excludes
+        `seed` and a non-zero `first_draw`.
+        Raises numpy.linalg.LinAlgError if Sigma + eps I is not positive definite."""
+        v = self.process_points(points)
+        n_draws, seed, z, jitter, first_draw = draw_arguments("GpRegressor", len(v), n_draws, seed, z, jitter, first_draw)
+        kw = dict(n_draws=n_draws, seed=0 if seed is None else seed, z=z, jitter=jitter, first_draw=first_draw)
+        if self._generic or self._mix is not None:
+            # ChangePoint and plugin kernels: mean and covariance as build_posterior evaluates them
+            mu, sigma = self.build_posterior(v)
+            draws, eps, info = self.engine.mvn_draws(mu, sigma, **kw)
+        else:
+            draws, _, eps, info = self.engine.posterior_draws(v, **kw)
+            if info == 0:
+                draws += self._mean_at(v)
+        self.last_sample_seed = seed
+        raise_if_not_positive_definite("GpRegressor", info, jitter, eps)
+        return draws
 
     def loo_predictions(self):
         """Leave-one-out predictions, R&W eq. 5.12 (regression.py:451-466)."""
