@@ -632,6 +632,55 @@ int gpmi_mvn_draws(gpmi_ctx*, int64_t m, const double* mean_host, const double* 
  * same integer code with the host's libm: within a few units in the last place of the device's */
 int gpmi_draws_normals(int64_t seed, int64_t first_draw, int64_t n_draws, int64_t m, double* z_host);
 
+/* ---- large data: the variational inducing-point approximation (Titsias 2009; an addition, the reference has none) ----
+ * N data points x (N x d) are summarised by m << N fixed inducing inputs Z (m x d): O(N m^2) time, O(N d + m^2) memory.
+ * With r = y - mu(x) (the caller's residual), sigma_i^2 = noise_var_i + white_var, W = diag(1 / sigma_i^2), k one
+ * stationary kernel of prior variance a^2 and eps = jitter_rel a^2:
+ *   K_mm + eps I = L L^T        G = K_mn W K_nm        H = L^-1 G L^-T (symmetrised)        B = I + H = L_B L_B^T
+ *   c = L_B^-1 L^-1 K_mn W r
+ *   F = -1/2 [N ln 2 pi + sum ln sigma_i^2 + 2 sum ln diag(L_B) + r^T W r - c^T c] - 1/2 [a^2 sum_i 1 / sigma_i^2 - tr H]
+ *   mean(q) = u^T c,   var(q) = a^2 - |v|^2 + |u|^2,   v = L^-1 k_m(q),   u = L_B^-1 v       (the latent f: no noise added)
+ * F is a lower bound of the log marginal likelihood (with its 2 pi constant) and equals it for Z = x, eps = 0.  Only B is
+ * ever factorised besides K_mm + eps I - never the N x N matrix, never K_mm^-1 times a data-sized array.
+ * K_mn is never held whole: x is walked in panels of `panel_rows` rows (0: the default, 8192; rounded up to a multiple of
+ * 128), one panel (m_pad x panel doubles) at a time, twice for a gradient.  F, the gradient and alpha may depend on
+ * panel_rows in their last digits (the grouping of the sums over the data changes); for given arguments every result is
+ * bit-reproducible: fixed-order reductions, no atomics.
+ * The gradient (n_theta + 1 values: the kernel's parameters in theta's order, then dF / d ln s with white_var = s^2,
+ * which is 0 for white_var = 0) includes d eps / d ln a = 2 eps.  alpha = W (r - K_nm gamma), gamma = (K_mm + eps I + G)^-1
+ * K_mn W r (N values): the mean function's gradient is (d mu / d theta)^T alpha on the host.
+ * info > 0 is not an error status: K_mm + eps I (info = the order of the leading minor that is not positive definite,
+ * 1..m) or B (m + that order) could not be factorised; F, grad and alpha are then untouched, the call returns GPMI_OK and
+ * the object stays usable.  GPMI_ERR_ARG (text via gpmi_last_error, object still usable): a NULL pointer that is not
+ * optional, a kernel other than GPMI_KERNEL_SE / _RQ / _M32 / _M52, an n_theta that does not match kernel and d, white_var
+ * or jitter_rel negative or not finite, panel_rows negative, noise_var_i + white_var not positive for some i (checked on
+ * the device), gpmi_sgp_bound / _fit before gpmi_sgp_set_targets, gpmi_sgp_predict before a successful gpmi_sgp_fit.
+ * Limits: 1 <= m <= GPMI_SGP_MAX_M, 2 <= n <= 2^30, d <= 64; m <= n is not required.
+ * gpmi_sgp_bound does not touch the state gpmi_sgp_fit left: predictions before and after it are bit-identical.
+ * Device memory of an object: x, Z, r, the noise variances and two more vectors of n doubles (1 / sigma_i^2, alpha); eleven
+ * matrices of m_pad (m_pad + 32) doubles (m_pad = m rounded up to 128; nine of work, two of the fit); three panels of
+ * max(m_pad, panel) x (max(m_pad, panel) + 32) doubles at most, allocated at the first call that needs them.
+ * Objects belong to their handle (calls on one handle are serialised); gpmi_destroy releases those still alive. */
+#define GPMI_SGP_MAX_M 4096
+#define GPMI_SGP_PANEL 8192
+typedef struct gpmi_sgp gpmi_sgp;
+int gpmi_sgp_create(gpmi_ctx* ctx, int64_t n, int64_t d, const double* x_host /* n x d */, int64_t m,
+                    const double* z_host /* m x d */, gpmi_sgp** out);
+/* release an object (NULL, or not a live object of its handle: GPMI_ERR_ARG); not after gpmi_destroy of the handle */
+int gpmi_sgp_destroy(gpmi_sgp* sgp);
+/* the residual r = y - mu(x) and the data variances y_err^2 (NULL: all zero), n values each; they stay on the device */
+int gpmi_sgp_set_targets(gpmi_sgp* sgp, const double* r_host, const double* noise_var_host);
+int gpmi_sgp_bound(gpmi_sgp* sgp, int kernel, const double* theta, int n_theta, double white_var, double jitter_rel,
+                   int64_t panel_rows, double* F, double* grad /* n_theta + 1, may be NULL */,
+                   double* alpha_host /* n, may be NULL */, int* info);
+/* the bound, and L^-1, L_B^-1, c and the kernel's parameters kept for gpmi_sgp_predict (kept only if info == 0; a failed
+ * fit leaves the previous one in place) */
+int gpmi_sgp_fit(gpmi_sgp* sgp, int kernel, const double* theta, int n_theta, double white_var, double jitter_rel,
+                 int64_t panel_rows, double* F, int* info);
+/* mean and variance of the latent function at mq points (panels of 1024 points); var_host may be NULL */
+int gpmi_sgp_predict(gpmi_sgp* sgp, const double* pts_host /* mq x d */, int64_t mq, double* mean_host,
+                     double* var_host);
+
 /* ---- instrumentation ---------------------------------------------------------------
  * HIP-event timing on the handle's own stream (torch.cuda.Event would not see it). */
 int gpmi_timer_start(gpmi_ctx* ctx);
@@ -664,7 +713,12 @@ int gpmi_flow_task_lists(int m, int nwg, int64_t cap, int32_t* out, int64_t* nta
 #define GPMI_PROF_DRAWS_FACTOR 10  /* max diag, + eps I, the factorisation, the zeroing of the upper triangle */
 #define GPMI_PROF_DRAWS_NORMALS 11 /* the normal generator (or the upload of the caller's Z) */
 #define GPMI_PROF_DRAWS_PRODUCT 12 /* D = Z L^T + mu */
-#define GPMI_PROF_NCLASS 13
+/* the four stages of gpmi_sgp_bound / gpmi_sgp_fit (tools/sparse_bench.py), each bracketed as a whole */
+#define GPMI_PROF_SGP_BUILD 13  /* pass 1: the panels of K_mn (cross build, column scaling, K_mn W r) */
+#define GPMI_PROF_SGP_GRAM 14   /* pass 1: G += (K_mn W^1/2)(K_mn W^1/2)^T, 2 N m^2 FLOP on the fp64 matrix cores */
+#define GPMI_PROF_SGP_FACTOR 15 /* the m x m algebra: two factorisations, their inverses, H, c, the reductions */
+#define GPMI_PROF_SGP_GRAD 16   /* the gradient: S, T, M2 and pass 2 (panel rebuild, T K_mn, the contraction) */
+#define GPMI_PROF_NCLASS 17
 /* on = 0: off; 1: every class; otherwise a class bitmask shifted left by one (2 << klass) */
 int gpmi_profile_enable(gpmi_ctx* ctx, int on);
 /* accumulated since the last reset: launches, total ms, algorithmic flops and bytes */

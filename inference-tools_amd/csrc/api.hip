@@ -675,6 +675,7 @@ int gpmi_destroy(gpmi_ctx* c) {
   // stream that has only been synchronised once blocked forever on ROCm 7.2 (round-2 probe, profiles/HISTORY.md)
   (void)gpmi_sync(c);
   kde_release_all(c);
+  sgp_release_all(c);
   DBG_FREE("comm destroy");
   (void)gpmi_comm_destroy(c);
   DBG_FREE("free data");

@@ -139,6 +139,7 @@ struct LinvState {
 };
 
 struct KdeState;  // kde.hip
+struct gpmi_sgp;  // sparse.hip
 
 struct gpmi_ctx {
   int device = 0;
@@ -225,6 +226,9 @@ struct gpmi_ctx {
   int64_t comm_buf_doubles = 0;
   hipStream_t dev_masked = nullptr;  // tools: CU-masked stream of the device-pointer entry points (GPMI_DEV_CUS)
   KdeState* kde = nullptr;  // kde.hip: stream, workspaces and live objects of the gpmi_kde_* entry points
+  // sparse.hip: the live objects of the gpmi_sgp_* entry points and the stream they share (created with the first one)
+  std::vector<gpmi_sgp*> sgp_live;
+  hipStream_t sgp_stream = nullptr;
   // instrumentation
   hipEvent_t t0 = nullptr, t1 = nullptr;
   unsigned prof_mask = 0;
@@ -243,6 +247,8 @@ struct gpmi_ctx {
 
 // kde.hip: destroy the handle's density objects and their stream / workspaces (gpmi_destroy)
 void kde_release_all(gpmi_ctx* c);
+// sparse.hip: the same for the inducing-point models (gpmi_destroy)
+void sgp_release_all(gpmi_ctx* c);
 
 // instrumentation helpers (api.hip)
 constexpr int GPMI_STAMP_SLOTS = 16384;

@@ -1,0 +1,774 @@
+// Variational inducing-point GP regression (include/gpmi.h: gpmi_sgp_*; Titsias 2009) on gfx950.
+//
+// N data points are summarised by m <= 4096 inducing inputs Z.  With W = diag(1 / sigma_i^2):
+//   K_mm + eps I = L L^T,  G = K_mn W K_nm,  H = L^-1 G L^-T,  B = I + H = L_B L_B^T,  c = L_B^-1 L^-1 K_mn W r,
+//   F = -1/2 [N ln 2 pi + sum ln sigma_i^2 + 2 sum ln diag(L_B) + r^T W r - c^T c] - 1/2 [a^2 sum w_i - tr H].
+// Pass 1 walks x in panels: cross build of the m x P panel of K_mn (kbuild.hip), columns scaled by 1 / sigma_i, G accumulated
+// on the fp64 matrix cores (gemm_f64.hip, lower tiles), b = K_mn W r by rows.  The m x m algebra is the lockstep
+// factorisation and inverse of the small-problem path (potrf_lower_batched, trsm_identity_batched, batch of one) and
+// products with the explicit triangular inverses L^-1, L_B^-1 - B is factorised, never K_mm^-1 G or the N x N matrix.
+// Pass 2 (gradient) rebuilds every panel transposed (P x m: rows are data points), forms alpha = W (r - K_nm gamma), the
+// weight panel T K_mn (one GEMM) and contracts  sum_ij M1_ij dK(z_i, x_j)/dtheta  in sgp_contract_kernel, which is new:
+// 64 x 64 tiles, both point panels staged in LDS, value and derivative profiles recomputed (kfun.h), one partial per tile
+// and parameter, summed by a second kernel in a fixed order.  The K_mm term runs through the same kernel (rows = Z).
+//   gamma = L^-T L_B^-T c;  beta = K_mm^-1 K_mn alpha = gamma (exactly: (K_mm + G) gamma = b);  S = L^-T B^-1 L^-1;
+//   T = L^-T L^-1 - S;  M1 = gamma alpha^T + T K_mn W;  M2 = gamma gamma^T + K_mm^-1 G K_mm^-1 - T;
+//   dF/dtheta = sum M1 o dK_mn - 1/2 sum M2 o d(K_mm + eps I) - 1/2 sum w_i da^2/dtheta;
+//   dF/d ln s = s^2 sum_i [alpha_i^2 - w_i + w_i^2 (a^2 - k_i^T T k_i)].
+// Every reduction has a fixed order, nothing uses atomics: a call repeated gives the same bits.
+#include <limits>
+
+#include "api_internal.h"
+#include "kfun.h"
+
+struct gpmi_sgp {
+  gpmi_ctx* ctx = nullptr;
+  int64_t n = 0, d = 0, m = 0, mp = 0, ld = 0;
+  double *x = nullptr, *z = nullptr, *r = nullptr, *nv = nullptr;  // n x d, m x d, n, n
+  double *w = nullptr, *alpha = nullptr;                           // n each: 1 / sigma_i^2, alpha
+  bool have_targets = false;
+  // mp x ld work matrices (roles in sgp_factor / sgp_gradient) and the inverse diagonal blocks of the two factors
+  double* M[9] = {};
+  double *invD1 = nullptr, *invD2 = nullptr;
+  double* vec = nullptr;   // 4 x mp: b, L^-1 b, c, gamma
+  double* red = nullptr;   // 128 small results
+  int* info = nullptr;     // 2 words
+  double* part = nullptr;  // SGP_RED_BLOCKS x 4 partial sums over the data
+  // panels (allocated at first use): three of max(mp (R + 32), R ld) doubles, three vectors of R, the contraction's partials
+  double* P[3] = {};
+  double* pvec = nullptr;
+  double* ws = nullptr;
+  int64_t panel_cap = 0;
+  // query staging: 1024 x d points, 2 x 1024 results
+  double *q_pts = nullptr, *q_out = nullptr;
+  // the fit: L^-1, L_B^-1 (mp x ld), c (mp), the kernel
+  double *fLinv = nullptr, *fLBinv = nullptr, *fc = nullptr;
+  KParams fp = {};
+  bool fitted = false;
+};
+
+namespace {
+
+constexpr int KT = 64;
+constexpr int SGP_NT = 256;
+constexpr int SGP_RED_BLOCKS = 1024;
+constexpr int SGP_QPANEL = 1024;
+constexpr int64_t SGP_MAX_PANEL = 32768;
+// slots of gpmi_sgp::red
+constexpr int RED_DATA = 0;   // r^T W r, sum ln sigma^2, sum w, count of non-positive variances
+constexpr int RED_MM = 4;     // sum ln diag(L_B), tr H, c^T c
+constexpr int RED_NOISE = 8;  // sum_i [alpha_i^2 - w_i + w_i^2 (a^2 - k_i^T T k_i)]
+constexpr int RED_GRAD = 16;  // n_theta partial derivatives
+
+__device__ inline double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+
+// block-wide sum (256 threads), the same value in every thread
+__device__ inline double block_sum(double v, double* red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+
+// w_i = 1 / (nv_i + white) and, per workgroup, the partial sums [r^T W r, sum ln sigma^2, sum w, bad] over its
+// grid-strided share of the data (bad: variances that are not positive and finite; their w is 0)
+__global__ __launch_bounds__(SGP_NT) void sgp_weights_kernel(const double* __restrict__ r, const double* __restrict__ nv,
+                                                             double white, int64_t n, double* __restrict__ w,
+                                                             double* __restrict__ part) {
+  __shared__ double red[4];
+  double rwr = 0.0, lns = 0.0, sw = 0.0, bad = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * SGP_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * SGP_NT) {
+    const double s2 = nv[i] + white;
+    const bool ok = s2 > 0.0 && s2 < std::numeric_limits<double>::infinity();
+    const double wi = ok ? 1.0 / s2 : 0.0;
+    w[i] = wi;
+    if (ok) {
+      rwr = fma(r[i] * r[i], wi, rwr);
+      lns += log(s2);
+      sw += wi;
+    } else {
+      bad += 1.0;
+    }
+  }
+  const double v0 = block_sum(rwr, red), v1 = block_sum(lns, red), v2 = block_sum(sw, red), v3 = block_sum(bad, red);
+  if (threadIdx.x == 0) {
+    double* o = part + (int64_t)blockIdx.x * 4;
+    o[0] = v0;
+    o[1] = v1;
+    o[2] = v2;
+    o[3] = v3;
+  }
+}
+
+// out[j] (+)= sum_t ws[t][j], t < nrows, in a fixed order: thread-strided partial sums, then a tree (workgroup j)
+__global__ __launch_bounds__(SGP_NT) void sgp_colsum_kernel(const double* __restrict__ ws, int64_t nrows, int width,
+                                                            double* __restrict__ out, int accumulate) {
+  __shared__ double red[4];
+  const int j = blockIdx.x;
+  double acc = 0.0;
+  for (int64_t t = threadIdx.x; t < nrows; t += SGP_NT) acc += ws[t * width + j];
+  const double v = block_sum(acc, red);
+  if (threadIdx.x == 0) out[j] = accumulate ? out[j] + v : v;
+}
+
+// K[i][j] *= sqrt(w[j]), i < rows (grid.y), j < cols
+__global__ __launch_bounds__(SGP_NT) void sgp_scale_cols_kernel(double* __restrict__ K, int64_t ld, int64_t cols,
+                                                                const double* __restrict__ w) {
+  const int64_t j = (int64_t)blockIdx.x * SGP_NT + threadIdx.x, i = blockIdx.y;
+  if (j < cols) K[i * ld + j] *= sqrt(w[j]);
+}
+
+// b[i] (+)= sum_j Kw[i][j] r[j] sqrt(w[j]), j < cols; workgroup i
+__global__ __launch_bounds__(SGP_NT) void sgp_bvec_kernel(const double* __restrict__ Kw, int64_t ld, int64_t cols,
+                                                          const double* __restrict__ r, const double* __restrict__ w,
+                                                          double* __restrict__ b, int accumulate) {
+  __shared__ double red[4];
+  const int64_t i = blockIdx.x;
+  double acc = 0.0;
+  for (int64_t j = threadIdx.x; j < cols; j += SGP_NT) acc = fma(Kw[i * ld + j], r[j] * sqrt(w[j]), acc);
+  const double v = block_sum(acc, red);
+  if (threadIdx.x == 0) b[i] = accumulate ? b[i] + v : v;
+}
+
+// A[i][i] += eps for i < m; = 1 in the padding (the cross build leaves zeros there)
+__global__ void sgp_pad_diag_kernel(double* __restrict__ A, int64_t ld, int64_t m, int64_t mp, double eps) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= mp) return;
+  if (i < m) A[i * ld + i] += eps;
+  else A[i * ld + i] = 1.0;
+}
+
+// dst = src^T (mp x mp, 64 x 64 tiles through LDS)
+__global__ __launch_bounds__(SGP_NT) void sgp_transpose_kernel(const double* __restrict__ src, double* __restrict__ dst,
+                                                               int64_t ld) {
+  __shared__ double t[64][65];
+  const int ti = blockIdx.y, tj = blockIdx.x;
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  for (int r = ty; r < 64; r += 4) t[r][tx] = src[((int64_t)ti * 64 + r) * ld + (int64_t)tj * 64 + tx];
+  __syncthreads();
+  for (int r = ty; r < 64; r += 4) dst[((int64_t)tj * 64 + r) * ld + (int64_t)ti * 64 + tx] = t[tx][r];
+}
+
+// B = 1/2 (H + H^T) + I
+__global__ __launch_bounds__(SGP_NT) void sgp_sym_b_kernel(const double* __restrict__ H, double* __restrict__ B, int64_t ld) {
+  __shared__ double t[64][65];
+  const int ti = blockIdx.y, tj = blockIdx.x;
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  for (int r = ty; r < 64; r += 4) t[r][tx] = H[((int64_t)tj * 64 + r) * ld + (int64_t)ti * 64 + tx];
+  __syncthreads();
+  for (int r = ty; r < 64; r += 4) {
+    const int64_t i = (int64_t)ti * 64 + r, j = (int64_t)tj * 64 + tx;
+    B[i * ld + j] = 0.5 * (H[i * ld + j] + t[tx][r]) + (i == j ? 1.0 : 0.0);
+  }
+}
+
+// out = [sum ln LB_ii, sum H_ii, sum c_i^2], i < m; one workgroup
+__global__ __launch_bounds__(SGP_NT) void sgp_mm_reduce_kernel(const double* __restrict__ LB, const double* __restrict__ H,
+                                                               int64_t ld, int64_t m, const double* __restrict__ c,
+                                                               double* __restrict__ out) {
+  __shared__ double red[4];
+  double a = 0.0, b = 0.0, q = 0.0;
+  for (int64_t i = threadIdx.x; i < m; i += SGP_NT) {
+    a += log(LB[i * ld + i]);
+    b += H[i * ld + i];
+    q = fma(c[i], c[i], q);
+  }
+  const double v0 = block_sum(a, red), v1 = block_sum(b, red), v2 = block_sum(q, red);
+  if (threadIdx.x == 0) {
+    out[0] = v0;
+    out[1] = v1;
+    out[2] = v2;
+  }
+}
+
+// C = A - B (mp rows in grid.y, mp columns)
+__global__ __launch_bounds__(SGP_NT) void sgp_sub_kernel(const double* __restrict__ A, const double* __restrict__ B,
+                                                         double* __restrict__ C, int64_t ld, int64_t mp) {
+  const int64_t j = (int64_t)blockIdx.x * SGP_NT + threadIdx.x, i = blockIdx.y;
+  if (j < mp) C[i * ld + j] = A[i * ld + j] - B[i * ld + j];
+}
+
+// out[j] = sum_a K[j][a] M[j][a], a < m; workgroup j
+__global__ __launch_bounds__(SGP_NT) void sgp_rowdot2_kernel(const double* __restrict__ K, const double* __restrict__ M,
+                                                             int64_t ld, int64_t m, double* __restrict__ out) {
+  __shared__ double red[4];
+  const int64_t j = blockIdx.x;
+  double acc = 0.0;
+  for (int64_t a = threadIdx.x; a < m; a += SGP_NT) acc = fma(K[j * ld + a], M[j * ld + a], acc);
+  const double v = block_sum(acc, red);
+  if (threadIdx.x == 0) out[j] = v;
+}
+
+// alpha_j = w_j (r_j - kg_j) and, with q (k_j^T T k_j), the noise-gradient term of the point; j < rows
+__global__ __launch_bounds__(SGP_NT) void sgp_alpha_kernel(const double* __restrict__ r, const double* __restrict__ w,
+                                                           const double* __restrict__ kg, const double* __restrict__ q,
+                                                           double a2, int64_t rows, double* __restrict__ alpha,
+                                                           double* __restrict__ term) {
+  const int64_t j = (int64_t)blockIdx.x * SGP_NT + threadIdx.x;
+  if (j >= rows) return;
+  const double wj = w[j], a = wj * (r[j] - kg[j]);
+  alpha[j] = a;
+  if (q) term[j] = a * a - wj + wj * wj * (a2 - q[j]);
+}
+
+// mean_j = sum_a U[j][a] c[a],  var_j = a2 - |V_j|^2 + |U_j|^2, a < m; workgroup j
+__global__ __launch_bounds__(SGP_NT) void sgp_predict_kernel(const double* __restrict__ V, const double* __restrict__ U,
+                                                             int64_t ld, int64_t m, const double* __restrict__ c, double a2,
+                                                             double* __restrict__ mean, double* __restrict__ var) {
+  __shared__ double red[4];
+  const int64_t j = blockIdx.x;
+  double mu = 0.0, sv = 0.0, su = 0.0;
+  for (int64_t a = threadIdx.x; a < m; a += SGP_NT) {
+    const double v = V[j * ld + a], u = U[j * ld + a];
+    mu = fma(u, c[a], mu);
+    sv = fma(v, v, sv);
+    su = fma(u, u, su);
+  }
+  const double t0 = block_sum(mu, red), t1 = block_sum(sv, red), t2 = block_sum(su, red);
+  if (threadIdx.x == 0) {
+    mean[j] = t0;
+    var[j] = a2 - t1 + t2;
+  }
+}
+
+// The rectangular weighted gradient contraction: tile (blockIdx.y, blockIdx.x) of (rows of U) x (rows of V) reduces
+//   sum_ij w_ij dK(u_i, v_j) / dtheta_k,   w_ij = m_scale rs_i Mw[i][j] + uv_scale uvec_i vvec_j   (rs == nullptr: 1),
+// to one partial per parameter at ws[(tile row * gridDim.x + tile column) * n_theta + k]: [ln a, (RQ: ln kappa,) ln l_1..d].
+// The two 64-point panels are staged in LDS ([dim][point], 2 x d x 64 doubles of dynamic LDS: 64 KiB at d = 64), every
+// thread owns a 4 x 4 block: s = 1/2 sum_k dx_k^2 / l_k^2 as the builders form it, value and derivative profiles in two
+// halves of eight elements (kfun.h: kprofiles), then one pass over the dimensions for the length scales.
+// square != 0: U and V are the same points (the K_mm term) and the diagonal carries diag_eps: d(K + eps I)_ii / d ln a =
+// 2 (a^2 + eps).  Reads Mw only where i < nu and j < nv; VALU-bound (the fp64 exp and the d-term sums).
+template <int KERNEL>
+__global__ __launch_bounds__(SGP_NT) void sgp_contract_kernel(KParams p, const double* __restrict__ U, int64_t nu,
+                                                              const double* __restrict__ V, int64_t nv,
+                                                              const double* __restrict__ Mw, int64_t ld,
+                                                              const double* __restrict__ rs, const double* __restrict__ uvec,
+                                                              const double* __restrict__ vvec, double m_scale,
+                                                              double uv_scale, int square, double diag_eps, int n_theta,
+                                                              double* __restrict__ ws) {
+  extern __shared__ double sc_lds[];
+  __shared__ double red[4];
+  const int ti = blockIdx.y, tj = blockIdx.x;
+  const int tid = threadIdx.x, d = p.d;
+  double* su = sc_lds;
+  double* sv = sc_lds + d * KT;
+  const int64_t i0 = (int64_t)ti * KT, j0 = (int64_t)tj * KT;
+  for (int idx = tid; idx < KT * d; idx += SGP_NT) {
+    const int pt = idx / d, k = idx - pt * d;
+    const int64_t gi = i0 + pt, gj = j0 + pt;
+    su[k * KT + pt] = (gi < nu) ? U[gi * d + k] : 0.0;
+    sv[k * KT + pt] = (gj < nv) ? V[gj * d + k] : 0.0;
+  }
+  __syncthreads();
+  const int ty = tid >> 4, tx = tid & 15;
+  double s[4][4], w[4][4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) s[r][c] = 0.0;
+  for (int k = 0; k < d; ++k) {
+    const double il2 = p.inv_l2[k];
+    double ur[4], vc[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ur[r] = su[k * KT + ty * 4 + r];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) vc[c] = sv[k * KT + tx * 4 + c];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const double dx = ur[r] - vc[c];
+        s[r][c] = fma(0.5 * dx * dx, il2, s[r][c]);
+      }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int64_t gi = i0 + ty * 4 + r;
+    const bool row_ok = gi < nu;
+    const double ui = row_ok ? uv_scale * uvec[gi] : 0.0;
+    const double ri = row_ok ? (rs ? m_scale * rs[gi] : m_scale) : 0.0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int64_t gj = j0 + tx * 4 + c;
+      w[r][c] = (row_ok && gj < nv) ? fma(ri, Mw[gi * ld + gj], ui * vvec[gj]) : 0.0;
+    }
+  }
+  double g_amp = 0.0, g_shape = 0.0;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    double s8[8], C8[8], g8[8], h8[8];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) s8[4 * r + c] = s[2 * h + r][c];
+    kprofiles<KERNEL>(p, s8, C8, g8, h8);
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int64_t gi = i0 + ty * 4 + 2 * h + r, gj = j0 + tx * 4 + c;
+        const double wv = w[2 * h + r][c];
+        double K = p.a2 * C8[4 * r + c];
+        if (square && gi == gj) K += diag_eps;
+        g_amp = fma(wv, 2.0 * K, g_amp);                            // dK/d ln a = 2 K
+        if (KERNEL == GPMI_KERNEL_RQ) g_shape = fma(wv, p.a2 * h8[4 * r + c], g_shape);
+        w[2 * h + r][c] = wv * (p.a2 * g8[4 * r + c]);              // times dx_k^2 / l_k^2: dK/d ln l_k
+      }
+  }
+  double* out = ws + ((int64_t)ti * gridDim.x + tj) * n_theta;
+  const int off = (KERNEL == GPMI_KERNEL_RQ) ? 2 : 1;
+  double v = block_sum(g_amp, red);
+  if (tid == 0) out[0] = v;
+  if (KERNEL == GPMI_KERNEL_RQ) {
+    v = block_sum(g_shape, red);
+    if (tid == 0) out[1] = v;
+  }
+  for (int k = 0; k < d; ++k) {
+    const double il2 = p.inv_l2[k];
+    double acc = 0.0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const double dx = su[k * KT + ty * 4 + r] - sv[k * KT + tx * 4 + c];
+        acc = fma(w[r][c], dx * dx * il2, acc);
+      }
+    v = block_sum(acc, red);
+    if (tid == 0) out[off + k] = v;
+  }
+}
+
+size_t contract_lds_bytes(int d) { return sizeof(double) * 2 * (size_t)d * KT; }
+
+// tiles (ceil(nu_padded / 64) x ceil(nv_padded / 64)) of partials into ws
+void launch_contract(hipStream_t s, const KParams& p, const double* U, int64_t nu, int64_t nup, const double* V, int64_t nv,
+                     int64_t nvp, const double* Mw, int64_t ld, const double* rs, const double* uvec, const double* vvec,
+                     double m_scale, double uv_scale, int square, double diag_eps, int n_theta, double* ws) {
+  const dim3 grid((unsigned)(nvp / KT), (unsigned)(nup / KT));
+  const size_t lds = contract_lds_bytes(p.d);
+#define SGP_CONTRACT(KIND)                                                                                              \
+  hipLaunchKernelGGL(sgp_contract_kernel<KIND>, grid, dim3(SGP_NT), lds, s, p, U, nu, V, nv, Mw, ld, rs, uvec, vvec, m_scale, \
+                     uv_scale, square, diag_eps, n_theta, ws)
+  switch (p.kernel) {
+    case GPMI_KERNEL_SE: SGP_CONTRACT(GPMI_KERNEL_SE); break;
+    case GPMI_KERNEL_RQ: SGP_CONTRACT(GPMI_KERNEL_RQ); break;
+    case GPMI_KERNEL_M32: SGP_CONTRACT(GPMI_KERNEL_M32); break;
+    case GPMI_KERNEL_M52: SGP_CONTRACT(GPMI_KERNEL_M52); break;
+    default: break;  // (sgp_params admits no other kind)
+  }
+#undef SGP_CONTRACT
+}
+
+unsigned blocks(int64_t n) { return (unsigned)((n + SGP_NT - 1) / SGP_NT); }
+
+void sgp_free(gpmi_sgp* g) {
+  for (double* q : {g->x, g->z, g->r, g->nv, g->w, g->alpha, g->invD1, g->invD2, g->vec, g->red, g->part, g->pvec, g->ws,
+                    g->q_pts, g->q_out, g->fLinv, g->fLBinv, g->fc, g->P[0], g->P[1], g->P[2]})
+    if (q) (void)hipFree(q);
+  for (double* q : g->M)
+    if (q) (void)hipFree(q);
+  if (g->info) (void)hipFree(g->info);
+  delete g;
+}
+
+bool sgp_live(gpmi_ctx* c, gpmi_sgp* g) {
+  return std::find(c->sgp_live.begin(), c->sgp_live.end(), g) != c->sgp_live.end();
+}
+
+int sgp_params(gpmi_sgp* g, int kernel, const double* theta, int n_theta, double white, double jitter, int64_t panel_rows,
+               KParams& p) {
+  gpmi_ctx* c = g->ctx;
+  ARGCHK(c, g->have_targets, "gpmi_sgp: gpmi_sgp_set_targets has not been called");
+  ARGCHK(c, kernel != GPMI_KERNEL_SUM && kernel_is_stationary(kernel),
+         "gpmi_sgp: the kernel must be GPMI_KERNEL_SE, _RQ, _M32 or _M52");
+  const int off = kernel_theta_offset(kernel);
+  ARGCHK(c, theta != nullptr, "gpmi_sgp: theta is NULL");
+  ARGCHK(c, n_theta == g->d + off, "gpmi_sgp: n_theta does not match the kernel and the data dimension");
+  for (int k = 0; k < n_theta; ++k) ARGCHK(c, std::isfinite(theta[k]), "gpmi_sgp: theta must be finite");
+  ARGCHK(c, std::isfinite(white) && white >= 0.0, "gpmi_sgp: white_var must be finite and not negative");
+  ARGCHK(c, std::isfinite(jitter) && jitter >= 0.0, "gpmi_sgp: jitter_rel must be finite and not negative");
+  ARGCHK(c, panel_rows >= 0 && panel_rows <= SGP_MAX_PANEL, "gpmi_sgp: panel_rows out of range (0 .. 32768)");
+  std::memset(&p, 0, sizeof(p));
+  p.kernel = kernel;
+  p.d = (int)g->d;
+  const double a = std::exp(theta[0]);
+  p.a2 = a * a;
+  p.kappa = (kernel == GPMI_KERNEL_RQ) ? std::exp(theta[1]) : 1.0;
+  for (int k = 0; k < p.d; ++k) {
+    const double l = std::exp(theta[off + k]);
+    p.inv_l2[k] = 1.0 / (l * l);
+  }
+  return GPMI_OK;
+}
+
+// panels for R rows (a multiple of 128)
+int sgp_ensure_panels(gpmi_sgp* g, int64_t R) {
+  gpmi_ctx* c = g->ctx;
+  if (R <= g->panel_cap) return GPMI_OK;
+  for (double** q : {&g->P[0], &g->P[1], &g->P[2], &g->pvec, &g->ws}) {
+    if (*q) (void)hipFree(*q);
+    *q = nullptr;
+  }
+  g->panel_cap = 0;
+  const int64_t each = std::max(g->mp * (R + 32), R * g->ld);
+  for (int k = 0; k < 3; ++k) HIPCHK(c, hipMalloc(&g->P[k], sizeof(double) * each));
+  HIPCHK(c, hipMalloc(&g->pvec, sizeof(double) * 3 * R));
+  const int64_t tiles = (std::max(R, g->mp) / KT) * (g->mp / KT);
+  HIPCHK(c, hipMalloc(&g->ws, sizeof(double) * tiles * (GPMI_MAX_D + 2)));
+  g->panel_cap = R;
+  return GPMI_OK;
+}
+
+// names of the work matrices: G, A (K_mm -> L; later T), LiT (L^-T), Linv, W1 (L^-1 G; later L^-T L_B^-T), W2 (H; later S,
+// then K_mm^-1 G K_mm^-1), LB (B -> L_B; later K_mm^-1 G, then the K_mm weights), W3 (L_B^-T; later K_mm^-1), LBinv
+enum { MG = 0, MA, MLIT, MLINV, MW1, MW2, MLB, MW3, MLBINV };
+
+void nt_square(hipStream_t s, double* C, const double* A, const double* B, int64_t mp, int64_t ld) {
+  const int nt = (int)(mp / GPMI_NB);
+  launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, C, ld, A, ld, B, ld, nt, nt, (int)mp);  // C = A B^T
+}
+
+// dst <- (factor at A)^-1, through its transpose in `scratch`
+void inverse_factor(hipStream_t s, const double* A, const double* invD, double* scratch, double* dst, int64_t mp, int64_t ld) {
+  trsm_identity_batched(s, A, mp, ld, invD, scratch, BatchShape());
+  hipLaunchKernelGGL(sgp_transpose_kernel, dim3((unsigned)(mp / KT), (unsigned)(mp / KT)), dim3(SGP_NT), 0, s, scratch, dst, ld);
+}
+
+int read_info(gpmi_sgp* g, int slot, int& inf) {
+  gpmi_ctx* c = g->ctx;
+  HIPCHK(c, hipMemcpyAsync(&inf, g->info + slot, sizeof(int), hipMemcpyDeviceToHost, c->sgp_stream));
+  HIPCHK(c, hipStreamSynchronize(c->sgp_stream));
+  return GPMI_OK;
+}
+
+// Pass 1 and the m x m algebra.  info = 0: M[MLINV], M[MLBINV], M[MLIT], vec (b, L^-1 b, c) and *F are valid.
+int sgp_factor(gpmi_sgp* g, const KParams& p, double white, double jitter, int64_t panel_rows, double* F, double* sum_w,
+               int* info) {
+  gpmi_ctx* c = g->ctx;
+  hipStream_t s = c->sgp_stream;
+  const int64_t n = g->n, m = g->m, mp = g->mp, ld = g->ld, d = g->d;
+  const int nt = (int)(mp / GPMI_NB);
+  const int64_t P = std::min<int64_t>(round_up(panel_rows > 0 ? panel_rows : GPMI_SGP_PANEL, GPMI_NB), round_up(n, GPMI_NB));
+  const int64_t ldp = P + 32;
+  if (int rc = sgp_ensure_panels(g, P)) return rc;
+  double *G = g->M[MG], *A = g->M[MA], *LiT = g->M[MLIT], *Linv = g->M[MLINV], *W1 = g->M[MW1], *W2 = g->M[MW2],
+         *LB = g->M[MLB], *W3 = g->M[MW3], *LBinv = g->M[MLBINV];
+  double *b = g->vec, *v1 = g->vec + mp, *cc = g->vec + 2 * mp;
+  double hred[4] = {};
+  {
+    const unsigned nblk = (unsigned)std::min<int64_t>(SGP_RED_BLOCKS, (n + SGP_NT - 1) / SGP_NT);
+    hipLaunchKernelGGL(sgp_weights_kernel, dim3(nblk), dim3(SGP_NT), 0, s, g->r, g->nv, white, n, g->w, g->part);
+    hipLaunchKernelGGL(sgp_colsum_kernel, dim3(4), dim3(SGP_NT), 0, s, g->part, (int64_t)nblk, 4, g->red + RED_DATA, 0);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(hred, g->red + RED_DATA, sizeof(hred), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    ARGCHK(c, hred[3] == 0.0, "gpmi_sgp: noise_var_i + white_var must be positive and finite for every data point");
+  }
+  HIPCHK(c, hipMemsetAsync(G, 0, sizeof(double) * mp * ld, s));
+  HIPCHK(c, hipMemsetAsync(g->vec, 0, sizeof(double) * 4 * mp, s));
+  for (int64_t j0 = 0; j0 < n; j0 += P) {
+    const int64_t rows = std::min<int64_t>(P, n - j0);
+    double* Kp = g->P[0];
+    {
+      ProfScope ps(c, s, GPMI_PROF_SGP_BUILD, 0.0, 8.0 * mp * P);
+      launch_kbuild_cross(s, p, g->z, m, mp, g->x + j0 * d, rows, P, Kp, ldp);  // (zeros in rows >= m and columns >= rows)
+      hipLaunchKernelGGL(sgp_scale_cols_kernel, dim3(blocks(rows), (unsigned)m), dim3(SGP_NT), 0, s, Kp, ldp, rows, g->w + j0);
+      hipLaunchKernelGGL(sgp_bvec_kernel, dim3((unsigned)m), dim3(SGP_NT), 0, s, Kp, ldp, rows, g->r + j0, g->w + j0, b,
+                         j0 > 0 ? 1 : 0);
+    }
+    {
+      ProfScope ps(c, s, GPMI_PROF_SGP_GRAM, (double)P * mp * (mp + GPMI_NB), 8.0 * (mp * P + 0.5 * mp * mp));
+      launch_gemm_nt(s, TILES_LOWER, OP_SUB, G, ld, Kp, ldp, Kp, ldp, nt, nt, (int)P);  // G holds -G until the sweep is over
+    }
+    HIPCHK(c, hipGetLastError());
+  }
+  int inf = 0;
+  {
+    ProfScope ps(c, s, GPMI_PROF_SGP_FACTOR, 2.0 * mp * mp * mp / 3.0 + 8.0 * mp * mp * mp, 8.0 * 12.0 * mp * mp);
+    launch_mirror_lower(s, G, ld, mp);
+    launch_negate(s, G, mp * ld);
+    launch_kbuild_cross(s, p, g->z, m, mp, g->z, m, mp, A, ld);
+    hipLaunchKernelGGL(sgp_pad_diag_kernel, dim3(blocks(mp)), dim3(SGP_NT), 0, s, A, ld, m, mp, jitter * p.a2);
+    HIPCHK(c, hipMemsetAsync(g->info, 0, 2 * sizeof(int), s));
+    potrf_lower_batched(c, s, A, mp, ld, g->invD1, g->info, BatchShape());
+    HIPCHK(c, hipGetLastError());
+  }
+  if (int rc = read_info(g, 0, inf)) return rc;
+  if (inf != 0) {
+    *info = inf;
+    return GPMI_OK;
+  }
+  {
+    ProfScope ps(c, s, GPMI_PROF_SGP_FACTOR, 0.0, 0.0);
+    inverse_factor(s, A, g->invD1, LiT, Linv, mp, ld);
+    nt_square(s, W1, Linv, G, mp, ld);   // L^-1 G   (G symmetric)
+    nt_square(s, W2, W1, Linv, mp, ld);  // H = L^-1 G L^-T
+    hipLaunchKernelGGL(sgp_sym_b_kernel, dim3((unsigned)(mp / KT), (unsigned)(mp / KT)), dim3(SGP_NT), 0, s, W2, LB, ld);
+    potrf_lower_batched(c, s, LB, mp, ld, g->invD2, g->info + 1, BatchShape());
+    HIPCHK(c, hipGetLastError());
+  }
+  if (int rc = read_info(g, 1, inf)) return rc;
+  if (inf != 0) {
+    *info = (int)m + inf;
+    return GPMI_OK;
+  }
+  double hmm[3] = {};
+  {
+    ProfScope ps(c, s, GPMI_PROF_SGP_FACTOR, 0.0, 0.0);
+    inverse_factor(s, LB, g->invD2, W3, LBinv, mp, ld);
+    launch_rows_dot(s, Linv, ld, mp, mp, b, v1);
+    launch_rows_dot(s, LBinv, ld, mp, mp, v1, cc);
+    hipLaunchKernelGGL(sgp_mm_reduce_kernel, dim3(1), dim3(SGP_NT), 0, s, LB, W2, ld, m, cc, g->red + RED_MM);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(hmm, g->red + RED_MM, sizeof(hmm), hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(c, hipStreamSynchronize(s));
+  const double LN_2PI = 1.8378770664093454836;
+  *F = -0.5 * ((double)n * LN_2PI + hred[1] + 2.0 * hmm[0] + hred[0] - hmm[2]) - 0.5 * (p.a2 * hred[2] - hmm[1]);
+  *sum_w = hred[2];
+  *info = 0;
+  return GPMI_OK;
+}
+
+// The gradient behind a successful sgp_factor (same parameters): grad (n_theta + 1) if not NULL, alpha into g->alpha.
+int sgp_gradient(gpmi_sgp* g, const KParams& p, int n_theta, double white, double jitter, int64_t panel_rows, double sum_w,
+                 double* grad) {
+  gpmi_ctx* c = g->ctx;
+  hipStream_t s = c->sgp_stream;
+  const int64_t n = g->n, m = g->m, mp = g->mp, ld = g->ld, d = g->d;
+  const int nt = (int)(mp / GPMI_NB);
+  const int64_t P = std::min<int64_t>(round_up(panel_rows > 0 ? panel_rows : GPMI_SGP_PANEL, GPMI_NB), round_up(n, GPMI_NB));
+  double *G = g->M[MG], *T = g->M[MA], *LiT = g->M[MLIT], *RT = g->M[MW1], *W2 = g->M[MW2], *LB = g->M[MLB], *Kinv = g->M[MW3],
+         *LBinv = g->M[MLBINV];
+  double *cc = g->vec + 2 * mp, *gamma = g->vec + 3 * mp;
+  double *kg = g->pvec, *q = g->pvec + P, *term = g->pvec + 2 * P;
+  ProfScope ps(c, s, GPMI_PROF_SGP_GRAD, 0.0, 0.0);
+  nt_square(s, RT, LiT, LBinv, mp, ld);  // L^-T L_B^-T
+  launch_rows_dot(s, RT, ld, mp, mp, cc, gamma);
+  if (grad) {
+    nt_square(s, W2, RT, RT, mp, ld);      // S = L^-T B^-1 L^-1
+    nt_square(s, Kinv, LiT, LiT, mp, ld);  // L^-T L^-1
+    hipLaunchKernelGGL(sgp_sub_kernel, dim3(blocks(mp), (unsigned)mp), dim3(SGP_NT), 0, s, Kinv, W2, T, ld, mp);
+    nt_square(s, LB, Kinv, G, mp, ld);     // K_mm^-1 G
+    nt_square(s, W2, LB, Kinv, mp, ld);    // K_mm^-1 G K_mm^-1
+    hipLaunchKernelGGL(sgp_sub_kernel, dim3(blocks(mp), (unsigned)mp), dim3(SGP_NT), 0, s, W2, T, LB, ld, mp);  // M2 - gamma gamma^T
+  }
+  HIPCHK(c, hipGetLastError());
+  for (int64_t j0 = 0; j0 < n; j0 += P) {
+    const int64_t rows = std::min<int64_t>(P, n - j0);
+    double *KTp = g->P[0], *Mp = g->P[1];
+    launch_kbuild_cross(s, p, g->x + j0 * d, rows, P, g->z, m, mp, KTp, ld);  // P x mp: row j = k_m(x_j)
+    launch_rows_dot(s, KTp, ld, P, mp, gamma, kg);
+    if (grad) {
+      launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, Mp, ld, KTp, ld, T, ld, (int)(P / GPMI_NB), nt, (int)mp);  // rows k_j^T T
+      hipLaunchKernelGGL(sgp_rowdot2_kernel, dim3((unsigned)rows), dim3(SGP_NT), 0, s, KTp, Mp, ld, m, q);
+    }
+    hipLaunchKernelGGL(sgp_alpha_kernel, dim3(blocks(rows)), dim3(SGP_NT), 0, s, g->r + j0, g->w + j0, kg,
+                       grad ? q : (const double*)nullptr, p.a2, rows, g->alpha + j0, term);
+    if (grad) {
+      hipLaunchKernelGGL(sgp_colsum_kernel, dim3(1), dim3(SGP_NT), 0, s, term, rows, 1, g->red + RED_NOISE, j0 > 0 ? 1 : 0);
+      launch_contract(s, p, g->x + j0 * d, rows, P, g->z, m, mp, Mp, ld, g->w + j0, g->alpha + j0, gamma, 1.0, 1.0, 0, 0.0,
+                      n_theta, g->ws);
+      hipLaunchKernelGGL(sgp_colsum_kernel, dim3((unsigned)n_theta), dim3(SGP_NT), 0, s, g->ws, (P / KT) * (mp / KT), n_theta,
+                         g->red + RED_GRAD, j0 > 0 ? 1 : 0);
+    }
+    HIPCHK(c, hipGetLastError());
+  }
+  if (!grad) return GPMI_OK;
+  // the K_mm term: weights -1/2 M2 = -1/2 (gamma gamma^T + LB), rows and columns are Z
+  launch_contract(s, p, g->z, m, mp, g->z, m, mp, LB, ld, nullptr, gamma, gamma, -0.5, -0.5, 1, jitter * p.a2, n_theta, g->ws);
+  hipLaunchKernelGGL(sgp_colsum_kernel, dim3((unsigned)n_theta), dim3(SGP_NT), 0, s, g->ws, (mp / KT) * (mp / KT), n_theta,
+                     g->red + RED_GRAD, 1);
+  HIPCHK(c, hipGetLastError());
+  double hg[GPMI_MAX_D + 2] = {}, hnoise = 0.0;
+  HIPCHK(c, hipMemcpyAsync(hg, g->red + RED_GRAD, sizeof(double) * n_theta, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(&hnoise, g->red + RED_NOISE, sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  for (int k = 0; k < n_theta; ++k) grad[k] = hg[k];
+  grad[0] -= p.a2 * sum_w;  // -1/2 sum w_i da^2 / d ln a
+  grad[n_theta] = white > 0.0 ? white * hnoise : 0.0;
+  return GPMI_OK;
+}
+
+}  // namespace
+
+void sgp_release_all(gpmi_ctx* c) {
+  if (c->sgp_stream) (void)hipStreamSynchronize(c->sgp_stream);
+  for (gpmi_sgp* g : c->sgp_live) sgp_free(g);
+  c->sgp_live.clear();
+  if (c->sgp_stream) (void)hipStreamDestroy(c->sgp_stream);
+  c->sgp_stream = nullptr;
+}
+
+extern "C" {
+
+int gpmi_sgp_create(gpmi_ctx* c, int64_t n, int64_t d, const double* x, int64_t m, const double* z, gpmi_sgp** out) {
+  if (!c) return GPMI_ERR_ARG;
+  ARGCHK(c, out != nullptr, "gpmi_sgp_create: out is NULL");
+  *out = nullptr;
+  ARGCHK(c, x != nullptr && z != nullptr, "gpmi_sgp_create: x_host and z_host must be non-NULL");
+  ARGCHK(c, n >= 2 && n <= ((int64_t)1 << 30), "gpmi_sgp_create: n out of range (2 .. 2^30)");
+  ARGCHK(c, d >= 1 && d <= GPMI_MAX_D, "gpmi_sgp_create: d out of range (1 .. 64)");
+  ARGCHK(c, m >= 1 && m <= GPMI_SGP_MAX_M, "gpmi_sgp_create: m out of range (1 .. 4096 = GPMI_SGP_MAX_M inducing points)");
+  if (int rc = set_device(c)) return rc;
+  if (!c->sgp_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->sgp_stream, hipStreamNonBlocking));
+  gpmi_sgp* g = new gpmi_sgp();
+  g->ctx = c;
+  g->n = n;
+  g->d = d;
+  g->m = m;
+  g->mp = round_up(m, GPMI_NB);
+  g->ld = g->mp + 32;  // rows 256-byte aligned, off a power-of-two pitch
+  const int64_t mp = g->mp, ld = g->ld, nd = mp / GPMI_NB * GPMI_NB * GPMI_NB;
+  auto alloc = [&](auto& ptr, size_t bytes) { return hipMalloc(reinterpret_cast<void**>(&ptr), bytes); };
+  hipError_t e = alloc(g->x, sizeof(double) * n * d);
+  if (e == hipSuccess) e = alloc(g->z, sizeof(double) * mp * d);
+  for (double** q : {&g->r, &g->nv, &g->w, &g->alpha})
+    if (e == hipSuccess) e = alloc(*q, sizeof(double) * n);
+  for (double*& q : g->M)
+    if (e == hipSuccess) e = alloc(q, sizeof(double) * mp * ld);
+  for (double** q : {&g->fLinv, &g->fLBinv})
+    if (e == hipSuccess) e = alloc(*q, sizeof(double) * mp * ld);
+  if (e == hipSuccess) e = alloc(g->fc, sizeof(double) * mp);
+  if (e == hipSuccess) e = alloc(g->invD1, sizeof(double) * nd);
+  if (e == hipSuccess) e = alloc(g->invD2, sizeof(double) * nd);
+  if (e == hipSuccess) e = alloc(g->vec, sizeof(double) * 4 * mp);
+  if (e == hipSuccess) e = alloc(g->red, sizeof(double) * 128);
+  if (e == hipSuccess) e = alloc(g->info, sizeof(int) * 2);
+  if (e == hipSuccess) e = alloc(g->part, sizeof(double) * SGP_RED_BLOCKS * 4);
+  if (e == hipSuccess) e = alloc(g->q_pts, sizeof(double) * SGP_QPANEL * d);
+  if (e == hipSuccess) e = alloc(g->q_out, sizeof(double) * 2 * SGP_QPANEL);
+  // potrf_diag writes the block-lower part of an inverse only: the zeros above stay from here (api.hip: lane_alloc, ZERO_SYNC)
+  if (e == hipSuccess) e = hipMemset(g->invD1, 0, sizeof(double) * nd);
+  if (e == hipSuccess) e = hipMemset(g->invD2, 0, sizeof(double) * nd);
+  if (e == hipSuccess) e = hipMemset(g->z, 0, sizeof(double) * mp * d);
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  if (e == hipSuccess) e = hipMemcpy(g->x, x, sizeof(double) * n * d, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(g->z, z, sizeof(double) * m * d, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    c->err = std::string("gpmi_sgp_create: ") + hipGetErrorString(e);
+    sgp_free(g);
+    return e == hipErrorOutOfMemory ? GPMI_ERR_NOMEM : GPMI_ERR_HIP;
+  }
+  c->sgp_live.push_back(g);
+  *out = g;
+  return GPMI_OK;
+}
+
+int gpmi_sgp_destroy(gpmi_sgp* g) {
+  if (!g) return GPMI_ERR_ARG;
+  gpmi_ctx* c = g->ctx;
+  auto it = std::find(c->sgp_live.begin(), c->sgp_live.end(), g);
+  ARGCHK(c, it != c->sgp_live.end(), "gpmi_sgp_destroy: not a live object of this handle");
+  if (int rc = set_device(c)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->sgp_stream));
+  c->sgp_live.erase(it);
+  sgp_free(g);
+  return GPMI_OK;
+}
+
+int gpmi_sgp_set_targets(gpmi_sgp* g, const double* r, const double* noise_var) {
+  if (!g) return GPMI_ERR_ARG;
+  gpmi_ctx* c = g->ctx;
+  ARGCHK(c, sgp_live(c, g), "gpmi_sgp_set_targets: not a live object of this handle");
+  ARGCHK(c, r != nullptr, "gpmi_sgp_set_targets: r_host is NULL");
+  if (int rc = set_device(c)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->sgp_stream));
+  HIPCHK(c, hipMemcpy(g->r, r, sizeof(double) * g->n, hipMemcpyHostToDevice));
+  if (noise_var) {
+    HIPCHK(c, hipMemcpy(g->nv, noise_var, sizeof(double) * g->n, hipMemcpyHostToDevice));
+  } else {
+    ZERO_SYNC(c, g->nv, sizeof(double) * g->n);
+  }
+  g->have_targets = true;
+  return GPMI_OK;
+}
+
+int gpmi_sgp_bound(gpmi_sgp* g, int kernel, const double* theta, int n_theta, double white_var, double jitter_rel,
+                   int64_t panel_rows, double* F, double* grad, double* alpha_host, int* info) {
+  if (!g) return GPMI_ERR_ARG;
+  gpmi_ctx* c = g->ctx;
+  ARGCHK(c, sgp_live(c, g), "gpmi_sgp_bound: not a live object of this handle");
+  ARGCHK(c, F != nullptr && info != nullptr, "gpmi_sgp_bound: F and info must be non-NULL");
+  KParams p;
+  if (int rc = sgp_params(g, kernel, theta, n_theta, white_var, jitter_rel, panel_rows, p)) return rc;
+  if (int rc = set_device(c)) return rc;
+  double f = 0.0, sum_w = 0.0;
+  int inf = 0;
+  if (int rc = sgp_factor(g, p, white_var, jitter_rel, panel_rows, &f, &sum_w, &inf)) return rc;
+  *info = inf;
+  if (inf != 0) return GPMI_OK;
+  if (grad || alpha_host) {
+    double gbuf[GPMI_MAX_D + 3];
+    if (int rc = sgp_gradient(g, p, n_theta, white_var, jitter_rel, panel_rows, sum_w, grad ? gbuf : nullptr)) return rc;
+    if (alpha_host) HIPCHK(c, hipMemcpyAsync(alpha_host, g->alpha, sizeof(double) * g->n, hipMemcpyDeviceToHost, c->sgp_stream));
+    HIPCHK(c, hipStreamSynchronize(c->sgp_stream));
+    if (grad) std::memcpy(grad, gbuf, sizeof(double) * (n_theta + 1));
+  }
+  *F = f;
+  return GPMI_OK;
+}
+
+int gpmi_sgp_fit(gpmi_sgp* g, int kernel, const double* theta, int n_theta, double white_var, double jitter_rel,
+                 int64_t panel_rows, double* F, int* info) {
+  if (!g) return GPMI_ERR_ARG;
+  gpmi_ctx* c = g->ctx;
+  ARGCHK(c, sgp_live(c, g), "gpmi_sgp_fit: not a live object of this handle");
+  ARGCHK(c, F != nullptr && info != nullptr, "gpmi_sgp_fit: F and info must be non-NULL");
+  KParams p;
+  if (int rc = sgp_params(g, kernel, theta, n_theta, white_var, jitter_rel, panel_rows, p)) return rc;
+  if (int rc = set_device(c)) return rc;
+  double f = 0.0, sum_w = 0.0;
+  int inf = 0;
+  if (int rc = sgp_factor(g, p, white_var, jitter_rel, panel_rows, &f, &sum_w, &inf)) return rc;
+  *info = inf;
+  if (inf != 0) return GPMI_OK;
+  hipStream_t s = c->sgp_stream;
+  launch_copy_rows(s, g->M[MLINV], g->ld, g->fLinv, g->ld, g->mp, g->mp);
+  launch_copy_rows(s, g->M[MLBINV], g->ld, g->fLBinv, g->ld, g->mp, g->mp);
+  launch_copy(s, g->vec + 2 * g->mp, g->fc, g->mp);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(s));
+  g->fp = p;
+  g->fitted = true;
+  *F = f;
+  return GPMI_OK;
+}
+
+int gpmi_sgp_predict(gpmi_sgp* g, const double* pts, int64_t mq, double* mean, double* var) {
+  if (!g) return GPMI_ERR_ARG;
+  gpmi_ctx* c = g->ctx;
+  ARGCHK(c, sgp_live(c, g), "gpmi_sgp_predict: not a live object of this handle");
+  ARGCHK(c, g->fitted, "gpmi_sgp_predict needs a successful gpmi_sgp_fit");
+  ARGCHK(c, mq >= 0, "gpmi_sgp_predict: mq must not be negative");
+  if (mq == 0) return GPMI_OK;
+  ARGCHK(c, pts != nullptr && mean != nullptr, "gpmi_sgp_predict: pts_host and mean_host must be non-NULL");
+  if (int rc = set_device(c)) return rc;
+  if (int rc = sgp_ensure_panels(g, SGP_QPANEL)) return rc;
+  hipStream_t s = c->sgp_stream;
+  const int64_t m = g->m, mp = g->mp, ld = g->ld, d = g->d;
+  const int nt = (int)(mp / GPMI_NB);
+  for (int64_t q0 = 0; q0 < mq; q0 += SGP_QPANEL) {
+    const int64_t rows = std::min<int64_t>(SGP_QPANEL, mq - q0), rp = round_up(rows, GPMI_NB);
+    double *Kq = g->P[0], *V = g->P[1], *U = g->P[2];
+    HIPCHK(c, hipMemcpyAsync(g->q_pts, pts + q0 * d, sizeof(double) * rows * d, hipMemcpyHostToDevice, s));
+    launch_kbuild_cross(s, g->fp, g->q_pts, rows, rp, g->z, m, mp, Kq, ld);
+    launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, V, ld, Kq, ld, g->fLinv, ld, (int)(rp / GPMI_NB), nt, (int)mp);   // rows (L^-1 k_q)^T
+    launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, U, ld, V, ld, g->fLBinv, ld, (int)(rp / GPMI_NB), nt, (int)mp);  // rows (L_B^-1 v)^T
+    hipLaunchKernelGGL(sgp_predict_kernel, dim3((unsigned)rows), dim3(SGP_NT), 0, s, V, U, ld, m, g->fc, g->fp.a2, g->q_out,
+                       g->q_out + SGP_QPANEL);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(mean + q0, g->q_out, sizeof(double) * rows, hipMemcpyDeviceToHost, s));
+    if (var) HIPCHK(c, hipMemcpyAsync(var + q0, g->q_out + SGP_QPANEL, sizeof(double) * rows, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));  // (the next panel overwrites the staging)
+  }
+  return GPMI_OK;
+}
+
+}  // extern "C"

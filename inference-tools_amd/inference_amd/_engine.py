@@ -675,3 +675,78 @@ class LinvEngine(_DrawsMixin):
         cov = np.empty((self.n, self.n)) if with_cov else None
         self.h.call("gpmi_linv_posterior_dense", dptr(K), dptr(mu), dptr(mean), dptr(cov), C.byref(info))
         return mean, cov, info.value
+
+
+class SparseEngine:
+    """One gpmi_sgp object (include/gpmi.h: the variational inducing-point model) on a handle of its own: x and the
+    inducing inputs go up once, the residual and the data variances with `set_targets`; every evaluation then moves
+    hyper-parameters up and a handful of numbers (and, on request, the N values of alpha) down."""
+
+    def __init__(self, x, z, device=None):
+        self.x, self.z = as_f64(x), as_f64(z)
+        self.n, self.d = self.x.shape
+        self.m = self.z.shape[0]
+        self.h = _lib.Handle(device)
+        self.ptr = C.c_void_p()
+        self.h.call("gpmi_sgp_create", self.n, self.d, dptr(self.x), self.m, dptr(self.z), C.byref(self.ptr))
+
+    def _call(self, name, *args):
+        if not self.h.ctx:
+            raise _lib.GpmiUnavailable("the device handle of this model has been closed")
+        rc = getattr(self.h.lib, name)(self.ptr, *args)
+        if rc != 0:
+            raise _lib.GpmiError(f"{name} failed with status {rc}: {self.h.lib.gpmi_last_error(self.h.ctx).decode()}")
+
+    def set_targets(self, r, noise_var=None):
+        r = as_f64(r)
+        nv = None if noise_var is None else as_f64(noise_var)
+        self._call("gpmi_sgp_set_targets", dptr(r), dptr(nv))
+
+    def bound(self, kernel, theta, white_var, jitter, panel_rows=0, want_grad=False, want_alpha=False):
+        """(F, gradient or None, alpha or None, info): info > 0 - not positive definite - leaves the rest undefined."""
+        theta = as_f64(theta)
+        F, info = C.c_double(0.0), C.c_int(0)
+        grad = np.zeros(theta.size + 1) if want_grad else None
+        alpha = np.zeros(self.n) if want_alpha else None
+        self._call("gpmi_sgp_bound", int(kernel), dptr(theta), theta.size, float(white_var), float(jitter), int(panel_rows),
+                   C.byref(F), dptr(grad), dptr(alpha), C.byref(info))
+        return F.value, grad, alpha, info.value
+
+    def fit(self, kernel, theta, white_var, jitter, panel_rows=0):
+        theta = as_f64(theta)
+        F, info = C.c_double(0.0), C.c_int(0)
+        self._call("gpmi_sgp_fit", int(kernel), dptr(theta), theta.size, float(white_var), float(jitter), int(panel_rows),
+                   C.byref(F), C.byref(info))
+        return F.value, info.value
+
+    def predict(self, pts, want_var=True):
+        pts = as_f64(pts)
+        mean = np.zeros(pts.shape[0])
+        var = np.zeros(pts.shape[0]) if want_var else None
+        self._call("gpmi_sgp_predict", dptr(pts), pts.shape[0], dptr(mean), dptr(var))
+        return mean, var
+
+    def profile_stages(self, on):
+        """HIP-event timing of the four stages (GPMI_PROF_SGP_*) on or off; `stage_ms` reads and resets them."""
+        mask = 0
+        for k in (_lib.PROF_SGP_BUILD, _lib.PROF_SGP_GRAM, _lib.PROF_SGP_FACTOR, _lib.PROF_SGP_GRAD):
+            mask |= 2 << k
+        self.h.call("gpmi_profile_enable", mask if on else 0)
+        self.h.call("gpmi_profile_reset")
+
+    def stage_ms(self):
+        out = {}
+        for name, k in (("build", _lib.PROF_SGP_BUILD), ("gram", _lib.PROF_SGP_GRAM), ("factor", _lib.PROF_SGP_FACTOR),
+                        ("grad", _lib.PROF_SGP_GRAD)):
+            n = C.c_int64(0)
+            ms, fl, by = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+            self.h.call("gpmi_profile_read", k, C.byref(n), C.byref(ms), C.byref(fl), C.byref(by))
+            out[name] = {"ms": ms.value, "flops": fl.value}
+        self.h.call("gpmi_profile_reset")
+        return out
+
+    def close(self):
+        if self.h.ctx and self.ptr:
+            self.h.lib.gpmi_sgp_destroy(self.ptr)
+        self.ptr = C.c_void_p()
+        self.h.close()

@@ -34,6 +34,8 @@ COV_MAX_COLUMNS = 512  # the most columns gpmi_cov_columns takes
 PROF_DRAWS_SIGMA, PROF_DRAWS_FACTOR, PROF_DRAWS_NORMALS, PROF_DRAWS_PRODUCT = 9, 10, 11, 12  # GPMI_PROF_DRAWS_*
 DRAWS_MAX_M = 16384  # GPMI_DRAWS_MAX_M: the most points gpmi_posterior_draws / gpmi_mvn_draws take
 DRAWS_PANEL = 4096  # GPMI_DRAWS_PANEL: draws per panel of those two
+PROF_SGP_BUILD, PROF_SGP_GRAM, PROF_SGP_FACTOR, PROF_SGP_GRAD = 13, 14, 15, 16  # GPMI_PROF_SGP_*
+SGP_MAX_M = 4096  # GPMI_SGP_MAX_M: the most inducing points a gpmi_sgp object takes
 
 
 class GpmiUnavailable(RuntimeError):
@@ -138,6 +140,12 @@ SIGNATURES = {
     "gpmi_posterior_draws": (C.c_int, [_vp, _dp, _i64, C.c_double, _i64, _dp, _i64, _i64, _dp, _dp, _dp, _ip]),
     "gpmi_mvn_draws": (C.c_int, [_vp, _i64, _dp, _dp, C.c_double, _i64, _dp, _i64, _i64, _dp, _dp, _ip]),
     "gpmi_draws_normals": (C.c_int, [_i64, _i64, _i64, _i64, _dp]),
+    "gpmi_sgp_create": (C.c_int, [_vp, _i64, _i64, _dp, _i64, _dp, C.POINTER(_vp)]),
+    "gpmi_sgp_destroy": (C.c_int, [_vp]),
+    "gpmi_sgp_set_targets": (C.c_int, [_vp, _dp, _dp]),
+    "gpmi_sgp_bound": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, _i64, _dp, _dp, _dp, _ip]),
+    "gpmi_sgp_fit": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, _i64, _dp, _ip]),
+    "gpmi_sgp_predict": (C.c_int, [_vp, _dp, _i64, _dp, _dp]),
     "gpmi_timer_start": (C.c_int, [_vp]),
     "gpmi_timer_stop": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "gpmi_profile_enable": (C.c_int, [_vp, C.c_int]),

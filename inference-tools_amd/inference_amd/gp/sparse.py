@@ -1,0 +1,230 @@
+"""
+`SparseGpRegressor` - Gaussian-process regression for data sets too large for the exact `GpRegressor`: the variational
+inducing-point approximation of Titsias (2009).  m << N inducing inputs Z summarise the N data points; an evaluation
+costs O(N m^2) time and O(N d + m^2) memory, and the objective of the hyper-parameter search is a lower bound F of the
+log marginal likelihood (with its 2 pi constant), equal to it for Z = x.  All of it runs on the device (include/gpmi.h:
+gpmi_sgp_*): x never comes back, K_mn is never held whole.  The class follows `GpRegressor`: theta = [mean parameters |
+covariance parameters], `marginal_likelihood`, `marginal_likelihood_gradient`, `set_hyperparameters`, `__call__`.
+
+Supported: one of SquaredExponential, RationalQuadratic, Matern32, Matern52 (class or instance), optionally
+`+ WhiteNoise()`; the mean functions of `inference_amd.gp.mean` (evaluated on the host); data errors `y_err`.
+Not supported: FITC, optimised inducing inputs, spatial derivatives, posterior draws, `GpOptimiser`, several GPUs.
+"""
+from copy import copy
+from inspect import isclass
+from warnings import warn
+
+import numpy as np
+from numpy.linalg import LinAlgError
+from numpy.random import random
+from scipy.optimize import differential_evolution, fmin_l_bfgs_b
+
+from inference_amd import _lib
+from inference_amd._engine import SparseEngine
+from inference_amd.gp import _messages as msg
+from inference_amd.gp.covariance import (CompositeCovariance, SquaredExponential, WhiteNoise, _StationaryDeviceKernel,
+                                         device_plan)
+from inference_amd.gp.mean import ConstantMean
+from inference_amd.gp.regression import GpRegressor
+
+SUPPORTED = ("one of SquaredExponential, RationalQuadratic, Matern32, Matern52 (class or instance), optionally "
+             "+ WhiteNoise(), with y_err data errors")
+
+
+class SparseGpRegressor:
+    """
+    :param x: (N, d) coordinates (1-D input means d = 1), d <= 64.
+    :param y: (N,) values.
+    :param y_err: (N,) standard deviations of the values, or None (then the kernel needs `+ WhiteNoise()`).
+    :param inducing_points: (m, d) array of inducing inputs, or an int m: m rows of x drawn by
+        ``numpy.random.default_rng(seed).choice(N, m, replace=False)``, sorted.  1 <= m <= 4096.
+    :param kernel: a stationary device kernel, optionally ``+ WhiteNoise()``.
+    :param mean: mean-function class or instance.
+    :param hyperpars: ``[mean params | covariance params]``; omitted: found by maximising the bound.
+    :param optimizer: ``"bfgs"`` (multi-start L-BFGS-B on the device gradient) or ``"diffev"``.
+    :param n_starts: number of L-BFGS-B starts (default as `GpRegressor`).
+    :param seed: seed of the inducing-point choice.
+    :param jitter: eps = jitter a^2 is added to the diagonal of K_mm.
+    :param panel_rows: (extension) rows of x per panel of the device sweep; 0: the library's default.
+    """
+
+    def __init__(self, x, y, y_err=None, inducing_points=256, kernel=SquaredExponential, mean=ConstantMean, hyperpars=None,
+                 optimizer="bfgs", n_starts=None, seed=None, jitter=1e-8, device=None, y_cov=None, panel_rows=0):
+        self.x, self.y = GpRegressor._coerce_training_data(x, y)
+        self.x = np.ascontiguousarray(self.x, dtype=float)
+        self.y = np.asarray(self.y, dtype=float)
+        self.n_points, self.n_dimensions = self.x.shape
+        if self.n_dimensions > msg.MAX_DIMENSIONS:
+            raise ValueError(msg.too_many_dimensions("SparseGpRegressor", self.n_dimensions))
+        if self.n_points < 2:
+            raise ValueError("SparseGpRegressor needs at least two data points")
+        if y_cov is not None:
+            raise NotImplementedError(f"SparseGpRegressor does not take a dense y_cov; supported: {SUPPORTED}")
+        self.n_points = self.y.size
+        self._noise_var, _ = GpRegressor.check_error_data(self, y_err, None)
+
+        self.cov = kernel() if isclass(kernel) else kernel
+        self.mean = mean() if isclass(mean) else mean
+        main = self.cov
+        if isinstance(self.cov, CompositeCovariance):
+            parts = self.cov.components
+            wn = [c for c in parts if isinstance(c, WhiteNoise)]
+            stat = [c for c in parts if isinstance(c, _StationaryDeviceKernel)]
+            if len(parts) != 2 or len(wn) != 1 or len(stat) != 1:
+                raise NotImplementedError(f"SparseGpRegressor: unsupported covariance {type(self.cov).__name__}; supported: {SUPPORTED}")
+            main = stat[0]
+        if not isinstance(main, _StationaryDeviceKernel):
+            raise NotImplementedError(f"SparseGpRegressor: unsupported covariance {type(main).__name__}; supported: {SUPPORTED}")
+        self.cov.pass_spatial_data(self.x)
+        self.mean.pass_spatial_data(self.x)
+        self._kernel_id, _, self._stat_slice, self._wn_index = device_plan(self.cov)
+        if self._noise_var is None and self._wn_index is None:
+            raise ValueError("SparseGpRegressor needs noise: pass y_err or add WhiteNoise() to the kernel")
+        if not (np.isfinite(jitter) and jitter >= 0.0):
+            raise ValueError("jitter must be finite and not negative")
+        self.jitter = float(jitter)
+        self.panel_rows = int(panel_rows)
+
+        if isinstance(inducing_points, (int, np.integer)):
+            m = int(inducing_points)
+            if not 1 <= m <= min(self.n_points, _lib.SGP_MAX_M):
+                raise ValueError(f"inducing_points = {m}: an int must lie in 1 .. min(N, {_lib.SGP_MAX_M})")
+            rows = np.sort(np.random.default_rng(seed).choice(self.n_points, m, replace=False))
+            self.inducing_points = self.x[rows].copy()
+        else:
+            z = np.asarray(inducing_points, dtype=float)
+            if z.ndim == 1 and self.n_dimensions == 1:
+                z = z.reshape(-1, 1)
+            if z.ndim != 2 or z.shape[1] != self.n_dimensions or not 1 <= z.shape[0] <= _lib.SGP_MAX_M:
+                raise ValueError(f"inducing_points must be an (m, {self.n_dimensions}) array with 1 <= m <= {_lib.SGP_MAX_M}, "
+                                 f"got shape {z.shape}")
+            if not np.isfinite(z).all():
+                raise ValueError("inducing_points must be finite")
+            self.inducing_points = np.ascontiguousarray(z)
+
+        if self.cov.bounds is None:
+            self.cov.estimate_hyperpar_bounds(self.y)
+        if self.mean.bounds is None:
+            self.mean.estimate_hyperpar_bounds(self.y)
+        self.hp_bounds = copy(self.mean.bounds)
+        self.hp_bounds.extend(copy(self.cov.bounds))
+        self.n_hyperpars = len(self.hp_bounds)
+        self.mean_slice = slice(0, self.mean.n_params)
+        self.cov_slice = slice(self.mean.n_params, self.n_hyperpars)
+        self.hyperpar_labels = [*self.mean.hyperpar_labels, *self.cov.hyperpar_labels]
+        self._device = device
+        self._engine = None
+        self._targets_mean = None
+
+        if hyperpars is None:
+            if optimizer not in ["bfgs", "diffev"]:
+                optimizer = "bfgs"
+                warn(msg.BAD_OPTIMIZER)
+            hyperpars = self.differential_evo() if optimizer == "diffev" else self.multistart_bfgs(starts=n_starts)
+        self.set_hyperparameters(hyperpars)
+
+    # ---- device plumbing -----------------------------------------------------------------------------------------
+    @property
+    def engine(self) -> SparseEngine:
+        if self._engine is None:
+            self._engine = SparseEngine(self.x, self.inducing_points, device=self._device)
+        return self._engine
+
+    def _split(self, theta):
+        """theta -> (stationary-kernel parameters, WhiteNoise variance); the residual of theta's mean goes to the device
+        when it differs from the one already there."""
+        theta = np.asarray(theta, dtype=float)
+        if theta.size != self.n_hyperpars:
+            raise ValueError(msg.wrong_hyperpar_count(self.n_hyperpars, theta.size))
+        theta_mean, theta_cov = theta[self.mean_slice], theta[self.cov_slice]
+        if self._targets_mean is None or not np.array_equal(self._targets_mean, theta_mean):
+            self.engine.set_targets(self.y - self.mean.build_mean(theta_mean), self._noise_var)
+            self._targets_mean = np.array(theta_mean)
+        white = float(np.exp(2.0 * theta_cov[self._wn_index])) if self._wn_index is not None else 0.0
+        return np.ascontiguousarray(theta_cov[self._stat_slice]), white
+
+    # ---- the bound -----------------------------------------------------------------------------------------------
+    def marginal_likelihood(self, theta) -> float:
+        """The variational lower bound F of the log marginal likelihood; -1e50 where a factorisation fails."""
+        theta_stat, white = self._split(theta)
+        F, _, _, info = self.engine.bound(self._kernel_id, theta_stat, white, self.jitter, self.panel_rows)
+        if info != 0:
+            warn("Cholesky decomposition failure in marginal_likelihood")
+            return -1e50
+        return float(F)
+
+    def marginal_likelihood_gradient(self, theta):
+        """(F, dF/dtheta) with the gradient from the device; the mean parameters' part is (d mu / d theta)^T alpha."""
+        theta = np.asarray(theta, dtype=float)
+        theta_stat, white = self._split(theta)
+        F, g, alpha, info = self.engine.bound(self._kernel_id, theta_stat, white, self.jitter, self.panel_rows, True, True)
+        if info != 0:
+            raise LinAlgError("Matrix is not positive definite")
+        grad = np.zeros(self.n_hyperpars)
+        _, mean_grads = self.mean.mean_and_gradients(theta[self.mean_slice])
+        grad[self.mean_slice] = [float(np.dot(dmu, alpha)) for dmu in mean_grads]
+        cov_grad = np.zeros(self.cov.n_params)
+        cov_grad[self._stat_slice] = g[:-1]
+        if self._wn_index is not None:
+            cov_grad[self._wn_index] = g[-1]
+        grad[self.cov_slice] = cov_grad
+        return float(F), grad
+
+    def set_hyperparameters(self, hyperpars):
+        hyperpars = np.asarray(hyperpars, dtype=float)
+        theta_stat, white = self._split(hyperpars)
+        F, info = self.engine.fit(self._kernel_id, theta_stat, white, self.jitter, self.panel_rows)
+        if info != 0:
+            raise LinAlgError("Matrix is not positive definite")
+        self.hyperpars = hyperpars
+        self.mean_hyperpars = hyperpars[self.mean_slice]
+        self.cov_hyperpars = hyperpars[self.cov_slice]
+        self.bound = float(F)
+
+    def __call__(self, points):
+        """(mean, standard deviation) of the latent function at the points, as `GpRegressor.__call__`."""
+        q = np.ascontiguousarray(GpRegressor.process_points(self, points), dtype=float)
+        mean, var = self.engine.predict(q)
+        return mean + GpRegressor._mean_at(self, q), np.sqrt(np.abs(var))
+
+    # ---- hyper-parameter search (as GpRegressor: SciPy on the host, every evaluation on the device) ----------------
+    def bfgs_cost_func(self, theta):
+        try:
+            F, g = self.marginal_likelihood_gradient(theta)
+        except LinAlgError:
+            return 1e50, np.zeros(self.n_hyperpars)
+        return -F, -g
+
+    def multistart_bfgs(self, starts=None):
+        if starts is None:
+            starts = int(2 * np.sqrt(len(self.hp_bounds))) + 1
+        lwr, upr = [np.array([k[i] for k in self.hp_bounds]) for i in [0, 1]]
+        starting_positions = [lwr + (upr - lwr) * random(size=len(self.hp_bounds)) for _ in range(starts - 1)]
+        starting_positions.append(0.5 * (lwr + upr))
+        results = [fmin_l_bfgs_b(func=self.bfgs_cost_func, x0=x0, approx_grad=False, bounds=self.hp_bounds)
+                   for x0 in starting_positions]
+        self.search_log = [(np.array(x0), np.array(r[0]), float(r[1])) for x0, r in zip(starting_positions, results)]
+        return sorted(results, key=lambda r: r[1])[0][0]
+
+    def differential_evo(self):
+        from warnings import catch_warnings, simplefilter
+
+        def neg(t):
+            with catch_warnings():
+                simplefilter("ignore")
+                return -self.marginal_likelihood(t)
+
+        return differential_evolution(func=neg, bounds=self.hp_bounds).x
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state["_engine"] = None
+        state["_targets_mean"] = None
+        return state
+
+    def __str__(self):
+        pad = max(len(label) for label in self.hyperpar_labels) + 2
+        lines = ["\n[ SparseGpRegressor hyperparameters ]\n"]
+        for label, val in zip(self.hyperpar_labels, self.hyperpars):
+            lines.append(f"{label:>{pad}} = {val:.4}\n")
+        return "".join(lines)

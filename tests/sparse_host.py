@@ -1,0 +1,176 @@
+"""
+NumPy / SciPy mirror of the variational inducing-point model (Titsias 2009) behind `SparseGpRegressor` and the
+gpmi_sgp_* entry points: the bound F, its analytic gradient and the prediction, all in the stable "B form".  The kernels
+come from tests/matern_host.py (formulas, not the package's code).
+
+    sigma_i^2 = noise_var_i + s^2,  W = diag(1 / sigma_i^2),  eps = jitter a^2
+    K_mm + eps I = L L^T,  G = K_mn W K_nm,  H = L^-1 G L^-T (symmetrised),  B = I + H = L_B L_B^T,  c = L_B^-1 L^-1 K_mn W r
+    F = -1/2 [N ln 2 pi + sum ln sigma_i^2 + 2 sum ln diag(L_B) + r^T W r - c^T c] - 1/2 [a^2 sum w_i - tr H]
+    mean(q) = u^T c,  var(q) = a^2 - |v|^2 + |u|^2,  v = L^-1 k_m(q),  u = L_B^-1 v
+
+    S = L^-T B^-1 L^-1,  gamma = S K_mn W r,  alpha = W (r - K_nm gamma),  beta = L^-T L^-1 K_mn alpha,
+    T = L^-T (I - B^-1) L^-1,  M1 = beta alpha^T + T K_mn W,  M2 = beta beta^T + L^-T (B - 2 I + B^-1) L^-1
+    dF/dtheta_k = sum M1 o dK_mn/dtheta_k - 1/2 sum M2 o d(K_mm + eps I)/dtheta_k - 1/2 sum_i w_i da^2/dtheta_k
+    dF/d ln s   = s^2 sum_i [alpha_i^2 - (R^-1)_ii + w_i^2 (a^2 - Q_ii)],  (R^-1)_ii = w_i - w_i^2 k_i^T S k_i,  Q_ii = |L^-1 k_i|^2
+
+`ripple`: a callable (name, matrix) -> matrix applied to K_mm ("mm"), K_mn ("mn") and a query's K_mq ("mq") before
+anything is computed from them - the tests perturb the entries by the K-build's accuracy class to size their tolerances.
+"""
+import numpy as np
+from scipy.linalg import cholesky, solve_triangular
+
+import matern_host as mh
+
+LN_2PI = float(np.log(2.0 * np.pi))
+
+
+def cross_and_grads(kind, u, v, theta):
+    """K(u, v) and its derivatives by theta = [ln a, (ln kappa,) ln l_1 .. ln l_d] (no diagonal term)."""
+    a2, kappa, scales = mh.split(kind, theta)
+    u2 = mh._u2(u, v, scales)
+    s = 0.5 * u2.sum(axis=0)
+    C, g = mh.profiles(kind, s, kappa)
+    K = a2 * C
+    grads = [2.0 * K]
+    if kind == "rq":
+        F = 1.0 + s / kappa
+        grads.append(-K * (kappa * np.log(F) - s / F))
+    grads.extend(a2 * g * u2k for u2k in u2)
+    return K, grads
+
+
+class SparseMirror:
+    def __init__(self, kind, x, z, jitter=1e-8, ripple=None):
+        self.kind, self.x, self.z, self.jitter = kind, np.asarray(x, float), np.asarray(z, float), float(jitter)
+        self.ripple = ripple or (lambda name, A: A)
+        self._key, self._kernels = None, None
+
+    def _kernel_matrices(self, theta, grads=False):
+        """Unrippled K_mm, K_mn and (grads) their derivatives at theta, kept for the last theta: rippled repeats are cheap."""
+        key = np.asarray(theta, float).tobytes()
+        if key != self._key or (grads and self._kernels[2] is None):
+            if grads:
+                Kmm, dmm = cross_and_grads(self.kind, self.z, self.z, theta)
+                Kmn, dmn = cross_and_grads(self.kind, self.z, self.x, theta)
+            else:
+                Kmm, Kmn, dmm, dmn = mh.cross(self.kind, self.z, self.z, theta), mh.cross(self.kind, self.z, self.x, theta), None, None
+            self._key, self._kernels = key, (Kmm, Kmn, dmm, dmn)
+        return self._kernels
+
+    def _matrices(self, theta):
+        a2 = mh.split(self.kind, theta)[0]
+        K0mm, K0mn, _, _ = self._kernel_matrices(theta)
+        Kmm, Kmn = self.ripple("mm", K0mm), self.ripple("mn", K0mn)
+        return a2, Kmm + self.jitter * a2 * np.eye(len(self.z)), Kmn
+
+    def state(self, theta, white_var, r, noise_var):
+        """Everything the bound, the prediction and the gradient share.  Raises numpy.linalg.LinAlgError if K_mm + eps I
+        or B is not positive definite."""
+        r = np.asarray(r, float)
+        sig2 = (np.zeros(len(r)) if noise_var is None else np.asarray(noise_var, float)) + white_var
+        w = 1.0 / sig2
+        a2, Kmm, Kmn = self._matrices(theta)
+        L = cholesky(Kmm, lower=True)
+        G = (Kmn * w) @ Kmn.T
+        H = solve_triangular(L, solve_triangular(L, G, lower=True).T, lower=True)
+        H = 0.5 * (H + H.T)
+        B = np.eye(len(H)) + H
+        LB = cholesky(B, lower=True)
+        b = Kmn @ (w * r)
+        c = solve_triangular(LB, solve_triangular(L, b, lower=True), lower=True)
+        F = (-0.5 * (len(r) * LN_2PI + np.log(sig2).sum() + 2.0 * np.log(np.diag(LB)).sum() + r @ (w * r) - c @ c)
+             - 0.5 * (a2 * w.sum() - np.trace(H)))
+        return dict(r=r, w=w, a2=a2, Kmm=Kmm, Kmn=Kmn, L=L, G=G, H=H, B=B, LB=LB, b=b, c=c, F=float(F))
+
+    def bound(self, theta, white_var, r, noise_var=None):
+        return self.state(theta, white_var, r, noise_var)["F"]
+
+    def cond_kmm(self, theta):
+        return float(np.linalg.cond(self._matrices(theta)[1]))
+
+    def predict(self, theta, white_var, r, noise_var, q, st=None):
+        st = st or self.state(theta, white_var, r, noise_var)
+        Kmq = self.ripple("mq", mh.cross(self.kind, self.z, np.asarray(q, float), theta))
+        v = solve_triangular(st["L"], Kmq, lower=True)
+        u = solve_triangular(st["LB"], v, lower=True)
+        return u.T @ st["c"], st["a2"] - (v**2).sum(axis=0) + (u**2).sum(axis=0)
+
+    def bound_and_gradient(self, theta, white_var, r, noise_var=None):
+        """(F, gradient by [theta, ln s], alpha): the last entry is 0 for white_var = 0."""
+        st = self.state(theta, white_var, r, noise_var)
+        r, w, a2, L, LB, Kmn, H, B = (st[k] for k in ("r", "w", "a2", "L", "LB", "Kmn", "H", "B"))
+        m = len(L)
+        Linv = solve_triangular(L, np.eye(m), lower=True)
+        Binv = solve_triangular(LB, solve_triangular(LB, np.eye(m), lower=True), lower=True, trans="T")
+        Binv = 0.5 * (Binv + Binv.T)
+        S = Linv.T @ Binv @ Linv
+        gamma = S @ st["b"]
+        alpha = w * (r - Kmn.T @ gamma)
+        beta = Linv.T @ (Linv @ (Kmn @ alpha))
+        T = Linv.T @ (np.eye(m) - Binv) @ Linv
+        M1 = np.outer(beta, alpha) + (T @ Kmn) * w
+        M2 = np.outer(beta, beta) + Linv.T @ (B - 2.0 * np.eye(m) + Binv) @ Linv
+        _, _, dmm, dmn = self._kernel_matrices(theta, grads=True)
+        grad = np.zeros(len(theta) + 1)
+        for k in range(len(theta)):
+            dKmm = dmm[k] + (2.0 * self.jitter * a2 * np.eye(m) if k == 0 else 0.0)  # d eps / d ln a = 2 eps
+            grad[k] = (M1 * dmn[k]).sum() - 0.5 * (M2 * dKmm).sum() - (a2 * w.sum() if k == 0 else 0.0)
+        if white_var > 0.0:
+            kSk = ((S @ Kmn) * Kmn).sum(axis=0)
+            Qii = (solve_triangular(L, Kmn, lower=True) ** 2).sum(axis=0)
+            grad[-1] = white_var * (alpha**2 - (w - w**2 * kSk) + w**2 * (a2 - Qii)).sum()
+        return st["F"], grad, alpha
+
+    def dense_bound(self, theta, white_var, r, noise_var=None):
+        """The definition: ln N(r | 0, Q + Sigma) - 1/2 tr(W (a^2 I - Q)), Q = K_nm (K_mm + eps I)^-1 K_mn, through the
+        N x N matrix (the form that loses digits when K_mm is ill conditioned; for well-conditioned checks only)."""
+        r = np.asarray(r, float)
+        sig2 = (np.zeros(len(r)) if noise_var is None else np.asarray(noise_var, float)) + white_var
+        a2, Kmm, Kmn = self._matrices(theta)
+        Q = Kmn.T @ np.linalg.solve(Kmm, Kmn)
+        C = cholesky(Q + np.diag(sig2), lower=True)
+        v = solve_triangular(C, r, lower=True)
+        return float(-0.5 * (len(r) * LN_2PI + 2.0 * np.log(np.diag(C)).sum() + v @ v) - 0.5 * ((a2 - np.diag(Q)) / sig2).sum())
+
+
+def fd4(f, theta, h=1e-3):
+    """Fourth-order central difference of a scalar function, coordinate by coordinate."""
+    theta = np.asarray(theta, float)
+    out = np.zeros(len(theta))
+    for k in range(len(theta)):
+        e = np.zeros(len(theta))
+        e[k] = h
+        out[k] = (-f(theta + 2 * e) + 8.0 * f(theta + e) - 8.0 * f(theta - e) + f(theta - 2 * e)) / (12.0 * h)
+    return out
+
+
+def rippler(seed, rel=1e-13):
+    """A `ripple` that multiplies every entry by 1 + rel xi, xi uniform in [-1, 1] (symmetric for K_mm)."""
+    rng = np.random.default_rng(seed)
+
+    def ripple(name, A):
+        xi = rng.uniform(-1.0, 1.0, size=A.shape)
+        if name == "mm":
+            xi = np.triu(xi) + np.triu(xi, 1).T
+        return A * (1.0 + rel * xi)
+
+    return ripple
+
+
+def dataset(n, d, seed=0):
+    """x uniform in the unit cube, a smooth y plus noise of 0.1, y_err between 0.05 and 0.15."""
+    rng = np.random.default_rng(5000 + 17 * n + d + seed)
+    x = rng.uniform(0.0, 1.0, size=(n, d))
+    y = np.sin(3.0 * x[:, 0]) + 0.5 * np.cos(2.0 * x.sum(axis=1)) + 0.1 * rng.standard_normal(n)
+    return x, y, rng.uniform(0.05, 0.15, size=n)
+
+
+def spread_rows(x, m):
+    """m rows of x, far apart: farthest-point selection from row 0, sorted (well-conditioned inducing inputs)."""
+    idx = [0]
+    dmin = ((x - x[0]) ** 2).sum(axis=1)
+    for _ in range(m - 1):
+        i = int(np.argmax(dmin))
+        idx.append(i)
+        dmin = np.minimum(dmin, ((x - x[i]) ** 2).sum(axis=1))
+    return np.sort(np.array(idx))
