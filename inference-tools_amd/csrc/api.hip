@@ -8,6 +8,8 @@
 //   api_mix.hip         mixture covariance (ChangePoint), per-point noise (HeteroscedasticNoise)
 //   api_linv.hip        linear inversion (GpLinearInverter)
 //   api_dense.hip       plugin covariance functions (dense path), rank-one append
+//   api_lockstep.hip    what the lockstep batch entry points share (Chunk, lockstep_stages)
+//   api_single.hip      what the single-evaluation entry points share (LaneEval, lane_stages, lane_collect)
 // api_internal.h declares what they share.
 #include "api_internal.h"
 #include <malloc.h>

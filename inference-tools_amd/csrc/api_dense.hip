@@ -1,7 +1,7 @@
 // C-ABI of libgpmi (include/gpmi.h): appending one training point at fixed hyper-parameters, and the dense entry points for covariance functions
 // that only implement the plugin ABC.
 // (split from api.hip in round 4; the handle, the lanes and the helpers these entry points are built from: api.hip,
-// api_internal.h)
+// api_internal.h; the pipeline of the single evaluations: api_single.hip)
 #include "api_internal.h"
 
 // ---- append one training point at fixed hyper-parameters (O(n^2)) ------------------------------------------------
@@ -71,7 +71,8 @@ int gpmi_append_point(gpmi_ctx* c, const double* x_new, double y_new, double noi
   HIPCHK(c, hipMemcpyAsync(c->pts, x_new, sizeof(double) * c->d, hipMemcpyHostToDevice, s));
   // k = K(x_new, X) against the n points present (zeros beyond), then l = L^-1 k (rows >= n of L are identity rows)
   launch_kbuild_cross(s, p, c->pts, 1, GPMI_NB, c->x, n, c->np, c->Q, c->ld);
-  double* lvec = L.vec + 2 * c->np;
+  const LaneEval ev(c, 0);
+  double* lvec = ev.slot2();
   HIPCHK(c, hipMemsetAsync(L.info, 0, sizeof(int), s));
   trsv_forward(c, s, L.A, c->np, c->ld, L.invD, c->Q, lvec, L.info);
   // K_nn = a^2 (1 + 1e-12) + WhiteNoise + data variance (covariance.py:254-255, regression.py:239)
@@ -96,12 +97,11 @@ int gpmi_append_point(gpmi_ctx* c, const double* x_new, double y_new, double noi
   HIPCHK(c, hipMemcpyAsync(c->noise + n, &noise_var_new, sizeof(double), hipMemcpyHostToDevice, s));
   c->n = n + 1;
   L.inv2_valid = false;
-  double* mu_dev = L.vec + 3 * c->np;
-  HIPCHK(c, hipMemcpyAsync(mu_dev, mu, sizeof(double) * c->n, hipMemcpyHostToDevice, s));
-  launch_residual(s, c->y, mu_dev, 0.0, L.vec + 2 * c->np, c->n, c->np);
-  trsv_forward(c, s, L.A, c->np, c->ld, L.invD, L.vec + 2 * c->np, L.vec, L.info);
-  launch_lml_reduce(s, L.vec, L.A, c->ld, c->np, L.red);
-  trsv_backward(c, s, L.A, c->np, c->ld, L.invD, L.vec, c->alpha, L.info);
+  HIPCHK(c, hipMemcpyAsync(ev.mu(), mu, sizeof(double) * c->n, hipMemcpyHostToDevice, s));
+  launch_residual(s, c->y, ev.mu(), 0.0, ev.resid(), c->n, c->np);
+  trsv_forward(c, s, L.A, c->np, c->ld, L.invD, ev.resid(), ev.v(), L.info);
+  launch_lml_reduce(s, ev.v(), L.A, c->ld, c->np, L.red);
+  trsv_backward(c, s, L.A, c->np, c->ld, L.invD, ev.v(), ev.alpha(), L.info);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(L.h_red, L.red, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipMemcpyAsync(L.h_info, L.info, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -140,6 +140,8 @@ __global__ void panel_pad_kernel(double* __restrict__ Q, int64_t ld, int64_t row
   if (i >= rows_valid || j >= n) Q[i * ld + j] = 0.0;
 }
 
+}  // namespace
+
 int upload_dense_matrix(gpmi_ctx* c, Lane& L, const double* K_host) {
   hipStream_t s = L.stream;
   HIPCHK(c, hipMemcpy2DAsync(L.A, sizeof(double) * c->ld, K_host, sizeof(double) * c->n, sizeof(double) * c->n,
@@ -163,6 +165,8 @@ int enqueue_dense_factor_and_forward(gpmi_ctx* c, Lane& L, const double* mu_dev,
   return GPMI_OK;
 }
 
+namespace {
+
 int upload_query_panel(gpmi_ctx* c, hipStream_t s, double* Q, const double* rows_host, int64_t mc, int64_t mp) {
   HIPCHK(c, hipMemcpy2DAsync(Q, sizeof(double) * c->ld, rows_host, sizeof(double) * c->n, sizeof(double) * c->n,
                              (size_t)mc, hipMemcpyHostToDevice, s));
@@ -181,23 +185,14 @@ int gpmi_fit_dense(gpmi_ctx* c, const double* K_host, const double* mu, double* 
   ARGCHK(c, c->n > 0, "gpmi_set_data has not been called");
   ARGCHK(c, K_host && mu, "K / mu is NULL");
   if (int rc = set_device(c)) return rc;
-  Lane& L = c->lanes[0];
-  hipStream_t s = L.stream;
-  double* mu_dev = L.vec + 3 * c->np;
-  HIPCHK(c, hipMemcpyAsync(mu_dev, mu, sizeof(double) * c->n, hipMemcpyHostToDevice, s));
-  if (int rc = upload_dense_matrix(c, L, K_host)) return rc;
-  if (int rc = enqueue_dense_factor_and_forward(c, L, mu_dev, 0)) return rc;
-  trsv_backward(c, s, L.A, c->np, c->ld, L.invD, L.vec, c->alpha, L.info);
-  HIPCHK(c, hipMemcpyAsync(L.h_red, L.red, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(L.h_info, L.info, sizeof(int), hipMemcpyDeviceToHost, s));
-  if (alpha_out) HIPCHK(c, hipMemcpyAsync(alpha_out, c->alpha, sizeof(double) * c->n, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  if (logdet_out) *logdet_out = L.h_red[1];
-  INFOCHK(c, L.h_info[0]);
-  if (info) *info = L.h_info[0];
+  const LaneEval ev(c, 0);
+  if (int rc = lane_stages(ev, LaneBuild::from_host(K_host), LN_BACKWARD, mu)) return rc;
+  int inf = 0;
+  if (int rc = lane_collect(ev, LC_LOGDET, 0, {{alpha_out, ev.alpha()}}, logdet_out, &inf)) return rc;
+  if (info) *info = inf;
   c->fit_params = CovParams();
   c->fit_params.kernel = -1;  // dense: the kernel-specific entry points (gpmi_predict, ...) do not apply
-  c->fitted = (L.h_info[0] == 0);
+  c->fitted = (inf == 0);
   c->mix_nk = 0;
   return GPMI_OK;
 }
@@ -208,35 +203,14 @@ int gpmi_lml_dense(gpmi_ctx* c, const double* K_host, const double* mu, double* 
   ARGCHK(c, c->n > 0, "gpmi_set_data has not been called");
   ARGCHK(c, K_host && mu && lml, "K / mu / lml is NULL");
   if (int rc = set_device(c)) return rc;
-  if (int rc = ensure_lanes(c, 2)) return rc;
-  Lane& L = c->lanes[1];
-  hipStream_t s = L.stream;
-  double* mu_dev = L.vec + 3 * c->np;
-  double* alpha_dev = L.vec + c->np;
-  HIPCHK(c, hipMemcpyAsync(mu_dev, mu, sizeof(double) * c->n, hipMemcpyHostToDevice, s));
-  if (int rc = upload_dense_matrix(c, L, K_host)) return rc;
-  if (int rc = enqueue_dense_factor_and_forward(c, L, mu_dev, 0)) return rc;
-  if (alpha_out || iK_out) trsv_backward(c, s, L.A, c->np, c->ld, L.invD, L.vec, alpha_dev, L.info);
-  if (iK_out) {
-    // K^-1 = L^-T L^-1 (regression.py:556-557): L^-T by forward substitution on the identity, then the k-skipped SYRK
-    if (int rc = ensure_second_matrix(c, L)) return rc;
-    if (int rc = enqueue_inverse_factor(c, L, L)) return rc;
-    launch_gemm(s, TILES_LOWER, OP_ASSIGN, false, true, L.A, c->ld, L.B2, c->ld, L.B2, c->ld, (int)(c->np / GPMI_NB),
-                (int)(c->np / GPMI_NB), (int)c->np);
-    launch_mirror_lower(s, L.A, c->ld, c->np);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpy2DAsync(iK_out, sizeof(double) * c->n, L.A, sizeof(double) * c->ld, sizeof(double) * c->n,
-                               (size_t)c->n, hipMemcpyDeviceToHost, s));
-  }
-  HIPCHK(c, hipMemcpyAsync(L.h_red, L.red, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(L.h_info, L.info, sizeof(int), hipMemcpyDeviceToHost, s));
-  if (alpha_out) HIPCHK(c, hipMemcpyAsync(alpha_out, alpha_dev, sizeof(double) * c->n, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  INFOCHK(c, L.h_info[0]);
-  // -1/2 v.v - sum ln L_ii (regression.py:539); the caller applies the -1e50 convention (regression.py:540-542)
-  *lml = (L.h_info[0] == 0) ? (-0.5 * L.h_red[0] - L.h_red[1]) : -1e50;
-  if (info) *info = L.h_info[0];
-  return GPMI_OK;
+  const LaneEval ev(c, 1);
+  // K^-1 = L^-T L^-1 in full, if asked for
+  const unsigned steps = iK_out ? LN_BACKWARD | LN_INVERSE | LN_SYRK | LN_MIRROR : alpha_out ? LN_BACKWARD : 0u;
+  if (int rc = lane_stages(ev, LaneBuild::from_host(K_host), steps, mu)) return rc;
+  if (iK_out)
+    HIPCHK(c, hipMemcpy2DAsync(iK_out, sizeof(double) * c->n, ev.L().A, sizeof(double) * c->ld, sizeof(double) * c->n,
+                               (size_t)c->n, hipMemcpyDeviceToHost, ev.stream()));
+  return lane_collect(ev, LC_LML, 0, {{alpha_out, ev.alpha()}}, lml, info);
 }
 
 int gpmi_loo_dense(gpmi_ctx* c, const double* K_host, const double* mu, double* alpha_out, double* ikdiag,
@@ -245,55 +219,16 @@ int gpmi_loo_dense(gpmi_ctx* c, const double* K_host, const double* mu, double* 
   ARGCHK(c, c->n > 0, "gpmi_set_data has not been called");
   ARGCHK(c, K_host && mu && alpha_out && ikdiag, "NULL argument");
   if (int rc = set_device(c)) return rc;
-  if (int rc = ensure_lanes(c, 2)) return rc;
-  Lane& L = c->lanes[1];
-  if (int rc = ensure_second_matrix(c, L)) return rc;
-  const int64_t need = 4 * c->np;
-  if (L.gws_doubles < need) {
-    if (L.gws) (void)hipFree(L.gws);
-    L.gws = nullptr;
-    L.gws_doubles = 0;
-    HIPCHK(c, hipMalloc(&L.gws, sizeof(double) * need));
-    L.gws_doubles = need;
-  }
-  hipStream_t s = L.stream;
-  const int nt = (int)(c->np / GPMI_NB);
-  double* mu_dev = L.vec + 3 * c->np;
-  double* alpha_dev = L.vec + c->np;
-  double *diag_dev = L.gws, *c1_dev = L.gws + c->np, *sc2_dev = L.gws + 2 * c->np, *p_dev = L.gws + 3 * c->np;
-  HIPCHK(c, hipMemcpyAsync(mu_dev, mu, sizeof(double) * c->n, hipMemcpyHostToDevice, s));
-  if (int rc = upload_dense_matrix(c, L, K_host)) return rc;
-  if (int rc = enqueue_dense_factor_and_forward(c, L, mu_dev, 0)) return rc;
-  trsv_backward(c, s, L.A, c->np, c->ld, L.invD, L.vec, alpha_dev, L.info);
-  if (int rc = enqueue_inverse_factor(c, L, L)) return rc;
-  launch_rows_sumsq(s, L.B2, c->ld, c->np, c->np, 0.0, diag_dev);  // = -diag(K^-1)   (regression.py:503)
-  launch_negate(s, diag_dev, c->np);
-  HIPCHK(c, hipMemcpyAsync(ikdiag, diag_dev, sizeof(double) * c->n, hipMemcpyDeviceToHost, s));
-  if (p_out || W_out) {
-    // the gradient's two parameter-independent pieces (regression.py:507-514 regrouped):
-    //   sum_i c1_i (K^-1 dK alpha)_i = p . (dK alpha),  p = K^-1 c1
-    //   sum_i c2_i (K^-1 dK K^-1)_ii = sum dK o W,       W = K^-1 diag(c2) K^-1 = G G^T, G = K^-1 diag(sqrt c2)
-    launch_gemm(s, TILES_LOWER, OP_ASSIGN, false, true, L.A, c->ld, L.B2, c->ld, L.B2, c->ld, nt, nt, (int)c->np);
-    launch_mirror_lower(s, L.A, c->ld, c->np);
-    launch_loo_vectors(s, alpha_dev, diag_dev, c1_dev, sc2_dev, c->n, c->np);
-    launch_rows_dot(s, L.A, c->ld, c->np, c->np, c1_dev, p_dev);
-    if (p_out) HIPCHK(c, hipMemcpyAsync(p_out, p_dev, sizeof(double) * c->n, hipMemcpyDeviceToHost, s));
-    if (W_out) {
-      launch_scale_columns(s, L.A, sc2_dev, L.B2, c->ld, c->np);
-      launch_gemm(s, TILES_LOWER, OP_ASSIGN, false, false, L.A, c->ld, L.B2, c->ld, L.B2, c->ld, nt, nt, (int)c->np);
-      launch_mirror_lower(s, L.A, c->ld, c->np);
-      HIPCHK(c, hipGetLastError());
-      HIPCHK(c, hipMemcpy2DAsync(W_out, sizeof(double) * c->n, L.A, sizeof(double) * c->ld, sizeof(double) * c->n,
-                                 (size_t)c->n, hipMemcpyDeviceToHost, s));
-    }
-  }
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(L.h_info, L.info, sizeof(int), hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(alpha_out, alpha_dev, sizeof(double) * c->n, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  INFOCHK(c, L.h_info[0]);
-  if (info) *info = L.h_info[0];
-  return GPMI_OK;
+  const LaneEval ev(c, 1);
+  if (int rc = lane_stages(ev, LaneBuild::from_host(K_host), LN_BACKWARD | LN_INVERSE | LN_LOO, mu)) return rc;
+  // the gradient's two parameter-independent pieces (regression.py:507-514 regrouped):
+  //   sum_i c1_i (K^-1 dK alpha)_i = p . (dK alpha),  p = K^-1 c1
+  //   sum_i c2_i (K^-1 dK K^-1)_ii = sum dK o W,       W = K^-1 diag(c2) K^-1 = G G^T, G = K^-1 diag(sqrt c2)
+  lane_loo_middle(ev, p_out || W_out, W_out != nullptr, true);
+  if (W_out)
+    HIPCHK(c, hipMemcpy2DAsync(W_out, sizeof(double) * c->n, ev.L().A, sizeof(double) * c->ld, sizeof(double) * c->n,
+                               (size_t)c->n, hipMemcpyDeviceToHost, ev.stream()));
+  return lane_collect(ev, 0, 0, {{alpha_out, ev.alpha()}, {ikdiag, ev.loo_diag()}, {p_out, ev.loo_p()}}, nullptr, info);
 }
 
 int gpmi_predict_dense(gpmi_ctx* c, const double* Kq_host, int64_t m, double* kalpha_out, double* sumsq_out) {
@@ -301,27 +236,10 @@ int gpmi_predict_dense(gpmi_ctx* c, const double* Kq_host, int64_t m, double* ka
   ARGCHK(c, c->fitted, "gpmi_predict_dense needs a successful fit");
   ARGCHK(c, Kq_host && m > 0, "Kq is NULL or m <= 0");
   if (int rc = set_device(c)) return rc;
-  Lane& L = c->lanes[0];
-  hipStream_t s = L.stream;
-  const int64_t chunk = 2048;
-  for (int64_t m0 = 0; m0 < m; m0 += chunk) {
-    const int64_t mc = (m - m0 < chunk) ? m - m0 : chunk;
-    const int64_t mp = round_up(mc, GPMI_NB);
-    if (int rc = ensure_query_ws(c, mp)) return rc;
-    if (int rc = upload_query_panel(c, s, c->Q, Kq_host + m0 * c->n, mc, mp)) return rc;
-    double* mu_dev = c->pvec;
-    double* ss_dev = c->pvec + mp;
-    if (kalpha_out) launch_rows_dot(s, c->Q, c->ld, mp, c->np, c->alpha, mu_dev);
-    if (sumsq_out) {
-      if (int rc = ensure_inv2(c, L, s)) return rc;
-      trsm_rows_forward(c, s, L.A, c->np, c->ld, L.inv2, c->Q, mp, false, c->Q2, nullptr);
-      launch_rows_sumsq(s, c->Q2, c->ld, mp, c->np, 0.0, ss_dev);  // - |L^-1 k|^2
-    }
-    HIPCHK(c, hipGetLastError());
-    if (kalpha_out) HIPCHK(c, hipMemcpyAsync(kalpha_out + m0, mu_dev, sizeof(double) * mc, hipMemcpyDeviceToHost, s));
-    if (sumsq_out) HIPCHK(c, hipMemcpyAsync(sumsq_out + m0, ss_dev, sizeof(double) * mc, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-  }
+  auto fill = [&](int64_t m0, int64_t mc, int64_t mp) {
+    return upload_query_panel(c, c->lanes[0].stream, c->Q, Kq_host + m0 * c->n, mc, mp);
+  };
+  if (int rc = predict_rows(c, m, fill, 0.0, kalpha_out, sumsq_out)) return rc;  // - |L^-1 k|^2
   if (sumsq_out)
     for (int64_t i = 0; i < m; ++i) sumsq_out[i] = -sumsq_out[i];
   return GPMI_OK;
@@ -344,18 +262,15 @@ int gpmi_solve_rows(gpmi_ctx* c, const double* Q_host, int64_t m, double* X_host
   if (X_host)
     HIPCHK(c, hipMemcpy2DAsync(X_host, sizeof(double) * c->n, c->Q2, sizeof(double) * c->ld, sizeof(double) * c->n,
                                (size_t)m, hipMemcpyDeviceToHost, s));
+  DevBuf G;  // (an error return below may leave work on it in flight: hipFree waits for the device before it releases)
   if (gram_host) {
     // G = X X^T (m x m): what posterior covariances are made of (regression.py:447-448)
-    double* G = nullptr;
     const int64_t ldg = mp + 32;
-    HIPCHK(c, hipMalloc(&G, sizeof(double) * mp * ldg));
-    launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, G, ldg, c->Q2, c->ld, c->Q2, c->ld, (int)(mp / GPMI_NB),
+    HIPCHK(c, hipMalloc(&G.p, sizeof(double) * mp * ldg));
+    launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, G.as<double>(), ldg, c->Q2, c->ld, c->Q2, c->ld, (int)(mp / GPMI_NB),
                    (int)(mp / GPMI_NB), (int)c->np);
-    hipError_t e = hipMemcpy2DAsync(gram_host, sizeof(double) * m, G, sizeof(double) * ldg, sizeof(double) * m,
-                                    (size_t)m, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(G);
-    HIPCHK(c, e);
+    HIPCHK(c, hipMemcpy2DAsync(gram_host, sizeof(double) * m, G.p, sizeof(double) * ldg, sizeof(double) * m, (size_t)m,
+                               hipMemcpyDeviceToHost, s));
   }
   HIPCHK(c, hipStreamSynchronize(s));
   return GPMI_OK;

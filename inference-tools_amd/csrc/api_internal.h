@@ -1,8 +1,10 @@
 // Shared by the translation units of the C-ABI (api.hip: handle, lanes, workspaces, lifecycle, instrumentation;
 // api_regression.hip: the GpRegressor entry points; api_mix.hip: ChangePoint mixtures and per-point noise; api_lockstep.hip:
 // the chunk pipeline every lockstep batch entry point of those two runs - Chunk, BatchParams, lockstep_stages, the
-// leave-one-out middle part, the mixture batches' workspace and staging; api_linv.hip: GpLinearInverter; api_dense.hip:
-// plugin covariance functions and the rank-one append): error macros and the helpers every entry point is built from.
+// leave-one-out middle part, the mixture batches' workspace and staging; api_single.hip: the lane pipeline of their
+// single-evaluation entry points - LaneEval, LaneBuild, lane_stages, lane_loo_middle, lane_collect; api_linv.hip:
+// GpLinearInverter; api_dense.hip: plugin covariance functions and the rank-one append): error macros and the helpers
+// every entry point is built from.
 // Internal - the public interface is include/gpmi.h.
 #pragma once
 #include <algorithm>
@@ -11,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <thread>
 
@@ -323,3 +326,134 @@ int stage_mix_inputs(RowStage& stage, const Chunk& k, const MixBatch& mx, int64_
 void mix_sub_kernel_terms(const Chunk& k, const MixBatch& mx, const double* p, int64_t sP);
 // grad_thetas row of problem b of the chunk from h_bGout, times `factor`
 void unpack_mix_gradient(const gpmi_ctx* c, const MixBatch& mx, int b, double factor, double* out);
+
+// ---- api_single.hip: one evaluation on one lane (any size): what the single-evaluation entry points share ----
+// api_dense.hip: the caller's matrix into L.A, and the dense twin of enqueue_factor_and_forward (no early work, no pair
+// quiesce, no split build)
+int upload_dense_matrix(gpmi_ctx* c, Lane& L, const double* K_host);
+int enqueue_dense_factor_and_forward(gpmi_ctx* c, Lane& L, const double* mu_dev, int slot);
+
+// host times of gpmi_fit's GPMI_DEBUG_TIMING line
+struct LaneTimes {
+  std::chrono::steady_clock::time_point start, forward, enqueued, done;
+};
+
+// One lane as an entry point sees it, the counterpart of Chunk: lane 0 holds the fit (its alpha is the handle's), lane 1
+// every other single evaluation.  The lane is named by its index: lane_stages creates it when it is not there yet.
+struct LaneEval {
+  gpmi_ctx* c;
+  int lane;
+  LaneTimes* times = nullptr;
+  LaneEval(gpmi_ctx* ctx, int index) : c(ctx), lane(index) {}
+  Lane& L() const { return c->lanes[(size_t)lane]; }
+  hipStream_t stream() const { return L().stream; }
+  // the four work vectors
+  double* v() const { return L().vec; }                                          // L^-1 (y - mu)
+  double* alpha() const { return lane == 0 ? c->alpha : L().vec + c->np; }       // K^-1 (y - mu)
+  double* resid() const { return L().vec + 2 * c->np; }                          // y - mu: spent after the forward sweep
+  double* slot2() const { return resid(); }                                      // ... then diag K^-1, or g_m o alpha
+  double* mu() const { return L().vec + 3 * c->np; }
+  // the four leave-one-out vectors in front of the contraction's partial sums (LN_LOO)
+  double* loo_diag() const { return L().gws; }
+  double* loo_c1() const { return L().gws + c->np; }
+  double* loo_sc2() const { return L().gws + 2 * c->np; }
+  double* loo_p() const { return L().gws + 3 * c->np; }
+  double* partial(bool behind_loo) const { return L().gws + (behind_loo ? 4 * c->np : 0); }
+  // the contraction's results: n_theta + 1 values (n_theta <= GPMI_MAX_SUM (GPMI_MAX_D + 2)), on the host after lane_collect
+  double* gout() const { return L().red + 16; }
+  const double* h_gout() const { return L().h_red + 16; }
+};
+
+// what fills L.A before the factorisation
+struct LaneBuild {
+  const CovParams* p;
+  const MixEval* mix;
+  const double* dense;  // n x n on the host (a plugin covariance)
+  static LaneBuild kernels(const CovParams& cp) { return {&cp, nullptr, nullptr}; }
+  static LaneBuild mixture(const MixEval& mx) { return {nullptr, &mx, nullptr}; }
+  static LaneBuild from_host(const double* K_host) { return {nullptr, nullptr, K_host}; }
+};
+
+// The stages every single-evaluation entry point shares: mu upload, build, factorisation, forward sweep and reduction
+// (lane_forward); then [backward sweep -> alpha()], [L^-T -> B2], [K^-1 = B2 B2^T, lower tiles of A], [mirror]
+// (lane_solves), the bracketed ones as `steps` says.  LN_FIT_SCHEDULE: gpmi_fit's - the inverse blocks of the predict
+// built beside the sweeps.  LN_LOO: room for the leave-one-out vectors.  n_theta >= 0: room for the contraction's partial
+// sums.  The lane, its second matrix and L.gws are allocated here as the steps need them (lane_prepare).
+enum : unsigned { LN_BACKWARD = 1, LN_INVERSE = 2, LN_SYRK = 4, LN_MIRROR = 8, LN_LOO = 16, LN_FIT_SCHEDULE = 32 };
+int lane_prepare(const LaneEval& ev, unsigned steps, int n_theta);
+int lane_forward(const LaneEval& ev, const LaneBuild& b, unsigned steps, const double* mu_host, int n_theta = -1);
+int lane_solves(const LaneEval& ev, unsigned steps);
+inline int lane_stages(const LaneEval& ev, const LaneBuild& b, unsigned steps, const double* mu_host, int n_theta = -1) {
+  if (int rc = lane_forward(ev, b, steps, mu_host, n_theta)) return rc;
+  return lane_solves(ev, steps);
+}
+// behind lane_stages(.., LN_BACKWARD | LN_INVERSE | LN_LOO): diag K^-1; with want_p K^-1 in full, the leave-one-out
+// vectors and p = K^-1 c1; with want_M also M = K^-1 diag(c2) K^-1 into A (lower tiles; both triangles with mirror_M)
+void lane_loo_middle(const LaneEval& ev, bool want_p, bool want_M, bool mirror_M);
+
+// n values of a device vector for the caller
+struct LaneVec {
+  double* host;
+  const double* dev;
+};
+// The end of an evaluation: copies of red[0..1] (if `what` asks for a value), info, n_gout values of gout() and the
+// vectors whose host pointer is not null; the sync; the info check.  *value: sum ln L_ii (LC_LOGDET; value may be null),
+// -1/2 v.v - sum ln L_ii as it is (LC_LML_RAW), or with -1e50 for a matrix that did not factorise (LC_LML:
+// regression.py:539-542); what = 0: none.
+enum : unsigned { LC_LOGDET = 1, LC_LML_RAW = 2, LC_LML = 4 };
+int lane_collect(const LaneEval& ev, unsigned what, int n_gout, std::initializer_list<LaneVec> vecs, double* value, int* info);
+// alpha and diag K^-1 of one evaluation (gpmi_loo_terms, gpmi_loo_terms_mix): lane_stages, the row norms of L^-T, lane_collect
+int lane_loo_terms(const LaneEval& ev, const LaneBuild& b, const double* mu_host, double* alpha_out, double* ikdiag, int* info);
+
+// ---- the fitted lane's queries ----
+// The 2048-row chunk loop of the predicts: fill(m0, mc, mp) leaves the chunk's cross-covariance in c->Q; the row dots
+// with alpha go to mu_out, sumsq_base - |L^-1 k|^2 to ss_out (each if not null).
+template <class Fill>
+int predict_rows(gpmi_ctx* c, int64_t m, Fill&& fill, double sumsq_base, double* mu_out, double* ss_out) {
+  Lane& L = c->lanes[0];
+  hipStream_t s = L.stream;
+  const int64_t chunk = 2048;
+  for (int64_t m0 = 0; m0 < m; m0 += chunk) {
+    const int64_t mc = (m - m0 < chunk) ? m - m0 : chunk;
+    const int64_t mp = round_up(mc, GPMI_NB);
+    if (int rc = ensure_query_ws(c, mp)) return rc;
+    if (int rc = fill(m0, mc, mp)) return rc;
+    double* mu_dev = c->pvec;
+    double* ss_dev = c->pvec + mp;
+    if (mu_out) launch_rows_dot(s, c->Q, c->ld, mp, c->np, c->alpha, mu_dev);
+    if (ss_out) {
+      if (int rc = ensure_inv2(c, L, s)) return rc;
+      trsm_rows_forward(c, s, L.A, c->np, c->ld, L.inv2, c->Q, mp, false, c->Q2, nullptr);
+      launch_rows_sumsq(s, c->Q2, c->ld, mp, c->np, sumsq_base, ss_dev);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (mu_out) HIPCHK(c, hipMemcpyAsync(mu_out + m0, mu_dev, sizeof(double) * mc, hipMemcpyDeviceToHost, s));
+    if (ss_out) HIPCHK(c, hipMemcpyAsync(ss_out + m0, ss_dev, sizeof(double) * mc, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+  }
+  return GPMI_OK;
+}
+
+// Posterior mean and covariance at m points (mp padded): fill_cross() leaves the cross-covariance in c->Q; its row dots
+// with alpha go to c->pvec (and to mu_out on the host, if not null); with Sigma != nullptr: Q2 = Q L^-T, fill_qq() leaves
+// K_qq in Sigma (leading dimension ldq), Sigma <- Sigma - Q2 Q2^T.  Enqueued on lane 0's stream: the caller synchronises.
+template <class Cross, class Qq>
+int posterior_sigma(gpmi_ctx* c, Cross&& fill_cross, Qq&& fill_qq, int64_t m, int64_t mp, double* mu_out, double* Sigma,
+                    int64_t ldq) {
+  Lane& L = c->lanes[0];
+  hipStream_t s = L.stream;
+  if (int rc = fill_cross()) return rc;
+  launch_rows_dot(s, c->Q, c->ld, mp, c->np, c->alpha, c->pvec);
+  if (mu_out) HIPCHK(c, hipMemcpyAsync(mu_out, c->pvec, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+  if (Sigma) {
+    if (int rc = ensure_inv2(c, L, s)) return rc;
+    trsm_rows_forward(c, s, L.A, c->np, c->ld, L.inv2, c->Q, mp, false, c->Q2, nullptr);
+    fill_qq();
+    launch_gemm_nt(s, TILES_RECT, OP_SUB, Sigma, ldq, c->Q2, c->ld, c->Q2, c->ld, (int)(mp / GPMI_NB), (int)(mp / GPMI_NB),
+                   (int)c->np);
+  }
+  HIPCHK(c, hipGetLastError());
+  return GPMI_OK;
+}
+// posterior_sigma with the fitted kernel (or sum) at the m points pts of the host (gpmi_posterior, gpmi_posterior_draws)
+int kernel_posterior_sigma(gpmi_ctx* c, const double* pts, int64_t m, int64_t mp, double* mu_out, double* Sigma, int64_t ldq);

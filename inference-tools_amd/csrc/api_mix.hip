@@ -1,6 +1,6 @@
 // C-ABI of libgpmi (include/gpmi.h): mixture covariance (ChangePoint) and per-point noise hyper-parameters (HeteroscedasticNoise).
 // (split from api.hip in round 4; the handle, the lanes and the helpers these entry points are built from: api.hip,
-// api_internal.h)
+// api_internal.h; the pipeline of the single evaluations: api_single.hip)
 #include "api_internal.h"
 
 // ---- mixture covariance (ChangePoint) -------------------------------------------------------------------
@@ -42,13 +42,24 @@ int ensure_q3(gpmi_ctx* c) {
   return GPMI_OK;
 }
 
-// c->Q (mp x ld) = sum_m diag(gq_m) K_m(pts, x) diag(g_m); gq_dev: nk x mp device weights of the query points
-void build_mix_cross(gpmi_ctx* c, hipStream_t s, const double* gq_dev, int64_t mc, int64_t mp) {
-  for (int m = 0; m < c->mix_nk; ++m) {
-    launch_kbuild_cross(s, c->mix_p[m], c->pts, mc, mp, c->x, c->n, c->np, c->Q3, c->ld);
-    launch_scale_add(s, c->Q, c->ld, c->Q3, c->ld, gq_dev + (int64_t)m * mp, c->mix_g + (int64_t)m * c->np, mp,
-                     c->np, m > 0);
+// Rows [m0, m0 + mc) of the m query points and of their nk x m weights gq_host to the device (the weights to gq_dev =
+// c->pvec + 2 mp: nk x mp, zero-padded; pvec holds mp (2 + 2 d + d^2 + 4) doubles), then
+// c->Q (mp x ld) = sum_m diag(gq_m) K_m(pts, x) diag(g_m)
+int upload_and_build_mix_cross(gpmi_ctx* c, const double* pts, const double* gq_host, int64_t m, int64_t m0, int64_t mc,
+                               int64_t mp) {
+  hipStream_t s = c->lanes[0].stream;
+  if (int rc = ensure_q3(c)) return rc;
+  double* gq_dev = c->pvec + 2 * mp;
+  HIPCHK(c, hipMemsetAsync(gq_dev, 0, sizeof(double) * c->mix_nk * mp, s));
+  HIPCHK(c, hipMemcpyAsync(c->pts, pts + m0 * c->d, sizeof(double) * mc * c->d, hipMemcpyHostToDevice, s));
+  for (int k = 0; k < c->mix_nk; ++k)
+    HIPCHK(c, hipMemcpyAsync(gq_dev + (int64_t)k * mp, gq_host + (int64_t)k * m + m0, sizeof(double) * mc,
+                             hipMemcpyHostToDevice, s));
+  for (int k = 0; k < c->mix_nk; ++k) {
+    launch_kbuild_cross(s, c->mix_p[k], c->pts, mc, mp, c->x, c->n, c->np, c->Q3, c->ld);
+    launch_scale_add(s, c->Q, c->ld, c->Q3, c->ld, gq_dev + (int64_t)k * mp, c->mix_g + (int64_t)k * c->np, mp, c->np, k > 0);
   }
+  return GPMI_OK;
 }
 
 }  // namespace
@@ -62,25 +73,16 @@ int gpmi_fit_mix(gpmi_ctx* c, int nk, const int* kernels, const double* thetas, 
   KParams ps[GPMI_MAX_MIX];
   if (int rc = mix_prepare(c, nk, kernels, thetas, n_thetas, g_host, ps)) return rc;
   ARGCHK(c, mu != nullptr, "mu is NULL");
-  Lane& L = c->lanes[0];
-  hipStream_t s = L.stream;
-  double* mu_dev = L.vec + 3 * c->np;
+  const LaneEval ev(c, 0);
   const MixEval mx{nk, ps, c->mix_g, extra_diag, c->mix_scratch, c->mix_zero};
-  HIPCHK(c, hipMemcpyAsync(mu_dev, mu, sizeof(double) * c->n, hipMemcpyHostToDevice, s));
-  if (int rc = enqueue_factor_and_forward(c, L, CovParams(ps[0]), mu_dev, 0.0, 0, true, &mx)) return rc;
-  trsv_backward(c, s, L.A, c->np, c->ld, L.invD, L.vec, c->alpha, L.info);
-  HIPCHK(c, hipMemcpyAsync(L.h_red, L.red, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(L.h_info, L.info, sizeof(int), hipMemcpyDeviceToHost, s));
-  if (alpha_out)
-    HIPCHK(c, hipMemcpyAsync(alpha_out, c->alpha, sizeof(double) * c->n, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  if (logdet_out) *logdet_out = L.h_red[1];
-  INFOCHK(c, L.h_info[0]);
-  if (info) *info = L.h_info[0];
+  if (int rc = lane_stages(ev, LaneBuild::mixture(mx), LN_BACKWARD, mu)) return rc;
+  int inf = 0;
+  if (int rc = lane_collect(ev, LC_LOGDET, 0, {{alpha_out, ev.alpha()}}, logdet_out, &inf)) return rc;
+  if (info) *info = inf;
   c->mix_nk = nk;
   for (int m = 0; m < nk; ++m) c->mix_p[m] = ps[m];
   c->fit_params = CovParams(ps[0]);
-  c->fitted = (L.h_info[0] == 0);
+  c->fitted = (inf == 0);
   return GPMI_OK;
 }
 
@@ -88,25 +90,15 @@ int gpmi_lml_mix(gpmi_ctx* c, int nk, const int* kernels, const double* thetas, 
                  const double* g_host, double extra_diag, const double* mu, double* lml, int* info) {
   if (!c) return GPMI_ERR_ARG;
   KParams ps[GPMI_MAX_MIX];
-  if (int rc = ensure_lanes(c, 2)) return rc;
   // the weights of a fitted mixture live in the same device buffer: an evaluation at other hyper-parameters
   // invalidates them for gpmi_predict_mix until the next gpmi_fit_mix (the host wrapper re-fits lazily)
   if (int rc = mix_prepare(c, nk, kernels, thetas, n_thetas, g_host, ps)) return rc;
   ARGCHK(c, mu && lml, "mu / lml is NULL");
   c->fitted = false;
-  Lane& L = c->lanes[1];
-  hipStream_t s = L.stream;
-  double* mu_dev = L.vec + 3 * c->np;
+  const LaneEval ev(c, 1);
   const MixEval mx{nk, ps, c->mix_g, extra_diag, c->mix_scratch, c->mix_zero};
-  HIPCHK(c, hipMemcpyAsync(mu_dev, mu, sizeof(double) * c->n, hipMemcpyHostToDevice, s));
-  if (int rc = enqueue_factor_and_forward(c, L, CovParams(ps[0]), mu_dev, 0.0, 0, true, &mx)) return rc;
-  HIPCHK(c, hipMemcpyAsync(L.h_red, L.red, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(L.h_info, L.info, sizeof(int), hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  INFOCHK(c, L.h_info[0]);
-  if (info) *info = L.h_info[0];
-  *lml = (L.h_info[0] == 0) ? (-0.5 * L.h_red[0] - L.h_red[1]) : -1e50;
-  return GPMI_OK;
+  if (int rc = lane_stages(ev, LaneBuild::mixture(mx), 0, mu)) return rc;
+  return lane_collect(ev, LC_LML, 0, {}, lml, info);
 }
 
 int gpmi_lml_grad_mix(gpmi_ctx* c, int nk, const int* kernels, const double* thetas, const int* n_thetas,
@@ -114,39 +106,32 @@ int gpmi_lml_grad_mix(gpmi_ctx* c, int nk, const int* kernels, const double* the
                       double* grad_thetas, double* hrows, double* alpha_out, int* info) {
   if (!c) return GPMI_ERR_ARG;
   KParams ps[GPMI_MAX_MIX];
-  if (int rc = ensure_lanes(c, 2)) return rc;
   if (int rc = mix_prepare(c, nk, kernels, thetas, n_thetas, g_host, ps)) return rc;
   ARGCHK(c, mu && lml && grad_thetas && hrows, "mu / lml / grad_thetas / hrows is NULL");
   c->fitted = false;
-  Lane& L = c->lanes[1];
-  if (int rc = ensure_second_matrix(c, L)) return rc;
+  const LaneEval ev(c, 1);
   int max_nt = 0;
   for (int m = 0; m < nk; ++m) max_nt = n_thetas[m] > max_nt ? n_thetas[m] : max_nt;
-  if (int rc = grow(c, L.gws, L.gws_doubles, grad_ws_doubles(c->np, max_nt), sizeof(double))) return rc;
-  hipStream_t s = L.stream;
-  double* mu_dev = L.vec + 3 * c->np;
-  double* alpha_dev = L.vec + c->np;
-  double* ua = L.vec + 2 * c->np;  // g_m o alpha
-  double* gout = L.red + 16;       // (n_theta_m + 1) values per sub-kernel, consecutive
   // row sums (nk x np, or nk x 2 x np with the caller's own weights hw behind them): the scratch matrix is free once
   // K is factorised
   const int nrow = hw_host ? 2 : 1;
   double* hdev = c->mix_scratch;
   double* wdev = c->mix_scratch + (int64_t)2 * GPMI_MAX_MIX * c->np;
   const MixEval mx{nk, ps, c->mix_g, extra_diag, c->mix_scratch, c->mix_zero};
-  HIPCHK(c, hipMemcpyAsync(mu_dev, mu, sizeof(double) * c->n, hipMemcpyHostToDevice, s));
-  if (int rc = enqueue_factor_and_forward(c, L, CovParams(ps[0]), mu_dev, 0.0, 0, true, &mx)) return rc;
+  // K^-1 = L^-T L^-1, lower tiles over L, then both triangles (it is read row-wise below)
+  const unsigned steps = LN_BACKWARD | LN_INVERSE | LN_SYRK | LN_MIRROR;
+  if (int rc = lane_forward(ev, LaneBuild::mixture(mx), steps, mu, max_nt)) return rc;
+  Lane& L = ev.L();
+  hipStream_t s = L.stream;
+  double* alpha_dev = ev.alpha();
+  double* ua = ev.slot2();     // g_m o alpha
+  double* gout = ev.gout();    // (n_theta_m + 1) values per sub-kernel, consecutive
   if (hw_host) {
     HIPCHK(c, hipMemsetAsync(wdev, 0, sizeof(double) * 2 * nk * c->np, s));
     HIPCHK(c, hipMemcpy2DAsync(wdev, sizeof(double) * c->np, hw_host, sizeof(double) * c->n, sizeof(double) * c->n,
                                (size_t)2 * nk, hipMemcpyHostToDevice, s));
   }
-  trsv_backward(c, s, L.A, c->np, c->ld, L.invD, L.vec, alpha_dev, L.info);
-  // K^-1 = L^-T L^-1, lower tiles over L, then both triangles (it is read row-wise below)
-  if (int rc = enqueue_inverse_factor(c, L, L)) return rc;
-  launch_gemm(s, TILES_LOWER, OP_ASSIGN, false, 1, L.A, c->ld, L.B2, c->ld, L.B2, c->ld,
-              (int)(c->np / GPMI_NB), (int)(c->np / GPMI_NB), (int)c->np);
-  launch_mirror_lower(s, L.A, c->ld, c->np);
+  if (int rc = lane_solves(ev, steps)) return rc;
   int goff = 0;
   for (int m = 0; m < nk; ++m) {
     const double* gm = c->mix_g + (int64_t)m * c->np;
@@ -154,7 +139,7 @@ int gpmi_lml_grad_mix(gpmi_ctx* c, int nk, const int* kernels, const double* the
     // the scaled inverse with u = v = g_m o alpha
     launch_scale_add(s, L.B2, c->ld, L.A, c->ld, gm, gm, c->np, c->np, false);
     launch_vec_mul(s, gm, alpha_dev, ua, c->np);
-    launch_lml_grad(s, ps[m], n_thetas[m], c->x, c->n, c->np, L.B2, c->ld, ua, ua, L.gws, gout + goff);
+    launch_lml_grad(s, ps[m], n_thetas[m], c->x, c->n, c->np, L.B2, c->ld, ua, ua, ev.partial(false), gout + goff);
     goff += n_thetas[m] + 1;
     // window parameters: h_m(i) = sum_j Q_ij K_m,ij g_m(j)  (the host contracts it with d g_m / d phi)
     KParams pm = ps[m];
@@ -168,24 +153,17 @@ int gpmi_lml_grad_mix(gpmi_ctx* c, int nk, const int* kernels, const double* the
       launch_mix_rowsum(s, L.A, L.B2, c->ld, alpha_dev, gm, hdev + (int64_t)m * c->np, c->n);
   }
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(L.h_red, L.red, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(L.h_red + 16, gout, sizeof(double) * goff, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(L.h_info, L.info, sizeof(int), hipMemcpyDeviceToHost, s));
   for (int row = 0; row < nk * nrow; ++row)
     HIPCHK(c, hipMemcpyAsync(hrows + (int64_t)row * c->n, hdev + (int64_t)row * c->np, sizeof(double) * c->n,
                              hipMemcpyDeviceToHost, s));
-  if (alpha_out) HIPCHK(c, hipMemcpyAsync(alpha_out, alpha_dev, sizeof(double) * c->n, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  *lml = -0.5 * L.h_red[0] - L.h_red[1];
+  const int rc = lane_collect(ev, LC_LML_RAW, goff, {{alpha_out, alpha_dev}}, lml, info);
   goff = 0;
   int o = 0;
   for (int m = 0; m < nk; ++m) {
-    for (int j = 0; j < n_thetas[m]; ++j) grad_thetas[o++] = L.h_red[16 + goff + j];
+    for (int j = 0; j < n_thetas[m]; ++j) grad_thetas[o++] = ev.h_gout()[goff + j];
     goff += n_thetas[m] + 1;
   }
-  INFOCHK(c, L.h_info[0]);
-  if (info) *info = L.h_info[0];
-  return GPMI_OK;
+  return rc;
 }
 
 // gpmi_lml_grad_mix for T hyper-parameter vectors at once (round 4).  For N <= 4096 the evaluations advance in lockstep:
@@ -357,31 +335,11 @@ int gpmi_loo_terms_mix(gpmi_ctx* c, int nk, const int* kernels, const double* th
                        double* ikdiag, int* info) {
   if (!c) return GPMI_ERR_ARG;
   KParams ps[GPMI_MAX_MIX];
-  if (int rc = ensure_lanes(c, 2)) return rc;
   if (int rc = mix_prepare(c, nk, kernels, thetas, n_thetas, g_host, ps)) return rc;
   ARGCHK(c, mu && alpha_out && ikdiag, "mu / alpha / ikdiag is NULL");
   c->fitted = false;
-  Lane& L = c->lanes[1];
-  if (int rc = ensure_second_matrix(c, L)) return rc;
-  hipStream_t s = L.stream;
-  double* mu_dev = L.vec + 3 * c->np;
-  double* alpha_dev = L.vec + c->np;
-  double* diag_dev = L.vec + 2 * c->np;
   const MixEval mx{nk, ps, c->mix_g, extra_diag, c->mix_scratch, c->mix_zero};
-  HIPCHK(c, hipMemcpyAsync(mu_dev, mu, sizeof(double) * c->n, hipMemcpyHostToDevice, s));
-  if (int rc = enqueue_factor_and_forward(c, L, CovParams(ps[0]), mu_dev, 0.0, 0, true, &mx)) return rc;
-  trsv_backward(c, s, L.A, c->np, c->ld, L.invD, L.vec, alpha_dev, L.info);
-  if (int rc = enqueue_inverse_factor(c, L, L)) return rc;
-  launch_rows_sumsq(s, L.B2, c->ld, c->np, c->np, 0.0, diag_dev);  // -diag(K^-1): squared row norms of L^-T
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(L.h_info, L.info, sizeof(int), hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(alpha_out, alpha_dev, sizeof(double) * c->n, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(ikdiag, diag_dev, sizeof(double) * c->n, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  for (int64_t i = 0; i < c->n; ++i) ikdiag[i] = -ikdiag[i];
-  INFOCHK(c, L.h_info[0]);
-  if (info) *info = L.h_info[0];
-  return GPMI_OK;
+  return lane_loo_terms(LaneEval(c, 1), LaneBuild::mixture(mx), mu, alpha_out, ikdiag, info);
 }
 
 int gpmi_predict_mix(gpmi_ctx* c, const double* pts, int64_t m, const double* gq_host, double* mu_out,
@@ -390,37 +348,8 @@ int gpmi_predict_mix(gpmi_ctx* c, const double* pts, int64_t m, const double* gq
   ARGCHK(c, c->fitted && c->mix_nk > 0, "gpmi_predict_mix needs a successful gpmi_fit_mix");
   ARGCHK(c, pts && gq_host && m > 0, "NULL argument or m <= 0");
   if (int rc = set_device(c)) return rc;
-  Lane& L = c->lanes[0];
-  hipStream_t s = L.stream;
-  const int64_t chunk = 2048;
-  const int nk = c->mix_nk;
-  for (int64_t m0 = 0; m0 < m; m0 += chunk) {
-    const int64_t mc = (m - m0 < chunk) ? m - m0 : chunk;
-    const int64_t mp = round_up(mc, GPMI_NB);
-    if (int rc = ensure_query_ws(c, mp)) return rc;
-    if (int rc = ensure_q3(c)) return rc;
-    double* gq_dev = c->pvec + 2 * mp;  // nk x mp  (pvec holds mp (2 + 2 d + d^2 + 4) doubles)
-    HIPCHK(c, hipMemsetAsync(gq_dev, 0, sizeof(double) * nk * mp, s));
-    HIPCHK(c, hipMemcpyAsync(c->pts, pts + m0 * c->d, sizeof(double) * mc * c->d, hipMemcpyHostToDevice, s));
-    for (int k = 0; k < nk; ++k)
-      HIPCHK(c, hipMemcpyAsync(gq_dev + (int64_t)k * mp, gq_host + (int64_t)k * m + m0, sizeof(double) * mc,
-                               hipMemcpyHostToDevice, s));
-    build_mix_cross(c, s, gq_dev, mc, mp);
-    double* mu_dev = c->pvec;
-    double* var_dev = c->pvec + mp;
-    if (mu_out) launch_rows_dot(s, c->Q, c->ld, mp, c->np, c->alpha, mu_dev);
-    if (negsumsq_out) {
-      if (int rc = ensure_inv2(c, L, s)) return rc;
-      trsm_rows_forward(c, s, L.A, c->np, c->ld, L.inv2, c->Q, mp, false, c->Q2, nullptr);
-      launch_rows_sumsq(s, c->Q2, c->ld, mp, c->np, 0.0, var_dev);  // -|L^-1 k|^2; the host adds K_qq[0, 0]
-    }
-    HIPCHK(c, hipGetLastError());
-    if (mu_out) HIPCHK(c, hipMemcpyAsync(mu_out + m0, mu_dev, sizeof(double) * mc, hipMemcpyDeviceToHost, s));
-    if (negsumsq_out)
-      HIPCHK(c, hipMemcpyAsync(negsumsq_out + m0, var_dev, sizeof(double) * mc, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-  }
-  return GPMI_OK;
+  auto fill = [&](int64_t m0, int64_t mc, int64_t mp) { return upload_and_build_mix_cross(c, pts, gq_host, m, m0, mc, mp); };
+  return predict_rows(c, m, fill, 0.0, mu_out, negsumsq_out);  // -|L^-1 k|^2; the host adds K_qq[0, 0]
 }
 
 int gpmi_posterior_mix(gpmi_ctx* c, const double* pts, int64_t m, const double* gq_host, double* mu_out,
@@ -429,49 +358,28 @@ int gpmi_posterior_mix(gpmi_ctx* c, const double* pts, int64_t m, const double* 
   ARGCHK(c, c->fitted && c->mix_nk > 0, "gpmi_posterior_mix needs a successful gpmi_fit_mix");
   ARGCHK(c, pts && gq_host && m > 0, "NULL argument or m <= 0");
   if (int rc = set_device(c)) return rc;
-  Lane& L = c->lanes[0];
-  hipStream_t s = L.stream;
-  const int nk = c->mix_nk;
-  const int64_t mp = round_up(m, GPMI_NB);
+  hipStream_t s = c->lanes[0].stream;
+  const int64_t mp = round_up(m, GPMI_NB), ldq = mp + 32;
   if (int rc = ensure_query_ws(c, mp)) return rc;
-  if (int rc = ensure_q3(c)) return rc;
-  double* gq_dev = c->pvec + 2 * mp;
-  HIPCHK(c, hipMemsetAsync(gq_dev, 0, sizeof(double) * nk * mp, s));
-  HIPCHK(c, hipMemcpyAsync(c->pts, pts, sizeof(double) * m * c->d, hipMemcpyHostToDevice, s));
-  for (int k = 0; k < nk; ++k)
-    HIPCHK(c, hipMemcpyAsync(gq_dev + (int64_t)k * mp, gq_host + (int64_t)k * m, sizeof(double) * m,
-                             hipMemcpyHostToDevice, s));
-  build_mix_cross(c, s, gq_dev, m, mp);
-  double* mu_dev = c->pvec;
-  launch_rows_dot(s, c->Q, c->ld, mp, c->np, c->alpha, mu_dev);
-  if (mu_out) HIPCHK(c, hipMemcpyAsync(mu_out, mu_dev, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+  // (an error return below may leave work on these in flight: hipFree waits for the device before it releases)
+  DevBuf Sigma, tmp;
   if (cov_out) {
-    const int64_t ldq = mp + 32;
-    double *Kqq = nullptr, *tmp = nullptr;
-    HIPCHK(c, hipMalloc(&Kqq, sizeof(double) * mp * ldq));
-    hipError_t e = hipMalloc(&tmp, sizeof(double) * mp * ldq);
-    if (e == hipSuccess) {
-      if (int rc = ensure_inv2(c, L, s)) {
-        (void)hipFree(Kqq);
-        (void)hipFree(tmp);
-        return rc;
-      }
-      trsm_rows_forward(c, s, L.A, c->np, c->ld, L.inv2, c->Q, mp, false, c->Q2, nullptr);
-      // K_qq = sum_m diag(gq_m) K_m(pts, pts) diag(gq_m): no jitter, no noise (covariance.py:529-544)
-      for (int k = 0; k < nk; ++k) {
-        launch_kbuild_cross(s, c->mix_p[k], c->pts, m, mp, c->pts, m, mp, tmp, ldq);
-        launch_scale_add(s, Kqq, ldq, tmp, ldq, gq_dev + (int64_t)k * mp, gq_dev + (int64_t)k * mp, mp, mp, k > 0);
-      }
-      launch_gemm_nt(s, TILES_RECT, OP_SUB, Kqq, ldq, c->Q2, c->ld, c->Q2, c->ld, (int)(mp / GPMI_NB),
-                     (int)(mp / GPMI_NB), (int)c->np);
-      e = hipMemcpy2DAsync(cov_out, sizeof(double) * m, Kqq, sizeof(double) * ldq, sizeof(double) * m, m,
-                           hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess) e = hipStreamSynchronize(s);
-    }
-    (void)hipFree(Kqq);
-    if (tmp) (void)hipFree(tmp);
-    HIPCHK(c, e);
+    HIPCHK(c, hipMalloc(&Sigma.p, sizeof(double) * mp * ldq));
+    HIPCHK(c, hipMalloc(&tmp.p, sizeof(double) * mp * ldq));
   }
+  auto cross = [&] { return upload_and_build_mix_cross(c, pts, gq_host, m, 0, m, mp); };
+  // K_qq = sum_m diag(gq_m) K_m(pts, pts) diag(gq_m): no jitter, no noise (covariance.py:529-544)
+  auto qq = [&] {
+    for (int k = 0; k < c->mix_nk; ++k) {
+      const double* gq = c->pvec + 2 * mp + (int64_t)k * mp;
+      launch_kbuild_cross(s, c->mix_p[k], c->pts, m, mp, c->pts, m, mp, tmp.as<double>(), ldq);
+      launch_scale_add(s, Sigma.as<double>(), ldq, tmp.as<double>(), ldq, gq, gq, mp, mp, k > 0);
+    }
+  };
+  if (int rc = posterior_sigma(c, cross, qq, m, mp, mu_out, Sigma.as<double>(), ldq)) return rc;
+  if (cov_out)
+    HIPCHK(c, hipMemcpy2DAsync(cov_out, sizeof(double) * m, Sigma.p, sizeof(double) * ldq, sizeof(double) * m, m,
+                               hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   return GPMI_OK;
 }
@@ -497,8 +405,8 @@ int gpmi_lml_grad_qdiag(gpmi_ctx* c, double* qdiag) {
   ARGCHK(c, c->lanes.size() >= 2 && c->lanes[1].B2, "gpmi_lml_grad has not been called");
   if (int rc = set_device(c)) return rc;
   Lane& L = c->lanes[1];  // after gpmi_lml_grad: L.A = K^-1 (lower tiles), vec + np = alpha
-  double* out = L.vec + 2 * c->np;
-  launch_qdiag(L.stream, L.A, c->ld, L.vec + c->np, out, c->n);
+  double* out = LaneEval(c, 1).slot2();
+  launch_qdiag(L.stream, L.A, c->ld, LaneEval(c, 1).alpha(), out, c->n);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(qdiag, out, sizeof(double) * c->n, hipMemcpyDeviceToHost, L.stream));
   HIPCHK(c, hipStreamSynchronize(L.stream));

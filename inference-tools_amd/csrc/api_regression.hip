@@ -1,7 +1,7 @@
 // C-ABI of libgpmi (include/gpmi.h): the GpRegressor entry points - fit, likelihood (single, lockstep batches, asynchronous slots), likelihood
 // and leave-one-out gradients, predict, posterior, spatial gradients, covariance downloads.
 // (split from api.hip in round 4; the handle, the lanes and the helpers these entry points are built from: api.hip,
-// api_internal.h)
+// api_internal.h; the pipeline of the single evaluations: api_single.hip)
 #include "api_internal.h"
 
 extern "C" {
@@ -13,34 +13,23 @@ int gpmi_fit(gpmi_ctx* c, int kernel, const double* theta, int n_theta, double e
   if (int rc = make_cov(c, kernel, theta, n_theta, extra_diag, p)) return rc;
   ARGCHK(c, mu != nullptr, "mu is NULL");
   if (int rc = set_device(c)) return rc;
-  Lane& L = c->lanes[0];
-  hipStream_t s = L.stream;
-  double* mu_dev = L.vec + 3 * c->np;
-  const bool dbg = std::getenv("GPMI_DEBUG_TIMING") != nullptr;
-  const auto h0 = std::chrono::steady_clock::now();
-  HIPCHK(c, hipMemcpyAsync(mu_dev, mu, sizeof(double) * c->n, hipMemcpyHostToDevice, s));
-  if (int rc = enqueue_factor_and_forward(c, L, p, mu_dev, 0.0, 0, true, nullptr, true, c->alpha)) return rc;
-  const auto h1 = std::chrono::steady_clock::now();
-  // alpha = L^-T v  (c->alpha already holds the sweep's sentinel: enqueue_factor_and_forward, backward_out)
-  trsv_backward(c, s, L.A, c->np, c->ld, L.invD, L.vec, c->alpha, L.info, BatchShape(), true);
-  if (L.inv2_valid) HIPCHK(c, hipStreamWaitEvent(s, L.ev_main, 0));  // (the inverse blocks built beside the sweeps)
-  HIPCHK(c, hipMemcpyAsync(L.h_red, L.red, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(L.h_info, L.info, sizeof(int), hipMemcpyDeviceToHost, s));
-  if (alpha_out)
-    HIPCHK(c, hipMemcpyAsync(alpha_out, c->alpha, sizeof(double) * c->n, hipMemcpyDeviceToHost, s));
-  const auto h2 = std::chrono::steady_clock::now();
-  HIPCHK(c, hipStreamSynchronize(s));
-  if (dbg) {
-    const auto h3 = std::chrono::steady_clock::now();
+  LaneEval ev(c, 0);
+  LaneTimes t;
+  ev.times = &t;
+  t.start = std::chrono::steady_clock::now();
+  // alpha = L^-T v, the predict's inverse blocks beside the two sweeps
+  if (int rc = lane_stages(ev, LaneBuild::kernels(p), LN_BACKWARD | LN_FIT_SCHEDULE, mu)) return rc;
+  int inf = 0;
+  const int rc = lane_collect(ev, LC_LOGDET, 0, {{alpha_out, ev.alpha()}}, logdet_out, &inf);
+  if (std::getenv("GPMI_DEBUG_TIMING") && t.done != std::chrono::steady_clock::time_point()) {
     auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     std::fprintf(stderr, "[gpmi_fit] host enqueue factor+forward %.2f ms, backward+copies %.2f ms, final sync %.2f ms\n",
-                 ms(h0, h1), ms(h1, h2), ms(h2, h3));
+                 ms(t.start, t.forward), ms(t.forward, t.enqueued), ms(t.enqueued, t.done));
   }
-  if (logdet_out) *logdet_out = L.h_red[1];
-  INFOCHK(c, L.h_info[0]);
-  if (info) *info = L.h_info[0];
+  if (rc != GPMI_OK) return rc;
+  if (info) *info = inf;
   c->fit_params = p;
-  c->fitted = (L.h_info[0] == 0);
+  c->fitted = (inf == 0);
   return GPMI_OK;
 }
 
@@ -117,7 +106,7 @@ int gpmi_lml_batch(gpmi_ctx* c, int kernel, int64_t T, const double* thetas, int
     slot_of[(size_t)t] = slot;
     double* mu_dev = nullptr;
     if (mus) {
-      mu_dev = L.vec + 3 * c->np;
+      mu_dev = LaneEval(c, 1 + li).mu();
       HIPCHK(c, hipMemcpyAsync(mu_dev, mus + t * c->n, sizeof(double) * c->n,
                                hipMemcpyHostToDevice, L.stream));
     }
@@ -238,22 +227,14 @@ int gpmi_lml_batch_wait(gpmi_ctx* c, int slot, double* lml, int* info) {
   return GPMI_OK;
 }
 
-// the evaluation lane of the likelihood gradient with everything gpmi_lml_grad allocates lazily: the lane itself
-// (matrix, inverse blocks, streams - for a large problem the CU-masked pair), the second matrix, the contraction's
-// partial sums for n_theta parameters
-static int ensure_gradient_lane(gpmi_ctx* c, int n_theta) {
-  if (int rc = ensure_lanes(c, 2)) return rc;
-  Lane& L = c->lanes[1];
-  if (int rc = ensure_second_matrix(c, L)) return rc;
-  return grow(c, L.gws, L.gws_doubles, grad_ws_doubles(c->np, n_theta), sizeof(double));
-}
-
 int gpmi_prepare_gradient(gpmi_ctx* c, int n_theta) {
   if (!c) return GPMI_ERR_ARG;
   ARGCHK(c, c->n > 0, "gpmi_set_data has not been called");
   ARGCHK(c, n_theta >= 1 && n_theta <= GPMI_MAX_SUM * (GPMI_MAX_D + 2), "n_theta out of range");
   if (int rc = set_device(c)) return rc;
-  if (int rc = ensure_gradient_lane(c, n_theta)) return rc;
+  // everything gpmi_lml_grad allocates lazily: the lane itself (matrix, inverse blocks, streams - for a large problem the
+  // CU-masked pair), the second matrix, the contraction's partial sums for n_theta parameters
+  if (int rc = lane_prepare(LaneEval(c, 1), LN_INVERSE, n_theta)) return rc;
   HIPCHK(c, hipDeviceSynchronize());  // the allocations have happened when this returns
   return GPMI_OK;
 }
@@ -266,34 +247,14 @@ int gpmi_lml_grad(gpmi_ctx* c, int kernel, const double* theta, int n_theta, dou
   if (int rc = make_cov(c, kernel, theta, n_theta, extra_diag, p)) return rc;
   ARGCHK(c, mu && lml && grad_theta, "mu / lml / grad_theta is NULL");
   if (int rc = set_device(c)) return rc;
-  if (int rc = ensure_gradient_lane(c, n_theta)) return rc;
-  Lane& L = c->lanes[1];
-  hipStream_t s = L.stream;
-  double* mu_dev = L.vec + 3 * c->np;
-  double* alpha_dev = L.vec + c->np;
-  double* gout = L.red + 16;  // n_theta + 1 values (n_theta <= GPMI_MAX_SUM (GPMI_MAX_D + 2))
-  HIPCHK(c, hipMemcpyAsync(mu_dev, mu, sizeof(double) * c->n, hipMemcpyHostToDevice, s));
-  if (int rc = enqueue_factor_and_forward(c, L, p, mu_dev, 0.0, 0, true, nullptr, false, nullptr, L.B2)) return rc;
-  trsv_backward(c, s, L.A, c->np, c->ld, L.invD, L.vec, alpha_dev, L.info);
-  // K^-1 = L^-T L^-1 (regression.py:556-557), lower tiles, overwriting L
-  if (int rc = enqueue_inverse_factor(c, L, L)) return rc;
-  launch_gemm(s, TILES_LOWER, OP_ASSIGN, false, true, L.A, c->ld, L.B2, c->ld, L.B2, c->ld,
-              (int)(c->np / GPMI_NB), (int)(c->np / GPMI_NB), (int)c->np);
-  launch_lml_grad(s, p, n_theta, c->x, c->n, c->np, L.A, c->ld, alpha_dev, alpha_dev, L.gws, gout);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(L.h_red, L.red, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(L.h_red + 16, gout, sizeof(double) * (n_theta + 1),
-                           hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(L.h_info, L.info, sizeof(int), hipMemcpyDeviceToHost, s));
-  if (alpha_out)
-    HIPCHK(c, hipMemcpyAsync(alpha_out, alpha_dev, sizeof(double) * c->n, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  *lml = -0.5 * L.h_red[0] - L.h_red[1];
-  for (int j = 0; j < n_theta; ++j) grad_theta[j] = L.h_red[16 + j];
-  if (trace_q) *trace_q = L.h_red[16 + n_theta];
-  INFOCHK(c, L.h_info[0]);
-  if (info) *info = L.h_info[0];
-  return GPMI_OK;
+  const LaneEval ev(c, 1);
+  // K^-1 in the lower tiles only: the contraction reads no others
+  if (int rc = lane_stages(ev, LaneBuild::kernels(p), LN_BACKWARD | LN_INVERSE | LN_SYRK, mu, n_theta)) return rc;
+  launch_lml_grad(ev.stream(), p, n_theta, c->x, c->n, c->np, ev.L().A, c->ld, ev.alpha(), ev.alpha(), ev.partial(false), ev.gout());
+  const int rc = lane_collect(ev, LC_LML_RAW, n_theta + 1, {{alpha_out, ev.alpha()}}, lml, info);
+  for (int j = 0; j < n_theta; ++j) grad_theta[j] = ev.h_gout()[j];
+  if (trace_q) *trace_q = ev.h_gout()[n_theta];
+  return rc;
 }
 
 // noise_batch (T x n, host) / qdiag_out (T x n, host): the per-problem noise variances of HeteroscedasticNoise
@@ -498,36 +459,15 @@ int gpmi_predict(gpmi_ctx* c, const double* pts, int64_t m, double* mu_out, doub
          "gpmi_predict: the model was fitted with a caller-built covariance (gpmi_fit_dense) - use gpmi_predict_dense / gpmi_solve_rows");
   ARGCHK(c, pts && m > 0, "pts is NULL or m <= 0");
   if (int rc = set_device(c)) return rc;
-  Lane& L = c->lanes[0];
-  hipStream_t s = L.stream;
-  const int64_t chunk = 2048;
+  hipStream_t s = c->lanes[0].stream;
   const CovParams& p = c->fit_params;
-  for (int64_t m0 = 0; m0 < m; m0 += chunk) {
-    const int64_t mc = (m - m0 < chunk) ? m - m0 : chunk;
-    const int64_t mp = round_up(mc, GPMI_NB);
-    if (int rc = ensure_query_ws(c, mp)) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->pts, pts + m0 * c->d, sizeof(double) * mc * c->d,
-                             hipMemcpyHostToDevice, s));
-    {
-      ProfScope ps(c, s, GPMI_PROF_KBUILD, 0.0, 8.0 * mp * c->np);
-      launch_kbuild_cross(s, p, c->pts, mc, mp, c->x, c->n, c->np, c->Q, c->ld);
-    }
-    double* mu_dev = c->pvec;
-    double* var_dev = c->pvec + mp;
-    if (mu_out) launch_rows_dot(s, c->Q, c->ld, mp, c->np, c->alpha, mu_dev);
-    if (var_out) {
-      if (int rc = ensure_inv2(c, L, s)) return rc;
-      trsm_rows_forward(c, s, L.A, c->np, c->ld, L.inv2, c->Q, mp, false, c->Q2, nullptr);
-      launch_rows_sumsq(s, c->Q2, c->ld, mp, c->np, p.a2, var_dev);  // K_qq[0,0] = a^2 (regression.py:210)
-    }
-    HIPCHK(c, hipGetLastError());
-    if (mu_out)
-      HIPCHK(c, hipMemcpyAsync(mu_out + m0, mu_dev, sizeof(double) * mc, hipMemcpyDeviceToHost, s));
-    if (var_out)
-      HIPCHK(c, hipMemcpyAsync(var_out + m0, var_dev, sizeof(double) * mc, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-  }
-  return GPMI_OK;
+  auto fill = [&](int64_t m0, int64_t mc, int64_t mp) -> int {
+    HIPCHK(c, hipMemcpyAsync(c->pts, pts + m0 * c->d, sizeof(double) * mc * c->d, hipMemcpyHostToDevice, s));
+    ProfScope ps(c, s, GPMI_PROF_KBUILD, 0.0, 8.0 * mp * c->np);
+    launch_kbuild_cross(s, p, c->pts, mc, mp, c->x, c->n, c->np, c->Q, c->ld);
+    return GPMI_OK;
+  };
+  return predict_rows(c, m, fill, p.a2, mu_out, var_out);  // K_qq[0,0] = a^2 (regression.py:210)
 }
 
 extern "C++" {
@@ -693,35 +633,16 @@ int gpmi_posterior(gpmi_ctx* c, const double* pts, int64_t m, double* mu_out, do
          "gpmi_posterior: the model was fitted with a caller-built covariance (gpmi_fit_dense) - use gpmi_predict_dense / gpmi_solve_rows");
   ARGCHK(c, pts && m > 0, "pts is NULL or m <= 0");
   if (int rc = set_device(c)) return rc;
-  Lane& L = c->lanes[0];
-  hipStream_t s = L.stream;
-  const CovParams& p = c->fit_params;
-  const int64_t mp = round_up(m, GPMI_NB);
+  hipStream_t s = c->lanes[0].stream;
+  const int64_t mp = round_up(m, GPMI_NB), ldq = mp + 32;
   if (int rc = ensure_query_ws(c, mp)) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->pts, pts, sizeof(double) * m * c->d, hipMemcpyHostToDevice, s));
-  launch_kbuild_cross(s, p, c->pts, m, mp, c->x, c->n, c->np, c->Q, c->ld);
-  double* mu_dev = c->pvec;
-  launch_rows_dot(s, c->Q, c->ld, mp, c->np, c->alpha, mu_dev);
-  if (mu_out) HIPCHK(c, hipMemcpyAsync(mu_out, mu_dev, sizeof(double) * m, hipMemcpyDeviceToHost, s));
-  if (cov_out) {
-    double* Kqq = nullptr;
-    const int64_t ldq = mp + 32;
-    HIPCHK(c, hipMalloc(&Kqq, sizeof(double) * mp * ldq));
-    if (int rc = ensure_inv2(c, L, s)) {
-      (void)hipFree(Kqq);
-      return rc;
-    }
-    trsm_rows_forward(c, s, L.A, c->np, c->ld, L.inv2, c->Q, mp, false, c->Q2, nullptr);
-    launch_kbuild_cross(s, p, c->pts, m, mp, c->pts, m, mp, Kqq, ldq);  // no jitter (regression.py:441)
-    // Sigma = K_qq - Q^T Q with Q = L^-1 K_qx^T, i.e. rows of c->Q2 dotted pairwise
-    launch_gemm_nt(s, TILES_RECT, OP_SUB, Kqq, ldq, c->Q2, c->ld, c->Q2, c->ld, (int)(mp / GPMI_NB),
-                   (int)(mp / GPMI_NB), (int)c->np);
-    hipError_t e = hipMemcpy2DAsync(cov_out, sizeof(double) * m, Kqq, sizeof(double) * ldq,
-                                    sizeof(double) * m, m, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(Kqq);
-    HIPCHK(c, e);
-  }
+  // (an error return below may leave work on Sigma in flight: hipFree waits for the device before it releases)
+  DevBuf Sigma;
+  if (cov_out) HIPCHK(c, hipMalloc(&Sigma.p, sizeof(double) * mp * ldq));
+  if (int rc = kernel_posterior_sigma(c, pts, m, mp, mu_out, Sigma.as<double>(), ldq)) return rc;
+  if (cov_out)
+    HIPCHK(c, hipMemcpy2DAsync(cov_out, sizeof(double) * m, Sigma.p, sizeof(double) * ldq, sizeof(double) * m, m,
+                               hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   return GPMI_OK;
 }
@@ -834,27 +755,7 @@ int gpmi_loo_terms(gpmi_ctx* c, int kernel, const double* theta, int n_theta, do
   if (int rc = make_cov(c, kernel, theta, n_theta, extra_diag, p)) return rc;
   ARGCHK(c, mu && alpha_out && ikdiag, "mu / alpha / ikdiag is NULL");
   if (int rc = set_device(c)) return rc;
-  if (int rc = ensure_lanes(c, 2)) return rc;
-  Lane& L = c->lanes[1];
-  if (int rc = ensure_second_matrix(c, L)) return rc;
-  hipStream_t s = L.stream;
-  double* mu_dev = L.vec + 3 * c->np;
-  double* alpha_dev = L.vec + c->np;
-  double* diag_dev = L.vec + 2 * c->np;
-  HIPCHK(c, hipMemcpyAsync(mu_dev, mu, sizeof(double) * c->n, hipMemcpyHostToDevice, s));
-  if (int rc = enqueue_factor_and_forward(c, L, p, mu_dev, 0.0, 0, true, nullptr, false, nullptr, L.B2)) return rc;
-  trsv_backward(c, s, L.A, c->np, c->ld, L.invD, L.vec, alpha_dev, L.info);
-  if (int rc = enqueue_inverse_factor(c, L, L)) return rc;
-  launch_rows_sumsq(s, L.B2, c->ld, c->np, c->np, 0.0, diag_dev);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(L.h_info, L.info, sizeof(int), hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(alpha_out, alpha_dev, sizeof(double) * c->n, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(ikdiag, diag_dev, sizeof(double) * c->n, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  for (int64_t i = 0; i < c->n; ++i) ikdiag[i] = -ikdiag[i];
-  INFOCHK(c, L.h_info[0]);
-  if (info) *info = L.h_info[0];
-  return GPMI_OK;
+  return lane_loo_terms(LaneEval(c, 1), LaneBuild::kernels(p), mu, alpha_out, ikdiag, info);
 }
 
 int gpmi_loo_grad(gpmi_ctx* c, int kernel, const double* theta, int n_theta, double extra_diag,
@@ -865,52 +766,15 @@ int gpmi_loo_grad(gpmi_ctx* c, int kernel, const double* theta, int n_theta, dou
   if (int rc = make_cov(c, kernel, theta, n_theta, extra_diag, p)) return rc;
   ARGCHK(c, mu && alpha_out && ikdiag && p_out && grad_theta, "NULL argument");
   if (int rc = set_device(c)) return rc;
-  if (int rc = ensure_lanes(c, 2)) return rc;
-  Lane& L = c->lanes[1];
-  if (int rc = ensure_second_matrix(c, L)) return rc;
-  if (int rc = grow(c, L.gws, L.gws_doubles, grad_ws_doubles(c->np, n_theta) + 4 * c->np, sizeof(double))) return rc;
-  hipStream_t s = L.stream;
-  const int nt = (int)(c->np / GPMI_NB);
-  double* mu_dev = L.vec + 3 * c->np;
-  double* alpha_dev = L.vec + c->np;
-  double* diag_dev = L.gws;              // 4 extra vectors live in front of the partial sums
-  double* c1_dev = L.gws + c->np;
-  double* sc2_dev = L.gws + 2 * c->np;
-  double* p_dev = L.gws + 3 * c->np;
-  double* partial = L.gws + 4 * c->np;
-  double* gout = L.red + 16;
-  HIPCHK(c, hipMemcpyAsync(mu_dev, mu, sizeof(double) * c->n, hipMemcpyHostToDevice, s));
-  if (int rc = enqueue_factor_and_forward(c, L, p, mu_dev, 0.0, 0, true, nullptr, false, nullptr, L.B2)) return rc;
-  trsv_backward(c, s, L.A, c->np, c->ld, L.invD, L.vec, alpha_dev, L.info);
-  // K^-1 (full, both triangles) in A
-  if (int rc = enqueue_inverse_factor(c, L, L)) return rc;
-  launch_rows_sumsq(s, L.B2, c->ld, c->np, c->np, 0.0, diag_dev);  // = -diag(K^-1)
-  launch_gemm(s, TILES_LOWER, OP_ASSIGN, false, true, L.A, c->ld, L.B2, c->ld, L.B2, c->ld, nt, nt,
-              (int)c->np);
-  launch_mirror_lower(s, L.A, c->ld, c->np);
-  // diag_dev holds -diag: flip sign inside the vector kernel by passing it through a scaled copy
-  launch_negate(s, diag_dev, c->np);
-  launch_loo_vectors(s, alpha_dev, diag_dev, c1_dev, sc2_dev, c->n, c->np);
-  // p = K^-1 c1  (regression.py:512-513, 518-519 folded: c1^T K^-1 dK_j alpha = p^T dK_j alpha)
-  launch_rows_dot(s, L.A, c->ld, c->np, c->np, c1_dev, p_dev);
-  // M = K^-1 diag(c2) K^-1 = G G^T with G = K^-1 diag(sqrt c2); lower tiles, overwriting K^-1
-  launch_scale_columns(s, L.A, sc2_dev, L.B2, c->ld, c->np);
-  launch_gemm(s, TILES_LOWER, OP_ASSIGN, false, false, L.A, c->ld, L.B2, c->ld, L.B2, c->ld, nt, nt,
-              (int)c->np);
-  launch_lml_grad(s, p, n_theta, c->x, c->n, c->np, L.A, c->ld, p_dev, alpha_dev, partial, gout);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(L.h_red + 16, gout, sizeof(double) * (n_theta + 1), hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(L.h_info, L.info, sizeof(int), hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(alpha_out, alpha_dev, sizeof(double) * c->n, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(ikdiag, diag_dev, sizeof(double) * c->n, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(p_out, p_dev, sizeof(double) * c->n, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
+  const LaneEval ev(c, 1);
+  if (int rc = lane_stages(ev, LaneBuild::kernels(p), LN_BACKWARD | LN_INVERSE | LN_LOO, mu, n_theta)) return rc;
+  lane_loo_middle(ev, true, true, false);
+  launch_lml_grad(ev.stream(), p, n_theta, c->x, c->n, c->np, ev.L().A, c->ld, ev.loo_p(), ev.alpha(), ev.partial(true), ev.gout());
+  const int rc = lane_collect(ev, 0, n_theta + 1, {{alpha_out, ev.alpha()}, {ikdiag, ev.loo_diag()}, {p_out, ev.loo_p()}}, nullptr, info);
   // the contraction returns 1/2 sum Q o dK; the LOO gradient has no 1/2 (regression.py:513)
-  for (int j = 0; j < n_theta; ++j) grad_theta[j] = 2.0 * L.h_red[16 + j];
-  if (trace_q) *trace_q = L.h_red[16 + n_theta];
-  INFOCHK(c, L.h_info[0]);
-  if (info) *info = L.h_info[0];
-  return GPMI_OK;
+  for (int j = 0; j < n_theta; ++j) grad_theta[j] = 2.0 * ev.h_gout()[j];
+  if (trace_q) *trace_q = ev.h_gout()[n_theta];
+  return rc;
 }
 
 int gpmi_covariance(gpmi_ctx* c, int kernel, const double* theta, int n_theta, double extra_diag,
@@ -922,20 +786,16 @@ int gpmi_covariance(gpmi_ctx* c, int kernel, const double* theta, int n_theta, d
   if (int rc = set_device(c)) return rc;
   if (int rc = ensure_lanes(c, 2)) return rc;
   Lane& L = c->lanes[1];
-  double* noise = c->noise;
-  double* zeros = nullptr;
+  DevBuf zeros;  // (an error return below may leave the build reading it: hipFree waits for the device before it releases)
   if (!with_noise) {
-    HIPCHK(c, hipMalloc(&zeros, sizeof(double) * c->np));
-    HIPCHK(c, hipMemsetAsync(zeros, 0, sizeof(double) * c->np, L.stream));
-    noise = zeros;
+    HIPCHK(c, hipMalloc(&zeros.p, sizeof(double) * c->np));
+    HIPCHK(c, hipMemsetAsync(zeros.p, 0, sizeof(double) * c->np, L.stream));
   }
-  launch_kbuild_square(L.stream, p, c->x, c->n, c->np, noise, L.A, c->ld, false);
+  launch_kbuild_square(L.stream, p, c->x, c->n, c->np, with_noise ? c->noise : zeros.as<double>(), L.A, c->ld, false);
   if (with_noise && c->ycov) launch_add_full(L.stream, L.A, c->ld, c->ycov, c->n);
-  hipError_t e = hipMemcpy2DAsync(K_host, sizeof(double) * c->n, L.A, sizeof(double) * c->ld,
-                                  sizeof(double) * c->n, c->n, hipMemcpyDeviceToHost, L.stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(L.stream);
-  if (zeros) (void)hipFree(zeros);
-  HIPCHK(c, e);
+  HIPCHK(c, hipMemcpy2DAsync(K_host, sizeof(double) * c->n, L.A, sizeof(double) * c->ld, sizeof(double) * c->n, c->n,
+                             hipMemcpyDeviceToHost, L.stream));
+  HIPCHK(c, hipStreamSynchronize(L.stream));
   return GPMI_OK;
 }
 

@@ -187,24 +187,16 @@ int gpmi_posterior_draws(gpmi_ctx* c, const double* pts, int64_t m, double jitte
   if (info) *info = 0;
   Lane& L = c->lanes[0];
   hipStream_t s = L.stream;
-  const CovParams& p = c->fit_params;
   const int64_t mp = round_up(m, GPMI_NB), ldq = mp + 32;
   if (int rc = ensure_query_ws(c, mp)) return rc;
   DevBuf Sigma;
   HIPCHK(c, hipMalloc(&Sigma.p, sizeof(double) * mp * ldq));
   double* mu_dev = c->pvec;
   {
-    // mu and Sigma = K_qq - Q^T Q, launch for launch as gpmi_posterior
+    // mu and Sigma = K_qq - Q^T Q: the pipeline of gpmi_posterior
     ProfScope ps(c, s, GPMI_PROF_DRAWS_SIGMA, 2.0 * mp * mp * c->np + (double)mp * c->np * c->np, 8.0 * mp * (2.0 * c->np + mp));
-    HIPCHK(c, hipMemcpyAsync(c->pts, pts, sizeof(double) * m * c->d, hipMemcpyHostToDevice, s));
-    launch_kbuild_cross(s, p, c->pts, m, mp, c->x, c->n, c->np, c->Q, c->ld);
-    launch_rows_dot(s, c->Q, c->ld, mp, c->np, c->alpha, mu_dev);
-    if (int rc = ensure_inv2(c, L, s)) return rc;
-    trsm_rows_forward(c, s, L.A, c->np, c->ld, L.inv2, c->Q, mp, false, c->Q2, nullptr);
-    launch_kbuild_cross(s, p, c->pts, m, mp, c->pts, m, mp, Sigma.as<double>(), ldq);  // no jitter (regression.py:441)
-    launch_gemm_nt(s, TILES_RECT, OP_SUB, Sigma.as<double>(), ldq, c->Q2, c->ld, c->Q2, c->ld, (int)(mp / GPMI_NB),
-                   (int)(mp / GPMI_NB), (int)c->np);
-    HIPCHK(c, hipGetLastError());
+    // (an error return leaves at most the kernel build on Sigma in flight: hipFree waits for the device before it releases)
+    if (int rc = kernel_posterior_sigma(c, pts, m, mp, nullptr, Sigma.as<double>(), ldq)) return rc;
   }
   if (mu_out) HIPCHK(c, hipMemcpyAsync(mu_out, mu_dev, sizeof(double) * m, hipMemcpyDeviceToHost, s));
   const int rc = draws_tail(c, L, Sigma.as<double>(), ldq, m, mp, mu_dev, jitter_rel, n_draws, z_host, seed, first_draw,
