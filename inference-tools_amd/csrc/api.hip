@@ -42,6 +42,10 @@ int lane_streams(gpmi_ctx* c, Lane& L) {
   HIPCHK(c, hipEventCreateWithFlags(&L.ev_join, hipEventDisableTiming));
   HIPCHK(c, hipEventCreateWithFlags(&L.ev_main, hipEventDisableTiming));
   HIPCHK(c, hipEventCreateWithFlags(&L.ev_slice, hipEventDisableTiming));
+  // flag block of the fused panel columns (potrf_panel.hip) - here, not in lane_alloc: the stream-only lane of a bare
+  // handle factorises too (gpmi_dev_potrf)
+  HIPCHK(c, hipMalloc(&L.panel_flags, sizeof(int) * GPMI_PANEL_FL_INTS));
+  ZERO_SYNC(c, L.panel_flags, sizeof(int) * GPMI_PANEL_FL_INTS);
   return GPMI_OK;
 }
 
@@ -166,6 +170,7 @@ void lane_free(Lane& L) {
   if (L.inv2_t) (void)hipFree(L.inv2_t);
   if (L.gws) (void)hipFree(L.gws);
   if (L.invD) (void)hipFree(L.invD);
+  if (L.panel_flags) (void)hipFree(L.panel_flags);
   if (L.vec) (void)hipFree(L.vec);
   if (L.red) (void)hipFree(L.red);
   if (L.info) (void)hipFree(L.info);
@@ -874,7 +879,7 @@ static int profile_collect(gpmi_ctx* c) {
       }
       if (t1 <= t0) continue;  // launch never ran
       const int kl = c->stamp_class[i];
-      if (kl >= GPMI_PROF_NCLASS) {  // GPMI_CHAIN_TRACE (potrf.hip): 0 potrf_diag, 1 panel TRSM, 2 inner update
+      if (kl >= GPMI_PROF_NCLASS) {  // GPMI_CHAIN_TRACE (potrf.hip): 0 potrf_diag, 1 panel TRSM (the fused column launch: its workgroup 0 / its workers), 2 inner update
         static unsigned long long origin = 0;
         if (!origin || kl == GPMI_PROF_NCLASS + 3) origin = t0;
         std::fprintf(stderr, "[chain] %d %.2f %.2f\n", kl - GPMI_PROF_NCLASS, (double)(t0 - origin) * 0.01,

@@ -113,7 +113,13 @@ struct Lane {
   int flow_m = 0, flow_nwg = 0, flow_nlists = 0;
   int64_t flow_ntasks = 0;
   double flow_flops_update = 0.0, flow_flops_trsm = 0.0;
+  // fused panel column of the stream-ordered chain (potrf_panel.hip): GPMI_PANEL_FL_INTS ints, zeroed once here - the row
+  // counters are monotone -, and the number of fused launches the lane has enqueued so far
+  int* panel_flags = nullptr;
+  unsigned panel_seq = 0;
 };
+// Lane::panel_flags: the row-block counters of the inverse on lines of their own (32 r), the abort word
+constexpr int GPMI_PANEL_FL_INVROW = 0, GPMI_PANEL_FL_ABORT = 256, GPMI_PANEL_FL_INTS = 288;
 
 // device state of the linear-inversion entry points (gpmi_linv_*): m data values, model matrix A (m x n)
 struct LinvState {
@@ -436,6 +442,11 @@ void launch_kbuild_square_batched(hipStream_t s, int kernel, const KParams* pdev
 // concurrently already fill the chip, and their masked stream pairs would only fight for HW queues)
 void potrf_lower(gpmi_ctx* c, Lane& lane, double* A, int64_t np, int64_t ld, double* invD,
                  int* info, bool allow_lookahead = true);
+
+// potrf_panel.hip: potrf_diag of a tile column and the panel TRSM under it in one launch (GPMI_PANEL_FUSED)
+bool potrf_panel_fused(gpmi_ctx* c, Lane& lane);
+void launch_panel_column(Lane& lane, hipStream_t s, double* Akk, int64_t ld, double* invD, int* info, int col0, int below,
+                         int ncu, unsigned long long* dbg = nullptr, unsigned long long* stamp = nullptr);
 
 // potrf_flow.hip: the chain-bound part of the factorisation as one persistent tile-task launch beside the panel chain
 bool potrf_flow_enabled(gpmi_ctx* c, Lane& lane, int m);

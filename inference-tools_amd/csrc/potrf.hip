@@ -7,6 +7,8 @@
 //   inner blocks of 128 columns -> potrf_diag (one workgroup: factor the 128 x 128 diagonal block
 //                                   and invert it), panel TRSM as a product with the inverse
 //                                   (MFMA), and the update of the rest of the outer panel (K = 128).
+//                                   potrf_diag and the panel TRSM of a column are ONE launch (potrf_panel.hip), the TRSM
+//                                   one row block of the inverse behind the factorisation.
 // A non-positive or non-finite pivot is reported LAPACK-style through `info` (first failing
 // column + 1); the factorisation then continues with a unit pivot so that the launch sequence stays
 // asynchronous — the host inspects `info` once at the end (regression.py:540-542 behaviour).
@@ -71,11 +73,13 @@ void launch_potrf_diag(hipStream_t s, double* Ablk, int64_t ld, double* invD, in
 namespace {
 
 // factor outer panel [J, Je): inner right-looking steps on stream sp
-void factor_panel(gpmi_ctx* c, hipStream_t sp, double* A, int64_t ld, double* invD, int* info, int nt,
+void factor_panel(gpmi_ctx* c, Lane& lane, hipStream_t sp, double* A, int64_t ld, double* invD, int* info, int nt,
                   int J, int Je, int ncu = 0) {
   GemmBatch on;  // one problem; the CU count of a masked panel stream steers the tile height of the TRSM
   on.ncu_hint = ncu;
   on.b_lower_tri = true;  // the panel TRSM's B is the inverse of the diagonal block
+  // potrf_diag and the panel TRSM of a column in one launch (potrf_panel.hip; GPMI_PANEL_FUSED=0: two launches, same bits)
+  const bool fused = potrf_panel_fused(c, lane);
   // GPMI_CHAIN_TRACE=1 (tools/chain_trace.py, with the profile enabled): in-kernel wall-clock stamps of every launch
   // of the chain, printed by the next profile read
   static const bool trace = std::getenv("GPMI_CHAIN_TRACE") != nullptr;
@@ -87,8 +91,13 @@ void factor_panel(gpmi_ctx* c, hipStream_t sp, double* A, int64_t ld, double* in
     {
       ProfScope ps(c, sp, GPMI_PROF_PANEL, (double)NB * NB * NB / 3.0 + 2.0 * below * NB * NB * NB,
                    8.0 * NB * NB * (2.0 + 2.0 * below));
-      launch_potrf_diag(sp, Ajj, ld, invDj, info, j * NB, slot(0));
-      if (below > 0) {
+      if (below > 0 && fused) {
+        unsigned long long* s0 = slot(0);  // (in this order: the trace prints the slots as they were taken)
+        launch_panel_column(lane, sp, Ajj, ld, invDj, info, j * NB, below, ncu > 0 ? ncu : c->ncu, s0, slot(1));
+      } else {
+        launch_potrf_diag(sp, Ajj, ld, invDj, info, j * NB, slot(0));
+      }
+      if (below > 0 && !fused) {
         // panel TRSM: A21 <- A21 * L11^-T  (in place: one tile column, see gemm_f64.hip)
         double* A21 = Ajj + (int64_t)NB * ld;
         launch_gemm_nt(sp, TILES_RECT, OP_ASSIGN, A21, ld, A21, ld, invDj, NB, below, 1, NB, slot(1), on);
@@ -166,7 +175,7 @@ void update_slice(gpmi_ctx* c, hipStream_t s, double* A, int64_t ld, int nt, int
 // balance point, rounded down to whole rounds of the reserved CUs.  Measured: 36.4 -> 35.9 ms per step at 100 and 130 %,
 // 37.0 at 160 % (the next update then waits for the slice); the 32 extra CUs lower the clock of the other 224 from
 // 2.364 to 2.352 GHz, and the chain's own launches wait behind them: the gain is a third of the idle time.
-int64_t slice_tiles(int rem, int64_t tiles_la, int64_t tiles_main, int kw, int ncu_main, int ncu_panel) {
+int64_t slice_tiles(int rem, int64_t tiles_la, int64_t tiles_main, int kw, int ncu_main, int ncu_panel, bool fused) {
   static const int PCT = [] {
     const char* e = std::getenv("GPMI_SLICE_PCT");
     return e ? std::atoi(e) : 100;
@@ -179,14 +188,20 @@ int64_t slice_tiles(int rem, int64_t tiles_la, int64_t tiles_main, int kw, int n
   // launch gaps): 146 + 6.1 us per row (200 + 7.6 until round 3).  The slices grow by 30 % with it: 32.76 -> 32.53 ms per
   // step (medians of six alternating runs, round-3 A/B script, profiles/HISTORY.md); 45 % more is too much (32.86: the next update waits
   // for the slice).  GPMI_SLICE_CHAIN_US / GPMI_SLICE_CHAIN_SLOPE for A/B runs.
-  static const double CHAIN0 = [] {
+  // With the fused panel column (potrf_panel.hip) the chain is 60 - 110 us shorter per panel (705 us at 124 trailing tile
+  // rows, 356 at 52: profiles/r18_panel_fused.txt), least squares over the 19 look-ahead panels of one traced step:
+  // 93 + 5.17 us per row.  Against 146 + 6.1 with the fused kernel: 31.42 -> 31.25 ms per step (medians of four alternating
+  // runs, every round lower; profiles/HISTORY.md).  The two-launch form (GPMI_PANEL_FUSED=0) keeps its own fit.
+  static const double CHAIN0_ENV = [] {
     const char* e = std::getenv("GPMI_SLICE_CHAIN_US");
-    return e ? std::atof(e) : 146.0;
+    return e ? std::atof(e) : -1.0;
   }();
-  static const double SLOPE = [] {
+  static const double SLOPE_ENV = [] {
     const char* e = std::getenv("GPMI_SLICE_CHAIN_SLOPE");
-    return e ? std::atof(e) : 6.1;
+    return e ? std::atof(e) : -1.0;
   }();
+  const double CHAIN0 = CHAIN0_ENV >= 0.0 ? CHAIN0_ENV : (fused ? 93.0 : 146.0);
+  const double SLOPE = SLOPE_ENV >= 0.0 ? SLOPE_ENV : (fused ? 5.17 : 6.1);
   const double chain = CHAIN0 + SLOPE * rem;
   const double su = 20.0 + (double)(tiles_la + tiles_main) * per_main;
   double x = (su - chain) / (per_main + per_panel) * PCT / 100.0;
@@ -276,7 +291,7 @@ void potrf_lower(gpmi_ctx* c, Lane& lane, double* A, int64_t np, int64_t ld, dou
   };
   auto tile0 = [&](int panel) { return panel * OBT < nt ? panel * OBT : nt; };  // first tile column of a panel
   const int NP = (nt + OBT - 1) / OBT;
-  factor_panel(c, sf, A, ld, invD, info, nt, 0, tile0(1));
+  factor_panel(c, lane, sf, A, ld, invD, info, nt, 0, tile0(1));
   hipStream_t panel_stream = sf;  // where the latest panel was factored (ev_panel recorded behind it)
   hipStream_t main_stream = sf;   // where the latest trailing update ran (ev_main recorded behind it)
   bool sliced = false;            // a slice of the latest update is in flight on the panel stream (ev_slice)
@@ -301,7 +316,7 @@ void potrf_lower(gpmi_ctx* c, Lane& lane, double* A, int64_t np, int64_t ld, dou
       (void)hipStreamWaitEvent(sp, lane.ev_la, 0);
       const int w = k2 - k1, r2 = nt - k2;
       slice = slice_tiles(rem, (int64_t)w * (w + 1) / 2 + (int64_t)(rem - w) * w, (int64_t)r2 * (r2 + 1) / 2,
-                          (k1 - k0) * NB, ncu, c->pair_cus[0]);
+                          (k1 - k0) * NB, ncu, c->pair_cus[0], potrf_panel_fused(c, lane));
       // the previous slice wrote tiles of this update's region
       if (sliced) (void)hipStreamWaitEvent(su, lane.ev_slice, 0);
       update_columns(c, su, A, ld, nt, k2, nt, k0, k1, ncu, slice);
@@ -314,7 +329,7 @@ void potrf_lower(gpmi_ctx* c, Lane& lane, double* A, int64_t np, int64_t ld, dou
     }
     sliced = false;
     main_stream = su;
-    factor_panel(c, sp, A, ld, invD, info, nt, k1, tile0(p + 2), overlap ? c->pair_cus[0] : 0);
+    factor_panel(c, lane, sp, A, ld, invD, info, nt, k1, tile0(p + 2), overlap ? c->pair_cus[0] : 0);
     if (overlap) (void)hipEventRecord(lane.ev_panel, sp);
     panel_stream = sp;
     if (slice > 0) {

@@ -50,6 +50,7 @@
 #include <vector>
 
 #include "gemm_tiles.h"
+#include "potrf_colblock.h"
 #include "potrf_diag.h"
 
 using namespace gemm_tiles;
@@ -544,31 +545,13 @@ __global__ __launch_bounds__(512) void chain_column_kernel(ChainColArgs g) {
     // ---- this wave's column block of a strip, if row block `row` of the inverse is its operand
     if (row == c || row == 7 - c) {
       const int strip = row == c ? 0 : 1;
-      {
-        int spins = 0;
-        while (flow_ld(fl + FL_INVROW + 32 * row) < row_target) {
-          __builtin_amdgcn_s_sleep(2);
-          if ((++spins & 63) == 0 && flow_ld(abortw)) break;
-          if (spins > FLOW_SPIN_LIMIT) {
-            give_up();
-            break;
-          }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      }
-      const double* brow = g.invD + (int64_t)(16 * row + fr) * NB + 4 * fk;
-      d4_t b[NB / 16];
-#pragma unroll
-      for (int s = 0; s <= row; ++s) b[s] = *reinterpret_cast<const d4_t*>(brow + 16 * s);
-      // (chain_trsm_kernel's sums: k = 16 s + 4 fk + q at step q of slab s, slabs beyond the block skipped)
-      d4_t x = {0.0, 0.0, 0.0, 0.0};
+      potrf_colblock::wait_inv_row(fl + FL_INVROW + 32 * row, row_target, abortw, give_up);
+      // (chain_trsm_kernel's sums: potrf_colblock.h)
       const double* ts = Ts + strip * 16 * CF_APITCH + fr * CF_APITCH + 4 * fk;
-#pragma unroll
-      for (int s = 0; s <= row; ++s) {
-        const d4_t a = *reinterpret_cast<const d4_t*>(ts + 16 * s);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) x = __builtin_amdgcn_mfma_f64_16x16x4f64(a[q], b[s][q], x, 0, 0, 0);
-      }
+      d4_t b[NB / 16];
+      potrf_colblock::load_inv_rowblock(g.invD, NB, row, fr, fk, b);
+      const d4_t x =
+          potrf_colblock::colblock_sums(row, [&](int s) { return *reinterpret_cast<const d4_t*>(ts + 16 * s); }, b);
       // X block to LDS in row-major form (the D layout of the MFMA: lane (fr, fk) holds rows fk + 4 r of its column block)
       double* xo = Xs + strip * 16 * CF_PITCH + fk * CF_PITCH + 16 * row + fr;
 #pragma unroll
