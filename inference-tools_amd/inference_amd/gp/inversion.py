@@ -9,9 +9,13 @@ over theta stays on the host as in the reference.
 Constructor arguments, attributes (`A, y, cov, mean, n_hyperpars, mean_slice, cov_slice,
 hyperpar_labels`) and methods are those of the reference.  The posterior is evaluated in its Woodbury
 form, K - K A^T J^-1 A K (symmetric positive-definite solves only), which equals the reference's
-solve(I + K A^T Sigma^-1 A, K) (inversion.py:150-155).  Supported priors: `SquaredExponential`,
-`RationalQuadratic`, each optionally `+ WhiteNoise()`; anything else raises `NotImplementedError`
-instead of silently running on the host.
+solve(I + K A^T Sigma^-1 A, K) (inversion.py:150-155).  Priors: `SquaredExponential`, `RationalQuadratic`,
+`Matern32` and `Matern52`, each optionally `+ WhiteNoise()`, are built on the device from their parameters
+(gpmi_linv_lml / _lml_grad / _posterior).  Every other `CovarianceFunction` - sums of stationary kernels,
+`ChangePoint`, `HeteroscedasticNoise`, user-defined plugins - is served by the dense entry points
+(gpmi_linv_*_dense): the host evaluates the object's own `build_covariance` / `covariance_and_gradients`, the
+device does every O(n^3) step, and for the gradient returns A^T J^-1 A for the host to contract with the
+object's dK_j.  Nothing raises `NotImplementedError`, and no O(n^3) step runs on the host.
 """
 from inspect import isclass
 
