@@ -659,7 +659,9 @@ int gpmi_draws_normals(int64_t seed, int64_t first_draw, int64_t n_draws, int64_
  * gpmi_sgp_bound does not touch the state gpmi_sgp_fit left: predictions before and after it are bit-identical.
  * Device memory of an object: x, Z, r, the noise variances and two more vectors of n doubles (1 / sigma_i^2, alpha); eleven
  * matrices of m_pad (m_pad + 32) doubles (m_pad = m rounded up to 128; nine of work, two of the fit); three panels of
- * max(m_pad, panel) x (max(m_pad, panel) + 32) doubles at most, allocated at the first call that needs them.
+ * max(m_pad, panel) x (max(m_pad, panel) + 32) doubles at most, allocated at the first call that needs them; behind the
+ * first gpmi_sgp_bound_zgrad m_pad x d doubles (dF/dZ) and its partial sums, m_pad x d x max(panel, m_pad) / 1024 doubles
+ * (for m_pad x panel < 2^19 up to eight times that, and never more than 32 MiB then).
  * Objects belong to their handle (calls on one handle are serialised); gpmi_destroy releases those still alive. */
 #define GPMI_SGP_MAX_M 4096
 #define GPMI_SGP_PANEL 8192
@@ -673,6 +675,20 @@ int gpmi_sgp_set_targets(gpmi_sgp* sgp, const double* r_host, const double* nois
 int gpmi_sgp_bound(gpmi_sgp* sgp, int kernel, const double* theta, int n_theta, double white_var, double jitter_rel,
                    int64_t panel_rows, double* F, double* grad /* n_theta + 1, may be NULL */,
                    double* alpha_host /* n, may be NULL */, int* info);
+/* gpmi_sgp_bound plus dF/dZ: F, grad (n_theta + 1, may be NULL) and alpha exactly as gpmi_sgp_bound returns them - the same
+ * bits - and grad_z (m x d, row i = dF/dz_i, required).  With M1 = gamma alpha^T + T K_mn W, M2 = gamma gamma^T + K_mm^-1 G
+ * K_mm^-1 - T (T = K_mm^-1 - (K_mm + G)^-1, with eps in K_mm), s_ij = 1/2 sum_k D_k^2 / l_k^2 and g the profile of
+ * dK / d ln l_k = a^2 g(s) D_k^2 / l_k^2:
+ *   dF/dz_ik = -1 / l_k^2 [sum_j M1_ij a^2 g(s(z_i, x_j)) (z_ik - x_jk) - sum_j M2_ij a^2 g(s(z_i, z_j)) (z_ik - z_jk)]
+ * (eps does not depend on Z; nothing is divided by a distance: coincident points contribute exact zeros).  The contraction
+ * runs behind the theta-gradient's on the same panels - no panel and no product is rebuilt - with sums whose order is
+ * fixed by (n, m, d, panel_rows): bit-reproducible, no atomics.  info != 0 leaves the outputs undefined, as there. */
+int gpmi_sgp_bound_zgrad(gpmi_sgp* sgp, int kernel, const double* theta, int n_theta, double white_var, double jitter_rel,
+                         int64_t panel_rows, double* F, double* grad /* n_theta + 1, may be NULL */,
+                         double* grad_z /* m x d */, double* alpha_host /* n, may be NULL */, int* info);
+/* replace the inducing inputs (same m, same d).  Non-finite values: GPMI_ERR_ARG, the old Z stays.  A fit kept by
+ * gpmi_sgp_fit is dropped: gpmi_sgp_predict before the next successful fit is GPMI_ERR_ARG, the object stays usable. */
+int gpmi_sgp_set_inducing(gpmi_sgp* sgp, const double* z_host /* m x d */);
 /* the bound, and L^-1, L_B^-1, c and the kernel's parameters kept for gpmi_sgp_predict (kept only if info == 0; a failed
  * fit leaves the previous one in place) */
 int gpmi_sgp_fit(gpmi_sgp* sgp, int kernel, const double* theta, int n_theta, double white_var, double jitter_rel,
@@ -717,7 +733,7 @@ int gpmi_flow_task_lists(int m, int nwg, int64_t cap, int32_t* out, int64_t* nta
 #define GPMI_PROF_SGP_BUILD 13  /* pass 1: the panels of K_mn (cross build, column scaling, K_mn W r) */
 #define GPMI_PROF_SGP_GRAM 14   /* pass 1: G += (K_mn W^1/2)(K_mn W^1/2)^T, 2 N m^2 FLOP on the fp64 matrix cores */
 #define GPMI_PROF_SGP_FACTOR 15 /* the m x m algebra: two factorisations, their inverses, H, c, the reductions */
-#define GPMI_PROF_SGP_GRAD 16   /* the gradient: S, T, M2 and pass 2 (panel rebuild, T K_mn, the contraction) */
+#define GPMI_PROF_SGP_GRAD 16   /* the gradient: S, T, M2 and pass 2 (panel rebuild, T K_mn, the contractions: theta, and Z on request) */
 #define GPMI_PROF_NCLASS 17
 /* on = 0: off; 1: every class; otherwise a class bitmask shifted left by one (2 << klass) */
 int gpmi_profile_enable(gpmi_ctx* ctx, int on);

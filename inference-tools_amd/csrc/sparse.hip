@@ -39,6 +39,9 @@ struct gpmi_sgp {
   double* pvec = nullptr;
   double* ws = nullptr;
   int64_t panel_cap = 0;
+  // the gradient by Z (allocated at first use): the partials per run of data tiles, the mp x d accumulator
+  double *zws = nullptr, *zacc = nullptr;
+  int64_t zws_cap = 0;
   // query staging: 1024 x d points, 2 x 1024 results
   double *q_pts = nullptr, *q_out = nullptr;
   // the fit: L^-1, L_B^-1 (mp x ld), c (mp), the kernel
@@ -365,10 +368,195 @@ void launch_contract(hipStream_t s, const KParams& p, const double* U, int64_t n
 #undef SGP_CONTRACT
 }
 
+// The contraction by the inducing inputs: for the 64 points v_j of tile blockIdx.x (the inducing inputs differentiated) and
+// the run blockIdx.y of `run_tiles` consecutive 64-row tiles of U (the points summed over),
+//   zws[(run * nvp + j) * d + k] = scale / l_k^2 * sum_i w_ij a^2 g(s(u_i, v_j)) (v_jk - u_ik),
+//   w_ij = rs_i Mw[i][j] + uvec_i vvec_j   (rs == nullptr: 1),
+// the operands and the weights of sgp_contract_kernel.  dK(u_i, v_j) / dv_jk = -a^2 g (v_jk - u_ik) / l_k^2: the difference
+// is formed from the staged coordinates, nothing is divided by a distance, coincident points contribute exact zeros.
+// The thread layout is the 4 x 4 blocks of sgp_contract_kernel; s and the profiles are recomputed per tile.  Per dimension
+// a thread's four column sums go through two xor shuffles (the four lanes of a wave that share the columns), then the four
+// waves through LDS, ZDK dimensions per barrier (double-buffered), into a [d][64] accumulator in LDS that one thread per
+// element owns; tiles are added in ascending order, rows >= nu and columns >= nv carry weight 0.  The order of every sum
+// is fixed by the shapes and run_tiles alone.  Dynamic LDS: (3 d + 2 ZDK 4) x 64 doubles - 112 KiB at d = 64, 28 KiB at
+// d = 8.  gfx950 (kernel-resource-usage; the state is independent of d), SE / RQ / Matern32 / Matern52: 126 / 167 / 132 /
+// 147 VGPRs, no AGPRs, scratch 0, no static LDS: 114688 bytes of LDS at d = 64 (one workgroup per CU there, five at d = 8).
+constexpr int ZDK = 4;
+constexpr int ZRUN_MAX = 16;
+
+template <int KERNEL>
+__global__ __launch_bounds__(SGP_NT) void sgp_zcontract_kernel(KParams p, const double* __restrict__ U, int64_t nu,
+                                                               const double* __restrict__ V, int64_t nv, int64_t nvp,
+                                                               const double* __restrict__ Mw, int64_t ld,
+                                                               const double* __restrict__ rs, const double* __restrict__ uvec,
+                                                               const double* __restrict__ vvec, double scale, int run_tiles,
+                                                               double* __restrict__ zws) {
+  extern __shared__ double sz_lds[];
+  const int tj = blockIdx.x, run = blockIdx.y;
+  const int tid = threadIdx.x, d = p.d;
+  double* sv = sz_lds;
+  double* su = sv + d * KT;
+  double* acc = su + d * KT;
+  double* red = acc + d * KT;  // [2][ZDK][4 waves][64]
+  const int64_t j0 = (int64_t)tj * KT;
+  for (int idx = tid; idx < KT * d; idx += SGP_NT) {
+    const int pt = idx / d, k = idx - pt * d;
+    const int64_t gj = j0 + pt;
+    sv[k * KT + pt] = (gj < nv) ? V[gj * d + k] : 0.0;
+    acc[idx] = 0.0;
+  }
+  const int ty = tid >> 4, tx = tid & 15, wave = tid >> 6, lane = tid & 63;
+  int chunk = 0;
+  for (int t = 0; t < run_tiles; ++t) {
+    const int64_t i0 = ((int64_t)run * run_tiles + t) * KT;
+    if (i0 >= nu) break;
+    __syncthreads();  // (the previous tile's readers of su)
+    for (int idx = tid; idx < KT * d; idx += SGP_NT) {
+      const int pt = idx / d, k = idx - pt * d;
+      const int64_t gi = i0 + pt;
+      su[k * KT + pt] = (gi < nu) ? U[gi * d + k] : 0.0;
+    }
+    __syncthreads();
+    double s[4][4], w[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) s[r][c] = 0.0;
+    for (int k = 0; k < d; ++k) {
+      const double il2 = p.inv_l2[k];
+      double ur[4], vc[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) ur[r] = su[k * KT + ty * 4 + r];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) vc[c] = sv[k * KT + tx * 4 + c];
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const double dx = ur[r] - vc[c];
+          s[r][c] = fma(0.5 * dx * dx, il2, s[r][c]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int64_t gi = i0 + ty * 4 + r;
+      const bool row_ok = gi < nu;
+      const double ui = row_ok ? uvec[gi] : 0.0;
+      const double ri = row_ok ? (rs ? rs[gi] : 1.0) : 0.0;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int64_t gj = j0 + tx * 4 + c;
+        w[r][c] = (row_ok && gj < nv) ? fma(ri, Mw[gi * ld + gj], ui * vvec[gj]) : 0.0;
+      }
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      double s8[8], C8[8], g8[8], h8[8];
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) s8[4 * r + c] = s[2 * h + r][c];
+      kprofiles<KERNEL>(p, s8, C8, g8, h8);
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) w[2 * h + r][c] *= p.a2 * g8[4 * r + c];
+    }
+    for (int k0 = 0; k0 < d; k0 += ZDK, ++chunk) {
+      double* buf = red + (chunk & 1) * (ZDK * 4 * KT);
+      for (int kk = 0; kk < ZDK && k0 + kk < d; ++kk) {
+        const int k = k0 + kk;
+        double ur[4], col[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) ur[r] = su[k * KT + ty * 4 + r];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const double vc = sv[k * KT + tx * 4 + c];
+          double a = 0.0;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) a = fma(w[r][c], vc - ur[r], a);
+          a += __shfl_xor(a, 16, 64);
+          a += __shfl_xor(a, 32, 64);
+          col[c] = a;
+        }
+        if (lane < 16) {
+#pragma unroll
+          for (int c = 0; c < 4; ++c) buf[(kk * 4 + wave) * KT + tx * 4 + c] = col[c];
+        }
+      }
+      __syncthreads();  // (one barrier per chunk: the other half of red is written only behind the next one)
+      const int kk = tid >> 6, k = k0 + kk;
+      if (k < d)
+        acc[k * KT + lane] += (buf[(kk * 4 + 0) * KT + lane] + buf[(kk * 4 + 1) * KT + lane]) +
+                              (buf[(kk * 4 + 2) * KT + lane] + buf[(kk * 4 + 3) * KT + lane]);
+    }
+  }
+  __syncthreads();
+  for (int idx = tid; idx < KT * d; idx += SGP_NT) {
+    const int pt = idx / d, k = idx - pt * d;
+    zws[((int64_t)run * nvp + j0 + pt) * d + k] = scale * p.inv_l2[k] * acc[k * KT + pt];
+  }
+}
+
+// zacc[e] (+)= sum_run zws[run * count + e], runs in ascending order; e < count
+__global__ __launch_bounds__(SGP_NT) void sgp_zsum_kernel(const double* __restrict__ zws, int nruns, int64_t count,
+                                                          double* __restrict__ zacc, int accumulate) {
+  const int64_t e = (int64_t)blockIdx.x * SGP_NT + threadIdx.x;
+  if (e >= count) return;
+  double v = 0.0;
+  for (int r = 0; r < nruns; ++r) v += zws[(int64_t)r * count + e];
+  zacc[e] = accumulate ? zacc[e] + v : v;
+}
+
+size_t zcontract_lds_bytes(int d) { return sizeof(double) * ((size_t)3 * d + 2 * ZDK * 4) * KT; }
+
+// tiles of U per workgroup: ZRUN_MAX, halved (not below 2) while the grid stays under 512 workgroups - a function of the
+// two padded shapes alone
+int zrun_tiles(int64_t nup, int64_t nvp) {
+  int r = ZRUN_MAX;
+  while (r > 2 && (nvp / KT) * ((nup / KT + r - 1) / r) < 512) r >>= 1;
+  return r;
+}
+
+int zruns(int64_t nup, int64_t nvp) {
+  const int r = zrun_tiles(nup, nvp);
+  return (int)((nup / KT + r - 1) / r);
+}
+
+// zacc (nvp x d) (+)= the contraction over the rows of U; zws holds zruns(nup, nvp) x nvp x d doubles
+int launch_zcontract(gpmi_ctx* c, hipStream_t s, const KParams& p, const double* U, int64_t nu, int64_t nup, const double* V,
+                     int64_t nv, int64_t nvp, const double* Mw, int64_t ld, const double* rs, const double* uvec,
+                     const double* vvec, double scale, double* zws, double* zacc, int accumulate) {
+  const int run_tiles = zrun_tiles(nup, nvp), nruns = zruns(nup, nvp);
+  const dim3 grid((unsigned)(nvp / KT), (unsigned)nruns);
+  const size_t lds = zcontract_lds_bytes(p.d);
+#define SGP_ZCONTRACT(KIND)                                                                                                 \
+  do {                                                                                                                      \
+    if (lds > 65536)                                                                                                        \
+      HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&sgp_zcontract_kernel<KIND>),                             \
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                 \
+    hipLaunchKernelGGL(sgp_zcontract_kernel<KIND>, grid, dim3(SGP_NT), lds, s, p, U, nu, V, nv, nvp, Mw, ld, rs, uvec, vvec,  \
+                       scale, run_tiles, zws);                                                                              \
+  } while (0)
+  switch (p.kernel) {
+    case GPMI_KERNEL_SE: SGP_ZCONTRACT(GPMI_KERNEL_SE); break;
+    case GPMI_KERNEL_RQ: SGP_ZCONTRACT(GPMI_KERNEL_RQ); break;
+    case GPMI_KERNEL_M32: SGP_ZCONTRACT(GPMI_KERNEL_M32); break;
+    case GPMI_KERNEL_M52: SGP_ZCONTRACT(GPMI_KERNEL_M52); break;
+    default: break;  // (sgp_params admits no other kind)
+  }
+#undef SGP_ZCONTRACT
+  const int64_t count = nvp * p.d;
+  hipLaunchKernelGGL(sgp_zsum_kernel, dim3((unsigned)((count + SGP_NT - 1) / SGP_NT)), dim3(SGP_NT), 0, s, zws, nruns, count,
+                     zacc, accumulate);
+  HIPCHK(c, hipGetLastError());
+  return GPMI_OK;
+}
+
 unsigned blocks(int64_t n) { return (unsigned)((n + SGP_NT - 1) / SGP_NT); }
 
 void sgp_free(gpmi_sgp* g) {
-  for (double* q : {g->x, g->z, g->r, g->nv, g->w, g->alpha, g->invD1, g->invD2, g->vec, g->red, g->part, g->pvec, g->ws,
+  for (double* q : {g->x, g->z, g->r, g->nv, g->w, g->alpha, g->invD1, g->invD2, g->vec, g->red, g->part, g->pvec, g->ws, g->zws, g->zacc,
                     g->q_pts, g->q_out, g->fLinv, g->fLBinv, g->fc, g->P[0], g->P[1], g->P[2]})
     if (q) (void)hipFree(q);
   for (double* q : g->M)
@@ -422,6 +610,20 @@ int sgp_ensure_panels(gpmi_sgp* g, int64_t R) {
   const int64_t tiles = (std::max(R, g->mp) / KT) * (g->mp / KT);
   HIPCHK(c, hipMalloc(&g->ws, sizeof(double) * tiles * (GPMI_MAX_D + 2)));
   g->panel_cap = R;
+  return GPMI_OK;
+}
+
+// the workspace of the Z pass for panels of R rows
+int sgp_ensure_zws(gpmi_sgp* g, int64_t R) {
+  gpmi_ctx* c = g->ctx;
+  if (!g->zacc) HIPCHK(c, hipMalloc(&g->zacc, sizeof(double) * g->mp * g->d));
+  const int64_t need = (int64_t)std::max(zruns(R, g->mp), zruns(g->mp, g->mp)) * g->mp * g->d;
+  if (need <= g->zws_cap) return GPMI_OK;
+  if (g->zws) (void)hipFree(g->zws);
+  g->zws = nullptr;
+  g->zws_cap = 0;
+  HIPCHK(c, hipMalloc(&g->zws, sizeof(double) * need));
+  g->zws_cap = need;
   return GPMI_OK;
 }
 
@@ -537,8 +739,9 @@ int sgp_factor(gpmi_sgp* g, const KParams& p, double white, double jitter, int64
 }
 
 // The gradient behind a successful sgp_factor (same parameters): grad (n_theta + 1) if not NULL, alpha into g->alpha.
+// want_z (needs grad): dF/dZ into g->zacc (m x d in its first rows) from the operands of every contraction, behind it.
 int sgp_gradient(gpmi_sgp* g, const KParams& p, int n_theta, double white, double jitter, int64_t panel_rows, double sum_w,
-                 double* grad) {
+                 double* grad, bool want_z = false) {
   gpmi_ctx* c = g->ctx;
   hipStream_t s = c->sgp_stream;
   const int64_t n = g->n, m = g->m, mp = g->mp, ld = g->ld, d = g->d;
@@ -548,6 +751,8 @@ int sgp_gradient(gpmi_sgp* g, const KParams& p, int n_theta, double white, doubl
          *LBinv = g->M[MLBINV];
   double *cc = g->vec + 2 * mp, *gamma = g->vec + 3 * mp;
   double *kg = g->pvec, *q = g->pvec + P, *term = g->pvec + 2 * P;
+  if (want_z)
+    if (int rc = sgp_ensure_zws(g, P)) return rc;
   ProfScope ps(c, s, GPMI_PROF_SGP_GRAD, 0.0, 0.0);
   nt_square(s, RT, LiT, LBinv, mp, ld);  // L^-T L_B^-T
   launch_rows_dot(s, RT, ld, mp, mp, cc, gamma);
@@ -577,6 +782,10 @@ int sgp_gradient(gpmi_sgp* g, const KParams& p, int n_theta, double white, doubl
                       n_theta, g->ws);
       hipLaunchKernelGGL(sgp_colsum_kernel, dim3((unsigned)n_theta), dim3(SGP_NT), 0, s, g->ws, (P / KT) * (mp / KT), n_theta,
                          g->red + RED_GRAD, j0 > 0 ? 1 : 0);
+      if (want_z)  // -sum_j M1_ij a^2 g (z_ik - x_jk) / l_k^2
+        if (int rc = launch_zcontract(c, s, p, g->x + j0 * d, rows, P, g->z, m, mp, Mp, ld, g->w + j0, g->alpha + j0, gamma,
+                                      -1.0, g->zws, g->zacc, j0 > 0 ? 1 : 0))
+          return rc;
     }
     HIPCHK(c, hipGetLastError());
   }
@@ -585,6 +794,9 @@ int sgp_gradient(gpmi_sgp* g, const KParams& p, int n_theta, double white, doubl
   launch_contract(s, p, g->z, m, mp, g->z, m, mp, LB, ld, nullptr, gamma, gamma, -0.5, -0.5, 1, jitter * p.a2, n_theta, g->ws);
   hipLaunchKernelGGL(sgp_colsum_kernel, dim3((unsigned)n_theta), dim3(SGP_NT), 0, s, g->ws, (mp / KT) * (mp / KT), n_theta,
                      g->red + RED_GRAD, 1);
+  if (want_z)  // +sum_j M2_ij a^2 g (z_ik - z_jk) / l_k^2: z_i is in row i and column i of K_mm, M2 symmetric - no 1/2
+    if (int rc = launch_zcontract(c, s, p, g->z, m, mp, g->z, m, mp, LB, ld, nullptr, gamma, gamma, 1.0, g->zws, g->zacc, 1))
+      return rc;
   HIPCHK(c, hipGetLastError());
   double hg[GPMI_MAX_D + 2] = {}, hnoise = 0.0;
   HIPCHK(c, hipMemcpyAsync(hg, g->red + RED_GRAD, sizeof(double) * n_theta, hipMemcpyDeviceToHost, s));
@@ -687,6 +899,44 @@ int gpmi_sgp_set_targets(gpmi_sgp* g, const double* r, const double* noise_var) 
     ZERO_SYNC(c, g->nv, sizeof(double) * g->n);
   }
   g->have_targets = true;
+  return GPMI_OK;
+}
+
+int gpmi_sgp_set_inducing(gpmi_sgp* g, const double* z) {
+  if (!g) return GPMI_ERR_ARG;
+  gpmi_ctx* c = g->ctx;
+  ARGCHK(c, sgp_live(c, g), "gpmi_sgp_set_inducing: not a live object of this handle");
+  ARGCHK(c, z != nullptr, "gpmi_sgp_set_inducing: z_host is NULL");
+  for (int64_t i = 0; i < g->m * g->d; ++i) ARGCHK(c, std::isfinite(z[i]), "gpmi_sgp_set_inducing: z_host must be finite");
+  if (int rc = set_device(c)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->sgp_stream));
+  HIPCHK(c, hipMemcpy(g->z, z, sizeof(double) * g->m * g->d, hipMemcpyHostToDevice));  // (the padding rows stay zero)
+  g->fitted = false;
+  return GPMI_OK;
+}
+
+int gpmi_sgp_bound_zgrad(gpmi_sgp* g, int kernel, const double* theta, int n_theta, double white_var, double jitter_rel,
+                         int64_t panel_rows, double* F, double* grad, double* grad_z, double* alpha_host, int* info) {
+  if (!g) return GPMI_ERR_ARG;
+  gpmi_ctx* c = g->ctx;
+  ARGCHK(c, sgp_live(c, g), "gpmi_sgp_bound_zgrad: not a live object of this handle");
+  ARGCHK(c, F != nullptr && info != nullptr, "gpmi_sgp_bound_zgrad: F and info must be non-NULL");
+  ARGCHK(c, grad_z != nullptr, "gpmi_sgp_bound_zgrad: grad_z is NULL");
+  KParams p;
+  if (int rc = sgp_params(g, kernel, theta, n_theta, white_var, jitter_rel, panel_rows, p)) return rc;
+  if (int rc = set_device(c)) return rc;
+  double f = 0.0, sum_w = 0.0;
+  int inf = 0;
+  if (int rc = sgp_factor(g, p, white_var, jitter_rel, panel_rows, &f, &sum_w, &inf)) return rc;
+  *info = inf;
+  if (inf != 0) return GPMI_OK;
+  double gbuf[GPMI_MAX_D + 3];
+  if (int rc = sgp_gradient(g, p, n_theta, white_var, jitter_rel, panel_rows, sum_w, gbuf, true)) return rc;
+  if (alpha_host) HIPCHK(c, hipMemcpyAsync(alpha_host, g->alpha, sizeof(double) * g->n, hipMemcpyDeviceToHost, c->sgp_stream));
+  HIPCHK(c, hipMemcpyAsync(grad_z, g->zacc, sizeof(double) * g->m * g->d, hipMemcpyDeviceToHost, c->sgp_stream));
+  HIPCHK(c, hipStreamSynchronize(c->sgp_stream));
+  if (grad) std::memcpy(grad, gbuf, sizeof(double) * (n_theta + 1));
+  *F = f;
   return GPMI_OK;
 }
 

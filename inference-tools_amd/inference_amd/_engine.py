@@ -702,12 +702,26 @@ class SparseEngine:
         nv = None if noise_var is None else as_f64(noise_var)
         self._call("gpmi_sgp_set_targets", dptr(r), dptr(nv))
 
-    def bound(self, kernel, theta, white_var, jitter, panel_rows=0, want_grad=False, want_alpha=False):
-        """(F, gradient or None, alpha or None, info): info > 0 - not positive definite - leaves the rest undefined."""
+    def set_inducing(self, z):
+        """Replace the inducing inputs on the device (same shape, finite); a kept fit is dropped."""
+        z = as_f64(z)
+        if z.shape != (self.m, self.d):
+            raise ValueError(f"the inducing inputs must keep their shape {(self.m, self.d)}, got {z.shape}")
+        self._call("gpmi_sgp_set_inducing", dptr(z))
+        self.z = z
+
+    def bound(self, kernel, theta, white_var, jitter, panel_rows=0, want_grad=False, want_alpha=False, want_zgrad=False):
+        """(F, gradient or None, alpha or None, info): info > 0 - not positive definite - leaves the rest undefined.
+        want_zgrad: dF/dZ, (m, d), as a fifth element (gpmi_sgp_bound_zgrad; the other four keep their bits)."""
         theta = as_f64(theta)
         F, info = C.c_double(0.0), C.c_int(0)
         grad = np.zeros(theta.size + 1) if want_grad else None
         alpha = np.zeros(self.n) if want_alpha else None
+        if want_zgrad:
+            zgrad = np.zeros((self.m, self.d))
+            self._call("gpmi_sgp_bound_zgrad", int(kernel), dptr(theta), theta.size, float(white_var), float(jitter),
+                       int(panel_rows), C.byref(F), dptr(grad), dptr(zgrad), dptr(alpha), C.byref(info))
+            return F.value, grad, alpha, info.value, zgrad
         self._call("gpmi_sgp_bound", int(kernel), dptr(theta), theta.size, float(white_var), float(jitter), int(panel_rows),
                    C.byref(F), dptr(grad), dptr(alpha), C.byref(info))
         return F.value, grad, alpha, info.value

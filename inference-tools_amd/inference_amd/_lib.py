@@ -144,6 +144,8 @@ SIGNATURES = {
     "gpmi_sgp_destroy": (C.c_int, [_vp]),
     "gpmi_sgp_set_targets": (C.c_int, [_vp, _dp, _dp]),
     "gpmi_sgp_bound": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, _i64, _dp, _dp, _dp, _ip]),
+    "gpmi_sgp_bound_zgrad": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, _i64, _dp, _dp, _dp, _dp, _ip]),
+    "gpmi_sgp_set_inducing": (C.c_int, [_vp, _dp]),
     "gpmi_sgp_fit": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, _i64, _dp, _ip]),
     "gpmi_sgp_predict": (C.c_int, [_vp, _dp, _i64, _dp, _dp]),
     "gpmi_timer_start": (C.c_int, [_vp]),

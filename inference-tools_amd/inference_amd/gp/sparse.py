@@ -6,9 +6,14 @@ log marginal likelihood (with its 2 pi constant), equal to it for Z = x.  All of
 gpmi_sgp_*): x never comes back, K_mn is never held whole.  The class follows `GpRegressor`: theta = [mean parameters |
 covariance parameters], `marginal_likelihood`, `marginal_likelihood_gradient`, `set_hyperparameters`, `__call__`.
 
+The inducing inputs are variational parameters: `marginal_likelihood_gradient(theta, inducing_points=True)` adds dF/dZ
+(gpmi_sgp_bound_zgrad: a contraction behind the theta-gradient's, on the same panels), `set_inducing_points` moves Z
+without rebuilding the object, and `optimise_inducing_points` (or the constructor's `optimise_inducing=True`) runs one
+L-BFGS-B over vec(Z), or over [theta | vec(Z)] jointly, every coordinate of Z inside the bounding box of x.
+
 Supported: one of SquaredExponential, RationalQuadratic, Matern32, Matern52 (class or instance), optionally
 `+ WhiteNoise()`; the mean functions of `inference_amd.gp.mean` (evaluated on the host); data errors `y_err`.
-Not supported: FITC, optimised inducing inputs, spatial derivatives, posterior draws, `GpOptimiser`, several GPUs.
+Not supported: FITC, spatial derivatives, posterior draws, `GpOptimiser`, several GPUs.
 """
 from copy import copy
 from inspect import isclass
@@ -46,10 +51,12 @@ class SparseGpRegressor:
     :param seed: seed of the inducing-point choice.
     :param jitter: eps = jitter a^2 is added to the diagonal of K_mm.
     :param panel_rows: (extension) rows of x per panel of the device sweep; 0: the library's default.
+    :param optimise_inducing: True: once the hyper-parameters are set, `optimise_inducing_points` moves Z - at the given
+        `hyperpars`, or, if they were searched for, jointly with them from the result of that search.
     """
 
     def __init__(self, x, y, y_err=None, inducing_points=256, kernel=SquaredExponential, mean=ConstantMean, hyperpars=None,
-                 optimizer="bfgs", n_starts=None, seed=None, jitter=1e-8, device=None, y_cov=None, panel_rows=0):
+                 optimizer="bfgs", n_starts=None, seed=None, jitter=1e-8, device=None, y_cov=None, panel_rows=0, optimise_inducing=False):
         self.x, self.y = GpRegressor._coerce_training_data(x, y)
         self.x = np.ascontiguousarray(self.x, dtype=float)
         self.y = np.asarray(self.y, dtype=float)
@@ -116,12 +123,15 @@ class SparseGpRegressor:
         self._engine = None
         self._targets_mean = None
 
+        searched = hyperpars is None
         if hyperpars is None:
             if optimizer not in ["bfgs", "diffev"]:
                 optimizer = "bfgs"
                 warn(msg.BAD_OPTIMIZER)
             hyperpars = self.differential_evo() if optimizer == "diffev" else self.multistart_bfgs(starts=n_starts)
         self.set_hyperparameters(hyperpars)
+        if optimise_inducing:
+            self.optimise_inducing_points(hyperpars=searched)
 
     # ---- device plumbing -----------------------------------------------------------------------------------------
     @property
@@ -153,11 +163,13 @@ class SparseGpRegressor:
             return -1e50
         return float(F)
 
-    def marginal_likelihood_gradient(self, theta):
-        """(F, dF/dtheta) with the gradient from the device; the mean parameters' part is (d mu / d theta)^T alpha."""
+    def marginal_likelihood_gradient(self, theta, inducing_points=False):
+        """(F, dF/dtheta) with the gradient from the device; the mean parameters' part is (d mu / d theta)^T alpha.
+        inducing_points=True: (F, dF/dtheta, dF/dZ) with the (m, d) gradient by the inducing inputs."""
         theta = np.asarray(theta, dtype=float)
         theta_stat, white = self._split(theta)
-        F, g, alpha, info = self.engine.bound(self._kernel_id, theta_stat, white, self.jitter, self.panel_rows, True, True)
+        F, g, alpha, info, *zgrad = self.engine.bound(self._kernel_id, theta_stat, white, self.jitter, self.panel_rows, True, True,
+                                                      want_zgrad=bool(inducing_points))
         if info != 0:
             raise LinAlgError("Matrix is not positive definite")
         grad = np.zeros(self.n_hyperpars)
@@ -168,6 +180,8 @@ class SparseGpRegressor:
         if self._wn_index is not None:
             cov_grad[self._wn_index] = g[-1]
         grad[self.cov_slice] = cov_grad
+        if inducing_points:
+            return float(F), grad, zgrad[0]
         return float(F), grad
 
     def set_hyperparameters(self, hyperpars):
@@ -180,6 +194,68 @@ class SparseGpRegressor:
         self.mean_hyperpars = hyperpars[self.mean_slice]
         self.cov_hyperpars = hyperpars[self.cov_slice]
         self.bound = float(F)
+
+    # ---- the inducing inputs ---------------------------------------------------------------------------------------
+    def _check_inducing(self, z):
+        z = np.asarray(z, dtype=float)
+        if z.ndim == 1 and self.n_dimensions == 1:
+            z = z.reshape(-1, 1)
+        if z.shape != self.inducing_points.shape:
+            raise ValueError(f"inducing points must keep their shape {self.inducing_points.shape}, got {z.shape}")
+        if not np.isfinite(z).all():
+            raise ValueError("inducing points must be finite")
+        return np.array(z, dtype=float, order="C")
+
+    def _move(self, z, hyperpars):
+        """Z and the hyper-parameters together, with one fit; a fit that fails puts the previous Z and fit back."""
+        old_z, old_hp = self.inducing_points, self.hyperpars
+        self.engine.set_inducing(z)
+        self.inducing_points = z
+        try:
+            self.set_hyperparameters(hyperpars)
+        except LinAlgError:
+            self.engine.set_inducing(old_z)
+            self.inducing_points = old_z
+            self.set_hyperparameters(old_hp)
+            raise
+
+    def set_inducing_points(self, z):
+        """Move the inducing inputs to the (m, d) finite array z (same m) and fit again at the current hyper-parameters.
+        ValueError for anything else, LinAlgError if the fit fails; both leave the previous Z and fit in place."""
+        self._move(self._check_inducing(z), self.hyperpars)
+
+    def optimise_inducing_points(self, hyperpars=True, maxiter=200):
+        """One L-BFGS-B on the device gradients from the current state, over vec(Z) or (hyperpars=True) [theta | vec(Z)]:
+        theta inside `hp_bounds`, every coordinate of Z inside the bounding box of that column of x.  Leaves the model
+        fitted at the best point found - the start, if nothing better was - and returns (F_before, F_after), also kept
+        with the number of evaluations and L-BFGS-B's warnflag in `inducing_log`."""
+        theta0, z0, F_before = np.array(self.hyperpars), self.inducing_points.copy(), self.bound
+        nh = self.n_hyperpars if hyperpars else 0
+        lo, hi = self.x.min(axis=0), self.x.max(axis=0)
+        bounds = list(self.hp_bounds[:nh]) + [(lo[k], hi[k]) for _ in range(z0.shape[0]) for k in range(z0.shape[1])]
+
+        def cost(v):
+            self.engine.set_inducing(v[nh:].reshape(z0.shape))
+            try:
+                F, g, gz = self.marginal_likelihood_gradient(v[:nh] if hyperpars else theta0, inducing_points=True)
+            except LinAlgError:
+                return 1e50, np.zeros(v.size)
+            return -F, -np.concatenate([g[:nh], gz.ravel()])
+
+        try:
+            best, _, info = fmin_l_bfgs_b(func=cost, x0=np.concatenate([theta0[:nh], z0.ravel()]), approx_grad=False,
+                                          bounds=bounds, maxiter=maxiter)
+        finally:
+            self.engine.set_inducing(z0)  # (the search moved the device's Z, not the model's)
+        try:
+            self._move(np.array(best[nh:].reshape(z0.shape), order="C"), best[:nh] if hyperpars else theta0)
+        except LinAlgError:
+            pass  # (_move has put the start back)
+        if self.bound < F_before:
+            self._move(z0, theta0)
+        self.inducing_log = dict(F_before=F_before, F_after=self.bound, evaluations=int(info["funcalls"]),
+                                 warnflag=int(info["warnflag"]))
+        return F_before, self.bound
 
     def __call__(self, points):
         """(mean, standard deviation) of the latent function at the points, as `GpRegressor.__call__`."""
