@@ -696,6 +696,52 @@ int gpmi_sgp_fit(gpmi_sgp* sgp, int kernel, const double* theta, int n_theta, do
 /* mean and variance of the latent function at mq points (panels of 1024 points); var_host may be NULL */
 int gpmi_sgp_predict(gpmi_sgp* sgp, const double* pts_host /* mq x d */, int64_t mq, double* mean_host,
                      double* var_host);
+/* ---- the fitted sparse model beyond mean and variance: joint posterior, joint draws, derivatives by the query point ----
+ * All three need a successful gpmi_sgp_fit (otherwise, and after gpmi_sgp_set_inducing without a new fit, GPMI_ERR_ARG and
+ * the object stays usable), leave the fit and every later result bit-identical, return GPMI_OK for mq == 0 without doing
+ * anything, and answer a NULL pointer that is not optional with GPMI_ERR_ARG.  They cost O(mq m^2) whatever N is.
+ *
+ * Joint posterior of the latent function (no data noise, as gpmi_posterior) at mq <= GPMI_DRAWS_MAX_M points Q.  With the
+ * rows V = [v(q_1) .. v(q_mq)]^T, U likewise (mq x m), v = L^-1 k_m(q), u = L_B^-1 v:
+ *   mean = U c,   cov = K_qq - V V^T + U U^T     (its diagonal is gpmi_sgp_predict's variance up to rounding)
+ * on the kernels of the fit: the cross builds, the two products with the kept inverses for all mq rows at once, the two
+ * Gram updates on the lower tiles (the product only subtracts: the sign of the matrix is turned in between), the mirror
+ * into the upper triangle - cov_host is symmetric bit for bit.  cov_host == NULL: the mean alone.
+ * Device memory, owned by the call and released at return: the points, V and U (mq_pad (m_pad + 32) doubles each, mq_pad =
+ * mq rounded up to 128) and, with cov_host, Sigma (mq_pad (mq_pad + 32) doubles). */
+int gpmi_sgp_posterior(gpmi_sgp* sgp, const double* pts_host /* mq x d */, int64_t mq, double* mean_host /* mq */,
+                       double* cov_host /* mq x mq, symmetric, may be NULL */);
+/* n_draws joint draws of the latent function at mq <= GPMI_DRAWS_MAX_M points: mean and Sigma as gpmi_sgp_posterior forms
+ * them stay on the device and go to the tail gpmi_posterior_draws and gpmi_mvn_draws share - D = mu + Z L^T, L L^T = Sigma +
+ * eps I, eps = jitter_rel * max_j Sigma[j][j], Z the caller's or the generator's stream.  Arguments, the generator, info
+ * (> 0: not an error status, draws_host untouched, GPMI_OK), eps_host and the invariants are gpmi_posterior_draws's; Sigma
+ * is numerically singular from a hundred points on, so jitter_rel = 0 rarely factorises.  The sparse work runs on the sparse
+ * stream and is waited for before the tail starts on the handle's first lane (created, streams and events alone, if the
+ * handle never held an exact model).  Device memory of the call: gpmi_sgp_posterior's plus the tail's (gpmi_posterior_draws),
+ * all released at return. */
+int gpmi_sgp_posterior_draws(gpmi_sgp* sgp, const double* pts_host /* mq x d */, int64_t mq, double jitter_rel,
+                             int64_t n_draws, const double* z_host /* n_draws x mq, or NULL: generated */, int64_t seed,
+                             int64_t first_draw, double* mean_host /* mq, may be NULL */,
+                             double* draws_host /* n_draws x mq */, double* eps_host /* 1, may be NULL */, int* info);
+/* d mean / d q and d var / d q at mq points (any mq: panels of 1024 points, as gpmi_sgp_predict), for all four kernels.
+ * With k(q, z) = a^2 C(s), s = 1/2 sum_k (q_k - z_k)^2 / l_k^2, g = -dC/ds (the profile of dK / d ln l_k),
+ *   gamma = L^-T L_B^-T c (kept by the fit: mean(q) = k_m(q)^T gamma),
+ *   t(q) = L^-T (L_B^-T u(q) - v(q))   (var(q) = a^2 + k_m(q)^T t(q); formed from v and u per point, as the variance is),
+ *   dmean[j][k] = -1 / l_k^2 sum_a gamma_a  a^2 g(s(q_j, z_a)) (q_jk - z_ak),
+ *   dvar [j][k] = -2 / l_k^2 sum_a t_a(q_j) a^2 g(s(q_j, z_a)) (q_jk - z_ak).
+ * Nothing is divided by a distance: a query point that is an inducing input gets an exact zero from that input.
+ * Accuracy: dmean contracts k'(q) with gamma, whose entries grow and cancel as K_mm + eps I loses condition (the mean
+ * itself, u^T c, does not): its error scales with cond(K_mm + eps I) - measured 1e-6 relative at cond 1e6 (m = 512 random
+ * rows of 1e5 points, profiles/r19_sparse_post.txt), 1e-12 at the well-conditioned shapes of the tests; dvar, formed from
+ * v and u, kept eight digits there.  Spread inducing inputs, or a larger jitter_rel, where the gradient matters.  One fused
+ * kernel forms the profile once for both sums; dvar_host == NULL skips the four products behind t and the second sum, and
+ * dmean_host has the same bits either way.  Row j of both results depends on (fit, q_j) alone: the same bits whether q_j is
+ * evaluated alone or anywhere inside a larger call, and on repeated calls - the sums over the inducing inputs have an order
+ * fixed by m alone (no atomics), the products run on tile shapes that do not depend on mq.
+ * Device memory, kept by the object from the first call on: m_pad / 128 + 1 times 2 x 1024 x d doubles (the partial sums per
+ * run of 128 inducing inputs and the panel's results), besides the three query panels of gpmi_sgp_predict. */
+int gpmi_sgp_spatial_derivatives(gpmi_sgp* sgp, const double* pts_host /* mq x d */, int64_t mq,
+                                 double* dmean_host /* mq x d */, double* dvar_host /* mq x d, may be NULL */);
 
 /* ---- instrumentation ---------------------------------------------------------------
  * HIP-event timing on the handle's own stream (torch.cuda.Event would not see it). */
@@ -734,6 +780,9 @@ int gpmi_flow_task_lists(int m, int nwg, int64_t cap, int32_t* out, int64_t* nta
 #define GPMI_PROF_SGP_GRAM 14   /* pass 1: G += (K_mn W^1/2)(K_mn W^1/2)^T, 2 N m^2 FLOP on the fp64 matrix cores */
 #define GPMI_PROF_SGP_FACTOR 15 /* the m x m algebra: two factorisations, their inverses, H, c, the reductions */
 #define GPMI_PROF_SGP_GRAD 16   /* the gradient: S, T, M2 and pass 2 (panel rebuild, T K_mn, the contractions: theta, and Z on request) */
+/* gpmi_sgp_spatial_derivatives (tools/sparse_post_bench.py) books the cross build and its four products per panel under
+ * GPMI_PROF_SGP_GRAM and the fused derivative kernel with its run sum under GPMI_PROF_SGP_GRAD; gpmi_sgp_posterior_draws
+ * books Sigma under GPMI_PROF_DRAWS_SIGMA, and its tail books the classes of gpmi_posterior_draws. */
 #define GPMI_PROF_NCLASS 17
 /* on = 0: off; 1: every class; otherwise a class bitmask shifted left by one (2 << klass) */
 int gpmi_profile_enable(gpmi_ctx* ctx, int on);

@@ -457,3 +457,11 @@ int posterior_sigma(gpmi_ctx* c, Cross&& fill_cross, Qq&& fill_qq, int64_t m, in
 }
 // posterior_sigma with the fitted kernel (or sum) at the m points pts of the host (gpmi_posterior, gpmi_posterior_draws)
 int kernel_posterior_sigma(gpmi_ctx* c, const double* pts, int64_t m, int64_t mp, double* mu_out, double* Sigma, int64_t ldq);
+
+// ---- draws.hip: what gpmi_posterior_draws, gpmi_mvn_draws and gpmi_sgp_posterior_draws share ----
+int draws_check_args(gpmi_ctx* c, int64_t m, double jitter_rel, int64_t n_draws, int64_t first_draw, const double* draws);
+// From Sigma (mp x ld on the device, lower triangle valid in the first m rows and columns; factorised in place) and mu
+// (m, device) to the draws on the host, on the stream of `lane`, whose matrices are not touched
+int draws_tail(gpmi_ctx* c, Lane& lane, double* A, int64_t ld, int64_t m, int64_t mp, const double* mu_dev, double jitter_rel,
+               int64_t n_draws, const double* z_host, int64_t seed, int64_t first_draw, double* draws_host, double* eps_host,
+               int* info);

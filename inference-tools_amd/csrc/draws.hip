@@ -86,7 +86,9 @@ __global__ __launch_bounds__(DRAWS_NT) void draws_add_mean_kernel(double* __rest
 
 unsigned blocks(int64_t n) { return (unsigned)((n + DRAWS_NT - 1) / DRAWS_NT); }
 
-// what the two device entry points share in arguments
+}  // namespace
+
+// what the device entry points share in arguments (declared in api_internal.h: sparse.hip's draws use both)
 int draws_check_args(gpmi_ctx* c, int64_t m, double jitter_rel, int64_t n_draws, int64_t first_draw, const double* draws) {
   ARGCHK(c, m >= 1 && m <= GPMI_DRAWS_MAX_M, "draws: m out of range (1 .. 16384 = GPMI_DRAWS_MAX_M points)");
   ARGCHK(c, n_draws >= 1, "draws: n_draws must be at least 1");
@@ -170,8 +172,6 @@ int draws_tail(gpmi_ctx* c, Lane& lane, double* A, int64_t ld, int64_t m, int64_
   }
   return GPMI_OK;
 }
-
-}  // namespace
 
 extern "C" {
 

@@ -15,6 +15,11 @@
 //   T = L^-T L^-1 - S;  M1 = gamma alpha^T + T K_mn W;  M2 = gamma gamma^T + K_mm^-1 G K_mm^-1 - T;
 //   dF/dtheta = sum M1 o dK_mn - 1/2 sum M2 o d(K_mm + eps I) - 1/2 sum w_i da^2/dtheta;
 //   dF/d ln s = s^2 sum_i [alpha_i^2 - w_i + w_i^2 (a^2 - k_i^T T k_i)].
+// The fitted model (L^-1, L_B^-1, c, gamma kept by gpmi_sgp_fit) answers in O(M m^2): mean and variance (gpmi_sgp_predict), the
+// joint posterior mu = U c, Sigma = K_qq - V V^T + U U^T and joint draws through the tail of draws.hip (gpmi_sgp_posterior,
+// gpmi_sgp_posterior_draws), and the derivatives of mean and variance by the query point (gpmi_sgp_spatial_derivatives):
+// four products per panel for the rows t(q)^T = (L^-T (L_B^-T u - v))^T, then sgp_qgrad_kernel, which is new - the tile scheme
+// of sgp_zcontract_kernel with one profile evaluation weighted twice, by gamma and by t(q).
 // Every reduction has a fixed order, nothing uses atomics: a call repeated gives the same bits.
 #include <limits>
 
@@ -44,8 +49,11 @@ struct gpmi_sgp {
   int64_t zws_cap = 0;
   // query staging: 1024 x d points, 2 x 1024 results
   double *q_pts = nullptr, *q_out = nullptr;
-  // the fit: L^-1, L_B^-1 (mp x ld), c (mp), the kernel
-  double *fLinv = nullptr, *fLBinv = nullptr, *fc = nullptr;
+  // the derivatives by the query point (allocated at first use): the partials per run of inducing tiles and the two
+  // results of a query panel, (mp / 128 + 1) x 2 x 1024 x d doubles
+  double* qws = nullptr;
+  // the fit: L^-1, L_B^-1 (mp x ld), c and gamma = L^-T L_B^-T c (mp each), the kernel
+  double *fLinv = nullptr, *fLBinv = nullptr, *fc = nullptr, *fgamma = nullptr;
   KParams fp = {};
   bool fitted = false;
 };
@@ -553,11 +561,198 @@ int launch_zcontract(gpmi_ctx* c, hipStream_t s, const KParams& p, const double*
   return GPMI_OK;
 }
 
+// The derivatives of the predictive mean and variance by the query point: for the 64 query points q_j of tile blockIdx.x and
+// the run blockIdx.y of QRUN_TILES consecutive 64-row tiles of the inducing inputs z_a,
+//   ws_mean[(run * nqp + j) * d + k] = -1 / l_k^2 * sum_a gamma_a  a^2 g(s(z_a, q_j)) (q_jk - z_ak),
+//   ws_var [(run * nqp + j) * d + k] = -2 / l_k^2 * sum_a Tq[j][a] a^2 g(s(z_a, q_j)) (q_jk - z_ak)      (want_var != 0),
+// with gamma = L^-T L_B^-T c (mean(q) = k_m(q)^T gamma) and the rows Tq[j] = t(q_j)^T = (L^-T (L_B^-T u(q_j) - v(q_j)))^T
+// (var(q) = a^2 + k_m(q)^T t(q)) as the products leave them, query-major.  d k(q, z_a) / d q_k = -a^2 g (q_k - z_ak) / l_k^2:
+// nothing is divided by a distance, a query point that is an inducing input gets an exact zero from it.
+// The thread layout, the staging of the two point panels ([dim][point]) and the recomputed profiles are those of
+// sgp_zcontract_kernel; the profile a^2 g is formed once and weighted twice, into two [d][64] accumulators in LDS.  The
+// column sums of a dimension go through the two xor shuffles, then the four waves through LDS: four (dimension, output)
+// slots per barrier - two dimensions of both outputs, or four of the mean alone - double-buffered; a slot's sum does not
+// depend on which of the two forms ran.  Tiles are added in ascending order; rows >= m and columns >= nq carry weight 0.
+// The order of every sum of column j is fixed by m alone: it does not depend on nq or on where q_j stands in the call.
+// Dynamic LDS: (4 d + 2 x 4 x 4) x 64 doubles - 147456 bytes (144 KiB of the CU's 160) at d = 64, one workgroup per CU
+// there; 32 KiB at d = 8.  gfx950 (kernel-resource-usage; the state is independent of d), SE / RQ / Matern32 / Matern52:
+// 130 / 172 / 130 / 130 VGPRs, no AGPRs, scratch 0, no static LDS.  VALU-bound (the fp64 exp), as the Z pass.
+constexpr int QRUN_TILES = 2;
+constexpr int QSLOTS = 4;
+
+template <int KERNEL>
+__global__ __launch_bounds__(SGP_NT) void sgp_qgrad_kernel(KParams p, const double* __restrict__ Z, int64_t m,
+                                                           const double* __restrict__ Q, int64_t nq, int64_t nqp,
+                                                           const double* __restrict__ gamma, const double* __restrict__ Tq,
+                                                           int64_t ld, int want_var, double* __restrict__ ws_mean,
+                                                           double* __restrict__ ws_var) {
+  extern __shared__ double sq_lds[];
+  const int tj = blockIdx.x, run = blockIdx.y;
+  const int tid = threadIdx.x, d = p.d;
+  double* sv = sq_lds;            // the query points
+  double* su = sv + d * KT;       // a tile of inducing inputs
+  double* acc_m = su + d * KT;
+  double* acc_v = acc_m + d * KT;
+  double* red = acc_v + d * KT;   // [2][QSLOTS][4 waves][64]
+  const int64_t j0 = (int64_t)tj * KT;
+  for (int idx = tid; idx < KT * d; idx += SGP_NT) {
+    const int pt = idx / d, k = idx - pt * d;
+    const int64_t gj = j0 + pt;
+    sv[k * KT + pt] = (gj < nq) ? Q[gj * d + k] : 0.0;
+    acc_m[idx] = 0.0;
+    acc_v[idx] = 0.0;
+  }
+  const int ty = tid >> 4, tx = tid & 15, wave = tid >> 6, lane = tid & 63;
+  const int dims = want_var ? QSLOTS / 2 : QSLOTS;  // dimensions per barrier
+  int chunk = 0;
+  for (int t = 0; t < QRUN_TILES; ++t) {
+    const int64_t i0 = ((int64_t)run * QRUN_TILES + t) * KT;
+    if (i0 >= m) break;
+    __syncthreads();  // (the previous tile's readers of su)
+    for (int idx = tid; idx < KT * d; idx += SGP_NT) {
+      const int pt = idx / d, k = idx - pt * d;
+      const int64_t gi = i0 + pt;
+      su[k * KT + pt] = (gi < m) ? Z[gi * d + k] : 0.0;
+    }
+    __syncthreads();
+    double wm[4][4], wv[4][4];  // s, then the profile times the two weights
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) wm[r][c] = 0.0;
+    for (int k = 0; k < d; ++k) {
+      const double il2 = p.inv_l2[k];
+      double ur[4], vc[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) ur[r] = su[k * KT + ty * 4 + r];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) vc[c] = sv[k * KT + tx * 4 + c];
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const double dx = ur[r] - vc[c];
+          wm[r][c] = fma(0.5 * dx * dx, il2, wm[r][c]);
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      double s8[8], C8[8], g8[8], h8[8];
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) s8[4 * r + c] = wm[2 * h + r][c];
+      kprofiles<KERNEL>(p, s8, C8, g8, h8);
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const int64_t gi = i0 + ty * 4 + 2 * h + r;
+        const double ga = (gi < m) ? gamma[gi] : 0.0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int64_t gj = j0 + tx * 4 + c;
+          const bool ok = gi < m && gj < nq;
+          const double pg = ok ? p.a2 * g8[4 * r + c] : 0.0;
+          wm[2 * h + r][c] = pg * ga;
+          wv[2 * h + r][c] = (want_var && ok) ? pg * Tq[gj * ld + gi] : 0.0;
+        }
+      }
+    }
+    for (int k0 = 0; k0 < d; k0 += dims, ++chunk) {
+      double* buf = red + (chunk & 1) * (QSLOTS * 4 * KT);
+      for (int kk = 0; kk < dims && k0 + kk < d; ++kk) {
+        const int k = k0 + kk;
+        double ur[4], cm[4], cv[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) ur[r] = su[k * KT + ty * 4 + r];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const double vc = sv[k * KT + tx * 4 + c];
+          double a = 0.0, b = 0.0;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const double dx = vc - ur[r];
+            a = fma(wm[r][c], dx, a);
+            b = fma(wv[r][c], dx, b);
+          }
+          a += __shfl_xor(a, 16, 64);
+          a += __shfl_xor(a, 32, 64);
+          cm[c] = a;
+          if (want_var) {
+            b += __shfl_xor(b, 16, 64);
+            b += __shfl_xor(b, 32, 64);
+          }
+          cv[c] = b;
+        }
+        if (lane < 16) {
+          const int slot = want_var ? 2 * kk : kk;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) buf[(slot * 4 + wave) * KT + tx * 4 + c] = cm[c];
+          if (want_var) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) buf[((slot + 1) * 4 + wave) * KT + tx * 4 + c] = cv[c];
+          }
+        }
+      }
+      __syncthreads();  // (one barrier per chunk: the other half of red is written only behind the next one)
+      const int slot = tid >> 6;
+      const int k = k0 + (want_var ? slot >> 1 : slot);
+      double* acc = (want_var && (slot & 1)) ? acc_v : acc_m;
+      if (k < d)
+        acc[k * KT + lane] += (buf[(slot * 4 + 0) * KT + lane] + buf[(slot * 4 + 1) * KT + lane]) +
+                              (buf[(slot * 4 + 2) * KT + lane] + buf[(slot * 4 + 3) * KT + lane]);
+    }
+  }
+  __syncthreads();
+  for (int idx = tid; idx < KT * d; idx += SGP_NT) {
+    const int pt = idx / d, k = idx - pt * d;
+    const int64_t o = ((int64_t)run * nqp + j0 + pt) * d + k;
+    ws_mean[o] = -p.inv_l2[k] * acc_m[k * KT + pt];
+    if (want_var) ws_var[o] = -2.0 * p.inv_l2[k] * acc_v[k * KT + pt];
+  }
+}
+
+size_t qgrad_lds_bytes(int d) { return sizeof(double) * ((size_t)4 * d + 2 * QSLOTS * 4) * KT; }
+
+// runs of inducing tiles per query tile: a function of m alone
+int qruns(int64_t mp) { return (int)((mp / KT + QRUN_TILES - 1) / QRUN_TILES); }
+
+// out_mean, out_var (nqp x d each; out_var only if want_var) = the derivatives at the nq points Q; ws_mean and ws_var hold
+// qruns(mp) x nqp x d doubles each
+int launch_qgrad(gpmi_ctx* c, hipStream_t s, const KParams& p, const double* Z, int64_t m, int64_t mp, const double* Q, int64_t nq,
+                 int64_t nqp, const double* gamma, const double* Tq, int64_t ld, bool want_var, double* ws_mean, double* ws_var,
+                 double* out_mean, double* out_var) {
+  const int nruns = qruns(mp);
+  const dim3 grid((unsigned)(nqp / KT), (unsigned)nruns);
+  const size_t lds = qgrad_lds_bytes(p.d);
+#define SGP_QGRAD(KIND)                                                                                                     \
+  do {                                                                                                                      \
+    if (lds > 65536)                                                                                                        \
+      HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&sgp_qgrad_kernel<KIND>),                                 \
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                 \
+    hipLaunchKernelGGL(sgp_qgrad_kernel<KIND>, grid, dim3(SGP_NT), lds, s, p, Z, m, Q, nq, nqp, gamma, Tq, ld, want_var ? 1 : 0, \
+                       ws_mean, ws_var);                                                                                    \
+  } while (0)
+  switch (p.kernel) {
+    case GPMI_KERNEL_SE: SGP_QGRAD(GPMI_KERNEL_SE); break;
+    case GPMI_KERNEL_RQ: SGP_QGRAD(GPMI_KERNEL_RQ); break;
+    case GPMI_KERNEL_M32: SGP_QGRAD(GPMI_KERNEL_M32); break;
+    case GPMI_KERNEL_M52: SGP_QGRAD(GPMI_KERNEL_M52); break;
+    default: break;  // (sgp_params admits no other kind)
+  }
+#undef SGP_QGRAD
+  const int64_t count = nqp * p.d;
+  const dim3 sgrid((unsigned)((count + SGP_NT - 1) / SGP_NT));
+  hipLaunchKernelGGL(sgp_zsum_kernel, sgrid, dim3(SGP_NT), 0, s, ws_mean, nruns, count, out_mean, 0);
+  if (want_var) hipLaunchKernelGGL(sgp_zsum_kernel, sgrid, dim3(SGP_NT), 0, s, ws_var, nruns, count, out_var, 0);
+  HIPCHK(c, hipGetLastError());
+  return GPMI_OK;
+}
+
 unsigned blocks(int64_t n) { return (unsigned)((n + SGP_NT - 1) / SGP_NT); }
 
 void sgp_free(gpmi_sgp* g) {
   for (double* q : {g->x, g->z, g->r, g->nv, g->w, g->alpha, g->invD1, g->invD2, g->vec, g->red, g->part, g->pvec, g->ws, g->zws, g->zacc,
-                    g->q_pts, g->q_out, g->fLinv, g->fLBinv, g->fc, g->P[0], g->P[1], g->P[2]})
+                    g->q_pts, g->q_out, g->qws, g->fLinv, g->fLBinv, g->fc, g->fgamma, g->P[0], g->P[1], g->P[2]})
     if (q) (void)hipFree(q);
   for (double* q : g->M)
     if (q) (void)hipFree(q);
@@ -649,7 +844,7 @@ int read_info(gpmi_sgp* g, int slot, int& inf) {
   return GPMI_OK;
 }
 
-// Pass 1 and the m x m algebra.  info = 0: M[MLINV], M[MLBINV], M[MLIT], vec (b, L^-1 b, c) and *F are valid.
+// Pass 1 and the m x m algebra.  info = 0: M[MLINV], M[MLBINV], M[MLIT], M[MW3] (L_B^-T), vec (b, L^-1 b, c) and *F are valid.
 int sgp_factor(gpmi_sgp* g, const KParams& p, double white, double jitter, int64_t panel_rows, double* F, double* sum_w,
                int* info) {
   gpmi_ctx* c = g->ctx;
@@ -848,6 +1043,7 @@ int gpmi_sgp_create(gpmi_ctx* c, int64_t n, int64_t d, const double* x, int64_t 
   for (double** q : {&g->fLinv, &g->fLBinv})
     if (e == hipSuccess) e = alloc(*q, sizeof(double) * mp * ld);
   if (e == hipSuccess) e = alloc(g->fc, sizeof(double) * mp);
+  if (e == hipSuccess) e = alloc(g->fgamma, sizeof(double) * mp);
   if (e == hipSuccess) e = alloc(g->invD1, sizeof(double) * nd);
   if (e == hipSuccess) e = alloc(g->invD2, sizeof(double) * nd);
   if (e == hipSuccess) e = alloc(g->vec, sizeof(double) * 4 * mp);
@@ -983,6 +1179,9 @@ int gpmi_sgp_fit(gpmi_sgp* g, int kernel, const double* theta, int n_theta, doub
   launch_copy_rows(s, g->M[MLINV], g->ld, g->fLinv, g->ld, g->mp, g->mp);
   launch_copy_rows(s, g->M[MLBINV], g->ld, g->fLBinv, g->ld, g->mp, g->mp);
   launch_copy(s, g->vec + 2 * g->mp, g->fc, g->mp);
+  // gamma = L^-T (L_B^-T c) from the two transposes sgp_factor left (the gradient path, which forms it too, did not run)
+  launch_rows_dot(s, g->M[MW3], g->ld, g->mp, g->mp, g->fc, g->vec + 3 * g->mp);
+  launch_rows_dot(s, g->M[MLIT], g->ld, g->mp, g->mp, g->vec + 3 * g->mp, g->fgamma);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(s));
   g->fp = p;
@@ -1018,6 +1217,181 @@ int gpmi_sgp_predict(gpmi_sgp* g, const double* pts, int64_t mq, double* mean, d
     if (var) HIPCHK(c, hipMemcpyAsync(var + q0, g->q_out + SGP_QPANEL, sizeof(double) * rows, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));  // (the next panel overwrites the staging)
   }
+  return GPMI_OK;
+}
+
+int gpmi_sgp_spatial_derivatives(gpmi_sgp* g, const double* pts, int64_t mq, double* dmean, double* dvar) {
+  if (!g) return GPMI_ERR_ARG;
+  gpmi_ctx* c = g->ctx;
+  ARGCHK(c, sgp_live(c, g), "gpmi_sgp_spatial_derivatives: not a live object of this handle");
+  ARGCHK(c, g->fitted, "gpmi_sgp_spatial_derivatives needs a successful gpmi_sgp_fit");
+  ARGCHK(c, mq >= 0, "gpmi_sgp_spatial_derivatives: mq must not be negative");
+  if (mq == 0) return GPMI_OK;
+  ARGCHK(c, pts != nullptr && dmean != nullptr, "gpmi_sgp_spatial_derivatives: pts_host and dmean_host must be non-NULL");
+  if (int rc = set_device(c)) return rc;
+  if (int rc = sgp_ensure_panels(g, SGP_QPANEL)) return rc;
+  const int64_t m = g->m, mp = g->mp, ld = g->ld, d = g->d;
+  const int64_t per = (int64_t)SGP_QPANEL * d;  // one result, or one run's partials, of a panel
+  if (!g->qws) HIPCHK(c, hipMalloc(&g->qws, sizeof(double) * 2 * (qruns(mp) + 1) * per));
+  double *ws_mean = g->qws, *ws_var = ws_mean + qruns(mp) * per, *out_mean = ws_var + qruns(mp) * per, *out_var = out_mean + per;
+  hipStream_t s = c->sgp_stream;
+  const int nt = (int)(mp / GPMI_NB);
+  // ring_order_only: a row of a product must not depend on the number of row tiles (gpmi_internal.h: GemmBatch)
+  GemmBatch gb;
+  gb.ring_order_only = true;
+  for (int64_t q0 = 0; q0 < mq; q0 += SGP_QPANEL) {
+    const int64_t rows = std::min<int64_t>(SGP_QPANEL, mq - q0), rp = round_up(rows, GPMI_NB), nqp = round_up(rows, KT);
+    const int ntr = (int)(rp / GPMI_NB);
+    double *Kq = g->P[0], *V = g->P[1], *U = g->P[2], *W = g->P[0], *D = g->P[2], *Tq = g->P[1];
+    HIPCHK(c, hipMemcpyAsync(g->q_pts, pts + q0 * d, sizeof(double) * rows * d, hipMemcpyHostToDevice, s));
+    if (dvar) {
+      // (profile classes: the products under GPMI_PROF_SGP_GRAM, the fused kernel under GPMI_PROF_SGP_GRAD)
+      ProfScope ps(c, s, GPMI_PROF_SGP_GRAM, 8.0 * rp * mp * mp, 8.0 * 6.0 * rp * mp);
+      launch_kbuild_cross(s, g->fp, g->q_pts, rows, rp, g->z, m, mp, Kq, ld);
+      launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, V, ld, Kq, ld, g->fLinv, ld, ntr, nt, (int)mp, nullptr, gb);   // rows v^T
+      launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, U, ld, V, ld, g->fLBinv, ld, ntr, nt, (int)mp, nullptr, gb);  // rows u^T
+      // the same two inverses the other way round (B k-major: no transposes are stored): rows (L_B^-T u)^T, then t^T
+      launch_gemm(s, TILES_RECT, OP_ASSIGN, true, 0, W, ld, U, ld, g->fLBinv, ld, ntr, nt, (int)mp, nullptr, gb);
+      hipLaunchKernelGGL(sgp_sub_kernel, dim3(blocks(mp), (unsigned)rp), dim3(SGP_NT), 0, s, W, V, D, ld, mp);
+      launch_gemm(s, TILES_RECT, OP_ASSIGN, true, 0, Tq, ld, D, ld, g->fLinv, ld, ntr, nt, (int)mp, nullptr, gb);
+      HIPCHK(c, hipGetLastError());
+    }
+    {
+      ProfScope ps(c, s, GPMI_PROF_SGP_GRAD, 0.0, 0.0);
+      if (int rc = launch_qgrad(c, s, g->fp, g->z, m, mp, g->q_pts, rows, nqp, g->fgamma, Tq, ld, dvar != nullptr, ws_mean, ws_var,
+                                out_mean, out_var))
+        return rc;
+    }
+    HIPCHK(c, hipMemcpyAsync(dmean + q0 * d, out_mean, sizeof(double) * rows * d, hipMemcpyDeviceToHost, s));
+    if (dvar) HIPCHK(c, hipMemcpyAsync(dvar + q0 * d, out_var, sizeof(double) * rows * d, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));  // (the next panel overwrites the staging)
+  }
+  return GPMI_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// mu (mq, device) and Sigma (mp x ldq, lower tiles; Sigma == nullptr: the mean alone) of the latent function at the mq
+// points of the host, enqueued on the sparse stream.  VU: two matrices of mp x ld(m) doubles.
+int sgp_posterior_sigma(gpmi_sgp* g, const double* pts, int64_t mq, int64_t mpq, double* pts_dev, double* VU, double* mu_dev,
+                        double* Sigma, int64_t ldq) {
+  gpmi_ctx* c = g->ctx;
+  hipStream_t s = c->sgp_stream;
+  const int64_t m = g->m, mp = g->mp, ld = g->ld, d = g->d;
+  const int nt = (int)(mp / GPMI_NB), ntq = (int)(mpq / GPMI_NB);
+  double *V = VU, *U = VU + mpq * ld;
+  HIPCHK(c, hipMemcpyAsync(pts_dev, pts, sizeof(double) * mq * d, hipMemcpyHostToDevice, s));
+  launch_kbuild_cross(s, g->fp, pts_dev, mq, mpq, g->z, m, mp, U, ld);  // K_qm, in the place U takes below
+  launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, V, ld, U, ld, g->fLinv, ld, ntq, nt, (int)mp);   // rows (L^-1 k_q)^T
+  launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, U, ld, V, ld, g->fLBinv, ld, ntq, nt, (int)mp);  // rows (L_B^-1 v)^T
+  launch_rows_dot(s, U, ld, mpq, mp, g->fc, mu_dev);
+  if (Sigma) {
+    // Sigma = K_qq - V V^T + U U^T on the lower tiles; the product only subtracts, so the sign is turned in between
+    launch_kbuild_cross(s, g->fp, pts_dev, mq, mpq, pts_dev, mq, mpq, Sigma, ldq);
+    launch_gemm_nt(s, TILES_LOWER, OP_SUB, Sigma, ldq, V, ld, V, ld, ntq, ntq, (int)mp);
+    launch_negate(s, Sigma, mpq * ldq);
+    launch_gemm_nt(s, TILES_LOWER, OP_SUB, Sigma, ldq, U, ld, U, ld, ntq, ntq, (int)mp);
+    launch_negate(s, Sigma, mpq * ldq);
+  }
+  HIPCHK(c, hipGetLastError());
+  return GPMI_OK;
+}
+
+int sgp_cov_args(gpmi_sgp* g, const char* who, int64_t mq) {
+  gpmi_ctx* c = g->ctx;
+  if (!sgp_live(c, g)) {
+    c->err = std::string(who) + ": not a live object of this handle";
+    return GPMI_ERR_ARG;
+  }
+  if (!g->fitted) {
+    c->err = std::string(who) + " needs a successful gpmi_sgp_fit";
+    return GPMI_ERR_ARG;
+  }
+  if (mq < 0 || mq > GPMI_DRAWS_MAX_M) {
+    c->err = std::string(who) + ": mq out of range (0 .. 16384 = GPMI_DRAWS_MAX_M points)";
+    return GPMI_ERR_ARG;
+  }
+  return GPMI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gpmi_sgp_posterior(gpmi_sgp* g, const double* pts, int64_t mq, double* mean, double* cov) {
+  if (!g) return GPMI_ERR_ARG;
+  gpmi_ctx* c = g->ctx;
+  if (int rc = sgp_cov_args(g, "gpmi_sgp_posterior", mq)) return rc;
+  if (mq == 0) return GPMI_OK;
+  ARGCHK(c, pts != nullptr && mean != nullptr, "gpmi_sgp_posterior: pts_host and mean_host must be non-NULL");
+  if (int rc = set_device(c)) return rc;
+  hipStream_t s = c->sgp_stream;
+  const int64_t mpq = round_up(mq, GPMI_NB), ldq = mpq + 32;
+  // (an error return below may leave work on these in flight: hipFree waits for the device before it releases)
+  DevBuf P, VU, mu, Sigma;
+  HIPCHK(c, hipMalloc(&P.p, sizeof(double) * mpq * g->d));
+  HIPCHK(c, hipMalloc(&VU.p, sizeof(double) * 2 * mpq * g->ld));
+  HIPCHK(c, hipMalloc(&mu.p, sizeof(double) * mpq));
+  if (cov) HIPCHK(c, hipMalloc(&Sigma.p, sizeof(double) * mpq * ldq));
+  int rc = sgp_posterior_sigma(g, pts, mq, mpq, P.as<double>(), VU.as<double>(), mu.as<double>(), Sigma.as<double>(), ldq);
+  hipError_t e = hipSuccess;
+  if (rc == GPMI_OK) {
+    e = hipMemcpyAsync(mean, mu.p, sizeof(double) * mq, hipMemcpyDeviceToHost, s);
+    if (cov && e == hipSuccess) {
+      launch_mirror_lower(s, Sigma.as<double>(), ldq, mpq);
+      e = hipMemcpy2DAsync(cov, sizeof(double) * mq, Sigma.p, sizeof(double) * ldq, sizeof(double) * mq, (size_t)mq,
+                           hipMemcpyDeviceToHost, s);
+    }
+  }
+  const hipError_t e2 = hipStreamSynchronize(s);  // (before the buffers are released, whatever happened)
+  if (rc != GPMI_OK) return rc;
+  HIPCHK(c, e);
+  HIPCHK(c, e2);
+  return GPMI_OK;
+}
+
+int gpmi_sgp_posterior_draws(gpmi_sgp* g, const double* pts, int64_t mq, double jitter_rel, int64_t n_draws, const double* z_host,
+                             int64_t seed, int64_t first_draw, double* mean, double* draws_host, double* eps_host, int* info) {
+  if (!g) return GPMI_ERR_ARG;
+  gpmi_ctx* c = g->ctx;
+  if (int rc = sgp_cov_args(g, "gpmi_sgp_posterior_draws", mq)) return rc;
+  if (mq == 0) return GPMI_OK;
+  if (int rc = draws_check_args(c, mq, jitter_rel, n_draws, first_draw, draws_host)) return rc;
+  ARGCHK(c, pts != nullptr, "gpmi_sgp_posterior_draws: pts_host is NULL");
+  if (int rc = set_device(c)) return rc;
+  if (info) *info = 0;
+  if (c->lanes.empty()) {
+    // a handle that only ever served sparse models: a lane of streams and events alone is all the tail needs (gpmi_mvn_draws)
+    c->lanes.emplace_back();
+    if (int rc = lane_streams(c, c->lanes[0])) return rc;
+  }
+  Lane& L = c->lanes[0];
+  const int64_t mpq = round_up(mq, GPMI_NB), ldq = mpq + 32;
+  DevBuf P, VU, mu, Sigma;
+  HIPCHK(c, hipMalloc(&P.p, sizeof(double) * mpq * g->d));
+  HIPCHK(c, hipMalloc(&VU.p, sizeof(double) * 2 * mpq * g->ld));
+  HIPCHK(c, hipMalloc(&mu.p, sizeof(double) * mpq));
+  HIPCHK(c, hipMalloc(&Sigma.p, sizeof(double) * mpq * ldq));
+  int rc;
+  {
+    ProfScope ps(c, c->sgp_stream, GPMI_PROF_DRAWS_SIGMA, 4.0 * mpq * g->mp * g->mp + 2.0 * mpq * mpq * g->mp,
+                 8.0 * mpq * (2.0 * g->mp + mpq));
+    rc = sgp_posterior_sigma(g, pts, mq, mpq, P.as<double>(), VU.as<double>(), mu.as<double>(), Sigma.as<double>(), ldq);
+  }
+  hipError_t e = hipSuccess;
+  if (rc == GPMI_OK && mean) e = hipMemcpyAsync(mean, mu.p, sizeof(double) * mq, hipMemcpyDeviceToHost, c->sgp_stream);
+  // the tail runs on the lane's stream: Sigma and mu are complete before it reads them
+  const hipError_t e1 = hipStreamSynchronize(c->sgp_stream);
+  if (rc == GPMI_OK && e == hipSuccess && e1 == hipSuccess)
+    rc = draws_tail(c, L, Sigma.as<double>(), ldq, mq, mpq, mu.as<double>(), jitter_rel, n_draws, z_host, seed, first_draw,
+                    draws_host, eps_host, info);
+  const hipError_t e2 = hipStreamSynchronize(L.stream);  // (before Sigma is released, whatever the tail returned)
+  if (rc != GPMI_OK) return rc;
+  HIPCHK(c, e);
+  HIPCHK(c, e1);
+  HIPCHK(c, e2);
   return GPMI_OK;
 }
 

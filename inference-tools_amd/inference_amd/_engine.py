@@ -740,6 +740,37 @@ class SparseEngine:
         self._call("gpmi_sgp_predict", dptr(pts), pts.shape[0], dptr(mean), dptr(var))
         return mean, var
 
+    def posterior(self, pts, mean_only=False):
+        """gpmi_sgp_posterior: (mean (M,), covariance (M, M) | None) of the latent function at `pts`, without the mean
+        function."""
+        pts = as_f64(pts)
+        m = pts.shape[0]
+        mu = np.zeros(m)
+        cov = None if mean_only else np.zeros((m, m))
+        self._call("gpmi_sgp_posterior", dptr(pts), m, dptr(mu), dptr(cov))
+        return mu, cov
+
+    def posterior_draws(self, pts, n_draws=1, seed=0, z=None, jitter=1e-9, first_draw=0):
+        """gpmi_sgp_posterior_draws: arguments and the result (draws | None, mu (M,), eps, info) as
+        `GpEngine.posterior_draws`."""
+        pts = as_f64(pts)
+        m = pts.shape[0]
+        z = None if z is None else as_f64(z).reshape(int(n_draws), m)
+        mu, draws = np.zeros(m), np.zeros((int(n_draws), m))
+        eps, info = C.c_double(0.0), C.c_int(0)
+        self._call("gpmi_sgp_posterior_draws", dptr(pts), m, float(jitter), int(n_draws), dptr(z), _seed_i64(seed),
+                   int(first_draw), dptr(mu), dptr(draws), C.byref(eps), C.byref(info))
+        return (draws if info.value == 0 else None), mu, eps.value, info.value
+
+    def spatial_derivatives(self, pts, want_var=True):
+        """gpmi_sgp_spatial_derivatives: (d mean / d q (M, d), d var / d q (M, d) | None)."""
+        pts = as_f64(pts)
+        m = pts.shape[0]
+        dmu = np.zeros((m, self.d))
+        dvar = np.zeros((m, self.d)) if want_var else None
+        self._call("gpmi_sgp_spatial_derivatives", dptr(pts), m, dptr(dmu), dptr(dvar))
+        return dmu, dvar
+
     def profile_stages(self, on):
         """HIP-event timing of the four stages (GPMI_PROF_SGP_*) on or off; `stage_ms` reads and resets them."""
         mask = 0

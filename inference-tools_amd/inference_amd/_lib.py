@@ -148,6 +148,9 @@ SIGNATURES = {
     "gpmi_sgp_set_inducing": (C.c_int, [_vp, _dp]),
     "gpmi_sgp_fit": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, _i64, _dp, _ip]),
     "gpmi_sgp_predict": (C.c_int, [_vp, _dp, _i64, _dp, _dp]),
+    "gpmi_sgp_posterior": (C.c_int, [_vp, _dp, _i64, _dp, _dp]),
+    "gpmi_sgp_posterior_draws": (C.c_int, [_vp, _dp, _i64, C.c_double, _i64, _dp, _i64, _i64, _dp, _dp, _dp, _ip]),
+    "gpmi_sgp_spatial_derivatives": (C.c_int, [_vp, _dp, _i64, _dp, _dp]),
     "gpmi_timer_start": (C.c_int, [_vp]),
     "gpmi_timer_stop": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "gpmi_profile_enable": (C.c_int, [_vp, C.c_int]),

@@ -13,7 +13,11 @@ L-BFGS-B over vec(Z), or over [theta | vec(Z)] jointly, every coordinate of Z in
 
 Supported: one of SquaredExponential, RationalQuadratic, Matern32, Matern52 (class or instance), optionally
 `+ WhiteNoise()`; the mean functions of `inference_amd.gp.mean` (evaluated on the host); data errors `y_err`.
-Not supported: FITC, spatial derivatives, posterior draws, `GpOptimiser`, several GPUs.
+The fitted model answers what `GpRegressor` answers, at O(M m^2) per call whatever N is: `build_posterior` (mean and
+joint covariance), `sample_posterior` (joint draws; the covariance and the normals stay on the device),
+`spatial_derivatives` / `spatial_derivatives_batch` (gradients of the predictive mean and variance, all four kernels) -
+and through them the acquisition functions of `inference_amd.gp.acquisition` (`update_gp(sparse_model)`).
+Not supported: FITC, `gradient` (the covariance of the gradient), `GpOptimiser`, several GPUs.
 """
 from copy import copy
 from inspect import isclass
@@ -27,6 +31,7 @@ from scipy.optimize import differential_evolution, fmin_l_bfgs_b
 from inference_amd import _lib
 from inference_amd._engine import SparseEngine
 from inference_amd.gp import _messages as msg
+from inference_amd.gp._draws import draw_arguments, raise_if_not_positive_definite
 from inference_amd.gp.covariance import (CompositeCovariance, SquaredExponential, WhiteNoise, _StationaryDeviceKernel,
                                          device_plan)
 from inference_amd.gp.mean import ConstantMean
@@ -138,6 +143,8 @@ class SparseGpRegressor:
     def engine(self) -> SparseEngine:
         if self._engine is None:
             self._engine = SparseEngine(self.x, self.inducing_points, device=self._device)
+            if "hyperpars" in self.__dict__:  # (a model back from pickle: the fit goes with the new engine)
+                self.set_hyperparameters(self.hyperpars)
         return self._engine
 
     def _split(self, theta):
@@ -262,6 +269,53 @@ class SparseGpRegressor:
         q = np.ascontiguousarray(GpRegressor.process_points(self, points), dtype=float)
         mean, var = self.engine.predict(q)
         return mean + GpRegressor._mean_at(self, q), np.sqrt(np.abs(var))
+
+    # ---- the fitted model beyond mean and standard deviation (as GpRegressor) ---------------------------------------
+    def process_points(self, points):
+        """Bring query points to shape (M, d), as `GpRegressor.process_points`."""
+        return GpRegressor.process_points(self, points)
+
+    def _query(self, points):
+        return np.ascontiguousarray(self.process_points(points), dtype=float)
+
+    def build_posterior(self, points, mean_only=False):
+        """Posterior mean vector (with the mean function) and covariance matrix of the latent function at the M points,
+        as `GpRegressor.build_posterior`: mu = U c, Sigma = K_qq - V V^T + U U^T (include/gpmi.h: gpmi_sgp_posterior)."""
+        q = self._query(points)
+        mu, sigma = self.engine.posterior(q, mean_only=mean_only)
+        mu = mu + GpRegressor._mean_at(self, q)
+        if mean_only:
+            return mu
+        return mu, sigma
+
+    def sample_posterior(self, points, n_draws=1, *, seed=None, z=None, jitter=1e-9, first_draw=0):
+        """`n_draws` joint draws of the latent function at the M `points`, shape (n_draws, M): mu + z_s L^T with
+        L L^T = Sigma + eps I for the mean and covariance of `build_posterior` and eps = jitter * max diag(Sigma), on the
+        device.  Arguments, the generator's stream and `last_sample_seed` as `GpRegressor.sample_posterior`.  Sigma is
+        numerically singular from about a hundred points on: keep a positive `jitter`.
+        Raises numpy.linalg.LinAlgError if Sigma + eps I is not positive definite."""
+        q = self._query(points)
+        n_draws, seed, z, jitter, first_draw = draw_arguments("SparseGpRegressor", len(q), n_draws, seed, z, jitter, first_draw)
+        draws, _, eps, info = self.engine.posterior_draws(q, n_draws=n_draws, seed=0 if seed is None else seed, z=z,
+                                                          jitter=jitter, first_draw=first_draw)
+        if info == 0:
+            draws += GpRegressor._mean_at(self, q)
+        self.last_sample_seed = seed
+        raise_if_not_positive_definite("SparseGpRegressor", info, jitter, eps)
+        return draws
+
+    def spatial_derivatives(self, points):
+        """Gradients of the predictive mean and variance at the points, squeezed as `GpRegressor.spatial_derivatives`
+        (all four kernels, RationalQuadratic included).  As there, the derivative of the mean function is not added: the
+        results are those of the zero-mean latent part, exact for `ConstantMean`.  The accuracy of the mean's gradient
+        scales with cond(K_mm + eps I) (include/gpmi.h): about 1e-6 relative at cond 1e6."""
+        dmu, dvar = self.engine.spatial_derivatives(self._query(points))
+        return dmu.squeeze(), dvar.squeeze()
+
+    def spatial_derivatives_batch(self, points):
+        """`spatial_derivatives` for M points with un-squeezed (M, d) results: the form the batched acquisition functions
+        consume.  Row j depends on (fit, point j) alone, bit for bit."""
+        return self.engine.spatial_derivatives(self._query(points))
 
     # ---- hyper-parameter search (as GpRegressor: SciPy on the host, every evaluation on the device) ----------------
     def bfgs_cost_func(self, theta):
