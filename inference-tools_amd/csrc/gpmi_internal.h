@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "gpmi.h"
@@ -42,6 +43,18 @@ __host__ __device__ inline int kernel_theta_offset(int kernel) {
 __host__ __device__ inline bool kernel_is_stationary(int kernel) { return kernel_theta_offset(kernel) > 0; }
 __host__ __device__ inline bool kernel_is_matern(int kernel) {
   return kernel == GPMI_KERNEL_M32 || kernel == GPMI_KERNEL_M52;
+}
+// The kernel id as a compile-time constant: f(K) with decltype(K)::value the id, for the kernels that take it as a
+// template parameter.  false (f not called): not a stationary kernel.
+template <class F>
+inline bool with_stationary_kernel(int kernel, F&& f) {
+  switch (kernel) {
+    case GPMI_KERNEL_SE: f(std::integral_constant<int, GPMI_KERNEL_SE>()); return true;
+    case GPMI_KERNEL_RQ: f(std::integral_constant<int, GPMI_KERNEL_RQ>()); return true;
+    case GPMI_KERNEL_M32: f(std::integral_constant<int, GPMI_KERNEL_M32>()); return true;
+    case GPMI_KERNEL_M52: f(std::integral_constant<int, GPMI_KERNEL_M52>()); return true;
+    default: return false;
+  }
 }
 
 // A covariance evaluation the entry points hold: one stationary kernel (the KParams base, nk = 0), or a sum of nk = 2..4 of

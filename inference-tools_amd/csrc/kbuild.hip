@@ -7,15 +7,14 @@
 #include <cassert>
 
 #include "gpmi_internal.h"
-#include "kfun.h"
-#include "kmath.h"
+#include "pair_tile.h"
 
 namespace {
 
-constexpr int KT = 64;  // output tile edge
+using pair_tile::KT;  // output tile edge
 
-// kfun, the covariance function of N elements at once, and its kinds KFUN_M32_G / KFUN_M52_G: kfun.h (shared with
-// sparse.hip)
+// The tile (staging, the thread's 4 x 4 block, s, the covariance function in two halves): pair_tile.h, shared with
+// sparse.hip.  kfun and its kinds KFUN_M32_G / KFUN_M52_G: kfun.h.
 
 // SQUARE: U == V, jitter + noise on the diagonal, identity in the padding (rows/cols >= n).
 template <bool SQUARE, int KERNEL>
@@ -84,48 +83,12 @@ __device__ inline void kbuild_body(const KParams& p, const double* __restrict__ 
   double* su = kb_lds;
   double* sv = kb_lds + d * KT;
   const int64_t i0 = (int64_t)ti * KT, j0 = (int64_t)tj * KT;
-  // stage panels transposed: s[k][pt]
-  for (int idx = tid; idx < KT * d; idx += 256) {
-    int pt = idx / d, k = idx - pt * d;
-    int64_t gi = i0 + pt, gj = j0 + pt;
-    su[k * KT + pt] = (gi < nu) ? U[gi * d + k] : 0.0;
-    sv[k * KT + pt] = (gj < nv) ? V[gj * d + k] : 0.0;
-  }
+  pair_tile::stage_panels(su, U, i0, nu, sv, V, j0, nv, d);
   __syncthreads();
-  const int ty = tid >> 4, tx = tid & 15;
-  double s[4][4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) s[r][c] = 0.0;
-  for (int k = 0; k < d; ++k) {
-    const double il2 = p.inv_l2[k];
-    double ur[4], vc[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) ur[r] = su[k * KT + ty * 4 + r];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) vc[c] = sv[k * KT + tx * 4 + c];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        double dx = ur[r] - vc[c];
-        s[r][c] = fma(0.5 * dx * dx, il2, s[r][c]);  // distances_k / l_k^2 accumulated (covariance.py:254)
-      }
-  }
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {  // two halves of eight elements: 16 at once cost occupancy, 8 already amortise the constants
-    double sv8[8], cf8[8];
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) sv8[4 * r + c] = s[2 * h + r][c];
-    kfun<KERNEL>(p, sv8, cf8);
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) s[2 * h + r][c] = cf8[4 * r + c];
-  }
+  const int ty = pair_tile::thread_row(tid), tx = pair_tile::thread_col(tid);
+  double s[4][4];  // s, then the covariance function of it
+  pair_tile::accumulate_s(p.inv_l2, d, su, sv, ty, tx, s);
+  pair_tile::for_each_profile<KERNEL, false>(p, s, [&](int r, int c, double C) { s[r][c] = C; });
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int64_t gi = i0 + ty * 4 + r;
@@ -202,12 +165,7 @@ __device__ __forceinline__ void ksum_body(const CovParams& p, const double* __re
   double* su = ks_lds;
   double* sv = ks_lds + d * KT;
   const int64_t i0 = (int64_t)ti * KT, j0 = (int64_t)tj * KT;
-  for (int idx = tid; idx < KT * d; idx += 256) {
-    int pt = idx / d, k = idx - pt * d;
-    int64_t gi = i0 + pt, gj = j0 + pt;
-    su[k * KT + pt] = (gi < nu) ? U[gi * d + k] : 0.0;
-    sv[k * KT + pt] = (gj < nv) ? V[gj * d + k] : 0.0;
-  }
+  pair_tile::stage_panels(su, U, i0, nu, sv, V, j0, nv, d);
   __syncthreads();
   const int ty = tid >> 4, tx = tid & 15;
   const int nk = __builtin_amdgcn_readfirstlane(p.nk);
@@ -318,26 +276,11 @@ static size_t kb_lds_bytes(int d) { return sizeof(double) * 2 * (size_t)d * KT; 
 template <bool SQUARE>
 static void launch_kb(dim3 grid, hipStream_t s, const KParams& p, const double* U, int64_t nu, const double* V,
                       int64_t nv, const double* noise, double* out, int64_t ld, int lower_only) {
-  assert(kernel_is_stationary(p.kernel) && "a sum of kernels must be passed as a CovParams");
-  switch (p.kernel) {
-    case GPMI_KERNEL_SE:
-      hipLaunchKernelGGL((kbuild_kernel<SQUARE, GPMI_KERNEL_SE>), grid, dim3(256), kb_lds_bytes(p.d), s, p, U, nu, V, nv,
-                         noise, out, ld, lower_only);
-      break;
-    case GPMI_KERNEL_RQ:
-      hipLaunchKernelGGL((kbuild_kernel<SQUARE, GPMI_KERNEL_RQ>), grid, dim3(256), kb_lds_bytes(p.d), s, p, U, nu, V, nv,
-                         noise, out, ld, lower_only);
-      break;
-    case GPMI_KERNEL_M32:
-      hipLaunchKernelGGL((kbuild_kernel<SQUARE, GPMI_KERNEL_M32>), grid, dim3(256), kb_lds_bytes(p.d), s, p, U, nu, V, nv,
-                         noise, out, ld, lower_only);
-      break;
-    case GPMI_KERNEL_M52:
-      hipLaunchKernelGGL((kbuild_kernel<SQUARE, GPMI_KERNEL_M52>), grid, dim3(256), kb_lds_bytes(p.d), s, p, U, nu, V, nv,
-                         noise, out, ld, lower_only);
-      break;
-    default: break;  // (make_params admits no other kind)
-  }
+  [[maybe_unused]] const bool ok = with_stationary_kernel(p.kernel, [&](auto K) {
+    hipLaunchKernelGGL((kbuild_kernel<SQUARE, decltype(K)::value>), grid, dim3(256), kb_lds_bytes(p.d), s, p, U, nu, V, nv,
+                       noise, out, ld, lower_only);
+  });
+  assert(ok && "a sum of kernels must be passed as a CovParams");  // (make_params admits no other kind)
 }
 
 // a CovParams: the fused build of its sum, or the single-kernel build of its base
@@ -402,28 +345,13 @@ void launch_kbuild_square_part(hipStream_t s, const CovParams& p, const double* 
 void launch_kbuild_square_batched(hipStream_t s, int kernel, const KParams* pdev, int batch, const double* x,
                                   int64_t n, int64_t np, const double* noise, double* A, int64_t ld,
                                   int64_t stride, int d, int64_t noise_stride) {
-  assert(kernel_is_stationary(kernel) && "a batch of sums is an array of CovParams");
   const unsigned nt = (unsigned)(np / KT);
   dim3 grid(nt * (nt + 1) / 2, 1, (unsigned)batch);  // lower tiles only, one-dimensional (kbuild_body, mode 2)
-  switch (kernel) {
-    case GPMI_KERNEL_SE:
-      hipLaunchKernelGGL(kbuild_batched_kernel<GPMI_KERNEL_SE>, grid, dim3(256), kb_lds_bytes(d), s, pdev, x, n, noise, A,
-                         ld, stride, noise_stride);
-      break;
-    case GPMI_KERNEL_RQ:
-      hipLaunchKernelGGL(kbuild_batched_kernel<GPMI_KERNEL_RQ>, grid, dim3(256), kb_lds_bytes(d), s, pdev, x, n, noise, A,
-                         ld, stride, noise_stride);
-      break;
-    case GPMI_KERNEL_M32:
-      hipLaunchKernelGGL(kbuild_batched_kernel<GPMI_KERNEL_M32>, grid, dim3(256), kb_lds_bytes(d), s, pdev, x, n, noise, A,
-                         ld, stride, noise_stride);
-      break;
-    case GPMI_KERNEL_M52:
-      hipLaunchKernelGGL(kbuild_batched_kernel<GPMI_KERNEL_M52>, grid, dim3(256), kb_lds_bytes(d), s, pdev, x, n, noise, A,
-                         ld, stride, noise_stride);
-      break;
-    default: break;
-  }
+  [[maybe_unused]] const bool ok = with_stationary_kernel(kernel, [&](auto K) {
+    hipLaunchKernelGGL(kbuild_batched_kernel<decltype(K)::value>, grid, dim3(256), kb_lds_bytes(d), s, pdev, x, n, noise, A,
+                       ld, stride, noise_stride);
+  });
+  assert(ok && "a batch of sums is an array of CovParams");
 }
 
 // a batch of sums (every pdev[z] of kind GPMI_KERNEL_SUM; the data variances are shared)
@@ -461,27 +389,12 @@ void launch_kbuild_cross_dprofile(hipStream_t s, const KParams& p, const double*
 void launch_kbuild_cross_batched(hipStream_t s, int kernel, const KParams* pdev, int batch, const double* U, int64_t mu,
                                  int64_t mp, const double* V, int64_t n, int64_t np, double* out, int64_t ld,
                                  int64_t stride, int d) {
-  assert(kernel_is_stationary(kernel) && "a batch of sums is an array of CovParams");
   dim3 grid((unsigned)(np / KT), (unsigned)(mp / KT), (unsigned)batch);
-  switch (kernel) {
-    case GPMI_KERNEL_SE:
-      hipLaunchKernelGGL(kbuild_cross_batched_kernel<GPMI_KERNEL_SE>, grid, dim3(256), kb_lds_bytes(d), s, pdev, U, mu, V,
-                         n, out, ld, stride);
-      break;
-    case GPMI_KERNEL_RQ:
-      hipLaunchKernelGGL(kbuild_cross_batched_kernel<GPMI_KERNEL_RQ>, grid, dim3(256), kb_lds_bytes(d), s, pdev, U, mu, V,
-                         n, out, ld, stride);
-      break;
-    case GPMI_KERNEL_M32:
-      hipLaunchKernelGGL(kbuild_cross_batched_kernel<GPMI_KERNEL_M32>, grid, dim3(256), kb_lds_bytes(d), s, pdev, U, mu, V,
-                         n, out, ld, stride);
-      break;
-    case GPMI_KERNEL_M52:
-      hipLaunchKernelGGL(kbuild_cross_batched_kernel<GPMI_KERNEL_M52>, grid, dim3(256), kb_lds_bytes(d), s, pdev, U, mu, V,
-                         n, out, ld, stride);
-      break;
-    default: break;
-  }
+  [[maybe_unused]] const bool ok = with_stationary_kernel(kernel, [&](auto K) {
+    hipLaunchKernelGGL(kbuild_cross_batched_kernel<decltype(K)::value>, grid, dim3(256), kb_lds_bytes(d), s, pdev, U, mu, V,
+                       n, out, ld, stride);
+  });
+  assert(ok && "a batch of sums is an array of CovParams");
 }
 void launch_kbuild_cross_batched(hipStream_t s, const CovParams* pdev, int batch, const double* U, int64_t mu, int64_t mp,
                                  const double* V, int64_t n, int64_t np, double* out, int64_t ld, int64_t stride, int d) {

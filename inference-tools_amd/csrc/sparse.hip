@@ -8,9 +8,11 @@
 // factorisation and inverse of the small-problem path (potrf_lower_batched, trsm_identity_batched, batch of one) and
 // products with the explicit triangular inverses L^-1, L_B^-1 - B is factorised, never K_mm^-1 G or the N x N matrix.
 // Pass 2 (gradient) rebuilds every panel transposed (P x m: rows are data points), forms alpha = W (r - K_nm gamma), the
-// weight panel T K_mn (one GEMM) and contracts  sum_ij M1_ij dK(z_i, x_j)/dtheta  in sgp_contract_kernel, which is new:
-// 64 x 64 tiles, both point panels staged in LDS, value and derivative profiles recomputed (kfun.h), one partial per tile
-// and parameter, summed by a second kernel in a fixed order.  The K_mm term runs through the same kernel (rows = Z).
+// weight panel T K_mn (one GEMM) and contracts  sum_ij M1_ij dK(z_i, x_j)/dtheta  in sgp_contract_kernel: the 64 x 64 pair
+// tile of the builders (pair_tile.h: both point panels staged in LDS, s and the value and derivative profiles of kfun.h
+// recomputed - C is bit for bit the builders' value), one partial per tile and parameter, summed by a second kernel in a
+// fixed order.  The K_mm term runs through the same kernel (rows = Z).  sgp_zcontract_kernel (dF/dZ) and sgp_qgrad_kernel
+// (below) stand on the same tile and on its column reduction, pair_tile::reduce_columns, with one and two weight arrays.
 //   gamma = L^-T L_B^-T c;  beta = K_mm^-1 K_mn alpha = gamma (exactly: (K_mm + G) gamma = b);  S = L^-T B^-1 L^-1;
 //   T = L^-T L^-1 - S;  M1 = gamma alpha^T + T K_mn W;  M2 = gamma gamma^T + K_mm^-1 G K_mm^-1 - T;
 //   dF/dtheta = sum M1 o dK_mn - 1/2 sum M2 o d(K_mm + eps I) - 1/2 sum w_i da^2/dtheta;
@@ -18,13 +20,13 @@
 // The fitted model (L^-1, L_B^-1, c, gamma kept by gpmi_sgp_fit) answers in O(M m^2): mean and variance (gpmi_sgp_predict), the
 // joint posterior mu = U c, Sigma = K_qq - V V^T + U U^T and joint draws through the tail of draws.hip (gpmi_sgp_posterior,
 // gpmi_sgp_posterior_draws), and the derivatives of mean and variance by the query point (gpmi_sgp_spatial_derivatives):
-// four products per panel for the rows t(q)^T = (L^-T (L_B^-T u - v))^T, then sgp_qgrad_kernel, which is new - the tile scheme
-// of sgp_zcontract_kernel with one profile evaluation weighted twice, by gamma and by t(q).
+// four products per panel for the rows t(q)^T = (L^-T (L_B^-T u - v))^T, then sgp_qgrad_kernel: one profile evaluation
+// weighted twice, by gamma and by t(q).
 // Every reduction has a fixed order, nothing uses atomics: a call repeated gives the same bits.
 #include <limits>
 
 #include "api_internal.h"
-#include "kfun.h"
+#include "pair_tile.h"
 
 struct gpmi_sgp {
   gpmi_ctx* ctx = nullptr;
@@ -60,8 +62,9 @@ struct gpmi_sgp {
 
 namespace {
 
-constexpr int KT = 64;
-constexpr int SGP_NT = 256;
+using pair_tile::block_sum;
+using pair_tile::KT;
+constexpr int SGP_NT = pair_tile::NT;
 constexpr int SGP_RED_BLOCKS = 1024;
 constexpr int SGP_QPANEL = 1024;
 constexpr int64_t SGP_MAX_PANEL = 32768;
@@ -70,21 +73,6 @@ constexpr int RED_DATA = 0;   // r^T W r, sum ln sigma^2, sum w, count of non-po
 constexpr int RED_MM = 4;     // sum ln diag(L_B), tr H, c^T c
 constexpr int RED_NOISE = 8;  // sum_i [alpha_i^2 - w_i + w_i^2 (a^2 - k_i^T T k_i)]
 constexpr int RED_GRAD = 16;  // n_theta partial derivatives
-
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-// block-wide sum (256 threads), the same value in every thread
-__device__ inline double block_sum(double v, double* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
 
 // w_i = 1 / (nv_i + white) and, per workgroup, the partial sums [r^T W r, sum ln sigma^2, sum w, bad] over its
 // grid-strided share of the data (bad: variances that are not positive and finite; their w is 0)
@@ -247,12 +235,32 @@ __global__ __launch_bounds__(SGP_NT) void sgp_predict_kernel(const double* __res
   }
 }
 
+// The weights of a thread's 4 x 4 block (rows gi0 .., columns gj0 ..) in the two weighted contractions:
+//   w_ij = m_scale rs_i Mw[i][j] + uv_scale uvec_i vvec_j   (rs == nullptr: 1);   0, and nothing read, where i >= nu or j >= nv
+__device__ __forceinline__ void pair_weights(int64_t gi0, int64_t nu, int64_t gj0, int64_t nv, const double* __restrict__ Mw,
+                                             int64_t ld, const double* __restrict__ rs, double m_scale,
+                                             const double* __restrict__ uvec, double uv_scale, const double* __restrict__ vvec,
+                                             double (&w)[4][4]) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int64_t gi = gi0 + r;
+    const bool row_ok = gi < nu;
+    const double ui = row_ok ? uv_scale * uvec[gi] : 0.0;
+    const double ri = row_ok ? (rs ? m_scale * rs[gi] : m_scale) : 0.0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int64_t gj = gj0 + c;
+      w[r][c] = (row_ok && gj < nv) ? fma(ri, Mw[gi * ld + gj], ui * vvec[gj]) : 0.0;
+    }
+  }
+}
+
 // The rectangular weighted gradient contraction: tile (blockIdx.y, blockIdx.x) of (rows of U) x (rows of V) reduces
 //   sum_ij w_ij dK(u_i, v_j) / dtheta_k,   w_ij = m_scale rs_i Mw[i][j] + uv_scale uvec_i vvec_j   (rs == nullptr: 1),
 // to one partial per parameter at ws[(tile row * gridDim.x + tile column) * n_theta + k]: [ln a, (RQ: ln kappa,) ln l_1..d].
-// The two 64-point panels are staged in LDS ([dim][point], 2 x d x 64 doubles of dynamic LDS: 64 KiB at d = 64), every
-// thread owns a 4 x 4 block: s = 1/2 sum_k dx_k^2 / l_k^2 as the builders form it, value and derivative profiles in two
-// halves of eight elements (kfun.h: kprofiles), then one pass over the dimensions for the length scales.
+// The pair tile of pair_tile.h: the two 64-point panels staged in LDS (2 x d x 64 doubles of dynamic LDS: 64 KiB at
+// d = 64), a 4 x 4 block per thread, s by pair_tile::accumulate_s - the builders' s - then value and derivative profiles
+// in two halves of eight elements (kfun.h: kprofiles) and one pass over the dimensions for the length scales.
 // square != 0: U and V are the same points (the K_mm term) and the diagonal carries diag_eps: d(K + eps I)_ii / d ln a =
 // 2 (a^2 + eps).  Reads Mw only where i < nu and j < nv; VALU-bound (the fp64 exp and the d-term sums).
 template <int KERNEL>
@@ -270,47 +278,16 @@ __global__ __launch_bounds__(SGP_NT) void sgp_contract_kernel(KParams p, const d
   double* su = sc_lds;
   double* sv = sc_lds + d * KT;
   const int64_t i0 = (int64_t)ti * KT, j0 = (int64_t)tj * KT;
-  for (int idx = tid; idx < KT * d; idx += SGP_NT) {
-    const int pt = idx / d, k = idx - pt * d;
-    const int64_t gi = i0 + pt, gj = j0 + pt;
-    su[k * KT + pt] = (gi < nu) ? U[gi * d + k] : 0.0;
-    sv[k * KT + pt] = (gj < nv) ? V[gj * d + k] : 0.0;
-  }
+  pair_tile::stage_panels(su, U, i0, nu, sv, V, j0, nv, d);
   __syncthreads();
-  const int ty = tid >> 4, tx = tid & 15;
+  const int ty = pair_tile::thread_row(tid), tx = pair_tile::thread_col(tid);
   double s[4][4], w[4][4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) s[r][c] = 0.0;
-  for (int k = 0; k < d; ++k) {
-    const double il2 = p.inv_l2[k];
-    double ur[4], vc[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) ur[r] = su[k * KT + ty * 4 + r];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) vc[c] = sv[k * KT + tx * 4 + c];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const double dx = ur[r] - vc[c];
-        s[r][c] = fma(0.5 * dx * dx, il2, s[r][c]);
-      }
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int64_t gi = i0 + ty * 4 + r;
-    const bool row_ok = gi < nu;
-    const double ui = row_ok ? uv_scale * uvec[gi] : 0.0;
-    const double ri = row_ok ? (rs ? m_scale * rs[gi] : m_scale) : 0.0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int64_t gj = j0 + tx * 4 + c;
-      w[r][c] = (row_ok && gj < nv) ? fma(ri, Mw[gi * ld + gj], ui * vvec[gj]) : 0.0;
-    }
-  }
+  pair_tile::accumulate_s(p.inv_l2, d, su, sv, ty, tx, s);
+  pair_weights(i0 + ty * 4, nu, j0 + tx * 4, nv, Mw, ld, rs, m_scale, uvec, uv_scale, vvec, w);
   double g_amp = 0.0, g_shape = 0.0;
+  // The two halves of eight are written out here, not through pair_tile::for_each_profile: behind the helper, with the
+  // element's work in a callback of any shape tried, the Matern32 instantiation took 132 VGPRs (three waves per SIMD)
+  // against 114 (four) in this form.
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     double s8[8], C8[8], g8[8], h8[8];
@@ -363,33 +340,33 @@ void launch_contract(hipStream_t s, const KParams& p, const double* U, int64_t n
                      double m_scale, double uv_scale, int square, double diag_eps, int n_theta, double* ws) {
   const dim3 grid((unsigned)(nvp / KT), (unsigned)(nup / KT));
   const size_t lds = contract_lds_bytes(p.d);
-#define SGP_CONTRACT(KIND)                                                                                              \
-  hipLaunchKernelGGL(sgp_contract_kernel<KIND>, grid, dim3(SGP_NT), lds, s, p, U, nu, V, nv, Mw, ld, rs, uvec, vvec, m_scale, \
-                     uv_scale, square, diag_eps, n_theta, ws)
-  switch (p.kernel) {
-    case GPMI_KERNEL_SE: SGP_CONTRACT(GPMI_KERNEL_SE); break;
-    case GPMI_KERNEL_RQ: SGP_CONTRACT(GPMI_KERNEL_RQ); break;
-    case GPMI_KERNEL_M32: SGP_CONTRACT(GPMI_KERNEL_M32); break;
-    case GPMI_KERNEL_M52: SGP_CONTRACT(GPMI_KERNEL_M52); break;
-    default: break;  // (sgp_params admits no other kind)
-  }
-#undef SGP_CONTRACT
+  with_stationary_kernel(p.kernel, [&](auto K) {  // (sgp_params admits no other kind)
+    hipLaunchKernelGGL(sgp_contract_kernel<decltype(K)::value>, grid, dim3(SGP_NT), lds, s, p, U, nu, V, nv, Mw, ld, rs, uvec,
+                       vvec, m_scale, uv_scale, square, diag_eps, n_theta, ws);
+  });
+}
+
+// A kernel launched with `lds` bytes of dynamic LDS: above 64 KiB a kernel has to opt in first
+template <class... KA>
+int launch_large_lds(gpmi_ctx* c, hipStream_t s, void (*kernel)(KA...), dim3 grid, size_t lds, std::common_type_t<KA>... args) {
+  if (lds > 65536)
+    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kernel, grid, dim3(SGP_NT), lds, s, args...);
+  return GPMI_OK;
 }
 
 // The contraction by the inducing inputs: for the 64 points v_j of tile blockIdx.x (the inducing inputs differentiated) and
 // the run blockIdx.y of `run_tiles` consecutive 64-row tiles of U (the points summed over),
 //   zws[(run * nvp + j) * d + k] = scale / l_k^2 * sum_i w_ij a^2 g(s(u_i, v_j)) (v_jk - u_ik),
 //   w_ij = rs_i Mw[i][j] + uvec_i vvec_j   (rs == nullptr: 1),
-// the operands and the weights of sgp_contract_kernel.  dK(u_i, v_j) / dv_jk = -a^2 g (v_jk - u_ik) / l_k^2: the difference
-// is formed from the staged coordinates, nothing is divided by a distance, coincident points contribute exact zeros.
-// The thread layout is the 4 x 4 blocks of sgp_contract_kernel; s and the profiles are recomputed per tile.  Per dimension
-// a thread's four column sums go through two xor shuffles (the four lanes of a wave that share the columns), then the four
-// waves through LDS, ZDK dimensions per barrier (double-buffered), into a [d][64] accumulator in LDS that one thread per
-// element owns; tiles are added in ascending order, rows >= nu and columns >= nv carry weight 0.  The order of every sum
-// is fixed by the shapes and run_tiles alone.  Dynamic LDS: (3 d + 2 ZDK 4) x 64 doubles - 112 KiB at d = 64, 28 KiB at
-// d = 8.  gfx950 (kernel-resource-usage; the state is independent of d), SE / RQ / Matern32 / Matern52: 126 / 167 / 132 /
-// 147 VGPRs, no AGPRs, scratch 0, no static LDS: 114688 bytes of LDS at d = 64 (one workgroup per CU there, five at d = 8).
-constexpr int ZDK = 4;
+// the operands and the weights of sgp_contract_kernel (pair_weights).  dK(u_i, v_j) / dv_jk = -a^2 g (v_jk - u_ik) / l_k^2.
+// The column panel is staged once, the row panel once per tile of the run; s and the profiles are recomputed per tile
+// (pair_tile.h), and the weighted differences are summed over the rows by pair_tile::reduce_columns with one weight
+// array: four dimensions per barrier into a [d][64] accumulator in LDS.  Tiles are added in ascending order, rows >= nu
+// and columns >= nv carry weight 0.  The order of every sum is fixed by the shapes and run_tiles alone.
+// Dynamic LDS (pair_tile::column_lds_bytes): (3 d + 32) x 64 doubles - 112 KiB at d = 64, 28 KiB at d = 8.  gfx950
+// (kernel-resource-usage; the state is independent of d), SE / RQ / Matern32 / Matern52: 124 / 157 / 127 / 139 VGPRs, no
+// AGPRs, scratch 0, no static LDS: 114688 bytes of LDS at d = 64 (one workgroup per CU there, five at d = 8).
 constexpr int ZRUN_MAX = 16;
 
 template <int KERNEL>
@@ -404,106 +381,29 @@ __global__ __launch_bounds__(SGP_NT) void sgp_zcontract_kernel(KParams p, const 
   const int tid = threadIdx.x, d = p.d;
   double* sv = sz_lds;
   double* su = sv + d * KT;
-  double* acc = su + d * KT;
-  double* red = acc + d * KT;  // [2][ZDK][4 waves][64]
+  double* const acc[1] = {su + d * KT};
+  double* red = acc[0] + d * KT;
   const int64_t j0 = (int64_t)tj * KT;
-  for (int idx = tid; idx < KT * d; idx += SGP_NT) {
-    const int pt = idx / d, k = idx - pt * d;
-    const int64_t gj = j0 + pt;
-    sv[k * KT + pt] = (gj < nv) ? V[gj * d + k] : 0.0;
-    acc[idx] = 0.0;
-  }
-  const int ty = tid >> 4, tx = tid & 15, wave = tid >> 6, lane = tid & 63;
+  pair_tile::for_each_coordinate(d, [&](int idx, int pt, int k) {
+    pair_tile::stage_coordinate(sv, V, j0, nv, d, pt, k);
+    acc[0][idx] = 0.0;
+  });
+  const int ty = pair_tile::thread_row(tid), tx = pair_tile::thread_col(tid);
   int chunk = 0;
   for (int t = 0; t < run_tiles; ++t) {
     const int64_t i0 = ((int64_t)run * run_tiles + t) * KT;
     if (i0 >= nu) break;
     __syncthreads();  // (the previous tile's readers of su)
-    for (int idx = tid; idx < KT * d; idx += SGP_NT) {
-      const int pt = idx / d, k = idx - pt * d;
-      const int64_t gi = i0 + pt;
-      su[k * KT + pt] = (gi < nu) ? U[gi * d + k] : 0.0;
-    }
+    pair_tile::stage_panel(su, U, i0, nu, d);
     __syncthreads();
-    double s[4][4], w[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) s[r][c] = 0.0;
-    for (int k = 0; k < d; ++k) {
-      const double il2 = p.inv_l2[k];
-      double ur[4], vc[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) ur[r] = su[k * KT + ty * 4 + r];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) vc[c] = sv[k * KT + tx * 4 + c];
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const double dx = ur[r] - vc[c];
-          s[r][c] = fma(0.5 * dx * dx, il2, s[r][c]);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int64_t gi = i0 + ty * 4 + r;
-      const bool row_ok = gi < nu;
-      const double ui = row_ok ? uvec[gi] : 0.0;
-      const double ri = row_ok ? (rs ? rs[gi] : 1.0) : 0.0;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const int64_t gj = j0 + tx * 4 + c;
-        w[r][c] = (row_ok && gj < nv) ? fma(ri, Mw[gi * ld + gj], ui * vvec[gj]) : 0.0;
-      }
-    }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      double s8[8], C8[8], g8[8], h8[8];
-#pragma unroll
-      for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) s8[4 * r + c] = s[2 * h + r][c];
-      kprofiles<KERNEL>(p, s8, C8, g8, h8);
-#pragma unroll
-      for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) w[2 * h + r][c] *= p.a2 * g8[4 * r + c];
-    }
-    for (int k0 = 0; k0 < d; k0 += ZDK, ++chunk) {
-      double* buf = red + (chunk & 1) * (ZDK * 4 * KT);
-      for (int kk = 0; kk < ZDK && k0 + kk < d; ++kk) {
-        const int k = k0 + kk;
-        double ur[4], col[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ur[r] = su[k * KT + ty * 4 + r];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const double vc = sv[k * KT + tx * 4 + c];
-          double a = 0.0;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) a = fma(w[r][c], vc - ur[r], a);
-          a += __shfl_xor(a, 16, 64);
-          a += __shfl_xor(a, 32, 64);
-          col[c] = a;
-        }
-        if (lane < 16) {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) buf[(kk * 4 + wave) * KT + tx * 4 + c] = col[c];
-        }
-      }
-      __syncthreads();  // (one barrier per chunk: the other half of red is written only behind the next one)
-      const int kk = tid >> 6, k = k0 + kk;
-      if (k < d)
-        acc[k * KT + lane] += (buf[(kk * 4 + 0) * KT + lane] + buf[(kk * 4 + 1) * KT + lane]) +
-                              (buf[(kk * 4 + 2) * KT + lane] + buf[(kk * 4 + 3) * KT + lane]);
-    }
+    double s[4][4], w[1][4][4];
+    pair_tile::accumulate_s(p.inv_l2, d, su, sv, ty, tx, s);
+    pair_weights(i0 + ty * 4, nu, j0 + tx * 4, nv, Mw, ld, rs, 1.0, uvec, 1.0, vvec, w[0]);
+    pair_tile::for_each_profile<KERNEL, true>(p, s, [&](int r, int c, double, double g, double) { w[0][r][c] *= p.a2 * g; });
+    pair_tile::reduce_columns<1>(su, sv, d, ty, tx, w, 1, acc, red, chunk);
   }
   __syncthreads();
-  for (int idx = tid; idx < KT * d; idx += SGP_NT) {
-    const int pt = idx / d, k = idx - pt * d;
-    zws[((int64_t)run * nvp + j0 + pt) * d + k] = scale * p.inv_l2[k] * acc[k * KT + pt];
-  }
+  pair_tile::write_columns<1>(p.inv_l2, d, acc, 1, {scale}, (int64_t)run * nvp + j0, {zws});
 }
 
 // zacc[e] (+)= sum_run zws[run * count + e], runs in ascending order; e < count
@@ -515,8 +415,6 @@ __global__ __launch_bounds__(SGP_NT) void sgp_zsum_kernel(const double* __restri
   for (int r = 0; r < nruns; ++r) v += zws[(int64_t)r * count + e];
   zacc[e] = accumulate ? zacc[e] + v : v;
 }
-
-size_t zcontract_lds_bytes(int d) { return sizeof(double) * ((size_t)3 * d + 2 * ZDK * 4) * KT; }
 
 // tiles of U per workgroup: ZRUN_MAX, halved (not below 2) while the grid stays under 512 workgroups - a function of the
 // two padded shapes alone
@@ -537,23 +435,12 @@ int launch_zcontract(gpmi_ctx* c, hipStream_t s, const KParams& p, const double*
                      const double* vvec, double scale, double* zws, double* zacc, int accumulate) {
   const int run_tiles = zrun_tiles(nup, nvp), nruns = zruns(nup, nvp);
   const dim3 grid((unsigned)(nvp / KT), (unsigned)nruns);
-  const size_t lds = zcontract_lds_bytes(p.d);
-#define SGP_ZCONTRACT(KIND)                                                                                                 \
-  do {                                                                                                                      \
-    if (lds > 65536)                                                                                                        \
-      HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&sgp_zcontract_kernel<KIND>),                             \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                 \
-    hipLaunchKernelGGL(sgp_zcontract_kernel<KIND>, grid, dim3(SGP_NT), lds, s, p, U, nu, V, nv, nvp, Mw, ld, rs, uvec, vvec,  \
-                       scale, run_tiles, zws);                                                                              \
-  } while (0)
-  switch (p.kernel) {
-    case GPMI_KERNEL_SE: SGP_ZCONTRACT(GPMI_KERNEL_SE); break;
-    case GPMI_KERNEL_RQ: SGP_ZCONTRACT(GPMI_KERNEL_RQ); break;
-    case GPMI_KERNEL_M32: SGP_ZCONTRACT(GPMI_KERNEL_M32); break;
-    case GPMI_KERNEL_M52: SGP_ZCONTRACT(GPMI_KERNEL_M52); break;
-    default: break;  // (sgp_params admits no other kind)
-  }
-#undef SGP_ZCONTRACT
+  int rc = GPMI_OK;
+  with_stationary_kernel(p.kernel, [&](auto K) {  // (sgp_params admits no other kind)
+    rc = launch_large_lds(c, s, sgp_zcontract_kernel<decltype(K)::value>, grid, pair_tile::column_lds_bytes(p.d, 1), p, U, nu, V,
+                          nv, nvp, Mw, ld, rs, uvec, vvec, scale, run_tiles, zws);
+  });
+  if (rc) return rc;
   const int64_t count = nvp * p.d;
   hipLaunchKernelGGL(sgp_zsum_kernel, dim3((unsigned)((count + SGP_NT - 1) / SGP_NT)), dim3(SGP_NT), 0, s, zws, nruns, count,
                      zacc, accumulate);
@@ -568,17 +455,17 @@ int launch_zcontract(gpmi_ctx* c, hipStream_t s, const KParams& p, const double*
 // with gamma = L^-T L_B^-T c (mean(q) = k_m(q)^T gamma) and the rows Tq[j] = t(q_j)^T = (L^-T (L_B^-T u(q_j) - v(q_j)))^T
 // (var(q) = a^2 + k_m(q)^T t(q)) as the products leave them, query-major.  d k(q, z_a) / d q_k = -a^2 g (q_k - z_ak) / l_k^2:
 // nothing is divided by a distance, a query point that is an inducing input gets an exact zero from it.
-// The thread layout, the staging of the two point panels ([dim][point]) and the recomputed profiles are those of
-// sgp_zcontract_kernel; the profile a^2 g is formed once and weighted twice, into two [d][64] accumulators in LDS.  The
-// column sums of a dimension go through the two xor shuffles, then the four waves through LDS: four (dimension, output)
-// slots per barrier - two dimensions of both outputs, or four of the mean alone - double-buffered; a slot's sum does not
-// depend on which of the two forms ran.  Tiles are added in ascending order; rows >= m and columns >= nq carry weight 0.
+// The query panel is staged once, a tile of inducing inputs once per tile of the run; s and the profiles are recomputed
+// per tile (pair_tile.h); the profile a^2 g is formed once and weighted twice, and pair_tile::reduce_columns sums the
+// weighted differences with two weight arrays into two [d][64] accumulators in LDS: two dimensions of both outputs per
+// barrier, or four of the mean alone - a slot's sum does not depend on which of the two forms ran.  Tiles are added in
+// ascending order; rows >= m and columns >= nq carry weight 0.
 // The order of every sum of column j is fixed by m alone: it does not depend on nq or on where q_j stands in the call.
-// Dynamic LDS: (4 d + 2 x 4 x 4) x 64 doubles - 147456 bytes (144 KiB of the CU's 160) at d = 64, one workgroup per CU
-// there; 32 KiB at d = 8.  gfx950 (kernel-resource-usage; the state is independent of d), SE / RQ / Matern32 / Matern52:
-// 130 / 172 / 130 / 130 VGPRs, no AGPRs, scratch 0, no static LDS.  VALU-bound (the fp64 exp), as the Z pass.
+// Dynamic LDS (pair_tile::column_lds_bytes): (4 d + 32) x 64 doubles - 147456 bytes (144 KiB of the CU's 160) at d = 64,
+// one workgroup per CU there; 32 KiB at d = 8.  gfx950 (kernel-resource-usage; the state is independent of d), SE / RQ /
+// Matern32 / Matern52: 128 / 170 / 128 / 128 VGPRs, no AGPRs, scratch 0, no static LDS.  VALU-bound (the fp64 exp), as
+// the Z pass.
 constexpr int QRUN_TILES = 2;
-constexpr int QSLOTS = 4;
 
 template <int KERNEL>
 __global__ __launch_bounds__(SGP_NT) void sgp_qgrad_kernel(KParams p, const double* __restrict__ Z, int64_t m,
@@ -591,127 +478,40 @@ __global__ __launch_bounds__(SGP_NT) void sgp_qgrad_kernel(KParams p, const doub
   const int tid = threadIdx.x, d = p.d;
   double* sv = sq_lds;            // the query points
   double* su = sv + d * KT;       // a tile of inducing inputs
-  double* acc_m = su + d * KT;
-  double* acc_v = acc_m + d * KT;
-  double* red = acc_v + d * KT;   // [2][QSLOTS][4 waves][64]
+  double* const acc[2] = {su + d * KT, su + 2 * d * KT};  // the mean's, the variance's
+  double* red = acc[1] + d * KT;
   const int64_t j0 = (int64_t)tj * KT;
-  for (int idx = tid; idx < KT * d; idx += SGP_NT) {
-    const int pt = idx / d, k = idx - pt * d;
-    const int64_t gj = j0 + pt;
-    sv[k * KT + pt] = (gj < nq) ? Q[gj * d + k] : 0.0;
-    acc_m[idx] = 0.0;
-    acc_v[idx] = 0.0;
-  }
-  const int ty = tid >> 4, tx = tid & 15, wave = tid >> 6, lane = tid & 63;
-  const int dims = want_var ? QSLOTS / 2 : QSLOTS;  // dimensions per barrier
+  pair_tile::for_each_coordinate(d, [&](int idx, int pt, int k) {
+    pair_tile::stage_coordinate(sv, Q, j0, nq, d, pt, k);
+    acc[0][idx] = 0.0;
+    acc[1][idx] = 0.0;
+  });
+  const int ty = pair_tile::thread_row(tid), tx = pair_tile::thread_col(tid);
+  const int nw = want_var ? 2 : 1;
   int chunk = 0;
   for (int t = 0; t < QRUN_TILES; ++t) {
     const int64_t i0 = ((int64_t)run * QRUN_TILES + t) * KT;
     if (i0 >= m) break;
     __syncthreads();  // (the previous tile's readers of su)
-    for (int idx = tid; idx < KT * d; idx += SGP_NT) {
-      const int pt = idx / d, k = idx - pt * d;
-      const int64_t gi = i0 + pt;
-      su[k * KT + pt] = (gi < m) ? Z[gi * d + k] : 0.0;
-    }
+    pair_tile::stage_panel(su, Z, i0, m, d);
     __syncthreads();
-    double wm[4][4], wv[4][4];  // s, then the profile times the two weights
+    double w[2][4][4];  // w[0]: s, then the profile times gamma; w[1]: the profile times t(q)
+    pair_tile::accumulate_s(p.inv_l2, d, su, sv, ty, tx, w[0]);
+    double ga[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) wm[r][c] = 0.0;
-    for (int k = 0; k < d; ++k) {
-      const double il2 = p.inv_l2[k];
-      double ur[4], vc[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) ur[r] = su[k * KT + ty * 4 + r];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) vc[c] = sv[k * KT + tx * 4 + c];
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const double dx = ur[r] - vc[c];
-          wm[r][c] = fma(0.5 * dx * dx, il2, wm[r][c]);
-        }
-    }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      double s8[8], C8[8], g8[8], h8[8];
-#pragma unroll
-      for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) s8[4 * r + c] = wm[2 * h + r][c];
-      kprofiles<KERNEL>(p, s8, C8, g8, h8);
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        const int64_t gi = i0 + ty * 4 + 2 * h + r;
-        const double ga = (gi < m) ? gamma[gi] : 0.0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const int64_t gj = j0 + tx * 4 + c;
-          const bool ok = gi < m && gj < nq;
-          const double pg = ok ? p.a2 * g8[4 * r + c] : 0.0;
-          wm[2 * h + r][c] = pg * ga;
-          wv[2 * h + r][c] = (want_var && ok) ? pg * Tq[gj * ld + gi] : 0.0;
-        }
-      }
-    }
-    for (int k0 = 0; k0 < d; k0 += dims, ++chunk) {
-      double* buf = red + (chunk & 1) * (QSLOTS * 4 * KT);
-      for (int kk = 0; kk < dims && k0 + kk < d; ++kk) {
-        const int k = k0 + kk;
-        double ur[4], cm[4], cv[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ur[r] = su[k * KT + ty * 4 + r];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const double vc = sv[k * KT + tx * 4 + c];
-          double a = 0.0, b = 0.0;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const double dx = vc - ur[r];
-            a = fma(wm[r][c], dx, a);
-            b = fma(wv[r][c], dx, b);
-          }
-          a += __shfl_xor(a, 16, 64);
-          a += __shfl_xor(a, 32, 64);
-          cm[c] = a;
-          if (want_var) {
-            b += __shfl_xor(b, 16, 64);
-            b += __shfl_xor(b, 32, 64);
-          }
-          cv[c] = b;
-        }
-        if (lane < 16) {
-          const int slot = want_var ? 2 * kk : kk;
-#pragma unroll
-          for (int c = 0; c < 4; ++c) buf[(slot * 4 + wave) * KT + tx * 4 + c] = cm[c];
-          if (want_var) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) buf[((slot + 1) * 4 + wave) * KT + tx * 4 + c] = cv[c];
-          }
-        }
-      }
-      __syncthreads();  // (one barrier per chunk: the other half of red is written only behind the next one)
-      const int slot = tid >> 6;
-      const int k = k0 + (want_var ? slot >> 1 : slot);
-      double* acc = (want_var && (slot & 1)) ? acc_v : acc_m;
-      if (k < d)
-        acc[k * KT + lane] += (buf[(slot * 4 + 0) * KT + lane] + buf[(slot * 4 + 1) * KT + lane]) +
-                              (buf[(slot * 4 + 2) * KT + lane] + buf[(slot * 4 + 3) * KT + lane]);
-    }
+    for (int r = 0; r < 4; ++r) ga[r] = (i0 + ty * 4 + r < m) ? gamma[i0 + ty * 4 + r] : 0.0;
+    pair_tile::for_each_profile<KERNEL, true>(p, w[0], [&](int r, int c, double, double g, double) {
+      const int64_t gi = i0 + ty * 4 + r, gj = j0 + tx * 4 + c;
+      const bool ok = gi < m && gj < nq;
+      const double pg = ok ? p.a2 * g : 0.0;
+      w[0][r][c] = pg * ga[r];
+      w[1][r][c] = (want_var && ok) ? pg * Tq[gj * ld + gi] : 0.0;
+    });
+    pair_tile::reduce_columns<2>(su, sv, d, ty, tx, w, nw, acc, red, chunk);
   }
   __syncthreads();
-  for (int idx = tid; idx < KT * d; idx += SGP_NT) {
-    const int pt = idx / d, k = idx - pt * d;
-    const int64_t o = ((int64_t)run * nqp + j0 + pt) * d + k;
-    ws_mean[o] = -p.inv_l2[k] * acc_m[k * KT + pt];
-    if (want_var) ws_var[o] = -2.0 * p.inv_l2[k] * acc_v[k * KT + pt];
-  }
+  pair_tile::write_columns<2>(p.inv_l2, d, acc, nw, {-1.0, -2.0}, (int64_t)run * nqp + j0, {ws_mean, ws_var});
 }
-
-size_t qgrad_lds_bytes(int d) { return sizeof(double) * ((size_t)4 * d + 2 * QSLOTS * 4) * KT; }
 
 // runs of inducing tiles per query tile: a function of m alone
 int qruns(int64_t mp) { return (int)((mp / KT + QRUN_TILES - 1) / QRUN_TILES); }
@@ -723,23 +523,12 @@ int launch_qgrad(gpmi_ctx* c, hipStream_t s, const KParams& p, const double* Z, 
                  double* out_mean, double* out_var) {
   const int nruns = qruns(mp);
   const dim3 grid((unsigned)(nqp / KT), (unsigned)nruns);
-  const size_t lds = qgrad_lds_bytes(p.d);
-#define SGP_QGRAD(KIND)                                                                                                     \
-  do {                                                                                                                      \
-    if (lds > 65536)                                                                                                        \
-      HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&sgp_qgrad_kernel<KIND>),                                 \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                 \
-    hipLaunchKernelGGL(sgp_qgrad_kernel<KIND>, grid, dim3(SGP_NT), lds, s, p, Z, m, Q, nq, nqp, gamma, Tq, ld, want_var ? 1 : 0, \
-                       ws_mean, ws_var);                                                                                    \
-  } while (0)
-  switch (p.kernel) {
-    case GPMI_KERNEL_SE: SGP_QGRAD(GPMI_KERNEL_SE); break;
-    case GPMI_KERNEL_RQ: SGP_QGRAD(GPMI_KERNEL_RQ); break;
-    case GPMI_KERNEL_M32: SGP_QGRAD(GPMI_KERNEL_M32); break;
-    case GPMI_KERNEL_M52: SGP_QGRAD(GPMI_KERNEL_M52); break;
-    default: break;  // (sgp_params admits no other kind)
-  }
-#undef SGP_QGRAD
+  int rc = GPMI_OK;
+  with_stationary_kernel(p.kernel, [&](auto K) {  // (sgp_params admits no other kind)
+    rc = launch_large_lds(c, s, sgp_qgrad_kernel<decltype(K)::value>, grid, pair_tile::column_lds_bytes(p.d, 2), p, Z, m, Q, nq,
+                          nqp, gamma, Tq, ld, want_var ? 1 : 0, ws_mean, ws_var);
+  });
+  if (rc) return rc;
   const int64_t count = nqp * p.d;
   const dim3 sgrid((unsigned)((count + SGP_NT - 1) / SGP_NT));
   hipLaunchKernelGGL(sgp_zsum_kernel, sgrid, dim3(SGP_NT), 0, s, ws_mean, nruns, count, out_mean, 0);
@@ -788,6 +577,11 @@ int sgp_params(gpmi_sgp* g, int kernel, const double* theta, int n_theta, double
     p.inv_l2[k] = 1.0 / (l * l);
   }
   return GPMI_OK;
+}
+
+// rows of x per panel of the two passes: the caller's panel_rows (0: GPMI_SGP_PANEL) in whole tiles, at most all of x
+int64_t sgp_panel_rows(const gpmi_sgp* g, int64_t panel_rows) {
+  return std::min<int64_t>(round_up(panel_rows > 0 ? panel_rows : GPMI_SGP_PANEL, GPMI_NB), round_up(g->n, GPMI_NB));
 }
 
 // panels for R rows (a multiple of 128)
@@ -851,7 +645,7 @@ int sgp_factor(gpmi_sgp* g, const KParams& p, double white, double jitter, int64
   hipStream_t s = c->sgp_stream;
   const int64_t n = g->n, m = g->m, mp = g->mp, ld = g->ld, d = g->d;
   const int nt = (int)(mp / GPMI_NB);
-  const int64_t P = std::min<int64_t>(round_up(panel_rows > 0 ? panel_rows : GPMI_SGP_PANEL, GPMI_NB), round_up(n, GPMI_NB));
+  const int64_t P = sgp_panel_rows(g, panel_rows);
   const int64_t ldp = P + 32;
   if (int rc = sgp_ensure_panels(g, P)) return rc;
   double *G = g->M[MG], *A = g->M[MA], *LiT = g->M[MLIT], *Linv = g->M[MLINV], *W1 = g->M[MW1], *W2 = g->M[MW2],
@@ -941,7 +735,7 @@ int sgp_gradient(gpmi_sgp* g, const KParams& p, int n_theta, double white, doubl
   hipStream_t s = c->sgp_stream;
   const int64_t n = g->n, m = g->m, mp = g->mp, ld = g->ld, d = g->d;
   const int nt = (int)(mp / GPMI_NB);
-  const int64_t P = std::min<int64_t>(round_up(panel_rows > 0 ? panel_rows : GPMI_SGP_PANEL, GPMI_NB), round_up(n, GPMI_NB));
+  const int64_t P = sgp_panel_rows(g, panel_rows);
   double *G = g->M[MG], *T = g->M[MA], *LiT = g->M[MLIT], *RT = g->M[MW1], *W2 = g->M[MW2], *LB = g->M[MLB], *Kinv = g->M[MW3],
          *LBinv = g->M[MLBINV];
   double *cc = g->vec + 2 * mp, *gamma = g->vec + 3 * mp;
@@ -1000,6 +794,120 @@ int sgp_gradient(gpmi_sgp* g, const KParams& p, int n_theta, double white, doubl
   for (int k = 0; k < n_theta; ++k) grad[k] = hg[k];
   grad[0] -= p.a2 * sum_w;  // -1/2 sum w_i da^2 / d ln a
   grad[n_theta] = white > 0.0 ? white * hnoise : 0.0;
+  return GPMI_OK;
+}
+
+// c->err = who + what
+int sgp_arg_error(gpmi_ctx* c, const char* who, const char* what) {
+  c->err = std::string(who) + what;
+  return GPMI_ERR_ARG;
+}
+
+// What the evaluations of the bound (gpmi_sgp_bound, gpmi_sgp_bound_zgrad, gpmi_sgp_fit: `who` in the messages) open with:
+// the checks of the object and the results (want_z: grad_z is one of them), the kernel parameters, pass 1 and the m x m
+// algebra.  *info != 0 behind GPMI_OK: a factorisation failed and nothing else is valid.
+int sgp_begin(gpmi_sgp* g, const char* who, int kernel, const double* theta, int n_theta, double white_var, double jitter_rel,
+              int64_t panel_rows, const double* F, int* info, bool want_z, const double* grad_z, KParams& p, double& f,
+              double& sum_w) {
+  gpmi_ctx* c = g->ctx;
+  if (!sgp_live(c, g)) return sgp_arg_error(c, who, ": not a live object of this handle");
+  if (!F || !info) return sgp_arg_error(c, who, ": F and info must be non-NULL");
+  if (want_z && !grad_z) return sgp_arg_error(c, who, ": grad_z is NULL");
+  if (int rc = sgp_params(g, kernel, theta, n_theta, white_var, jitter_rel, panel_rows, p)) return rc;
+  if (int rc = set_device(c)) return rc;
+  int inf = 0;
+  if (int rc = sgp_factor(g, p, white_var, jitter_rel, panel_rows, &f, &sum_w, &inf)) return rc;
+  *info = inf;
+  return GPMI_OK;
+}
+
+// gpmi_sgp_bound (want_z false, grad_z unused) and gpmi_sgp_bound_zgrad (want_z: the gradient always runs, dF/dZ to grad_z)
+int sgp_bound(gpmi_sgp* g, const char* who, bool want_z, int kernel, const double* theta, int n_theta, double white_var,
+              double jitter_rel, int64_t panel_rows, double* F, double* grad, double* grad_z, double* alpha_host, int* info) {
+  KParams p;
+  double f = 0.0, sum_w = 0.0;
+  if (int rc = sgp_begin(g, who, kernel, theta, n_theta, white_var, jitter_rel, panel_rows, F, info, want_z, grad_z, p, f, sum_w))
+    return rc;
+  if (*info != 0) return GPMI_OK;
+  gpmi_ctx* c = g->ctx;
+  if (want_z || grad || alpha_host) {
+    double gbuf[GPMI_MAX_D + 3];
+    if (int rc = sgp_gradient(g, p, n_theta, white_var, jitter_rel, panel_rows, sum_w, (want_z || grad) ? gbuf : nullptr, want_z))
+      return rc;
+    if (alpha_host) HIPCHK(c, hipMemcpyAsync(alpha_host, g->alpha, sizeof(double) * g->n, hipMemcpyDeviceToHost, c->sgp_stream));
+    if (want_z) HIPCHK(c, hipMemcpyAsync(grad_z, g->zacc, sizeof(double) * g->m * g->d, hipMemcpyDeviceToHost, c->sgp_stream));
+    HIPCHK(c, hipStreamSynchronize(c->sgp_stream));
+    if (grad) std::memcpy(grad, gbuf, sizeof(double) * (n_theta + 1));
+  }
+  *F = f;
+  return GPMI_OK;
+}
+
+// What the queries of a fitted model open with (`who` in the messages).  bounded: mq <= GPMI_DRAWS_MAX_M, the calls that
+// hold an mq x mq covariance.  proceed == false behind GPMI_OK: mq == 0, the call has nothing to do.
+int sgp_query_args(gpmi_sgp* g, const char* who, int64_t mq, bool bounded, bool& proceed) {
+  gpmi_ctx* c = g->ctx;
+  proceed = false;
+  if (!sgp_live(c, g)) return sgp_arg_error(c, who, ": not a live object of this handle");
+  if (!g->fitted) return sgp_arg_error(c, who, " needs a successful gpmi_sgp_fit");
+  if (bounded) {
+    if (mq < 0 || mq > GPMI_DRAWS_MAX_M) return sgp_arg_error(c, who, ": mq out of range (0 .. 16384 = GPMI_DRAWS_MAX_M points)");
+  } else if (mq < 0) {
+    return sgp_arg_error(c, who, ": mq must not be negative");
+  }
+  proceed = mq > 0;
+  return GPMI_OK;
+}
+
+// The query panel of the fitted model: K_qm of the `rows` points at pts_dev (rp rows: whole tiles) into Kq, then the rows
+// v^T = (L^-1 k_q)^T into V and u^T = (L_B^-1 v)^T into U.  Kq may be U.
+void sgp_query_panel(gpmi_sgp* g, hipStream_t s, const double* pts_dev, int64_t rows, int64_t rp, double* Kq, double* V,
+                     double* U, const GemmBatch& gb = GemmBatch()) {
+  const int64_t mp = g->mp, ld = g->ld;
+  const int nt = (int)(mp / GPMI_NB), ntr = (int)(rp / GPMI_NB);
+  launch_kbuild_cross(s, g->fp, pts_dev, rows, rp, g->z, g->m, mp, Kq, ld);
+  launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, V, ld, Kq, ld, g->fLinv, ld, ntr, nt, (int)mp, nullptr, gb);
+  launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, U, ld, V, ld, g->fLBinv, ld, ntr, nt, (int)mp, nullptr, gb);
+}
+
+// The device buffers of a posterior call at mq points: the points, V and U (two matrices of mpq x ld(m)), mu and, if asked
+// for, Sigma (mpq x ldq).  (An error return may leave work on these in flight: hipFree waits for the device before it
+// releases.)
+struct PosteriorBufs {
+  DevBuf P, VU, mu, Sigma;
+  int64_t mpq = 0, ldq = 0;
+  int alloc(gpmi_sgp* g, int64_t mq, bool want_sigma) {
+    gpmi_ctx* c = g->ctx;
+    mpq = round_up(mq, GPMI_NB);
+    ldq = mpq + 32;
+    HIPCHK(c, hipMalloc(&P.p, sizeof(double) * mpq * g->d));
+    HIPCHK(c, hipMalloc(&VU.p, sizeof(double) * 2 * mpq * g->ld));
+    HIPCHK(c, hipMalloc(&mu.p, sizeof(double) * mpq));
+    if (want_sigma) HIPCHK(c, hipMalloc(&Sigma.p, sizeof(double) * mpq * ldq));
+    return GPMI_OK;
+  }
+};
+
+// mu (mq) and Sigma (lower tiles; the mean alone if b holds no Sigma) of the latent function at the mq points of the host,
+// enqueued on the sparse stream
+int sgp_posterior_sigma(gpmi_sgp* g, const double* pts, int64_t mq, PosteriorBufs& b) {
+  gpmi_ctx* c = g->ctx;
+  hipStream_t s = c->sgp_stream;
+  const int64_t mp = g->mp, ld = g->ld, mpq = b.mpq, ldq = b.ldq;
+  const int ntq = (int)(mpq / GPMI_NB);
+  double *pts_dev = b.P.as<double>(), *V = b.VU.as<double>(), *U = V + mpq * ld, *Sigma = b.Sigma.as<double>();
+  HIPCHK(c, hipMemcpyAsync(pts_dev, pts, sizeof(double) * mq * g->d, hipMemcpyHostToDevice, s));
+  sgp_query_panel(g, s, pts_dev, mq, mpq, U, V, U);  // (K_qm in the place U takes)
+  launch_rows_dot(s, U, ld, mpq, mp, g->fc, b.mu.as<double>());
+  if (Sigma) {
+    // Sigma = K_qq - V V^T + U U^T on the lower tiles; the product only subtracts, so the sign is turned in between
+    launch_kbuild_cross(s, g->fp, pts_dev, mq, mpq, pts_dev, mq, mpq, Sigma, ldq);
+    launch_gemm_nt(s, TILES_LOWER, OP_SUB, Sigma, ldq, V, ld, V, ld, ntq, ntq, (int)mp);
+    launch_negate(s, Sigma, mpq * ldq);
+    launch_gemm_nt(s, TILES_LOWER, OP_SUB, Sigma, ldq, U, ld, U, ld, ntq, ntq, (int)mp);
+    launch_negate(s, Sigma, mpq * ldq);
+  }
+  HIPCHK(c, hipGetLastError());
   return GPMI_OK;
 }
 
@@ -1114,67 +1022,27 @@ int gpmi_sgp_set_inducing(gpmi_sgp* g, const double* z) {
 int gpmi_sgp_bound_zgrad(gpmi_sgp* g, int kernel, const double* theta, int n_theta, double white_var, double jitter_rel,
                          int64_t panel_rows, double* F, double* grad, double* grad_z, double* alpha_host, int* info) {
   if (!g) return GPMI_ERR_ARG;
-  gpmi_ctx* c = g->ctx;
-  ARGCHK(c, sgp_live(c, g), "gpmi_sgp_bound_zgrad: not a live object of this handle");
-  ARGCHK(c, F != nullptr && info != nullptr, "gpmi_sgp_bound_zgrad: F and info must be non-NULL");
-  ARGCHK(c, grad_z != nullptr, "gpmi_sgp_bound_zgrad: grad_z is NULL");
-  KParams p;
-  if (int rc = sgp_params(g, kernel, theta, n_theta, white_var, jitter_rel, panel_rows, p)) return rc;
-  if (int rc = set_device(c)) return rc;
-  double f = 0.0, sum_w = 0.0;
-  int inf = 0;
-  if (int rc = sgp_factor(g, p, white_var, jitter_rel, panel_rows, &f, &sum_w, &inf)) return rc;
-  *info = inf;
-  if (inf != 0) return GPMI_OK;
-  double gbuf[GPMI_MAX_D + 3];
-  if (int rc = sgp_gradient(g, p, n_theta, white_var, jitter_rel, panel_rows, sum_w, gbuf, true)) return rc;
-  if (alpha_host) HIPCHK(c, hipMemcpyAsync(alpha_host, g->alpha, sizeof(double) * g->n, hipMemcpyDeviceToHost, c->sgp_stream));
-  HIPCHK(c, hipMemcpyAsync(grad_z, g->zacc, sizeof(double) * g->m * g->d, hipMemcpyDeviceToHost, c->sgp_stream));
-  HIPCHK(c, hipStreamSynchronize(c->sgp_stream));
-  if (grad) std::memcpy(grad, gbuf, sizeof(double) * (n_theta + 1));
-  *F = f;
-  return GPMI_OK;
+  return sgp_bound(g, "gpmi_sgp_bound_zgrad", true, kernel, theta, n_theta, white_var, jitter_rel, panel_rows, F, grad, grad_z,
+                   alpha_host, info);
 }
 
 int gpmi_sgp_bound(gpmi_sgp* g, int kernel, const double* theta, int n_theta, double white_var, double jitter_rel,
                    int64_t panel_rows, double* F, double* grad, double* alpha_host, int* info) {
   if (!g) return GPMI_ERR_ARG;
-  gpmi_ctx* c = g->ctx;
-  ARGCHK(c, sgp_live(c, g), "gpmi_sgp_bound: not a live object of this handle");
-  ARGCHK(c, F != nullptr && info != nullptr, "gpmi_sgp_bound: F and info must be non-NULL");
-  KParams p;
-  if (int rc = sgp_params(g, kernel, theta, n_theta, white_var, jitter_rel, panel_rows, p)) return rc;
-  if (int rc = set_device(c)) return rc;
-  double f = 0.0, sum_w = 0.0;
-  int inf = 0;
-  if (int rc = sgp_factor(g, p, white_var, jitter_rel, panel_rows, &f, &sum_w, &inf)) return rc;
-  *info = inf;
-  if (inf != 0) return GPMI_OK;
-  if (grad || alpha_host) {
-    double gbuf[GPMI_MAX_D + 3];
-    if (int rc = sgp_gradient(g, p, n_theta, white_var, jitter_rel, panel_rows, sum_w, grad ? gbuf : nullptr)) return rc;
-    if (alpha_host) HIPCHK(c, hipMemcpyAsync(alpha_host, g->alpha, sizeof(double) * g->n, hipMemcpyDeviceToHost, c->sgp_stream));
-    HIPCHK(c, hipStreamSynchronize(c->sgp_stream));
-    if (grad) std::memcpy(grad, gbuf, sizeof(double) * (n_theta + 1));
-  }
-  *F = f;
-  return GPMI_OK;
+  return sgp_bound(g, "gpmi_sgp_bound", false, kernel, theta, n_theta, white_var, jitter_rel, panel_rows, F, grad, nullptr,
+                   alpha_host, info);
 }
 
 int gpmi_sgp_fit(gpmi_sgp* g, int kernel, const double* theta, int n_theta, double white_var, double jitter_rel,
                  int64_t panel_rows, double* F, int* info) {
   if (!g) return GPMI_ERR_ARG;
   gpmi_ctx* c = g->ctx;
-  ARGCHK(c, sgp_live(c, g), "gpmi_sgp_fit: not a live object of this handle");
-  ARGCHK(c, F != nullptr && info != nullptr, "gpmi_sgp_fit: F and info must be non-NULL");
   KParams p;
-  if (int rc = sgp_params(g, kernel, theta, n_theta, white_var, jitter_rel, panel_rows, p)) return rc;
-  if (int rc = set_device(c)) return rc;
   double f = 0.0, sum_w = 0.0;
-  int inf = 0;
-  if (int rc = sgp_factor(g, p, white_var, jitter_rel, panel_rows, &f, &sum_w, &inf)) return rc;
-  *info = inf;
-  if (inf != 0) return GPMI_OK;
+  if (int rc = sgp_begin(g, "gpmi_sgp_fit", kernel, theta, n_theta, white_var, jitter_rel, panel_rows, F, info, false, nullptr, p, f,
+                         sum_w))
+    return rc;
+  if (*info != 0) return GPMI_OK;
   hipStream_t s = c->sgp_stream;
   launch_copy_rows(s, g->M[MLINV], g->ld, g->fLinv, g->ld, g->mp, g->mp);
   launch_copy_rows(s, g->M[MLBINV], g->ld, g->fLBinv, g->ld, g->mp, g->mp);
@@ -1193,24 +1061,20 @@ int gpmi_sgp_fit(gpmi_sgp* g, int kernel, const double* theta, int n_theta, doub
 int gpmi_sgp_predict(gpmi_sgp* g, const double* pts, int64_t mq, double* mean, double* var) {
   if (!g) return GPMI_ERR_ARG;
   gpmi_ctx* c = g->ctx;
-  ARGCHK(c, sgp_live(c, g), "gpmi_sgp_predict: not a live object of this handle");
-  ARGCHK(c, g->fitted, "gpmi_sgp_predict needs a successful gpmi_sgp_fit");
-  ARGCHK(c, mq >= 0, "gpmi_sgp_predict: mq must not be negative");
-  if (mq == 0) return GPMI_OK;
+  bool proceed;
+  if (int rc = sgp_query_args(g, "gpmi_sgp_predict", mq, false, proceed)) return rc;
+  if (!proceed) return GPMI_OK;
   ARGCHK(c, pts != nullptr && mean != nullptr, "gpmi_sgp_predict: pts_host and mean_host must be non-NULL");
   if (int rc = set_device(c)) return rc;
   if (int rc = sgp_ensure_panels(g, SGP_QPANEL)) return rc;
   hipStream_t s = c->sgp_stream;
-  const int64_t m = g->m, mp = g->mp, ld = g->ld, d = g->d;
-  const int nt = (int)(mp / GPMI_NB);
+  const int64_t d = g->d;
   for (int64_t q0 = 0; q0 < mq; q0 += SGP_QPANEL) {
     const int64_t rows = std::min<int64_t>(SGP_QPANEL, mq - q0), rp = round_up(rows, GPMI_NB);
     double *Kq = g->P[0], *V = g->P[1], *U = g->P[2];
     HIPCHK(c, hipMemcpyAsync(g->q_pts, pts + q0 * d, sizeof(double) * rows * d, hipMemcpyHostToDevice, s));
-    launch_kbuild_cross(s, g->fp, g->q_pts, rows, rp, g->z, m, mp, Kq, ld);
-    launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, V, ld, Kq, ld, g->fLinv, ld, (int)(rp / GPMI_NB), nt, (int)mp);   // rows (L^-1 k_q)^T
-    launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, U, ld, V, ld, g->fLBinv, ld, (int)(rp / GPMI_NB), nt, (int)mp);  // rows (L_B^-1 v)^T
-    hipLaunchKernelGGL(sgp_predict_kernel, dim3((unsigned)rows), dim3(SGP_NT), 0, s, V, U, ld, m, g->fc, g->fp.a2, g->q_out,
+    sgp_query_panel(g, s, g->q_pts, rows, rp, Kq, V, U);
+    hipLaunchKernelGGL(sgp_predict_kernel, dim3((unsigned)rows), dim3(SGP_NT), 0, s, V, U, g->ld, g->m, g->fc, g->fp.a2, g->q_out,
                        g->q_out + SGP_QPANEL);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(mean + q0, g->q_out, sizeof(double) * rows, hipMemcpyDeviceToHost, s));
@@ -1223,10 +1087,9 @@ int gpmi_sgp_predict(gpmi_sgp* g, const double* pts, int64_t mq, double* mean, d
 int gpmi_sgp_spatial_derivatives(gpmi_sgp* g, const double* pts, int64_t mq, double* dmean, double* dvar) {
   if (!g) return GPMI_ERR_ARG;
   gpmi_ctx* c = g->ctx;
-  ARGCHK(c, sgp_live(c, g), "gpmi_sgp_spatial_derivatives: not a live object of this handle");
-  ARGCHK(c, g->fitted, "gpmi_sgp_spatial_derivatives needs a successful gpmi_sgp_fit");
-  ARGCHK(c, mq >= 0, "gpmi_sgp_spatial_derivatives: mq must not be negative");
-  if (mq == 0) return GPMI_OK;
+  bool proceed;
+  if (int rc = sgp_query_args(g, "gpmi_sgp_spatial_derivatives", mq, false, proceed)) return rc;
+  if (!proceed) return GPMI_OK;
   ARGCHK(c, pts != nullptr && dmean != nullptr, "gpmi_sgp_spatial_derivatives: pts_host and dmean_host must be non-NULL");
   if (int rc = set_device(c)) return rc;
   if (int rc = sgp_ensure_panels(g, SGP_QPANEL)) return rc;
@@ -1247,9 +1110,7 @@ int gpmi_sgp_spatial_derivatives(gpmi_sgp* g, const double* pts, int64_t mq, dou
     if (dvar) {
       // (profile classes: the products under GPMI_PROF_SGP_GRAM, the fused kernel under GPMI_PROF_SGP_GRAD)
       ProfScope ps(c, s, GPMI_PROF_SGP_GRAM, 8.0 * rp * mp * mp, 8.0 * 6.0 * rp * mp);
-      launch_kbuild_cross(s, g->fp, g->q_pts, rows, rp, g->z, m, mp, Kq, ld);
-      launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, V, ld, Kq, ld, g->fLinv, ld, ntr, nt, (int)mp, nullptr, gb);   // rows v^T
-      launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, U, ld, V, ld, g->fLBinv, ld, ntr, nt, (int)mp, nullptr, gb);  // rows u^T
+      sgp_query_panel(g, s, g->q_pts, rows, rp, Kq, V, U, gb);
       // the same two inverses the other way round (B k-major: no transposes are stored): rows (L_B^-T u)^T, then t^T
       launch_gemm(s, TILES_RECT, OP_ASSIGN, true, 0, W, ld, U, ld, g->fLBinv, ld, ntr, nt, (int)mp, nullptr, gb);
       hipLaunchKernelGGL(sgp_sub_kernel, dim3(blocks(mp), (unsigned)rp), dim3(SGP_NT), 0, s, W, V, D, ld, mp);
@@ -1269,79 +1130,24 @@ int gpmi_sgp_spatial_derivatives(gpmi_sgp* g, const double* pts, int64_t mq, dou
   return GPMI_OK;
 }
 
-}  // extern "C"
-
-namespace {
-
-// mu (mq, device) and Sigma (mp x ldq, lower tiles; Sigma == nullptr: the mean alone) of the latent function at the mq
-// points of the host, enqueued on the sparse stream.  VU: two matrices of mp x ld(m) doubles.
-int sgp_posterior_sigma(gpmi_sgp* g, const double* pts, int64_t mq, int64_t mpq, double* pts_dev, double* VU, double* mu_dev,
-                        double* Sigma, int64_t ldq) {
-  gpmi_ctx* c = g->ctx;
-  hipStream_t s = c->sgp_stream;
-  const int64_t m = g->m, mp = g->mp, ld = g->ld, d = g->d;
-  const int nt = (int)(mp / GPMI_NB), ntq = (int)(mpq / GPMI_NB);
-  double *V = VU, *U = VU + mpq * ld;
-  HIPCHK(c, hipMemcpyAsync(pts_dev, pts, sizeof(double) * mq * d, hipMemcpyHostToDevice, s));
-  launch_kbuild_cross(s, g->fp, pts_dev, mq, mpq, g->z, m, mp, U, ld);  // K_qm, in the place U takes below
-  launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, V, ld, U, ld, g->fLinv, ld, ntq, nt, (int)mp);   // rows (L^-1 k_q)^T
-  launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, U, ld, V, ld, g->fLBinv, ld, ntq, nt, (int)mp);  // rows (L_B^-1 v)^T
-  launch_rows_dot(s, U, ld, mpq, mp, g->fc, mu_dev);
-  if (Sigma) {
-    // Sigma = K_qq - V V^T + U U^T on the lower tiles; the product only subtracts, so the sign is turned in between
-    launch_kbuild_cross(s, g->fp, pts_dev, mq, mpq, pts_dev, mq, mpq, Sigma, ldq);
-    launch_gemm_nt(s, TILES_LOWER, OP_SUB, Sigma, ldq, V, ld, V, ld, ntq, ntq, (int)mp);
-    launch_negate(s, Sigma, mpq * ldq);
-    launch_gemm_nt(s, TILES_LOWER, OP_SUB, Sigma, ldq, U, ld, U, ld, ntq, ntq, (int)mp);
-    launch_negate(s, Sigma, mpq * ldq);
-  }
-  HIPCHK(c, hipGetLastError());
-  return GPMI_OK;
-}
-
-int sgp_cov_args(gpmi_sgp* g, const char* who, int64_t mq) {
-  gpmi_ctx* c = g->ctx;
-  if (!sgp_live(c, g)) {
-    c->err = std::string(who) + ": not a live object of this handle";
-    return GPMI_ERR_ARG;
-  }
-  if (!g->fitted) {
-    c->err = std::string(who) + " needs a successful gpmi_sgp_fit";
-    return GPMI_ERR_ARG;
-  }
-  if (mq < 0 || mq > GPMI_DRAWS_MAX_M) {
-    c->err = std::string(who) + ": mq out of range (0 .. 16384 = GPMI_DRAWS_MAX_M points)";
-    return GPMI_ERR_ARG;
-  }
-  return GPMI_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
 int gpmi_sgp_posterior(gpmi_sgp* g, const double* pts, int64_t mq, double* mean, double* cov) {
   if (!g) return GPMI_ERR_ARG;
   gpmi_ctx* c = g->ctx;
-  if (int rc = sgp_cov_args(g, "gpmi_sgp_posterior", mq)) return rc;
-  if (mq == 0) return GPMI_OK;
+  bool proceed;
+  if (int rc = sgp_query_args(g, "gpmi_sgp_posterior", mq, true, proceed)) return rc;
+  if (!proceed) return GPMI_OK;
   ARGCHK(c, pts != nullptr && mean != nullptr, "gpmi_sgp_posterior: pts_host and mean_host must be non-NULL");
   if (int rc = set_device(c)) return rc;
   hipStream_t s = c->sgp_stream;
-  const int64_t mpq = round_up(mq, GPMI_NB), ldq = mpq + 32;
-  // (an error return below may leave work on these in flight: hipFree waits for the device before it releases)
-  DevBuf P, VU, mu, Sigma;
-  HIPCHK(c, hipMalloc(&P.p, sizeof(double) * mpq * g->d));
-  HIPCHK(c, hipMalloc(&VU.p, sizeof(double) * 2 * mpq * g->ld));
-  HIPCHK(c, hipMalloc(&mu.p, sizeof(double) * mpq));
-  if (cov) HIPCHK(c, hipMalloc(&Sigma.p, sizeof(double) * mpq * ldq));
-  int rc = sgp_posterior_sigma(g, pts, mq, mpq, P.as<double>(), VU.as<double>(), mu.as<double>(), Sigma.as<double>(), ldq);
+  PosteriorBufs b;
+  if (int rc = b.alloc(g, mq, cov != nullptr)) return rc;
+  int rc = sgp_posterior_sigma(g, pts, mq, b);
   hipError_t e = hipSuccess;
   if (rc == GPMI_OK) {
-    e = hipMemcpyAsync(mean, mu.p, sizeof(double) * mq, hipMemcpyDeviceToHost, s);
+    e = hipMemcpyAsync(mean, b.mu.p, sizeof(double) * mq, hipMemcpyDeviceToHost, s);
     if (cov && e == hipSuccess) {
-      launch_mirror_lower(s, Sigma.as<double>(), ldq, mpq);
-      e = hipMemcpy2DAsync(cov, sizeof(double) * mq, Sigma.p, sizeof(double) * ldq, sizeof(double) * mq, (size_t)mq,
+      launch_mirror_lower(s, b.Sigma.as<double>(), b.ldq, b.mpq);
+      e = hipMemcpy2DAsync(cov, sizeof(double) * mq, b.Sigma.p, sizeof(double) * b.ldq, sizeof(double) * mq, (size_t)mq,
                            hipMemcpyDeviceToHost, s);
     }
   }
@@ -1356,8 +1162,9 @@ int gpmi_sgp_posterior_draws(gpmi_sgp* g, const double* pts, int64_t mq, double 
                              int64_t seed, int64_t first_draw, double* mean, double* draws_host, double* eps_host, int* info) {
   if (!g) return GPMI_ERR_ARG;
   gpmi_ctx* c = g->ctx;
-  if (int rc = sgp_cov_args(g, "gpmi_sgp_posterior_draws", mq)) return rc;
-  if (mq == 0) return GPMI_OK;
+  bool proceed;
+  if (int rc = sgp_query_args(g, "gpmi_sgp_posterior_draws", mq, true, proceed)) return rc;
+  if (!proceed) return GPMI_OK;
   if (int rc = draws_check_args(c, mq, jitter_rel, n_draws, first_draw, draws_host)) return rc;
   ARGCHK(c, pts != nullptr, "gpmi_sgp_posterior_draws: pts_host is NULL");
   if (int rc = set_device(c)) return rc;
@@ -1368,24 +1175,21 @@ int gpmi_sgp_posterior_draws(gpmi_sgp* g, const double* pts, int64_t mq, double 
     if (int rc = lane_streams(c, c->lanes[0])) return rc;
   }
   Lane& L = c->lanes[0];
-  const int64_t mpq = round_up(mq, GPMI_NB), ldq = mpq + 32;
-  DevBuf P, VU, mu, Sigma;
-  HIPCHK(c, hipMalloc(&P.p, sizeof(double) * mpq * g->d));
-  HIPCHK(c, hipMalloc(&VU.p, sizeof(double) * 2 * mpq * g->ld));
-  HIPCHK(c, hipMalloc(&mu.p, sizeof(double) * mpq));
-  HIPCHK(c, hipMalloc(&Sigma.p, sizeof(double) * mpq * ldq));
+  PosteriorBufs b;
+  if (int rc = b.alloc(g, mq, true)) return rc;
+  const int64_t mpq = b.mpq, ldq = b.ldq;
   int rc;
   {
     ProfScope ps(c, c->sgp_stream, GPMI_PROF_DRAWS_SIGMA, 4.0 * mpq * g->mp * g->mp + 2.0 * mpq * mpq * g->mp,
                  8.0 * mpq * (2.0 * g->mp + mpq));
-    rc = sgp_posterior_sigma(g, pts, mq, mpq, P.as<double>(), VU.as<double>(), mu.as<double>(), Sigma.as<double>(), ldq);
+    rc = sgp_posterior_sigma(g, pts, mq, b);
   }
   hipError_t e = hipSuccess;
-  if (rc == GPMI_OK && mean) e = hipMemcpyAsync(mean, mu.p, sizeof(double) * mq, hipMemcpyDeviceToHost, c->sgp_stream);
+  if (rc == GPMI_OK && mean) e = hipMemcpyAsync(mean, b.mu.p, sizeof(double) * mq, hipMemcpyDeviceToHost, c->sgp_stream);
   // the tail runs on the lane's stream: Sigma and mu are complete before it reads them
   const hipError_t e1 = hipStreamSynchronize(c->sgp_stream);
   if (rc == GPMI_OK && e == hipSuccess && e1 == hipSuccess)
-    rc = draws_tail(c, L, Sigma.as<double>(), ldq, mq, mpq, mu.as<double>(), jitter_rel, n_draws, z_host, seed, first_draw,
+    rc = draws_tail(c, L, b.Sigma.as<double>(), ldq, mq, mpq, b.mu.as<double>(), jitter_rel, n_draws, z_host, seed, first_draw,
                     draws_host, eps_host, info);
   const hipError_t e2 = hipStreamSynchronize(L.stream);  // (before Sigma is released, whatever the tail returned)
   if (rc != GPMI_OK) return rc;

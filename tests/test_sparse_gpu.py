@@ -31,30 +31,9 @@ import pytest
 from numpy.linalg import LinAlgError
 
 import sparse_host as sh
+from sparse_host import MU, N_RIPPLES, case as _case, check, full_theta, make_gp
 
 pytestmark = pytest.mark.gpu
-
-N_RIPPLES = 48
-MU = 0.2  # the constant mean of every case
-
-
-def _case(number):
-    if number == 1:
-        kind, n, d, m, panel, white, use_err, ell = "se", 300, 3, 33, 128, 0.02, True, 0.35
-    elif number == 2:
-        kind, n, d, m, panel, white, use_err, ell = "m52", 2100, 2, 130, 512, 0.0, True, 0.2
-    elif number == 3:
-        kind, n, d, m, panel, white, use_err, ell = "rq", 257, 17, 64, 0, 0.01, False, 1.5
-    elif number == 4:
-        kind, n, d, m, panel, white, use_err, ell = "m32", 200, 64, 1, 0, 0.0, True, 3.0
-    else:
-        kind, n, d, m, panel, white, use_err, ell = "se", 70, 1, 129, 0, 0.0, True, 0.005
-    x, y, e = sh.dataset(n, d, seed=number)
-    z = np.linspace(0.0, 1.0, m).reshape(-1, 1) if number == 5 else x[sh.spread_rows(x, m)].copy()
-    scales = ell * (1.0 + 0.1 * np.arange(d) / max(d - 1, 1))  # (unequal length scales: every dimension has its own gradient)
-    theta = np.array([0.1] + ([0.3] if kind == "rq" else []) + list(np.log(scales)))
-    q = np.random.default_rng(40 + number).uniform(0.0, 1.0, size=(17, d))
-    return dict(number=number, kind=kind, x=x, y=y, e=e if use_err else None, z=z, theta=theta, white=white, panel=panel, q=q)
 
 
 def _quantities(case, mir, ripple=None):
@@ -87,30 +66,6 @@ def reference(number):
         allow = {k: max(10.0 * spread[k], 1e-10 * scale[k]) for k in base}
         _REFERENCE[number] = (case, base, allow)
     return _REFERENCE[number]
-
-
-def make_gp(case, panel_rows=None, jitter=1e-8):
-    from inference_amd.gp import Matern32, Matern52, RationalQuadratic, SparseGpRegressor, SquaredExponential, WhiteNoise
-
-    kern = {"se": SquaredExponential, "m52": Matern52, "m32": Matern32, "rq": RationalQuadratic}[case["kind"]]()
-    if case["white"] > 0.0:
-        kern = kern + WhiteNoise()
-    return SparseGpRegressor(case["x"], case["y"], y_err=case["e"], inducing_points=case["z"], kernel=kern,
-                             hyperpars=full_theta(case), jitter=jitter,
-                             panel_rows=case["panel"] if panel_rows is None else panel_rows)
-
-
-def full_theta(case):
-    th = [MU] + list(case["theta"])
-    if case["white"] > 0.0:
-        th.append(0.5 * np.log(case["white"]))
-    return np.array(th)
-
-
-def check(label, got, want, allow):
-    err = float(np.abs(np.asarray(got) - np.asarray(want)).max())
-    print(f"{label}: device error {err:.3e}, allowance {allow:.3e}")
-    assert err <= allow, (label, err, allow)
 
 
 @pytest.mark.parametrize("number", [1, 2, 3, 4, 5])

@@ -48,31 +48,12 @@ import pytest
 
 import sparse_host as sh
 import sparse_post_host as sph
+from sparse_host import MU, N_RIPPLES, case as _case, check, full_theta, make_gp
 
 pytestmark = pytest.mark.gpu
 
-N_RIPPLES = 48
-MU = 0.2  # the constant mean of every case
 JITTER = 1e-9  # of the draws
 SIZES = {1: (1, 65, 130, 1025, 129), 2: (1, 65, 130), 3: (1, 65, 130), 4: (1, 65, 130), 5: (1, 65, 130)}
-
-
-def _case(number):
-    if number == 1:
-        kind, n, d, m, panel, white, use_err, ell = "se", 300, 3, 33, 128, 0.02, True, 0.35
-    elif number == 2:
-        kind, n, d, m, panel, white, use_err, ell = "m52", 2100, 2, 130, 512, 0.0, True, 0.2
-    elif number == 3:
-        kind, n, d, m, panel, white, use_err, ell = "rq", 257, 17, 64, 0, 0.01, False, 1.5
-    elif number == 4:
-        kind, n, d, m, panel, white, use_err, ell = "m32", 200, 64, 1, 0, 0.0, True, 3.0
-    else:
-        kind, n, d, m, panel, white, use_err, ell = "se", 70, 1, 129, 0, 0.0, True, 0.005
-    x, y, e = sh.dataset(n, d, seed=number)
-    z = np.linspace(0.0, 1.0, m).reshape(-1, 1) if number == 5 else x[sh.spread_rows(x, m)].copy()
-    scales = ell * (1.0 + 0.1 * np.arange(d) / max(d - 1, 1))  # (unequal length scales: every dimension has its own gradient)
-    theta = np.array([0.1] + ([0.3] if kind == "rq" else []) + list(np.log(scales)))
-    return dict(number=number, kind=kind, x=x, y=y, e=e if use_err else None, z=z, theta=theta, white=white, panel=panel)
 
 
 def queries(case, M):
@@ -126,23 +107,6 @@ def reference(number):
     return _REFERENCE[number]
 
 
-def full_theta(case):
-    th = [MU] + list(case["theta"])
-    if case["white"] > 0.0:
-        th.append(0.5 * np.log(case["white"]))
-    return np.array(th)
-
-
-def make_gp(case):
-    from inference_amd.gp import Matern32, Matern52, RationalQuadratic, SparseGpRegressor, SquaredExponential, WhiteNoise
-
-    kern = {"se": SquaredExponential, "m52": Matern52, "m32": Matern32, "rq": RationalQuadratic}[case["kind"]]()
-    if case["white"] > 0.0:
-        kern = kern + WhiteNoise()
-    return SparseGpRegressor(case["x"], case["y"], y_err=case["e"], inducing_points=case["z"], kernel=kern,
-                             hyperpars=full_theta(case), jitter=1e-8, panel_rows=case["panel"])
-
-
 _MODELS = {}
 
 
@@ -151,12 +115,6 @@ def model(number):
     if number not in _MODELS:
         _MODELS[number] = make_gp(reference(number)[0])
     return _MODELS[number]
-
-
-def check(label, got, want, allow):
-    err = float(np.abs(np.asarray(got) - np.asarray(want)).max())
-    print(f"{label}: device error {err:.3e}, allowance {allow:.3e}")
-    assert err <= allow, (label, err, allow)
 
 
 POINTS = [(n, M) for n in (1, 2, 3, 4, 5) for M in (1, 65, 130)] + [(1, 1025)]
