@@ -743,6 +743,36 @@ int gpmi_sgp_posterior_draws(gpmi_sgp* sgp, const double* pts_host /* mq x d */,
 int gpmi_sgp_spatial_derivatives(gpmi_sgp* sgp, const double* pts_host /* mq x d */, int64_t mq,
                                  double* dmean_host /* mq x d */, double* dvar_host /* mq x d, may be NULL */);
 
+/* Greedy conditional-variance selection of inducing points among the rows of x: the pivoted partial Cholesky factorisation
+ * of K_nn (the greedy MAP of a k-DPP; Burt, Rasmussen and van der Wilk, JMLR 2020).  It needs no gpmi_sgp object and no
+ * gpmi_set_data.  The work is done in unit prior variance, C = K / a^2: theta has the layout of gpmi_sgp_bound, theta[0] =
+ * ln a is read and not used.  weight_host: w_i >= 0 (NULL: all 1; for the bound of gpmi_sgp_bound, 1 / sigma_i^2).
+ *   State: d_i = 1;  V, count x n, row t contiguous in i;  tr_0 = sum_i w_i.
+ *   Step t = 0, 1, ...:
+ *   1. eligible are the i with d_i > floor_rel and w_i > 0.  Stop - count = t - if none is left, if t = m_max or if
+ *      tr_t <= trace_tol tr_0.
+ *   2. the pivot p = argmax over the eligible of w_i d_i, the lowest index among equal scores (numpy.argmax; step 0 without
+ *      weights is a tie of ones: row 0).  pivot_var[t] = d_p.
+ *   3. c_i = C(x_i, x_p) - sum_{l<t} V_li V_lp in ascending l,  V_ti = c_i / sqrt(d_p).  C(x_i, x_p) has the bits of the
+ *      covariance builders (s = sum_k 1/2 dx_k^2 / l_k^2 by one fma per dimension in ascending k, then the kernel's profile),
+ *      so V_ti depends on (x_i, the pivots, theta) alone: not on n, not on the place of row i.
+ *   4. d_i <- max(d_i - V_ti^2, 0),  d_p <- 0,  tr_{t+1} = sum_i w_i d_i: a sum of fixed order, no atomics.
+ * Results: count; index_host[0 .. count): the pivots in the order chosen - the first k are the selection of size k;
+ * trace_host[0 .. count]: tr_0 .. tr_count (a^2 tr_k is the trace term a^2 sum w - tr H of the bound at Z = x[first k pivots],
+ * jitter 0); pivot_var_host[0 .. count).  Entries beyond count are left untouched.  Repeated calls give the same bits.
+ * One launch per step and no host synchronisation between them; a step reads t n doubles of V, a selection moves about
+ * 8 n m_max^2 / 2 bytes: it is bound by HBM.
+ * Limits: 1 <= n <= 2^30, 1 <= d <= 64, 1 <= m_max <= min(n, GPMI_SGP_MAX_M).
+ * GPMI_ERR_ARG (the handle stays usable): a NULL pointer that is not optional; a kernel other than GPMI_KERNEL_SE, _RQ, _M32,
+ * _M52; n_theta that does not match the kernel and d; x or theta not finite; weights negative, not finite or without a
+ * positive entry; floor_rel or trace_tol negative or not finite.  GPMI_ERR_NOMEM: V could not be allocated.
+ * Device memory, allocated for the call and released at return: V, 8 n m_max bytes, x, and two or three vectors of n
+ * doubles. */
+int gpmi_select_points(gpmi_ctx* ctx, int64_t n, int64_t d, const double* x_host /* n x d */,
+                       const double* weight_host /* n, may be NULL */, int kernel, const double* theta, int n_theta,
+                       int64_t m_max, double floor_rel, double trace_tol, int64_t* index_host /* m_max */,
+                       double* trace_host /* m_max + 1 */, double* pivot_var_host /* m_max, may be NULL */, int64_t* count);
+
 /* ---- instrumentation ---------------------------------------------------------------
  * HIP-event timing on the handle's own stream (torch.cuda.Event would not see it). */
 int gpmi_timer_start(gpmi_ctx* ctx);

@@ -10,6 +10,8 @@ The inducing inputs are variational parameters: `marginal_likelihood_gradient(th
 (gpmi_sgp_bound_zgrad: a contraction behind the theta-gradient's, on the same panels), `set_inducing_points` moves Z
 without rebuilding the object, and `optimise_inducing_points` (or the constructor's `optimise_inducing=True`) runs one
 L-BFGS-B over vec(Z), or over [theta | vec(Z)] jointly, every coordinate of Z inside the bounding box of x.
+Where Z starts: a random subset of x, or (`inducing_method="greedy"`, `select_inducing_points`,
+`reselect_inducing_points`) the rows greedy conditional-variance selection picks on the device (gpmi_select_points).
 
 Supported: one of SquaredExponential, RationalQuadratic, Matern32, Matern52 (class or instance), optionally
 `+ WhiteNoise()`; the mean functions of `inference_amd.gp.mean` (evaluated on the host); data errors `y_err`.
@@ -19,7 +21,8 @@ joint covariance), `sample_posterior` (joint draws; the covariance and the norma
 and through them the acquisition functions of `inference_amd.gp.acquisition` (`update_gp(sparse_model)`).
 Not supported: FITC, `gradient` (the covariance of the gradient), `GpOptimiser`, several GPUs.
 """
-from copy import copy
+import ctypes as C
+from copy import copy, deepcopy
 from inspect import isclass
 from warnings import warn
 
@@ -39,6 +42,81 @@ from inference_amd.gp.regression import GpRegressor
 
 SUPPORTED = ("one of SquaredExponential, RationalQuadratic, Matern32, Matern52 (class or instance), optionally "
              "+ WhiteNoise(), with y_err data errors")
+INDUCING_METHODS = ("random", "greedy")
+
+
+def _select_on_device(x, m, kernel_id, theta_stat, weights, tol, min_variance, device):
+    """gpmi_select_points on a handle of its own: (indices (count,), trace (count + 1,), pivot variances (count,))."""
+    x = _lib.as_f64(x)
+    theta_stat = _lib.as_f64(theta_stat)
+    weights = None if weights is None else _lib.as_f64(weights)
+    if weights is not None and weights.shape != (x.shape[0],):
+        raise ValueError(f"weights must have shape ({x.shape[0]},), got {weights.shape}")
+    index, trace, pivot_var = np.zeros(m, dtype=np.int64), np.zeros(m + 1), np.zeros(m)
+    count = C.c_int64(0)
+    h = _lib.Handle(device)
+    try:
+        h.call("gpmi_select_points", x.shape[0], x.shape[1], _lib.dptr(x), _lib.dptr(weights), int(kernel_id),
+               _lib.dptr(theta_stat), theta_stat.size, int(m), float(min_variance), float(tol),
+               index.ctypes.data_as(C.POINTER(C.c_int64)), _lib.dptr(trace), _lib.dptr(pivot_var), C.byref(count))
+    finally:
+        h.close()
+    k = count.value
+    return index[:k].copy(), trace[:k + 1].copy(), pivot_var[:k].copy()
+
+
+def select_inducing_points(x, m, kernel, theta_cov, *, weights=None, tol=0.0, min_variance=1e-8, candidates=None, seed=None,
+                           device=None):
+    """
+    Greedy conditional-variance selection of m rows of x as inducing inputs, on the device (include/gpmi.h:
+    gpmi_select_points): the pivoted partial Cholesky factorisation of K_nn.  Each step takes the point whose prior
+    variance is least explained by the points already chosen (times its weight), so the first k indices are the selection
+    of size k, and the quantity driven down, sum_i w_i (a^2 - Q_ii), is the trace term of the bound.
+
+    :param x: (N, d) points (1-D input means d = 1).
+    :param m: the most points to select, 1 <= m <= min(N, 4096).
+    :param kernel: a stationary device kernel (class or instance), optionally ``+ WhiteNoise()``, whose part is ignored.
+    :param theta_cov: the kernel's parameters in its own layout.
+    :param weights: (N,) weights w_i >= 0, e.g. 1 / sigma_i^2; None: all 1.  Rows of weight 0 are never selected.
+    :param tol: stop once the trace has fallen to `tol` times its start.
+    :param min_variance: points whose conditional variance (in units of a^2) is not above it are not selected.
+    :param candidates: k: select among k rows drawn by ``default_rng(seed).choice(N, k, replace=False)``, sorted, which
+        bounds the device memory at k m 8 bytes.  The indices returned refer to x.
+    :return: (indices (count,), trace (count + 1,), pivot_variances (count,)) with count <= m: the rows in the order
+        chosen, tr_0 .. tr_count in units of a^2, and the conditional variance of each row when it was chosen.
+    """
+    x = np.asarray(x, dtype=float)
+    if x.ndim == 1:
+        x = x.reshape(-1, 1)
+    if x.ndim != 2 or x.shape[1] > msg.MAX_DIMENSIONS:
+        raise ValueError(f"x must be an (N, d) array with d <= {msg.MAX_DIMENSIONS}, got shape {x.shape}")
+    cov = deepcopy(kernel() if isclass(kernel) else kernel)
+    cov.pass_spatial_data(x)
+    plan = device_plan(cov)
+    if plan is None or not isinstance(plan[1], _StationaryDeviceKernel):
+        raise NotImplementedError(f"select_inducing_points: unsupported covariance {type(cov).__name__}; supported: {SUPPORTED}")
+    kernel_id, _, stat_slice, _ = plan
+    theta_cov = np.asarray(theta_cov, dtype=float)
+    if theta_cov.shape != (cov.n_params,):
+        raise ValueError(f"theta_cov must have {cov.n_params} entries, got shape {theta_cov.shape}")
+    rows = None
+    if candidates is not None:
+        k = int(candidates)
+        if not 1 <= k <= x.shape[0]:
+            raise ValueError(f"candidates = {k}: must lie in 1 .. N = {x.shape[0]}")
+        rows = np.sort(np.random.default_rng(seed).choice(x.shape[0], k, replace=False))
+    n = x.shape[0] if rows is None else len(rows)
+    m = int(m)
+    if not 1 <= m <= min(n, _lib.SGP_MAX_M):
+        raise ValueError(f"m = {m}: must lie in 1 .. min(number of candidate rows, {_lib.SGP_MAX_M})")
+    if weights is not None:
+        weights = np.asarray(weights, dtype=float)
+        if weights.shape != (x.shape[0],):
+            raise ValueError(f"weights must have shape ({x.shape[0]},), got {weights.shape}")
+    index, trace, pivot_var = _select_on_device(x if rows is None else x[rows], m, kernel_id, theta_cov[stat_slice],
+                                                weights if weights is None or rows is None else weights[rows], tol,
+                                                min_variance, device)
+    return (index if rows is None else rows[index]), trace, pivot_var
 
 
 class SparseGpRegressor:
@@ -54,6 +132,11 @@ class SparseGpRegressor:
     :param optimizer: ``"bfgs"`` (multi-start L-BFGS-B on the device gradient) or ``"diffev"``.
     :param n_starts: number of L-BFGS-B starts (default as `GpRegressor`).
     :param seed: seed of the inducing-point choice.
+    :param inducing_method: what an int `inducing_points` means: ``"random"`` - the draw above - or ``"greedy"``: the rows
+        `select_inducing_points` picks on the device at `hyperpars` (or, if they are to be searched, at the midpoint of
+        `hp_bounds`, the search's own last start), weighted by 1 / (y_err^2 + s^2) when `y_err` was given.  Z keeps the
+        order in which the rows were chosen; the selection is kept in `inducing_selection`.  A selection that stops
+        short of m warns and the model is built with the rows it found.
     :param jitter: eps = jitter a^2 is added to the diagonal of K_mm.
     :param panel_rows: (extension) rows of x per panel of the device sweep; 0: the library's default.
     :param optimise_inducing: True: once the hyper-parameters are set, `optimise_inducing_points` moves Z - at the given
@@ -61,7 +144,12 @@ class SparseGpRegressor:
     """
 
     def __init__(self, x, y, y_err=None, inducing_points=256, kernel=SquaredExponential, mean=ConstantMean, hyperpars=None,
-                 optimizer="bfgs", n_starts=None, seed=None, jitter=1e-8, device=None, y_cov=None, panel_rows=0, optimise_inducing=False):
+                 optimizer="bfgs", n_starts=None, seed=None, jitter=1e-8, device=None, y_cov=None, panel_rows=0, optimise_inducing=False,
+                 inducing_method="random"):
+        if inducing_method not in INDUCING_METHODS:
+            raise ValueError(f"inducing_method = {inducing_method!r}: must be one of {INDUCING_METHODS}")
+        if inducing_method == "greedy" and not isinstance(inducing_points, (int, np.integer)):
+            raise ValueError('inducing_method = "greedy" selects the inducing points itself: inducing_points must be an int')
         self.x, self.y = GpRegressor._coerce_training_data(x, y)
         self.x = np.ascontiguousarray(self.x, dtype=float)
         self.y = np.asarray(self.y, dtype=float)
@@ -101,8 +189,11 @@ class SparseGpRegressor:
             m = int(inducing_points)
             if not 1 <= m <= min(self.n_points, _lib.SGP_MAX_M):
                 raise ValueError(f"inducing_points = {m}: an int must lie in 1 .. min(N, {_lib.SGP_MAX_M})")
-            rows = np.sort(np.random.default_rng(seed).choice(self.n_points, m, replace=False))
-            self.inducing_points = self.x[rows].copy()
+            if inducing_method == "greedy":
+                self.inducing_points = None  # (selected below, once the hyper-parameters' bounds are known)
+            else:
+                rows = np.sort(np.random.default_rng(seed).choice(self.n_points, m, replace=False))
+                self.inducing_points = self.x[rows].copy()
         else:
             z = np.asarray(inducing_points, dtype=float)
             if z.ndim == 1 and self.n_dimensions == 1:
@@ -127,6 +218,10 @@ class SparseGpRegressor:
         self._device = device
         self._engine = None
         self._targets_mean = None
+
+        if self.inducing_points is None:
+            at = hyperpars if hyperpars is not None else [0.5 * (lo + hi) for lo, hi in self.hp_bounds]
+            self.inducing_points, self.inducing_selection = self._greedy_selection(int(inducing_points), at, 0.0)
 
         searched = hyperpars is None
         if hyperpars is None:
@@ -230,6 +325,49 @@ class SparseGpRegressor:
         """Move the inducing inputs to the (m, d) finite array z (same m) and fit again at the current hyper-parameters.
         ValueError for anything else, LinAlgError if the fit fails; both leave the previous Z and fit in place."""
         self._move(self._check_inducing(z), self.hyperpars)
+
+    def _greedy_selection(self, m, theta, tol):
+        """(Z in pivot order, dict(indices, trace, pivot_variances)) of the greedy selection at theta; warns if it stopped
+        short of m."""
+        theta = np.asarray(theta, dtype=float)
+        if theta.size != self.n_hyperpars:
+            raise ValueError(msg.wrong_hyperpar_count(self.n_hyperpars, theta.size))
+        theta_cov = theta[self.cov_slice]
+        white = float(np.exp(2.0 * theta_cov[self._wn_index])) if self._wn_index is not None else 0.0
+        weights = None if self._noise_var is None else 1.0 / (self._noise_var + white)
+        index, trace, pivot_var = _select_on_device(self.x, m, self._kernel_id, theta_cov[self._stat_slice], weights, tol, 1e-8,
+                                                    self._device)
+        if len(index) < m:
+            warn(f"the greedy selection stopped at {len(index)} of {m} inducing points: the model is built with those")
+        return self.x[index].copy(), dict(indices=index, trace=trace, pivot_variances=pivot_var)
+
+    def reselect_inducing_points(self, m=None, tol=0.0):
+        """Select the inducing points again, greedily at the current hyper-parameters (`select_inducing_points`; m: the
+        current number), and fit there.  Returns (F_before, F_after).  Another number of points rebuilds the device
+        object.  LinAlgError if the fit fails: the previous Z and fit are put back."""
+        m = self.inducing_points.shape[0] if m is None else int(m)
+        if not 1 <= m <= min(self.n_points, _lib.SGP_MAX_M):
+            raise ValueError(f"m = {m}: must lie in 1 .. min(N, {_lib.SGP_MAX_M})")
+        F_before = self.bound
+        z, selection = self._greedy_selection(m, self.hyperpars, tol)
+        if z.shape == self.inducing_points.shape:
+            self._move(z, self.hyperpars)
+        else:
+            old_z = self.inducing_points
+            try:
+                self._rebuild(z)
+            except LinAlgError:
+                self._rebuild(old_z)
+                raise
+        self.inducing_selection = selection
+        return F_before, self.bound
+
+    def _rebuild(self, z):
+        """Z of another shape: the engine is dropped and built anew with the fit, as for a model back from pickle."""
+        self.inducing_points = z
+        self._engine = None
+        self._targets_mean = None
+        self.set_hyperparameters(self.hyperpars)
 
     def optimise_inducing_points(self, hyperpars=True, maxiter=200):
         """One L-BFGS-B on the device gradients from the current state, over vec(Z) or (hyperpars=True) [theta | vec(Z)]:
