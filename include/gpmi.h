@@ -742,6 +742,13 @@ int gpmi_sgp_posterior_draws(gpmi_sgp* sgp, const double* pts_host /* mq x d */,
  * run of 128 inducing inputs and the panel's results), besides the three query panels of gpmi_sgp_predict. */
 int gpmi_sgp_spatial_derivatives(gpmi_sgp* sgp, const double* pts_host /* mq x d */, int64_t mq,
                                  double* dmean_host /* mq x d */, double* dvar_host /* mq x d, may be NULL */);
+/* Host-only (no device call): the size-dependent schedule of gpmi_sgp_bound / _bound_zgrad / _fit for n data points, m
+ * inducing points and the caller's panel_rows, from the functions the launches themselves call.  out = {P, the rows of x per
+ * panel; m_pad; the 64-row tiles one workgroup of the dF/dZ contraction sums over a data panel (2, 4, 8 or 16); the same for
+ * its K_mm term; the workgroups of the pass that forms 1 / sigma_i^2 (at most 1024: beyond 262144 points a workgroup strides);
+ * the number of panels, ceil(n / P)}.  GPMI_ERR_ARG on the ranges of gpmi_sgp_create and gpmi_sgp_bound: n outside 2 .. 2^30,
+ * m outside 1 .. GPMI_SGP_MAX_M, panel_rows outside 0 .. 32768, out NULL.  The tests use it to prove which branch they ran. */
+int gpmi_sgp_schedule(int64_t n, int64_t m, int64_t panel_rows, int64_t out[6]);
 
 /* Greedy conditional-variance selection of inducing points among the rows of x: the pivoted partial Cholesky factorisation
  * of K_nn (the greedy MAP of a k-DPP; Burt, Rasmussen and van der Wilk, JMLR 2020).  It needs no gpmi_sgp object and no
@@ -772,6 +779,10 @@ int gpmi_select_points(gpmi_ctx* ctx, int64_t n, int64_t d, const double* x_host
                        const double* weight_host /* n, may be NULL */, int kernel, const double* theta, int n_theta,
                        int64_t m_max, double floor_rel, double trace_tol, int64_t* index_host /* m_max */,
                        double* trace_host /* m_max + 1 */, double* pivot_var_host /* m_max, may be NULL */, int64_t* count);
+/* Host-only (no device call): out = {the workgroups of a selection step over n points, ceil(n / 256)} - as many block partials
+ * as every workgroup reduces at the next launch (beyond 65536 points a thread reads more than one).  n outside 1 .. 2^30 or
+ * out NULL: GPMI_ERR_ARG. */
+int gpmi_select_schedule(int64_t n, int64_t out[1]);
 
 /* ---- instrumentation ---------------------------------------------------------------
  * HIP-event timing on the handle's own stream (torch.cuda.Event would not see it). */

@@ -174,6 +174,10 @@ __global__ __launch_bounds__(SEL_NT) void select_step_kernel(KParams p, SelState
   if (tid == 0) st.part[(size_t)((t + 1) & 1) * st.nblocks + blockIdx.x] = mine;
 }
 
+// workgroups of a step (one point per thread), the block partials every workgroup reduces at the next launch
+int select_blocks(int64_t n) { return (int)((n + SEL_NT - 1) / SEL_NT); }
+bool select_n_ok(int64_t n) { return n >= 1 && n <= ((int64_t)1 << 30); }
+
 int select_arg_error(gpmi_ctx* c, const char* what) {
   c->err = std::string("gpmi_select_points: ") + what;
   return GPMI_ERR_ARG;
@@ -181,13 +185,19 @@ int select_arg_error(gpmi_ctx* c, const char* what) {
 
 }  // namespace
 
+extern "C" int gpmi_select_schedule(int64_t n, int64_t out[1]) {
+  if (!out || !select_n_ok(n)) return GPMI_ERR_ARG;
+  out[0] = select_blocks(n);
+  return GPMI_OK;
+}
+
 extern "C" int gpmi_select_points(gpmi_ctx* c, int64_t n, int64_t d, const double* x, const double* weight, int kernel,
                                   const double* theta, int n_theta, int64_t m_max, double floor_rel, double trace_tol,
                                   int64_t* index, double* trace, double* pivot_var, int64_t* count) {
   if (!c) return GPMI_ERR_ARG;
   if (!x || !theta || !index || !trace || !count)
     return select_arg_error(c, "x_host, theta, index_host, trace_host and count must be non-NULL");
-  if (n < 1 || n > ((int64_t)1 << 30)) return select_arg_error(c, "n out of range (1 .. 2^30)");
+  if (!select_n_ok(n)) return select_arg_error(c, "n out of range (1 .. 2^30)");
   if (d < 1 || d > GPMI_MAX_D) return select_arg_error(c, "d out of range (1 .. 64)");
   if (m_max < 1 || m_max > std::min<int64_t>(n, GPMI_SGP_MAX_M))
     return select_arg_error(c, "m_max out of range (1 .. min(n, 4096 = GPMI_SGP_MAX_M))");
@@ -224,7 +234,7 @@ extern "C" int gpmi_select_points(gpmi_ctx* c, int64_t n, int64_t d, const doubl
   hipStream_t s = c->sgp_stream;
 
   // device memory of the call, released at return
-  const int nblocks = (int)((n + SEL_NT - 1) / SEL_NT);
+  const int nblocks = select_blocks(n);
   const int mm = (int)m_max;
   DevBuf bx, bw, bd, bV, bpart, bidx, btr, bpv, bword;
   HIPCHK(c, hipMalloc(&bV.p, sizeof(double) * (size_t)n * (size_t)m_max));

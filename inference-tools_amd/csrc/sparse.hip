@@ -539,6 +539,9 @@ int launch_qgrad(gpmi_ctx* c, hipStream_t s, const KParams& p, const double* Z, 
 
 unsigned blocks(int64_t n) { return (unsigned)((n + SGP_NT - 1) / SGP_NT); }
 
+// workgroups of sgp_weights_kernel: one element per thread up to SGP_RED_BLOCKS workgroups, a grid-stride loop beyond
+unsigned weights_blocks(int64_t n) { return (unsigned)std::min<int64_t>(SGP_RED_BLOCKS, (n + SGP_NT - 1) / SGP_NT); }
+
 void sgp_free(gpmi_sgp* g) {
   for (double* q : {g->x, g->z, g->r, g->nv, g->w, g->alpha, g->invD1, g->invD2, g->vec, g->red, g->part, g->pvec, g->ws, g->zws, g->zacc,
                     g->q_pts, g->q_out, g->qws, g->fLinv, g->fLBinv, g->fc, g->fgamma, g->P[0], g->P[1], g->P[2]})
@@ -548,6 +551,11 @@ void sgp_free(gpmi_sgp* g) {
   if (g->info) (void)hipFree(g->info);
   delete g;
 }
+
+// the ranges gpmi_sgp_create, sgp_params and gpmi_sgp_schedule share
+bool sgp_n_ok(int64_t n) { return n >= 2 && n <= ((int64_t)1 << 30); }
+bool sgp_m_ok(int64_t m) { return m >= 1 && m <= GPMI_SGP_MAX_M; }
+bool sgp_panel_ok(int64_t panel_rows) { return panel_rows >= 0 && panel_rows <= SGP_MAX_PANEL; }
 
 bool sgp_live(gpmi_ctx* c, gpmi_sgp* g) {
   return std::find(c->sgp_live.begin(), c->sgp_live.end(), g) != c->sgp_live.end();
@@ -565,7 +573,7 @@ int sgp_params(gpmi_sgp* g, int kernel, const double* theta, int n_theta, double
   for (int k = 0; k < n_theta; ++k) ARGCHK(c, std::isfinite(theta[k]), "gpmi_sgp: theta must be finite");
   ARGCHK(c, std::isfinite(white) && white >= 0.0, "gpmi_sgp: white_var must be finite and not negative");
   ARGCHK(c, std::isfinite(jitter) && jitter >= 0.0, "gpmi_sgp: jitter_rel must be finite and not negative");
-  ARGCHK(c, panel_rows >= 0 && panel_rows <= SGP_MAX_PANEL, "gpmi_sgp: panel_rows out of range (0 .. 32768)");
+  ARGCHK(c, sgp_panel_ok(panel_rows), "gpmi_sgp: panel_rows out of range (0 .. 32768)");
   std::memset(&p, 0, sizeof(p));
   p.kernel = kernel;
   p.d = (int)g->d;
@@ -580,9 +588,10 @@ int sgp_params(gpmi_sgp* g, int kernel, const double* theta, int n_theta, double
 }
 
 // rows of x per panel of the two passes: the caller's panel_rows (0: GPMI_SGP_PANEL) in whole tiles, at most all of x
-int64_t sgp_panel_rows(const gpmi_sgp* g, int64_t panel_rows) {
-  return std::min<int64_t>(round_up(panel_rows > 0 ? panel_rows : GPMI_SGP_PANEL, GPMI_NB), round_up(g->n, GPMI_NB));
+int64_t sgp_panel_rows(int64_t n, int64_t panel_rows) {
+  return std::min<int64_t>(round_up(panel_rows > 0 ? panel_rows : GPMI_SGP_PANEL, GPMI_NB), round_up(n, GPMI_NB));
 }
+int64_t sgp_panel_rows(const gpmi_sgp* g, int64_t panel_rows) { return sgp_panel_rows(g->n, panel_rows); }
 
 // panels for R rows (a multiple of 128)
 int sgp_ensure_panels(gpmi_sgp* g, int64_t R) {
@@ -653,7 +662,7 @@ int sgp_factor(gpmi_sgp* g, const KParams& p, double white, double jitter, int64
   double *b = g->vec, *v1 = g->vec + mp, *cc = g->vec + 2 * mp;
   double hred[4] = {};
   {
-    const unsigned nblk = (unsigned)std::min<int64_t>(SGP_RED_BLOCKS, (n + SGP_NT - 1) / SGP_NT);
+    const unsigned nblk = weights_blocks(n);
     hipLaunchKernelGGL(sgp_weights_kernel, dim3(nblk), dim3(SGP_NT), 0, s, g->r, g->nv, white, n, g->w, g->part);
     hipLaunchKernelGGL(sgp_colsum_kernel, dim3(4), dim3(SGP_NT), 0, s, g->part, (int64_t)nblk, 4, g->red + RED_DATA, 0);
     HIPCHK(c, hipGetLastError());
@@ -923,14 +932,26 @@ void sgp_release_all(gpmi_ctx* c) {
 
 extern "C" {
 
+int gpmi_sgp_schedule(int64_t n, int64_t m, int64_t panel_rows, int64_t out[6]) {
+  if (!out || !sgp_n_ok(n) || !sgp_m_ok(m) || !sgp_panel_ok(panel_rows)) return GPMI_ERR_ARG;
+  const int64_t P = sgp_panel_rows(n, panel_rows), mp = round_up(m, GPMI_NB);
+  out[0] = P;
+  out[1] = mp;
+  out[2] = zrun_tiles(P, mp);   // launch_zcontract of a data panel: rows = the panel, columns = Z
+  out[3] = zrun_tiles(mp, mp);  // and of the K_mm term
+  out[4] = weights_blocks(n);
+  out[5] = (n + P - 1) / P;
+  return GPMI_OK;
+}
+
 int gpmi_sgp_create(gpmi_ctx* c, int64_t n, int64_t d, const double* x, int64_t m, const double* z, gpmi_sgp** out) {
   if (!c) return GPMI_ERR_ARG;
   ARGCHK(c, out != nullptr, "gpmi_sgp_create: out is NULL");
   *out = nullptr;
   ARGCHK(c, x != nullptr && z != nullptr, "gpmi_sgp_create: x_host and z_host must be non-NULL");
-  ARGCHK(c, n >= 2 && n <= ((int64_t)1 << 30), "gpmi_sgp_create: n out of range (2 .. 2^30)");
+  ARGCHK(c, sgp_n_ok(n), "gpmi_sgp_create: n out of range (2 .. 2^30)");
   ARGCHK(c, d >= 1 && d <= GPMI_MAX_D, "gpmi_sgp_create: d out of range (1 .. 64)");
-  ARGCHK(c, m >= 1 && m <= GPMI_SGP_MAX_M, "gpmi_sgp_create: m out of range (1 .. 4096 = GPMI_SGP_MAX_M inducing points)");
+  ARGCHK(c, sgp_m_ok(m), "gpmi_sgp_create: m out of range (1 .. 4096 = GPMI_SGP_MAX_M inducing points)");
   if (int rc = set_device(c)) return rc;
   if (!c->sgp_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->sgp_stream, hipStreamNonBlocking));
   gpmi_sgp* g = new gpmi_sgp();

@@ -677,6 +677,28 @@ class LinvEngine(_DrawsMixin):
         return mean, cov, info.value
 
 
+SGP_SCHEDULE_FIELDS = ("panel", "m_pad", "data_run_tiles", "kmm_run_tiles", "weight_blocks", "panels")
+
+
+def sgp_schedule(n, m, panel_rows=0):
+    """gpmi_sgp_schedule (host only, needs no device): the size-dependent schedule of the sparse model's evaluations as a
+    dict - rows of x per panel, m padded, the tiles per workgroup of the dF/dZ contraction over a data panel and over
+    K_mm, the workgroups of the weights pass and the number of panels.  ValueError outside the library's ranges."""
+    out = (C.c_int64 * 6)()
+    if _lib.load().gpmi_sgp_schedule(int(n), int(m), int(panel_rows), out) != 0:
+        raise ValueError(f"sgp_schedule: n = {n} (2 .. 2^30), m = {m} (1 .. {_lib.SGP_MAX_M}) or panel_rows = {panel_rows} "
+                         "(0 .. 32768) out of range")
+    return dict(zip(SGP_SCHEDULE_FIELDS, (int(v) for v in out)))
+
+
+def select_schedule(n):
+    """gpmi_select_schedule (host only): the workgroups - block partials - of a selection step over n points."""
+    out = (C.c_int64 * 1)()
+    if _lib.load().gpmi_select_schedule(int(n), out) != 0:
+        raise ValueError(f"select_schedule: n = {n} out of range (1 .. 2^30)")
+    return int(out[0])
+
+
 class SparseEngine:
     """One gpmi_sgp object (include/gpmi.h: the variational inducing-point model) on a handle of its own: x and the
     inducing inputs go up once, the residual and the data variances with `set_targets`; every evaluation then moves

@@ -95,9 +95,10 @@ class SparseMirror:
         u = solve_triangular(st["LB"], v, lower=True)
         return u.T @ st["c"], st["a2"] - (v**2).sum(axis=0) + (u**2).sum(axis=0)
 
-    def bound_and_gradient(self, theta, white_var, r, noise_var=None):
-        """(F, gradient by [theta, ln s], alpha): the last entry is 0 for white_var = 0."""
-        st = self.state(theta, white_var, r, noise_var)
+    def bound_and_gradient(self, theta, white_var, r, noise_var=None, st=None):
+        """(F, gradient by [theta, ln s], alpha): the last entry is 0 for white_var = 0.  st: the `state` of the same
+        arguments, if the caller has it already."""
+        st = st or self.state(theta, white_var, r, noise_var)
         r, w, a2, L, LB, Kmn, H, B = (st[k] for k in ("r", "w", "a2", "L", "LB", "Kmn", "H", "B"))
         m = len(L)
         Linv = solve_triangular(L, np.eye(m), lower=True)
@@ -199,6 +200,66 @@ def case(number):
     theta = np.array([0.1] + ([0.3] if kind == "rq" else []) + list(np.log(scales)))
     q = np.random.default_rng(40 + number).uniform(0.0, 1.0, size=(17, d))  # (the query points of test_sparse_gpu.py)
     return dict(number=number, kind=kind, x=x, y=y, e=e if use_err else None, z=z, theta=theta, white=white, panel=panel, q=q)
+
+
+# ---- the cases at the shapes where the device's schedules change (test_sparse_scale_*.py, golden/sparse_scale.npz) ----
+# name: (kind, N, d, m, panel_rows, WhiteNoise variance, length scale); every case has y_err
+SCALE_CASES = {
+    "tiles3": ("se", 700, 2, 300, 256, 0.02, 0.05),
+    "run4": ("m32", 32700, 1, 200, 32768, 0.0, 0.006),
+    "run8": ("m52", 32700, 1, 450, 32768, 0.0, 0.003),
+    "run16": ("m32", 32700, 1, 1000, 32768, 0.0, 0.0012),
+    "long": ("se", 262444, 1, 5, 0, 0.01, 0.3),
+    "max_m": ("m52", 300, 3, 4096, 0, 0.0, 0.04),
+    "bench_like": ("se", 16385, 8, 512, 0, 0.01, 0.8),
+}
+SCALE_NAMES = tuple(SCALE_CASES)
+# what gpmi_sgp_schedule must report for a case (inference_amd._engine.sgp_schedule), and a neighbouring smaller shape
+# (n, m, panel_rows) -> the fields that must differ there: the case is on the branch it is named after, the neighbour is not
+SCALE_SCHEDULE = {
+    "tiles3": (dict(panel=256, m_pad=384, panels=3), (700, 256, 256), dict(m_pad=256)),
+    "run4": (dict(panel=32768, m_pad=256, data_run_tiles=4, panels=1), (32700, 200, 16384), dict(data_run_tiles=2)),
+    "run8": (dict(panel=32768, m_pad=512, data_run_tiles=8, panels=1), (32700, 450, 16384), dict(data_run_tiles=4)),
+    "run16": (dict(panel=32768, m_pad=1024, data_run_tiles=16, panels=1), (32700, 1000, 16384), dict(data_run_tiles=8)),
+    "long": (dict(panel=8192, m_pad=128, weight_blocks=1024, panels=33), (262144, 5, 0), dict(weight_blocks=1024, panels=32)),
+    "max_m": (dict(m_pad=4096, kmm_run_tiles=8, panels=1), (300, 3968, 0), dict(kmm_run_tiles=4)),
+    "bench_like": (dict(panel=8192, m_pad=512, panels=3), (16384, 512, 0), dict(panels=2)),
+}
+SELECT_N, SELECT_M, SELECT_EXTRA = 66000, 24, 700  # the selection at 258 workgroups (261 with the appended rows)
+
+
+def scale_case(name):
+    """The case `name` of SCALE_CASES, in the layout of `case`: the same data set, mean and unequal length scales, Z
+    `spread_rows` of x except for max_m (the 16 x 16 x 16 cell centres of the unit cube, jittered) and bench_like (512
+    random rows, sorted: the benchmark's choice)."""
+    kind, n, d, m, panel, white, ell = SCALE_CASES[name]
+    number = 11 + SCALE_NAMES.index(name)
+    x, y, e = dataset(n, d, seed=number)
+    if name == "max_m":
+        c = (np.arange(16) + 0.5) / 16.0
+        z = np.stack(np.meshgrid(c, c, c, indexing="ij"), axis=-1).reshape(-1, 3)
+        z = z + np.random.default_rng(3).uniform(-0.01, 0.01, size=z.shape)
+    elif name == "bench_like":
+        z = x[np.sort(np.random.default_rng(number).choice(n, m, replace=False))].copy()
+    else:
+        z = x[spread_rows(x, m)].copy()
+    scales = ell * (1.0 + 0.1 * np.arange(d) / max(d - 1, 1))
+    theta = np.array([0.1] + list(np.log(scales)))
+    q = np.random.default_rng(40 + number).uniform(0.0, 1.0, size=(17, d))
+    return dict(number=number, name=name, kind=kind, x=x, y=y, e=e, z=np.ascontiguousarray(z), theta=theta, white=white,
+                panel=panel, q=q)
+
+
+def select_case():
+    """The selection at n = 66000: (x, theta of Matern52 with l = (0.2, 0.22), weights 1 / y_err^2)."""
+    x, _, e = dataset(SELECT_N, 2, seed=21)
+    return x, np.array([0.0, np.log(0.2), np.log(0.22)]), 1.0 / e**2
+
+
+def later_tile_rows(rows, run_tiles):
+    """Mask over `rows` points summed in 64-row tiles, `run_tiles` tiles per workgroup: the rows in the third and later
+    tiles of their run."""
+    return (np.arange(rows) // 64) % run_tiles >= 2
 
 
 def full_theta(case):

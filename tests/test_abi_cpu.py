@@ -19,7 +19,8 @@ def declared_symbols():
 
 def test_header_declares_the_path():
     syms = declared_symbols()
-    for must in ("gpmi_set_data", "gpmi_fit", "gpmi_lml", "gpmi_lml_batch", "gpmi_lml_grad", "gpmi_predict"):
+    for must in ("gpmi_set_data", "gpmi_fit", "gpmi_lml", "gpmi_lml_batch", "gpmi_lml_grad", "gpmi_predict",
+                 "gpmi_sgp_schedule", "gpmi_select_schedule"):
         assert must in syms
 
 
