@@ -73,6 +73,10 @@ int gpmi_destroy(gpmi_ctx* ctx);
 const char* gpmi_last_error(const gpmi_ctx* ctx);
 /* block until all work queued on the handle's stream has finished */
 int gpmi_sync(gpmi_ctx* ctx);
+/* bytes the library holds at this moment, over every handle and object of the process: out[0] device memory, out[1]
+ * pinned host memory.  Takes no handle and makes no HIP call (two counters kept where the library allocates and frees);
+ * what gpmi_destroy returns to the totals is what the handle had taken. */
+int gpmi_live_bytes(int64_t out[2]);
 
 /* ---- data -------------------------------------------------------------------------
  * Replaces GpRegressor.__init__ storing x, y and sig (regression.py:94-133, 246-322) and

@@ -245,11 +245,10 @@ int gpmi_acf_columns(gpmi_ctx* c, int64_t n, int64_t m, int64_t row_stride, int6
   const size_t y_b = kde_align256(y_bytes * mb_max);
   const size_t part_b = kde_align256(p_bytes * mb_max);
   const size_t d8_b = kde_align256(8 * (size_t)mb_max), d4_b = kde_align256(4 * (size_t)mb_max);
-  if (int rc = kde_grow_device(c, reinterpret_cast<void**>(&st->d_work), &st->d_work_bytes,
-                               raw_b + y_b + part_b + 3 * d8_b + 3 * d4_b))
+  if (int rc = st->reserve_work(c, raw_b + y_b + part_b + 3 * d8_b + 3 * d4_b))
     return rc;
-  if (int rc = kde_grow_pinned(c, st, 3 * d8_b + 3 * d4_b)) return rc;
-  char* w = reinterpret_cast<char*>(st->d_work);
+  if (int rc = st->reserve_pinned(c, 3 * d8_b + 3 * d4_b)) return rc;
+  char* w = st->d_work;
   double* d_raw = reinterpret_cast<double*>(w);
   double* d_y = reinterpret_cast<double*>(w + raw_b);
   double* d_part = reinterpret_cast<double*>(w + raw_b + y_b);

@@ -44,9 +44,7 @@ int lane_streams(gpmi_ctx* c, Lane& L) {
   HIPCHK(c, hipEventCreateWithFlags(&L.ev_slice, hipEventDisableTiming));
   // flag block of the fused panel columns (potrf_panel.hip) - here, not in lane_alloc: the stream-only lane of a bare
   // handle factorises too (gpmi_dev_potrf)
-  HIPCHK(c, hipMalloc(&L.panel_flags, sizeof(int) * GPMI_PANEL_FL_INTS));
-  ZERO_SYNC(c, L.panel_flags, sizeof(int) * GPMI_PANEL_FL_INTS);
-  return GPMI_OK;
+  return L.panel_flags.alloc_zeroed(c, GPMI_PANEL_FL_INTS);
 }
 
 
@@ -117,17 +115,15 @@ int lane_alloc(gpmi_ctx* c, Lane& L) {
     L.owns_pair = false;
   }
   const int64_t nt = c->np / GPMI_NB;
-  HIPCHK(c, hipMalloc(&L.A, sizeof(double) * c->np * c->ld));
-  HIPCHK(c, hipMalloc(&L.invD, sizeof(double) * nt * GPMI_NB * GPMI_NB));
+  if (int rc = L.A.alloc(c, c->np * c->ld)) return rc;
   // potrf_diag writes the block-lower part of an inverse only: the zeros above stay from here (round 4: zeroing them
   // in the kernel cost it 57 KB of stores per launch through one CU's memory path, as much as loading the block)
-  ZERO_SYNC(c, L.invD, sizeof(double) * nt * GPMI_NB * GPMI_NB);
-  HIPCHK(c, hipMalloc(&L.vec, sizeof(double) * 4 * c->np));
-  HIPCHK(c, hipMalloc(&L.red, sizeof(double) * 2 * RED_SLOTS));
-  HIPCHK(c, hipMalloc(&L.info, sizeof(int) * RED_SLOTS));
-  HIPCHK(c, hipHostMalloc(&L.h_red, sizeof(double) * 2 * RED_SLOTS));
-  HIPCHK(c, hipHostMalloc(&L.h_info, sizeof(int) * RED_SLOTS));
-  return GPMI_OK;
+  if (int rc = L.invD.alloc_zeroed(c, nt * GPMI_NB * GPMI_NB)) return rc;
+  if (int rc = L.vec.alloc(c, 4 * c->np)) return rc;
+  if (int rc = L.red.alloc(c, 2 * RED_SLOTS)) return rc;
+  if (int rc = L.info.alloc(c, RED_SLOTS)) return rc;
+  if (int rc = L.h_red.alloc(c, 2 * RED_SLOTS)) return rc;
+  return L.h_info.alloc(c, RED_SLOTS);
 }
 
 #define DBG_FREE(msg) do { if (std::getenv("GPMI_DEBUG_FREE")) std::fprintf(stderr, "[free] %s\n", msg); } while (0)
@@ -164,18 +160,7 @@ void lane_free(Lane& L) {
     if (L.su[k]) (void)hipStreamDestroy(L.su[k]);
   }
   DBG_FREE("lane: free buffers");
-  if (L.A) (void)hipFree(L.A);
-  if (L.B2) (void)hipFree(L.B2);
-  if (L.inv2) (void)hipFree(L.inv2);
-  if (L.inv2_t) (void)hipFree(L.inv2_t);
-  if (L.gws) (void)hipFree(L.gws);
-  if (L.invD) (void)hipFree(L.invD);
-  if (L.panel_flags) (void)hipFree(L.panel_flags);
-  if (L.vec) (void)hipFree(L.vec);
-  if (L.red) (void)hipFree(L.red);
-  if (L.info) (void)hipFree(L.info);
-  if (L.h_red) (void)hipHostFree(L.h_red);
-  if (L.h_info) (void)hipHostFree(L.h_info);
+  static_cast<LaneBufs&>(L) = LaneBufs();  // here, between the masked streams and the main stream: not at `L = Lane()`
   DBG_FREE("lane: destroy main stream");
   if (L.stream && L.owns_stream) (void)hipStreamDestroy(L.stream);
   DBG_FREE("lane: done");
@@ -195,61 +180,23 @@ int ensure_lanes(gpmi_ctx* c, size_t count) {
   return GPMI_OK;
 }
 
-void linv_free(LinvState& S);
-
-// the lockstep workspace: everything ensure_batch_ws, ensure_batch_grad_ws and the batch entry points allocate per problem
-// (the gradient batches' buffers were left behind at a new data set until round 4: a handle given a second data set of
-// another size kept using the first one's)
-void free_batch_ws(gpmi_ctx* c) {
-  for (double** q : {&c->bA, &c->bInv, &c->bVec, &c->bRed, &c->bMu, &c->bB2, &c->bGws, &c->bGout, &c->bLoo, &c->bQ, &c->bNoise,
-                     &c->bMixG, &c->bMixH, &c->bMixW, &c->bMixExtra}) {
-    if (*q) (void)hipFree(*q);
-    *q = nullptr;
-  }
-  for (void* q : {(void*)c->bMixP, (void*)c->bInfo, (void*)c->bParams, (void*)c->bSum})
-    if (q) (void)hipFree(q);
-  c->bMixP = nullptr;
-  c->bInfo = nullptr;
-  c->bParams = nullptr;
-  c->bSum = nullptr;
-  for (void* q : {(void*)c->h_bGout, (void*)c->h_bRed, (void*)c->h_bInfo})
-    if (q) (void)hipHostFree(q);
-  c->h_bGout = c->h_bRed = nullptr;
-  c->h_bInfo = nullptr;
-  c->bcap = c->bgrad_cap = c->bgrad_ntheta = c->bLoo_cap = c->bNoise_cap = c->bMix_cap = c->bQ_cap = 0;
-}
+// the lockstep workspace: everything ensure_batch_ws, ensure_batch_grad_ws and the batch entry points allocate per problem,
+// capacities to 0 (the gradient batches' buffers were left behind at a new data set until round 4: a handle given a second
+// data set of another size kept using the first one's)
+void free_batch_ws(gpmi_ctx* c) { static_cast<BatchBufs&>(*c) = BatchBufs(); }
 
 void free_data(gpmi_ctx* c) {
-  linv_free(c->linv);
-  for (double** q : {&c->mix_g, &c->mix_scratch, &c->mix_zero, &c->Q3}) {
-    if (*q) (void)hipFree(*q);
-    *q = nullptr;
-  }
-  c->mix_nk = 0;
-  c->q3_cap = 0;
+  c->linv = LinvState();
+  static_cast<MixBufs&>(*c) = MixBufs();
   for (size_t i = c->lanes.size(); i-- > 0;) lane_free(c->lanes[i]);  // (lanes >= 2 borrow the streams of lanes 0, 1)
   c->lanes.clear();
-  auto fr = [](double*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-  };
-  fr(c->x);
-  fr(c->y);
-  fr(c->noise);
-  fr(c->ycov);
-  fr(c->alpha);
-  fr(c->Q);
-  fr(c->Q2);
-  fr(c->pts);
-  fr(c->pvec);
+  static_cast<DataBufs&>(*c) = DataBufs();
+  static_cast<QueryBufs&>(*c) = QueryBufs();
   free_batch_ws(c);
   for (int k = 0; k < 2; ++k) {
-    if (c->h_bStage[k]) (void)hipHostFree(c->h_bStage[k]);
-    c->h_bStage[k] = nullptr;
-    c->h_bStage_bytes[k] = 0;
+    c->h_bStage[k].release();
     c->bpend[k] = 0;
   }
-  c->mq_cap = 0;
   c->fitted = false;
   c->n = c->d = c->np = c->ld = 0;
 }
@@ -415,8 +362,7 @@ int enqueue_factor_and_forward(gpmi_ctx* c, Lane& L, const CovParams& p, const d
 }
 
 int ensure_second_matrix(gpmi_ctx* c, Lane& L) {
-  if (!L.B2) HIPCHK(c, hipMalloc(&L.B2, sizeof(double) * c->np * c->ld));
-  return GPMI_OK;
+  return L.B2 ? GPMI_OK : L.B2.alloc(c, c->np * c->ld);
 }
 
 // inverses of the 512-wide diagonal blocks of the factor held by lane F, built on stream s (which must
@@ -424,8 +370,10 @@ int ensure_second_matrix(gpmi_ctx* c, Lane& L) {
 int ensure_inv2(gpmi_ctx* c, Lane& F, hipStream_t s) {
   if (F.inv2_valid) return GPMI_OK;
   const int64_t nob = (c->np / GPMI_NB + 3) / 4;
-  if (!F.inv2) HIPCHK(c, hipMalloc(&F.inv2, sizeof(double) * nob * GPMI_OB * GPMI_OB));
-  if (!F.inv2_t) HIPCHK(c, hipMalloc(&F.inv2_t, sizeof(double) * nob * 256 * 256));
+  if (!F.inv2)
+    if (int rc = F.inv2.alloc(c, nob * GPMI_OB * GPMI_OB)) return rc;
+  if (!F.inv2_t)
+    if (int rc = F.inv2_t.alloc(c, nob * 256 * 256)) return rc;
   build_inv2(s, F.A, c->np, c->ld, F.invD, F.inv2, F.inv2_t);
   HIPCHK(c, hipGetLastError());
   F.inv2_valid = true;
@@ -433,13 +381,7 @@ int ensure_inv2(gpmi_ctx* c, Lane& F, hipStream_t s) {
 }
 
 int ensure_trsm_panel(gpmi_ctx* c, int64_t rows) {
-  if (rows <= c->trsm_panel_rows) return GPMI_OK;
-  if (c->trsm_panel) (void)hipFree(c->trsm_panel);
-  c->trsm_panel = nullptr;
-  c->trsm_panel_rows = 0;
-  HIPCHK(c, hipMalloc(&c->trsm_panel, sizeof(double) * rows * (GPMI_OB + 32)));
-  c->trsm_panel_rows = rows;
-  return GPMI_OK;
+  return c->trsm_panel.reserve(c, rows * (GPMI_OB + 32));
 }
 
 // L.B2 <- F^-T (row j = column j of the inverse of lane F's factor), by forward substitution on the identity
@@ -477,17 +419,16 @@ int ensure_batch_ws(gpmi_ctx* c, int want) {
          "the batch workspace cannot grow while an asynchronous batch is pending (gpmi_lml_batch_wait first)");
   free_batch_ws(c);
   const int64_t nt = c->np / GPMI_NB;
-  HIPCHK(c, hipMalloc(&c->bA, sizeof(double) * want * c->np * c->ld));
-  HIPCHK(c, hipMalloc(&c->bInv, sizeof(double) * want * nt * GPMI_NB * GPMI_NB));
-  ZERO_SYNC(c, c->bInv, sizeof(double) * want * nt * GPMI_NB * GPMI_NB);  // see lane_alloc
-  HIPCHK(c, hipMalloc(&c->bVec, sizeof(double) * want * 4 * c->np));
-  HIPCHK(c, hipMalloc(&c->bRed, sizeof(double) * 2 * want));
-  HIPCHK(c, hipMalloc(&c->bMu, sizeof(double) * want * c->np));
-  HIPCHK(c, hipMalloc(&c->bInfo, sizeof(int) * want));
-  HIPCHK(c, hipMalloc(&c->bParams, sizeof(KParams) * want));
-  HIPCHK(c, hipMalloc(&c->bSum, sizeof(CovParams) * want));
-  HIPCHK(c, hipHostMalloc(&c->h_bRed, sizeof(double) * 2 * want));
-  HIPCHK(c, hipHostMalloc(&c->h_bInfo, sizeof(int) * want));
+  if (int rc = c->bA.alloc(c, want * c->np * c->ld)) return rc;
+  if (int rc = c->bInv.alloc_zeroed(c, want * nt * GPMI_NB * GPMI_NB)) return rc;  // see lane_alloc
+  if (int rc = c->bVec.alloc(c, want * 4 * c->np)) return rc;
+  if (int rc = c->bRed.alloc(c, 2 * want)) return rc;
+  if (int rc = c->bMu.alloc(c, want * c->np)) return rc;
+  if (int rc = c->bInfo.alloc(c, want)) return rc;
+  if (int rc = c->bParams.alloc(c, want)) return rc;
+  if (int rc = c->bSum.alloc(c, want)) return rc;
+  if (int rc = c->h_bRed.alloc(c, 2 * want)) return rc;
+  if (int rc = c->h_bInfo.alloc(c, want)) return rc;
   c->bcap = want;
   return GPMI_OK;
 }
@@ -496,21 +437,12 @@ int ensure_batch_ws(gpmi_ctx* c, int want) {
 int ensure_batch_grad_ws(gpmi_ctx* c, int want, int n_theta) {
   if (want > c->bcap) want = c->bcap;
   if (want <= c->bgrad_cap && n_theta <= c->bgrad_ntheta) return GPMI_OK;
-  auto fr = [](double*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-  };
-  fr(c->bB2);
-  fr(c->bGws);
-  fr(c->bGout);
-  if (c->h_bGout) (void)hipHostFree(c->h_bGout);
-  c->h_bGout = nullptr;
-  c->bgrad_cap = c->bgrad_ntheta = 0;
+  static_cast<BatchGradBufs&>(*c) = BatchGradBufs();
   const int cap = c->bcap;
-  HIPCHK(c, hipMalloc(&c->bB2, sizeof(double) * cap * c->np * c->ld));
-  HIPCHK(c, hipMalloc(&c->bGws, sizeof(double) * cap * grad_ws_doubles(c->np, n_theta)));
-  HIPCHK(c, hipMalloc(&c->bGout, sizeof(double) * cap * (n_theta + 1)));
-  HIPCHK(c, hipHostMalloc(&c->h_bGout, sizeof(double) * cap * (n_theta + 1)));
+  if (int rc = c->bB2.alloc(c, cap * c->np * c->ld)) return rc;
+  if (int rc = c->bGws.alloc(c, cap * grad_ws_doubles(c->np, n_theta))) return rc;
+  if (int rc = c->bGout.alloc(c, (int64_t)cap * (n_theta + 1))) return rc;
+  if (int rc = c->h_bGout.alloc(c, (int64_t)cap * (n_theta + 1))) return rc;
   c->bgrad_cap = cap;
   c->bgrad_ntheta = n_theta;
   return GPMI_OK;
@@ -518,19 +450,11 @@ int ensure_batch_grad_ws(gpmi_ctx* c, int want, int n_theta) {
 
 int ensure_query_ws(gpmi_ctx* c, int64_t mp) {
   if (mp <= c->mq_cap) return GPMI_OK;
-  auto fr = [](double*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-  };
-  fr(c->Q);
-  fr(c->Q2);
-  fr(c->pts);
-  fr(c->pvec);
-  c->mq_cap = 0;
-  HIPCHK(c, hipMalloc(&c->Q, sizeof(double) * mp * c->ld));
-  HIPCHK(c, hipMalloc(&c->Q2, sizeof(double) * mp * c->ld));
-  HIPCHK(c, hipMalloc(&c->pts, sizeof(double) * mp * c->d));
-  HIPCHK(c, hipMalloc(&c->pvec, sizeof(double) * mp * (2 + 2 * c->d + c->d * c->d + GPMI_MAX_MIX)));
+  static_cast<QueryBufs&>(*c) = QueryBufs();
+  if (int rc = c->Q.alloc(c, mp * c->ld)) return rc;
+  if (int rc = c->Q2.alloc(c, mp * c->ld)) return rc;
+  if (int rc = c->pts.alloc(c, mp * c->d)) return rc;
+  if (int rc = c->pvec.alloc(c, mp * (2 + 2 * c->d + c->d * c->d + GPMI_MAX_MIX))) return rc;
   c->mq_cap = mp;
   return GPMI_OK;
 }
@@ -692,13 +616,21 @@ int gpmi_destroy(gpmi_ctx* c) {
     (void)hipEventDestroy(sl.e0);
     (void)hipEventDestroy(sl.e1);
   }
-  if (c->stamp_pool) (void)hipFree(c->stamp_pool);
+  c->stamp_pool.release();
   if (c->dev_masked) (void)hipStreamDestroy(c->dev_masked);
-  if (c->trsm_panel) (void)hipFree(c->trsm_panel);
-  if (c->h_stage) (void)hipHostFree(c->h_stage);
+  c->trsm_panel.release();
+  c->h_stage.release();
+  c->dev_allocs.clear();
   if (c->t0) (void)hipEventDestroy(c->t0);
   if (c->t1) (void)hipEventDestroy(c->t1);
   delete c;
+  return GPMI_OK;
+}
+
+int gpmi_live_bytes(int64_t out[2]) {
+  if (!out) return GPMI_ERR_ARG;
+  out[0] = BufMem::live[0].load();
+  out[1] = BufMem::live[1].load();
   return GPMI_OK;
 }
 
@@ -728,17 +660,17 @@ int gpmi_set_data(gpmi_ctx* c, const double* x, const double* y, const double* n
   c->d = d;
   c->np = round_up(n + c->reserve, GPMI_NB);
   c->ld = c->np + 32;  // keep rows 256-byte aligned but off a power-of-two pitch
-  HIPCHK(c, hipMalloc(&c->x, sizeof(double) * c->np * d));
-  HIPCHK(c, hipMalloc(&c->y, sizeof(double) * c->np));
-  HIPCHK(c, hipMalloc(&c->noise, sizeof(double) * c->np));
-  HIPCHK(c, hipMalloc(&c->alpha, sizeof(double) * c->np));
+  if (int rc = c->x.alloc(c, c->np * d)) return rc;
+  if (int rc = c->y.alloc(c, c->np)) return rc;
+  if (int rc = c->noise.alloc(c, c->np)) return rc;
+  if (int rc = c->alpha.alloc(c, c->np)) return rc;
   ZERO_SYNC(c, c->x, sizeof(double) * c->np * d);
   ZERO_SYNC(c, c->y, sizeof(double) * c->np);
   ZERO_SYNC(c, c->noise, sizeof(double) * c->np);
   HIPCHK(c, hipMemcpy(c->x, x, sizeof(double) * n * d, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(c->y, y, sizeof(double) * n, hipMemcpyHostToDevice));
   if (y_cov) {
-    HIPCHK(c, hipMalloc(&c->ycov, sizeof(double) * n * n));
+    if (int rc = c->ycov.alloc(c, n * n)) return rc;
     HIPCHK(c, hipMemcpy(c->ycov, y_cov, sizeof(double) * n * n, hipMemcpyHostToDevice));
   } else if (noise_var) {
     HIPCHK(c, hipMemcpy(c->noise, noise_var, sizeof(double) * n, hipMemcpyHostToDevice));
@@ -836,7 +768,7 @@ int gpmi_profile_enable(gpmi_ctx* c, int on) {
   c->prof_mask = (on == 1) ? ((1u << GPMI_PROF_NCLASS) - 1u) : (unsigned)on >> 1;
   if (((c->prof_mask >> GPMI_PROF_SYRK) & 1) && !c->stamp_pool) {
     if (int rc = set_device(c)) return rc;
-    HIPCHK(c, hipMalloc(&c->stamp_pool, sizeof(unsigned long long) * GPMI_STAMP_WORDS * GPMI_STAMP_SLOTS));
+    if (int rc = c->stamp_pool.alloc(c, (int64_t)GPMI_STAMP_WORDS * GPMI_STAMP_SLOTS)) return rc;
     // on the library's own stream: a kernel launched on the NULL stream left every later launch of the process
     // with a ~10 us dispatch gap to its predecessor (1.2 ms per fit at N = 16384)
     hipStream_t s0;
@@ -939,13 +871,20 @@ int gpmi_profile_reset(gpmi_ctx* c) {
 int gpmi_dev_alloc(gpmi_ctx* c, int64_t bytes, void** ptr) {
   if (!c || !ptr) return GPMI_ERR_ARG;
   if (int rc = set_device(c)) return rc;
-  HIPCHK(c, hipMalloc(ptr, (size_t)bytes));
+  *ptr = nullptr;
+  DevBuf<char> b;
+  if (int rc = b.alloc(c, bytes)) return rc;
+  *ptr = b;
+  c->dev_allocs.push_back(std::move(b));
   return GPMI_OK;
 }
 int gpmi_dev_free(gpmi_ctx* c, void* ptr) {
   if (!c) return GPMI_ERR_ARG;
   if (int rc = set_device(c)) return rc;
-  HIPCHK(c, hipFree(ptr));
+  if (!ptr) return GPMI_OK;
+  auto it = std::find_if(c->dev_allocs.begin(), c->dev_allocs.end(), [ptr](const DevBuf<char>& b) { return b == ptr; });
+  ARGCHK(c, it != c->dev_allocs.end(), "gpmi_dev_free: not a pointer of gpmi_dev_alloc on this handle");
+  c->dev_allocs.erase(it);
   return GPMI_OK;
 }
 int gpmi_dev_upload(gpmi_ctx* c, void* dst, const void* src, int64_t bytes) {
@@ -968,18 +907,17 @@ int gpmi_dev_potrf(gpmi_ctx* c, double* A, int64_t n, int64_t ld, int* info) {
   if (int rc = set_device(c)) return rc;
   hipStream_t s;
   if (int rc = dev_stream(c, &s)) return rc;
-  double* invD = nullptr;
-  int* dinfo = nullptr;
-  HIPCHK(c, hipMalloc(&invD, sizeof(double) * (n / GPMI_NB) * GPMI_NB * GPMI_NB));
-  ZERO_SYNC(c, invD, sizeof(double) * (n / GPMI_NB) * GPMI_NB * GPMI_NB);  // see lane_alloc
-  HIPCHK(c, hipMalloc(&dinfo, sizeof(int)));
+  DevBuf<double> invD;
+  DevBuf<int> dinfo;
+  if (int rc = invD.alloc_zeroed(c, (n / GPMI_NB) * GPMI_NB * GPMI_NB)) return rc;  // see lane_alloc
+  if (int rc = dinfo.alloc(c, 1)) return rc;
   HIPCHK(c, hipMemsetAsync(dinfo, 0, sizeof(int), s));
   if (n == GPMI_NB && std::getenv("GPMI_DIAG_STAMPS")) {
     // tools only: phase cycle counts of one potrf_diag launch
     // tools only: phase cycle counts and the per-wave timeline of one potrf_diag launch (potrf.hip: DIAG_TRACE_*)
     constexpr int TRACE_WORDS = 8 * 9 * 6;
-    unsigned long long* dbg = nullptr;
-    HIPCHK(c, hipMalloc(&dbg, (GPMI_STAMP_WORDS + TRACE_WORDS) * sizeof(unsigned long long)));
+    DevBuf<unsigned long long> dbg;
+    if (int rc = dbg.alloc(c, GPMI_STAMP_WORDS + TRACE_WORDS)) return rc;
     HIPCHK(c, hipMemsetAsync(dbg, 0, (GPMI_STAMP_WORDS + TRACE_WORDS) * sizeof(unsigned long long), s));
     const unsigned long long magic = 0x7ACEull;
     HIPCHK(c, hipMemcpyAsync(dbg + 22, &magic, sizeof(magic), hipMemcpyHostToDevice, s));
@@ -1002,14 +940,11 @@ int gpmi_dev_potrf(gpmi_ctx* c, double* A, int64_t n, int64_t ld, int* info) {
       }
       std::fprintf(stderr, "\n");
     }
-    (void)hipFree(dbg);
   } else
   potrf_lower(c, c->lanes[0], A, n, ld, invD, dinfo);
   int h = 0;
   hipError_t e = hipMemcpyAsync(&h, dinfo, sizeof(int), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  (void)hipFree(invD);
-  (void)hipFree(dinfo);
   HIPCHK(c, e);
   if (info) *info = h;
   return GPMI_OK;

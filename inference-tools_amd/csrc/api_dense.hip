@@ -262,14 +262,14 @@ int gpmi_solve_rows(gpmi_ctx* c, const double* Q_host, int64_t m, double* X_host
   if (X_host)
     HIPCHK(c, hipMemcpy2DAsync(X_host, sizeof(double) * c->n, c->Q2, sizeof(double) * c->ld, sizeof(double) * c->n,
                                (size_t)m, hipMemcpyDeviceToHost, s));
-  DevBuf G;  // (an error return below may leave work on it in flight: hipFree waits for the device before it releases)
+  DevBuf<double> G;  // (an error return below may leave work on it in flight: hipFree waits for the device before it releases)
   if (gram_host) {
     // G = X X^T (m x m): what posterior covariances are made of (regression.py:447-448)
     const int64_t ldg = mp + 32;
-    HIPCHK(c, hipMalloc(&G.p, sizeof(double) * mp * ldg));
-    launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, G.as<double>(), ldg, c->Q2, c->ld, c->Q2, c->ld, (int)(mp / GPMI_NB),
+    if (int rc = G.alloc(c, mp * ldg)) return rc;
+    launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, G, ldg, c->Q2, c->ld, c->Q2, c->ld, (int)(mp / GPMI_NB),
                    (int)(mp / GPMI_NB), (int)c->np);
-    HIPCHK(c, hipMemcpy2DAsync(gram_host, sizeof(double) * m, G.p, sizeof(double) * ldg, sizeof(double) * m, (size_t)m,
+    HIPCHK(c, hipMemcpy2DAsync(gram_host, sizeof(double) * m, G, sizeof(double) * ldg, sizeof(double) * m, (size_t)m,
                                hipMemcpyDeviceToHost, s));
   }
   HIPCHK(c, hipStreamSynchronize(s));

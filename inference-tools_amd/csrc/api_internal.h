@@ -97,13 +97,7 @@ struct RowStage {
   RowStage(gpmi_ctx* ctx, hipStream_t stream) : c(ctx), s(stream) {}
   // capacity for everything staged until the next finish(); only while nothing is staged
   int reserve(size_t bytes) {
-    if ((int64_t)bytes <= c->h_stage_bytes) return GPMI_OK;
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    c->h_stage = nullptr;
-    c->h_stage_bytes = 0;
-    HIPCHK(c, hipHostMalloc(&c->h_stage, bytes, hipHostMallocMapped | hipHostMallocPortable));
-    c->h_stage_bytes = (int64_t)bytes;
-    return GPMI_OK;
+    return c->h_stage.reserve(c, (int64_t)bytes, hipHostMallocMapped | hipHostMallocPortable);
   }
   size_t take(size_t bytes) {
     const size_t off = used;
@@ -111,23 +105,23 @@ struct RowStage {
     return off;
   }
   // pinned scratch of `bytes` (a multiple of 8) the caller fills in place, then put()
-  double* host(size_t bytes) { return reinterpret_cast<double*>(reinterpret_cast<char*>(c->h_stage) + take(bytes)); }
+  double* host(size_t bytes) { return reinterpret_cast<double*>(c->h_stage + take(bytes)); }
   int put(void* dst_dev, const double* pinned, size_t bytes) {
-    ARGCHK(c, used <= (size_t)c->h_stage_bytes && bytes % 8 == 0, "internal: staging buffer too small");
+    ARGCHK(c, used <= (size_t)c->h_stage.capacity() && bytes % 8 == 0, "internal: staging buffer too small");
     launch_copy_rows(s, pinned, 0, static_cast<double*>(dst_dev), 0, (int64_t)(bytes / 8), 1);
     return GPMI_OK;
   }
   // a contiguous caller array -> device
   int put_copy(void* dst_dev, const void* src, size_t bytes) {
     const size_t padded = (bytes + 7) & ~(size_t)7;
-    ARGCHK(c, used + padded + 256 <= (size_t)c->h_stage_bytes, "internal: staging buffer too small");
+    ARGCHK(c, used + padded + 256 <= (size_t)c->h_stage.capacity(), "internal: staging buffer too small");
     double* p = host(padded);
     std::memcpy(p, src, bytes);
     return put(dst_dev, p, padded);
   }
   // caller rows (pitch `spitch` bytes) -> device rows (pitch `dpitch` bytes)
   int up(void* dst_dev, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height) {
-    ARGCHK(c, used + width * height + 256 <= (size_t)c->h_stage_bytes, "internal: staging buffer too small");
+    ARGCHK(c, used + width * height + 256 <= (size_t)c->h_stage.capacity(), "internal: staging buffer too small");
     double* p = host(width * height);
     for (size_t r = 0; r < height; ++r)
       std::memcpy(reinterpret_cast<char*>(p) + r * width, static_cast<const char*>(src) + r * spitch, width);
@@ -137,17 +131,17 @@ struct RowStage {
   }
   // `height` device rows of `width` bytes (pitch `spitch`) -> caller rows (pitch `dpitch`), after the sync and finish()
   int down(void* dst, size_t dpitch, const void* src_dev, size_t spitch, size_t width, size_t height) {
-    ARGCHK(c, used + width * height + 256 <= (size_t)c->h_stage_bytes, "internal: staging buffer too small");
+    ARGCHK(c, used + width * height + 256 <= (size_t)c->h_stage.capacity(), "internal: staging buffer too small");
     const size_t off = take(width * height);
     launch_copy_rows(s, static_cast<const double*>(src_dev), (int64_t)(spitch / 8),
-                     reinterpret_cast<double*>(reinterpret_cast<char*>(c->h_stage) + off), (int64_t)(width / 8),
+                     reinterpret_cast<double*>(c->h_stage + off), (int64_t)(width / 8),
                      (int64_t)(width / 8), (int64_t)height);
     items.push_back({static_cast<char*>(dst), dpitch, off, width, height});
     return GPMI_OK;
   }
   // after the stream has been synchronised
   void finish() {
-    const char* base = reinterpret_cast<const char*>(c->h_stage);
+    const char* base = c->h_stage;
     for (const Item& it : items)
       for (size_t r = 0; r < it.height; ++r) std::memcpy(it.dst + r * it.dpitch, base + it.off + r * it.width, it.width);
     items.clear();
@@ -182,40 +176,11 @@ void free_batch_ws(gpmi_ctx* c);  // every lockstep buffer, caps to 0
 int ensure_batch_ws(gpmi_ctx* c, int want);
 int ensure_batch_grad_ws(gpmi_ctx* c, int want, int n_theta);
 int ensure_query_ws(gpmi_ctx* c, int64_t mp);
-void linv_free(LinvState& S);  // api_linv.hip
 // v <- -v;  out_i = alpha_i^2 - iK_ii (one problem / problem z of a batch)
 void launch_negate(hipStream_t s, double* v, int64_t n);
 void launch_qdiag(hipStream_t s, const double* iK, int64_t ld, const double* alpha, double* out, int64_t n);
 void launch_qdiag_batched(hipStream_t s, int batch, const double* iK, int64_t ld, const double* alpha, double* out, int64_t n,
                           int64_t sMat, int64_t sVec, int64_t sOut);
-
-// A device buffer of at least `want` elements of `bytes_each`: freed and allocated anew when it is smaller (contents
-// lost).  On failure the pointer is null and the capacity 0.
-template <class P, class N>
-int grow(gpmi_ctx* c, P*& ptr, N& cap, int64_t want, size_t bytes_each) {
-  if (cap >= want) return GPMI_OK;
-  if (ptr) (void)hipFree(ptr);
-  ptr = nullptr;
-  cap = 0;
-  HIPCHK(c, hipMalloc(&ptr, bytes_each * (size_t)want));
-  cap = (N)want;
-  return GPMI_OK;
-}
-
-// device memory of one call
-struct DevBuf {
-  void* p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  template <class T>
-  T* as() const {
-    return static_cast<T*>(p);
-  }
-};
 
 // T evaluations one at a time (beyond the lockstep sizes): row(t, mu_t) with the mean of evaluation t as n values
 template <class F>

@@ -4,16 +4,6 @@
 #include "api_internal.h"
 
 // ---- Gaussian-process linear inversion --------------------------------------------------------------
-// (called by api.hip when a handle's data set is replaced or the handle destroyed)
-void linv_free(LinvState& S) {
-  for (double** p : {&S.A, &S.At, &S.y, &S.sig2, &S.zero, &S.K, &S.T, &S.J, &S.J2, &S.Q, &S.X, &S.invD, &S.inv2,
-                     &S.inv2_t, &S.panel, &S.vec, &S.gws}) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
-  S = LinvState();
-}
-
 namespace {
 
 __global__ void linv_add_diag_kernel(double* __restrict__ J, int64_t ld, const double* __restrict__ sig2,
@@ -23,11 +13,8 @@ __global__ void linv_add_diag_kernel(double* __restrict__ J, int64_t ld, const d
 }
 
 
-int linv_alloc(gpmi_ctx* c, double** p, int64_t doubles) {
-  if (*p) return GPMI_OK;
-  HIPCHK(c, hipMalloc(p, sizeof(double) * doubles));
-  ZERO_SYNC(c, *p, sizeof(double) * doubles);  // (the inverses' upper 16-blocks rely on it, see lane_alloc)
-  return GPMI_OK;
+int linv_alloc(gpmi_ctx* c, DevBuf<double>& b, int64_t doubles) {
+  return b ? GPMI_OK : b.alloc_zeroed(c, doubles);  // (zeroed: the inverses' upper 16-blocks rely on it, see lane_alloc)
 }
 
 // J = A K(theta) A^T + Sigma -> L, v = L^-1 (y - A mu) in vec[0:mp], red = {v.v, sum ln L_ii} in lanes[0].red
@@ -83,22 +70,22 @@ int gpmi_linv_set(gpmi_ctx* c, const double* A, int64_t m, const double* y, cons
   ARGCHK(c, A && y && y_err && m > 0, "A, y, y_err must be non-NULL and m positive");
   if (int rc = set_device(c)) return rc;
   LinvState& S = c->linv;
-  linv_free(S);
+  S = LinvState();
   S.m = m;
   S.mp = round_up(m, GPMI_NB);
   S.ldm = S.mp + 32;
   const int64_t n = c->n, np = c->np, ld = c->ld, mp = S.mp, ldm = S.ldm;
   const int64_t vmax = mp > np ? mp : np;
-  if (int rc = linv_alloc(c, &S.A, mp * ld)) return rc;
-  if (int rc = linv_alloc(c, &S.At, np * ldm)) return rc;
-  if (int rc = linv_alloc(c, &S.y, mp)) return rc;
-  if (int rc = linv_alloc(c, &S.sig2, mp)) return rc;
-  if (int rc = linv_alloc(c, &S.zero, np)) return rc;
-  if (int rc = linv_alloc(c, &S.K, np * ld)) return rc;
-  if (int rc = linv_alloc(c, &S.T, mp * ld)) return rc;
-  if (int rc = linv_alloc(c, &S.J, mp * ldm)) return rc;
-  if (int rc = linv_alloc(c, &S.invD, (mp / GPMI_NB) * GPMI_NB * GPMI_NB)) return rc;
-  if (int rc = linv_alloc(c, &S.vec, 8 * vmax)) return rc;
+  if (int rc = linv_alloc(c, S.A, mp * ld)) return rc;
+  if (int rc = linv_alloc(c, S.At, np * ldm)) return rc;
+  if (int rc = linv_alloc(c, S.y, mp)) return rc;
+  if (int rc = linv_alloc(c, S.sig2, mp)) return rc;
+  if (int rc = linv_alloc(c, S.zero, np)) return rc;
+  if (int rc = linv_alloc(c, S.K, np * ld)) return rc;
+  if (int rc = linv_alloc(c, S.T, mp * ld)) return rc;
+  if (int rc = linv_alloc(c, S.J, mp * ldm)) return rc;
+  if (int rc = linv_alloc(c, S.invD, (mp / GPMI_NB) * GPMI_NB * GPMI_NB)) return rc;
+  if (int rc = linv_alloc(c, S.vec, 8 * vmax)) return rc;
   ZERO_SYNC(c, S.A, sizeof(double) * mp * ld);
   ZERO_SYNC(c, S.At, sizeof(double) * np * ldm);
   ZERO_SYNC(c, S.y, sizeof(double) * mp);
@@ -162,18 +149,12 @@ static int linv_lml_grad_impl(gpmi_ctx* c, const KParams& p, int n_theta, const 
   hipStream_t s = L.stream;
   const int nt = (int)(c->np / GPMI_NB), mt = (int)(S.mp / GPMI_NB);
   const int64_t vmax = S.mp > c->np ? S.mp : c->np;
-  if (int rc = linv_alloc(c, &S.J2, S.mp * S.ldm)) return rc;
-  if (int rc = linv_alloc(c, &S.inv2, (int64_t)((mt + 3) / 4) * GPMI_OB * GPMI_OB)) return rc;
-  if (int rc = linv_alloc(c, &S.inv2_t, (int64_t)((mt + 3) / 4) * 256 * 256)) return rc;
-  if (int rc = linv_alloc(c, &S.panel, S.mp * (GPMI_OB + 32))) return rc;
+  if (int rc = linv_alloc(c, S.J2, S.mp * S.ldm)) return rc;
+  if (int rc = linv_alloc(c, S.inv2, (int64_t)((mt + 3) / 4) * GPMI_OB * GPMI_OB)) return rc;
+  if (int rc = linv_alloc(c, S.inv2_t, (int64_t)((mt + 3) / 4) * 256 * 256)) return rc;
+  if (int rc = linv_alloc(c, S.panel, S.mp * (GPMI_OB + 32))) return rc;
   const int64_t need = n_theta >= 0 ? grad_ws_doubles(c->np, n_theta) : 0;
-  if (S.gws_doubles < need) {
-    if (S.gws) (void)hipFree(S.gws);
-    S.gws = nullptr;
-    S.gws_doubles = 0;
-    HIPCHK(c, hipMalloc(&S.gws, sizeof(double) * need));
-    S.gws_doubles = need;
-  }
+  if (int rc = S.gws.reserve(c, need)) return rc;
   if (int rc = linv_factor(c, p, mu, K_host)) return rc;
   double* v = S.vec;
   double* alpha = S.vec + 4 * vmax;  // mp
@@ -238,10 +219,10 @@ static int linv_posterior_impl(gpmi_ctx* c, const KParams& p, const double* K_ho
   hipStream_t s = L.stream;
   const int nt = (int)(c->np / GPMI_NB), mt = (int)(S.mp / GPMI_NB);
   const int64_t vmax = S.mp > c->np ? S.mp : c->np;
-  if (int rc = linv_alloc(c, &S.Q, c->np * S.ldm)) return rc;
-  if (int rc = linv_alloc(c, &S.X, c->np * S.ldm)) return rc;
-  if (int rc = linv_alloc(c, &S.inv2, (int64_t)((mt + 3) / 4) * GPMI_OB * GPMI_OB)) return rc;
-  if (int rc = linv_alloc(c, &S.inv2_t, (int64_t)((mt + 3) / 4) * 256 * 256)) return rc;
+  if (int rc = linv_alloc(c, S.Q, c->np * S.ldm)) return rc;
+  if (int rc = linv_alloc(c, S.X, c->np * S.ldm)) return rc;
+  if (int rc = linv_alloc(c, S.inv2, (int64_t)((mt + 3) / 4) * GPMI_OB * GPMI_OB)) return rc;
+  if (int rc = linv_alloc(c, S.inv2_t, (int64_t)((mt + 3) / 4) * 256 * 256)) return rc;
   if (int rc = linv_factor(c, p, mu, K_host)) return rc;
   double* v = S.vec;
   double* dm = S.vec + 5 * vmax;  // np

@@ -115,25 +115,19 @@ void loo_middle(const Chunk& k, const LooVectors& lv, bool want_mdiag, bool mirr
 
 // ---- mixture batches ---------------------------------------------------------------------------------------------
 int ensure_batch_mix_ws(gpmi_ctx* c) {
-  if (!c->mix_zero) {
-    HIPCHK(c, hipMalloc(&c->mix_zero, sizeof(double) * c->np));
-    ZERO_SYNC(c, c->mix_zero, sizeof(double) * c->np);
-  }
+  if (!c->mix_zero)
+    if (int rc = c->mix_zero.alloc_zeroed(c, c->np)) return rc;
   const int cap = c->bgrad_cap;
   if (c->bMix_cap >= cap) return GPMI_OK;
-  for (double** q : {&c->bMixG, &c->bMixH, &c->bMixW, &c->bMixExtra}) {
-    if (*q) (void)hipFree(*q);
-    *q = nullptr;
-  }
-  if (c->bMixP) (void)hipFree(c->bMixP);
-  c->bMixP = nullptr;
   c->bMix_cap = 0;
-  HIPCHK(c, hipMalloc(&c->bMixG, sizeof(double) * cap * GPMI_MAX_MIX * c->np));
+  for (DevBuf<double>* q : {&c->bMixG, &c->bMixH, &c->bMixW, &c->bMixExtra}) q->release();
+  c->bMixP.release();
+  if (int rc = c->bMixG.alloc(c, (int64_t)cap * GPMI_MAX_MIX * c->np)) return rc;
   // (row sums and the caller's row-sum weights: up to two per sub-kernel)
-  HIPCHK(c, hipMalloc(&c->bMixH, sizeof(double) * cap * 2 * GPMI_MAX_MIX * c->np));
-  HIPCHK(c, hipMalloc(&c->bMixW, sizeof(double) * cap * 2 * GPMI_MAX_MIX * c->np));
-  HIPCHK(c, hipMalloc(&c->bMixExtra, sizeof(double) * cap));
-  HIPCHK(c, hipMalloc(&c->bMixP, sizeof(KParams) * cap * GPMI_MAX_MIX));
+  if (int rc = c->bMixH.alloc(c, (int64_t)cap * 2 * GPMI_MAX_MIX * c->np)) return rc;
+  if (int rc = c->bMixW.alloc(c, (int64_t)cap * 2 * GPMI_MAX_MIX * c->np)) return rc;
+  if (int rc = c->bMixExtra.alloc(c, cap)) return rc;
+  if (int rc = c->bMixP.alloc(c, (int64_t)cap * GPMI_MAX_MIX)) return rc;
   c->bMix_cap = cap;
   return GPMI_OK;
 }

@@ -18,12 +18,12 @@ int mix_prepare(gpmi_ctx* c, int nk, const int* kernels, const double* thetas, c
     off += n_thetas[m];
   }
   if (int rc = set_device(c)) return rc;
-  if (!c->mix_g) HIPCHK(c, hipMalloc(&c->mix_g, sizeof(double) * GPMI_MAX_MIX * c->np));
-  if (!c->mix_scratch) HIPCHK(c, hipMalloc(&c->mix_scratch, sizeof(double) * c->np * c->ld));
-  if (!c->mix_zero) {
-    HIPCHK(c, hipMalloc(&c->mix_zero, sizeof(double) * c->np));
-    ZERO_SYNC(c, c->mix_zero, sizeof(double) * c->np);
-  }
+  if (!c->mix_g)
+    if (int rc = c->mix_g.alloc(c, GPMI_MAX_MIX * c->np)) return rc;
+  if (!c->mix_scratch)
+    if (int rc = c->mix_scratch.alloc(c, c->np * c->ld)) return rc;
+  if (!c->mix_zero)
+    if (int rc = c->mix_zero.alloc_zeroed(c, c->np)) return rc;
   if (int rc = gpmi_sync(c)) return rc;  // nothing may still be reading the previous weights
   std::vector<double> g((size_t)nk * c->np);
   for (int m = 0; m < nk; ++m)
@@ -33,14 +33,7 @@ int mix_prepare(gpmi_ctx* c, int nk, const int* kernels, const double* thetas, c
   return GPMI_OK;
 }
 
-int ensure_q3(gpmi_ctx* c) {
-  if (c->q3_cap >= c->mq_cap && c->Q3) return GPMI_OK;
-  if (c->Q3) (void)hipFree(c->Q3);
-  c->Q3 = nullptr;
-  HIPCHK(c, hipMalloc(&c->Q3, sizeof(double) * c->mq_cap * c->ld));
-  c->q3_cap = c->mq_cap;
-  return GPMI_OK;
-}
+int ensure_q3(gpmi_ctx* c) { return c->Q3.reserve(c, c->mq_cap * c->ld); }
 
 // Rows [m0, m0 + mc) of the m query points and of their nk x m weights gq_host to the device (the weights to gq_dev =
 // c->pvec + 2 mp: nk x mp, zero-padded; pvec holds mp (2 + 2 d + d^2 + 4) doubles), then
@@ -206,7 +199,7 @@ int gpmi_lml_grad_batch_mix(gpmi_ctx* c, int nk, const int* kernels, int64_t T, 
   if (int rc = ensure_batch_mix_ws(c)) return rc;
   const int cap = c->bgrad_cap;
   if (qdiag_out)
-    if (int rc = grow(c, c->bNoise, c->bNoise_cap, cap, sizeof(double) * c->np)) return rc;
+    if (int rc = c->bNoise.reserve(c, cap * c->np)) return rc;
   hipStream_t s = c->lanes[1].stream;
   static const bool stage_times = std::getenv("GPMI_DEBUG_STAGES") != nullptr;  // debugging aid: host time per stage
   RowStage stage(c, s);  // strided outputs reach the caller's arrays through pinned memory (api_internal.h)
@@ -290,7 +283,7 @@ int gpmi_loo_grad_batch_mix(gpmi_ctx* c, int nk, const int* kernels, int64_t T, 
   const int cap = c->bgrad_cap;
   // four more vectors per problem: diag(K^-1), c1, sqrt(c2) - later diag(M) -, p = K^-1 c1 (regression.py:505-513).
   // (the same stride as the work vectors': the fused contraction takes u = p and v = alpha with ONE stride)
-  if (int rc = grow(c, c->bLoo, c->bLoo_cap, cap, sizeof(double) * 4 * c->np)) return rc;
+  if (int rc = c->bLoo.reserve(c, cap * 4 * c->np)) return rc;
   const LooVectors lv(c);
   hipStream_t s = c->lanes[1].stream;
   RowStage stage(c, s);  // strided outputs reach the caller's arrays through pinned memory (api_internal.h)
@@ -362,23 +355,23 @@ int gpmi_posterior_mix(gpmi_ctx* c, const double* pts, int64_t m, const double* 
   const int64_t mp = round_up(m, GPMI_NB), ldq = mp + 32;
   if (int rc = ensure_query_ws(c, mp)) return rc;
   // (an error return below may leave work on these in flight: hipFree waits for the device before it releases)
-  DevBuf Sigma, tmp;
+  DevBuf<double> Sigma, tmp;
   if (cov_out) {
-    HIPCHK(c, hipMalloc(&Sigma.p, sizeof(double) * mp * ldq));
-    HIPCHK(c, hipMalloc(&tmp.p, sizeof(double) * mp * ldq));
+    if (int rc = Sigma.alloc(c, mp * ldq)) return rc;
+    if (int rc = tmp.alloc(c, mp * ldq)) return rc;
   }
   auto cross = [&] { return upload_and_build_mix_cross(c, pts, gq_host, m, 0, m, mp); };
   // K_qq = sum_m diag(gq_m) K_m(pts, pts) diag(gq_m): no jitter, no noise (covariance.py:529-544)
   auto qq = [&] {
     for (int k = 0; k < c->mix_nk; ++k) {
       const double* gq = c->pvec + 2 * mp + (int64_t)k * mp;
-      launch_kbuild_cross(s, c->mix_p[k], c->pts, m, mp, c->pts, m, mp, tmp.as<double>(), ldq);
-      launch_scale_add(s, Sigma.as<double>(), ldq, tmp.as<double>(), ldq, gq, gq, mp, mp, k > 0);
+      launch_kbuild_cross(s, c->mix_p[k], c->pts, m, mp, c->pts, m, mp, tmp, ldq);
+      launch_scale_add(s, Sigma, ldq, tmp, ldq, gq, gq, mp, mp, k > 0);
     }
   };
-  if (int rc = posterior_sigma(c, cross, qq, m, mp, mu_out, Sigma.as<double>(), ldq)) return rc;
+  if (int rc = posterior_sigma(c, cross, qq, m, mp, mu_out, Sigma, ldq)) return rc;
   if (cov_out)
-    HIPCHK(c, hipMemcpy2DAsync(cov_out, sizeof(double) * m, Sigma.p, sizeof(double) * ldq, sizeof(double) * m, m,
+    HIPCHK(c, hipMemcpy2DAsync(cov_out, sizeof(double) * m, Sigma, sizeof(double) * ldq, sizeof(double) * m, m,
                                hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   return GPMI_OK;

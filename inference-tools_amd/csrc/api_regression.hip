@@ -175,30 +175,25 @@ int gpmi_lml_batch_submit(gpmi_ctx* c, int kernel, int64_t T, const double* thet
   const int64_t mu_doubles = mus ? T * c->n : T;
   const size_t psize = (kernel == GPMI_KERNEL_SUM) ? sizeof(CovParams) : sizeof(KParams);
   const int64_t need = (int64_t)psize * T + (int64_t)sizeof(double) * mu_doubles;
-  if (c->h_bStage_bytes[slot] < need) {
-    if (c->h_bStage[slot]) (void)hipHostFree(c->h_bStage[slot]);
-    c->h_bStage[slot] = nullptr;
-    c->h_bStage_bytes[slot] = 0;
-    HIPCHK(c, hipHostMalloc(&c->h_bStage[slot], (size_t)need));
-    c->h_bStage_bytes[slot] = need;
-  }
-  double* mu_stage = reinterpret_cast<double*>(c->h_bStage[slot] + psize * T);
+  if (int rc = c->h_bStage[slot].reserve(c, need)) return rc;
+  char* const h_stage = c->h_bStage[slot];
+  double* mu_stage = reinterpret_cast<double*>(h_stage + psize * T);
   if (kernel == GPMI_KERNEL_SUM) {
-    CovParams* sps = reinterpret_cast<CovParams*>(c->h_bStage[slot]);
+    CovParams* sps = reinterpret_cast<CovParams*>(h_stage);
     for (int64_t t = 0; t < T; ++t)
       if (int rc = make_cov(c, kernel, thetas + t * n_theta, n_theta, extra ? extra[t] : 0.0, sps[t])) return rc;
   } else {
-    KParams* ps = reinterpret_cast<KParams*>(c->h_bStage[slot]);
+    KParams* ps = reinterpret_cast<KParams*>(h_stage);
     for (int64_t t = 0; t < T; ++t)
       if (int rc = make_params(c, kernel, thetas + t * n_theta, n_theta, extra ? extra[t] : 0.0, ps[t])) return rc;
   }
   std::memcpy(mu_stage, mus ? mus : mu_const, sizeof(double) * mu_doubles);
   hipStream_t s = c->lanes[1 + slot].stream;
   const bool sum = (kernel == GPMI_KERNEL_SUM);
-  const BatchParams bp = sum ? BatchParams(kernel, nullptr, reinterpret_cast<const CovParams*>(c->h_bStage[slot]))
-                             : BatchParams(kernel, reinterpret_cast<const KParams*>(c->h_bStage[slot]), nullptr);
+  const BatchParams bp = sum ? BatchParams(kernel, nullptr, reinterpret_cast<const CovParams*>(h_stage))
+                             : BatchParams(kernel, reinterpret_cast<const KParams*>(h_stage), nullptr);
   const Chunk k(c, s, off, (int)T, mus != nullptr);
-  HIPCHK(c, hipMemcpyAsync(bp.device(c, off), c->h_bStage[slot], bp.bytes_each() * T, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(bp.device(c, off), h_stage, bp.bytes_each() * T, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpyAsync(k.Mu, mu_stage, sizeof(double) * mu_doubles, hipMemcpyHostToDevice, s));
   if (int rc = lockstep_stages(k, ChunkBuild::kernels(bp), LS_CLEAR_INFO | LS_REDUCE)) return rc;
   HIPCHK(c, hipGetLastError());
@@ -295,7 +290,7 @@ static int lml_grad_batch_impl(gpmi_ctx* c, int kernel, int64_t T, const double*
   if (int rc = ensure_batch_ws(c, (int)(T < 64 ? (T < 2 ? 2 : T) : 64))) return rc;
   if (int rc = ensure_batch_grad_ws(c, c->bcap, n_theta)) return rc;
   if (noise_batch || qdiag_out)
-    if (int rc = grow(c, c->bNoise, c->bNoise_cap, c->bgrad_cap, sizeof(double) * c->np)) return rc;
+    if (int rc = c->bNoise.reserve(c, c->bgrad_cap * c->np)) return rc;
   hipStream_t s = c->lanes[1].stream;
   const int W = n_theta + 1;
   const size_t rowb = sizeof(double) * c->n;
@@ -391,10 +386,10 @@ static int loo_grad_batch_impl(gpmi_ctx* c, int kernel, int64_t T, const double*
   if (int rc = ensure_batch_ws(c, (int)(T < 64 ? (T < 2 ? 2 : T) : 64))) return rc;
   if (int rc = ensure_batch_grad_ws(c, c->bcap, n_theta)) return rc;
   if (noise_batch)
-    if (int rc = grow(c, c->bNoise, c->bNoise_cap, c->bgrad_cap, sizeof(double) * c->np)) return rc;
+    if (int rc = c->bNoise.reserve(c, c->bgrad_cap * c->np)) return rc;
   // four more vectors per problem: diag(K^-1), c1, sqrt(c2) - later diag(M) -, p = K^-1 c1 (regression.py:505-513).
   // (the same stride as the work vectors': the fused contraction takes u = p and v = alpha with ONE stride)
-  if (int rc = grow(c, c->bLoo, c->bLoo_cap, c->bgrad_cap, sizeof(double) * 4 * c->np)) return rc;
+  if (int rc = c->bLoo.reserve(c, c->bgrad_cap * 4 * c->np)) return rc;
   const LooVectors lv(c);
   hipStream_t s = c->lanes[1].stream;
   const int W = n_theta + 1;
@@ -524,20 +519,21 @@ int gpmi_predict_batch(gpmi_ctx* c, int kernel, int64_t T, const double* thetas,
   const bool want_var = var_t || mix_var;
   const int64_t P = GPMI_PREDICT_PANEL;
   const int64_t sQ = 2 * P * c->ld;  // per problem: the panel K* and, behind it, V = K* L^-T
-  if (int rc = grow(c, c->bQ, c->bQ_cap, c->bgrad_cap, sizeof(double) * sQ)) return rc;
+  if (int rc = c->bQ.reserve(c, c->bgrad_cap * sQ)) return rc;
   const bool two = batch_split_enabled() && T >= 16 && ensure_lanes(c, 3) == GPMI_OK;
   const int cap = c->bgrad_cap;
   // the call's own device arrays: points, prior means at the points, the T x m results, the mixture's row list
-  DevBuf dPts, dPrior, dMean, dVar, dSq, dIdx, dW, dMix;
-  HIPCHK(c, hipMalloc(&dPts.p, sizeof(double) * m * c->d));
-  HIPCHK(c, hipMalloc(&dPrior.p, sizeof(double) * (mu_q ? T * m : T)));
-  HIPCHK(c, hipMalloc(&dMean.p, sizeof(double) * T * m));
+  DevBuf<double> dPts, dPrior, dMean, dVar, dSq, dW, dMix;
+  DevBuf<int> dIdx;
+  if (int rc = dPts.alloc(c, m * c->d)) return rc;
+  if (int rc = dPrior.alloc(c, mu_q ? T * m : T)) return rc;
+  if (int rc = dMean.alloc(c, T * m)) return rc;
   if (want_var) {
-    HIPCHK(c, hipMalloc(&dVar.p, sizeof(double) * T * m));
-    HIPCHK(c, hipMalloc(&dSq.p, sizeof(double) * P * cap));
+    if (int rc = dVar.alloc(c, T * m)) return rc;
+    if (int rc = dSq.alloc(c, P * cap)) return rc;
   }
-  HIPCHK(c, hipMemcpy(dPts.p, pts, sizeof(double) * m * c->d, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(dPrior.p, mu_q ? mu_q : mu_const, sizeof(double) * (mu_q ? T * m : T), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dPts, pts, sizeof(double) * m * c->d, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dPrior, mu_q ? mu_q : mu_const, sizeof(double) * (mu_q ? T * m : T), hipMemcpyHostToDevice));
   HIPCHK(c, hipStreamSynchronize(nullptr));  // (the lanes' streams do not wait for the null stream)
   const int nt = (int)(c->np / GPMI_NB);
   auto enqueue = [&](hipStream_t s, int64_t t_first, int off, int B) -> int {
@@ -551,13 +547,13 @@ int gpmi_predict_batch(gpmi_ctx* c, int kernel, int64_t T, const double* thetas,
     // slots 2 and 3 (2 np >= GPMI_PREDICT_PANEL doubles; the residual is spent) take a panel's row dots: launch_rows_dot
     // strides its output like alpha
     double* dot_dev = k.resid();
-    double* sq_dev = want_var ? dSq.as<double>() + (int64_t)off * P : nullptr;
+    double* sq_dev = want_var ? dSq + (int64_t)off * P : nullptr;
     GemmBatch gb{B, sQ, sQ, k.bs.sMat};
     gb.ring_order_only = true;
     for (int64_t m0 = 0; m0 < m; m0 += P) {
       const int64_t mc = (m - m0 < P) ? m - m0 : P;
       const int64_t mp = round_up(mc, GPMI_NB);
-      launch_kbuild_cross_batched(k, bp, dPts.as<double>() + m0 * c->d, mc, mp, Q, sQ);
+      launch_kbuild_cross_batched(k, bp, dPts + m0 * c->d, mc, mp, Q, sQ);
       launch_rows_dot(s, Q, c->ld, mc, c->np, k.alpha(), dot_dev, B, sQ, k.bs.sVec);
       if (want_var) {
         launch_gemm(s, TILES_RECT, OP_ASSIGN, true, 2, V, c->ld, Q, c->ld, k.B2, c->ld, (int)(mp / GPMI_NB), nt, (int)c->np,
@@ -565,8 +561,8 @@ int gpmi_predict_batch(gpmi_ctx* c, int kernel, int64_t T, const double* thetas,
         launch_rows_sumsq(s, V, c->ld, mc, c->np, 0.0, sq_dev, B, sQ, P, -1.0);  // (-(0 - sum): the sum itself)
       }
       launch_predict_store(s, B, t_first, m0, mc, m, dot_dev, sq_dev, k.bs.sVec, P, bp.device(c, off), (int64_t)bp.bytes_each(),
-                           k.info, mu_q ? dPrior.as<double>() : nullptr, mu_q ? nullptr : dPrior.as<double>(),
-                           dMean.as<double>(), dVar.as<double>());
+                           k.info, mu_q ? dPrior : nullptr, mu_q ? nullptr : dPrior,
+                           dMean, dVar);
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(c->h_bInfo + off, k.info, sizeof(int) * B, hipMemcpyDeviceToHost, s));
@@ -607,21 +603,21 @@ int gpmi_predict_batch(gpmi_ctx* c, int kernel, int64_t T, const double* thetas,
       }
     } else {
       for (double& v : w) v = weights ? v / wsum : 1.0 / (double)G;
-      HIPCHK(c, hipMalloc(&dIdx.p, sizeof(int) * G));
-      HIPCHK(c, hipMalloc(&dW.p, sizeof(double) * G));
-      HIPCHK(c, hipMalloc(&dMix.p, sizeof(double) * 2 * m));
-      HIPCHK(c, hipMemcpyAsync(dIdx.p, idx.data(), sizeof(int) * G, hipMemcpyHostToDevice, s));
-      HIPCHK(c, hipMemcpyAsync(dW.p, w.data(), sizeof(double) * G, hipMemcpyHostToDevice, s));
-      launch_predict_mix(s, G, dIdx.as<int>(), dW.as<double>(), m, dMean.as<double>(), dVar.as<double>(), dMix.as<double>(),
-                         mix_var ? dMix.as<double>() + m : nullptr);
+      if (int rc = dIdx.alloc(c, G)) return rc;
+      if (int rc = dW.alloc(c, G)) return rc;
+      if (int rc = dMix.alloc(c, 2 * m)) return rc;
+      HIPCHK(c, hipMemcpyAsync(dIdx, idx.data(), sizeof(int) * G, hipMemcpyHostToDevice, s));
+      HIPCHK(c, hipMemcpyAsync(dW, w.data(), sizeof(double) * G, hipMemcpyHostToDevice, s));
+      launch_predict_mix(s, G, dIdx, dW, m, dMean, dVar, dMix,
+                         mix_var ? dMix + m : nullptr);
       HIPCHK(c, hipGetLastError());
-      HIPCHK(c, hipMemcpyAsync(mix_mean, dMix.p, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+      HIPCHK(c, hipMemcpyAsync(mix_mean, dMix, sizeof(double) * m, hipMemcpyDeviceToHost, s));
       if (mix_var)
-        HIPCHK(c, hipMemcpyAsync(mix_var, dMix.as<double>() + m, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(mix_var, dMix + m, sizeof(double) * m, hipMemcpyDeviceToHost, s));
     }
   }
-  if (mean_t) HIPCHK(c, hipMemcpyAsync(mean_t, dMean.p, sizeof(double) * T * m, hipMemcpyDeviceToHost, s));
-  if (var_t) HIPCHK(c, hipMemcpyAsync(var_t, dVar.p, sizeof(double) * T * m, hipMemcpyDeviceToHost, s));
+  if (mean_t) HIPCHK(c, hipMemcpyAsync(mean_t, dMean, sizeof(double) * T * m, hipMemcpyDeviceToHost, s));
+  if (var_t) HIPCHK(c, hipMemcpyAsync(var_t, dVar, sizeof(double) * T * m, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   return GPMI_OK;
 }
@@ -637,11 +633,12 @@ int gpmi_posterior(gpmi_ctx* c, const double* pts, int64_t m, double* mu_out, do
   const int64_t mp = round_up(m, GPMI_NB), ldq = mp + 32;
   if (int rc = ensure_query_ws(c, mp)) return rc;
   // (an error return below may leave work on Sigma in flight: hipFree waits for the device before it releases)
-  DevBuf Sigma;
-  if (cov_out) HIPCHK(c, hipMalloc(&Sigma.p, sizeof(double) * mp * ldq));
-  if (int rc = kernel_posterior_sigma(c, pts, m, mp, mu_out, Sigma.as<double>(), ldq)) return rc;
+  DevBuf<double> Sigma;
   if (cov_out)
-    HIPCHK(c, hipMemcpy2DAsync(cov_out, sizeof(double) * m, Sigma.p, sizeof(double) * ldq, sizeof(double) * m, m,
+    if (int rc = Sigma.alloc(c, mp * ldq)) return rc;
+  if (int rc = kernel_posterior_sigma(c, pts, m, mp, mu_out, Sigma, ldq)) return rc;
+  if (cov_out)
+    HIPCHK(c, hipMemcpy2DAsync(cov_out, sizeof(double) * m, Sigma, sizeof(double) * ldq, sizeof(double) * m, m,
                                hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   return GPMI_OK;
@@ -786,12 +783,12 @@ int gpmi_covariance(gpmi_ctx* c, int kernel, const double* theta, int n_theta, d
   if (int rc = set_device(c)) return rc;
   if (int rc = ensure_lanes(c, 2)) return rc;
   Lane& L = c->lanes[1];
-  DevBuf zeros;  // (an error return below may leave the build reading it: hipFree waits for the device before it releases)
+  DevBuf<double> zeros;  // (an error return below may leave the build reading it: hipFree waits for the device before it releases)
   if (!with_noise) {
-    HIPCHK(c, hipMalloc(&zeros.p, sizeof(double) * c->np));
-    HIPCHK(c, hipMemsetAsync(zeros.p, 0, sizeof(double) * c->np, L.stream));
+    if (int rc = zeros.alloc(c, c->np)) return rc;
+    HIPCHK(c, hipMemsetAsync(zeros, 0, sizeof(double) * c->np, L.stream));
   }
-  launch_kbuild_square(L.stream, p, c->x, c->n, c->np, with_noise ? c->noise : zeros.as<double>(), L.A, c->ld, false);
+  launch_kbuild_square(L.stream, p, c->x, c->n, c->np, with_noise ? c->noise : zeros, L.A, c->ld, false);
   if (with_noise && c->ycov) launch_add_full(L.stream, L.A, c->ld, c->ycov, c->n);
   HIPCHK(c, hipMemcpy2DAsync(K_host, sizeof(double) * c->n, L.A, sizeof(double) * c->ld, sizeof(double) * c->n, c->n,
                              hipMemcpyDeviceToHost, L.stream));

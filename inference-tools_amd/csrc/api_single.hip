@@ -17,7 +17,7 @@ int lane_prepare(const LaneEval& ev, unsigned steps, int n_theta) {
   if (steps & LN_INVERSE)
     if (int rc = ensure_second_matrix(c, L)) return rc;
   const int64_t want = (n_theta >= 0 ? grad_ws_doubles(c->np, n_theta) : 0) + ((steps & LN_LOO) ? 4 * c->np : 0);
-  return grow(c, L.gws, L.gws_doubles, want, sizeof(double));
+  return L.gws.reserve(c, want);
 }
 
 int lane_forward(const LaneEval& ev, const LaneBuild& b, unsigned steps, const double* mu_host, int n_theta) {

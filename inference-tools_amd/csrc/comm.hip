@@ -128,15 +128,9 @@ int gpmi_comm_allgather(gpmi_ctx* c, const double* send_host, double* recv_host,
   }
   if (hipError_t e = hipSetDevice(c->device); e != hipSuccess) return hip_fail(c, "hipSetDevice", e);
   const int64_t need = count * (1 + (int64_t)c->comm_world);
-  if (c->comm_buf_doubles < need) {
-    if (c->comm_buf) (void)hipFree(c->comm_buf);
-    c->comm_buf = nullptr;
-    c->comm_buf_doubles = 0;
-    if (hipMalloc(&c->comm_buf, sizeof(double) * need) != hipSuccess) {
-      c->err = "out of device memory for the gather buffer";
-      return GPMI_ERR_NOMEM;
-    }
-    c->comm_buf_doubles = need;
+  if (c->comm_buf.reserve(c, need)) {
+    c->err = "out of device memory for the gather buffer";
+    return GPMI_ERR_NOMEM;
   }
   hipStream_t s = c->comm_stream;
   double* send = c->comm_buf;
@@ -171,15 +165,9 @@ int gpmi_comm_broadcast(gpmi_ctx* c, double* buf_host, int64_t count, int root) 
     return GPMI_ERR_ARG;
   }
   if (hipError_t e = hipSetDevice(c->device); e != hipSuccess) return hip_fail(c, "hipSetDevice", e);
-  if (c->comm_buf_doubles < count) {
-    if (c->comm_buf) (void)hipFree(c->comm_buf);
-    c->comm_buf = nullptr;
-    c->comm_buf_doubles = 0;
-    if (hipMalloc(&c->comm_buf, sizeof(double) * count) != hipSuccess) {
-      c->err = "out of device memory for the broadcast buffer";
-      return GPMI_ERR_NOMEM;
-    }
-    c->comm_buf_doubles = count;
+  if (c->comm_buf.reserve(c, count)) {
+    c->err = "out of device memory for the broadcast buffer";
+    return GPMI_ERR_NOMEM;
   }
   hipStream_t s = c->comm_stream;
   if (c->comm_rank == root)
@@ -217,9 +205,7 @@ int gpmi_comm_destroy(gpmi_ctx* c) {
     if (r) r->comm_destroy(c->comm);
   }
   c->comm = nullptr;
-  if (c->comm_buf) (void)hipFree(c->comm_buf);
-  c->comm_buf = nullptr;
-  c->comm_buf_doubles = 0;
+  c->comm_buf.release();
   if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
   c->comm_stream = nullptr;
   return GPMI_OK;

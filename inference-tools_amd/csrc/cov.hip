@@ -259,11 +259,10 @@ int gpmi_cov_columns(gpmi_ctx* c, int64_t n, int64_t m, int64_t row_stride, int6
   const size_t run_b = kde_align256(group_bytes), pair_b = kde_align256(4 * (size_t)npair);
   const size_t part_b = kde_align256(group_bytes * (size_t)gmax);
   const size_t res_b = mean_b + flag_b + cov_b;  // one run, copied back together
-  if (int rc = kde_grow_device(c, reinterpret_cast<void**>(&st->d_work), &st->d_work_bytes,
-                               x_b + ps_b + pb_b + res_b + run_b + 2 * pair_b + part_b))
+  if (int rc = st->reserve_work(c, x_b + ps_b + pb_b + res_b + run_b + 2 * pair_b + part_b))
     return rc;
-  if (int rc = kde_grow_pinned(c, st, std::max(res_b, 2 * pair_b))) return rc;
-  char* w = reinterpret_cast<char*>(st->d_work);
+  if (int rc = st->reserve_pinned(c, std::max(res_b, 2 * pair_b))) return rc;
+  char* w = st->d_work;
   double* d_x = reinterpret_cast<double*>(w);
   double* d_ps = reinterpret_cast<double*>(w + x_b);
   int* d_pb = reinterpret_cast<int*>(w + x_b + ps_b);
@@ -277,7 +276,7 @@ int gpmi_cov_columns(gpmi_ctx* c, int64_t n, int64_t m, int64_t row_stride, int6
   double* d_part = reinterpret_cast<double*>(d_res + res_b + run_b + 2 * pair_b);
 
   // the pairs of the upper triangle, row by row
-  int* h_pi = reinterpret_cast<int*>(st->h_stage);
+  int* h_pi = reinterpret_cast<int*>(st->h_stage.get());
   int* h_pj = reinterpret_cast<int*>(st->h_stage + pair_b);
   int k = 0;
   for (int i = 0; i < (int)nt; ++i)

@@ -107,20 +107,19 @@ int draws_tail(gpmi_ctx* c, Lane& lane, double* A, int64_t ld, int64_t m, int64_
   hipStream_t s = lane.stream;
   const int64_t nt = mp / GPMI_NB;
   const int64_t P = std::min<int64_t>(GPMI_DRAWS_PANEL, round_up(n_draws, GPMI_NB));
-  DevBuf invD, small, Z, D;
-  HIPCHK(c, hipMalloc(&invD.p, sizeof(double) * nt * GPMI_NB * GPMI_NB));
-  ZERO_SYNC(c, invD.p, sizeof(double) * nt * GPMI_NB * GPMI_NB);  // potrf_diag writes the block-lower part only (lane_alloc)
-  HIPCHK(c, hipMalloc(&small.p, 2 * sizeof(double)));  // [0] max diag, [1] the info word
-  HIPCHK(c, hipMalloc(&Z.p, sizeof(double) * P * ld));
-  HIPCHK(c, hipMalloc(&D.p, sizeof(double) * P * ld));
-  int* info_dev = reinterpret_cast<int*>(small.as<double>() + 1);
+  DevBuf<double> invD, small, Z, D;
+  if (int rc = invD.alloc_zeroed(c, nt * GPMI_NB * GPMI_NB)) return rc;  // potrf_diag writes the block-lower part only (lane_alloc)
+  if (int rc = small.alloc(c, 2)) return rc;  // [0] max diag, [1] the info word
+  if (int rc = Z.alloc(c, P * ld)) return rc;
+  if (int rc = D.alloc(c, P * ld)) return rc;
+  int* info_dev = reinterpret_cast<int*>(small + 1);
   double maxd = 0.0;
   int inf = 0;
   {
     ProfScope ps(c, s, GPMI_PROF_DRAWS_FACTOR, (double)mp * mp * mp / 3.0, 8.0 * mp * mp);
-    hipLaunchKernelGGL(draws_maxdiag_kernel, dim3(1), dim3(DRAWS_NT), 0, s, A, ld, m, small.as<double>());
+    hipLaunchKernelGGL(draws_maxdiag_kernel, dim3(1), dim3(DRAWS_NT), 0, s, A, ld, m, small);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(&maxd, small.p, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(&maxd, small, sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     if (!(std::isfinite(maxd) && maxd > 0.0)) {
       if (info) *info = 1;
@@ -131,7 +130,7 @@ int draws_tail(gpmi_ctx* c, Lane& lane, double* A, int64_t ld, int64_t m, int64_
     hipLaunchKernelGGL(draws_shift_pad_kernel, dim3(blocks(mp), (unsigned)mp), dim3(DRAWS_NT), 0, s, A, ld, m, mp, eps);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemsetAsync(info_dev, 0, sizeof(int), s));
-    potrf_lower(c, lane, A, mp, ld, invD.as<double>(), info_dev);
+    potrf_lower(c, lane, A, mp, ld, invD, info_dev);
     hipLaunchKernelGGL(draws_zero_upper_kernel, dim3(blocks(mp), (unsigned)mp), dim3(DRAWS_NT), 0, s, A, ld, mp);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(&inf, info_dev, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -149,24 +148,24 @@ int draws_tail(gpmi_ctx* c, Lane& lane, double* A, int64_t ld, int64_t m, int64_
     {
       ProfScope ps(c, s, GPMI_PROF_DRAWS_NORMALS, 0.0, 8.0 * rp * mp);
       if (z_host) {
-        HIPCHK(c, hipMemsetAsync(Z.p, 0, sizeof(double) * rp * ld, s));
-        HIPCHK(c, hipMemcpy2DAsync(Z.p, sizeof(double) * ld, z_host + s0 * m, sizeof(double) * m, sizeof(double) * m,
+        HIPCHK(c, hipMemsetAsync(Z, 0, sizeof(double) * rp * ld, s));
+        HIPCHK(c, hipMemcpy2DAsync(Z, sizeof(double) * ld, z_host + s0 * m, sizeof(double) * m, sizeof(double) * m,
                                    (size_t)rows, hipMemcpyHostToDevice, s));
       } else {
-        hipLaunchKernelGGL(draws_normals_kernel, dim3(blocks(mp / 2), (unsigned)rp), dim3(DRAWS_NT), 0, s, Z.as<double>(), ld,
+        hipLaunchKernelGGL(draws_normals_kernel, dim3(blocks(mp / 2), (unsigned)rp), dim3(DRAWS_NT), 0, s, Z, ld,
                            (uint64_t)seed, (uint64_t)(first_draw + s0), rows, m, mp);
         HIPCHK(c, hipGetLastError());
       }
     }
     {
       ProfScope ps(c, s, GPMI_PROF_DRAWS_PRODUCT, 2.0 * rp * mp * mp, 8.0 * (2.0 * rp * mp + (double)mp * mp));
-      launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, D.as<double>(), ld, Z.as<double>(), ld, A, ld, (int)(rp / GPMI_NB), (int)nt,
+      launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, D, ld, Z, ld, A, ld, (int)(rp / GPMI_NB), (int)nt,
                      (int)mp, nullptr, gb);
-      hipLaunchKernelGGL(draws_add_mean_kernel, dim3(blocks(m), (unsigned)rows), dim3(DRAWS_NT), 0, s, D.as<double>(), ld, mu_dev,
+      hipLaunchKernelGGL(draws_add_mean_kernel, dim3(blocks(m), (unsigned)rows), dim3(DRAWS_NT), 0, s, D, ld, mu_dev,
                          m);
       HIPCHK(c, hipGetLastError());
     }
-    HIPCHK(c, hipMemcpy2DAsync(draws_host + s0 * m, sizeof(double) * m, D.p, sizeof(double) * ld, sizeof(double) * m,
+    HIPCHK(c, hipMemcpy2DAsync(draws_host + s0 * m, sizeof(double) * m, D, sizeof(double) * ld, sizeof(double) * m,
                                (size_t)rows, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));  // (the next panel overwrites Z and D)
   }
@@ -189,17 +188,17 @@ int gpmi_posterior_draws(gpmi_ctx* c, const double* pts, int64_t m, double jitte
   hipStream_t s = L.stream;
   const int64_t mp = round_up(m, GPMI_NB), ldq = mp + 32;
   if (int rc = ensure_query_ws(c, mp)) return rc;
-  DevBuf Sigma;
-  HIPCHK(c, hipMalloc(&Sigma.p, sizeof(double) * mp * ldq));
+  DevBuf<double> Sigma;
+  if (int rc = Sigma.alloc(c, mp * ldq)) return rc;
   double* mu_dev = c->pvec;
   {
     // mu and Sigma = K_qq - Q^T Q: the pipeline of gpmi_posterior
     ProfScope ps(c, s, GPMI_PROF_DRAWS_SIGMA, 2.0 * mp * mp * c->np + (double)mp * c->np * c->np, 8.0 * mp * (2.0 * c->np + mp));
     // (an error return leaves at most the kernel build on Sigma in flight: hipFree waits for the device before it releases)
-    if (int rc = kernel_posterior_sigma(c, pts, m, mp, nullptr, Sigma.as<double>(), ldq)) return rc;
+    if (int rc = kernel_posterior_sigma(c, pts, m, mp, nullptr, Sigma, ldq)) return rc;
   }
   if (mu_out) HIPCHK(c, hipMemcpyAsync(mu_out, mu_dev, sizeof(double) * m, hipMemcpyDeviceToHost, s));
-  const int rc = draws_tail(c, L, Sigma.as<double>(), ldq, m, mp, mu_dev, jitter_rel, n_draws, z_host, seed, first_draw,
+  const int rc = draws_tail(c, L, Sigma, ldq, m, mp, mu_dev, jitter_rel, n_draws, z_host, seed, first_draw,
                             draws_host, eps_host, info);
   const hipError_t e = hipStreamSynchronize(s);  // (before Sigma is released, whatever the tail returned)
   if (rc != GPMI_OK) return rc;
@@ -222,17 +221,17 @@ int gpmi_mvn_draws(gpmi_ctx* c, int64_t m, const double* mean, const double* cov
   Lane& L = c->lanes[0];
   hipStream_t s = L.stream;
   const int64_t mp = round_up(m, GPMI_NB), ldq = mp + 32;
-  DevBuf Sigma, mu;
-  HIPCHK(c, hipMalloc(&Sigma.p, sizeof(double) * mp * ldq));
-  HIPCHK(c, hipMalloc(&mu.p, sizeof(double) * m));
+  DevBuf<double> Sigma, mu;
+  if (int rc = Sigma.alloc(c, mp * ldq)) return rc;
+  if (int rc = mu.alloc(c, m)) return rc;
   {
     ProfScope ps(c, s, GPMI_PROF_DRAWS_SIGMA, 0.0, 8.0 * m * m);
-    HIPCHK(c, hipMemcpyAsync(mu.p, mean, sizeof(double) * m, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(mu, mean, sizeof(double) * m, hipMemcpyHostToDevice, s));
     // (the columns m .. mp - 1 of the first m rows lie above the diagonal: draws_shift_pad_kernel zeroes them)
-    HIPCHK(c, hipMemcpy2DAsync(Sigma.p, sizeof(double) * ldq, cov, sizeof(double) * m, sizeof(double) * m, (size_t)m,
+    HIPCHK(c, hipMemcpy2DAsync(Sigma, sizeof(double) * ldq, cov, sizeof(double) * m, sizeof(double) * m, (size_t)m,
                                hipMemcpyHostToDevice, s));
   }
-  const int rc = draws_tail(c, L, Sigma.as<double>(), ldq, m, mp, mu.as<double>(), jitter_rel, n_draws, z_host, seed, first_draw,
+  const int rc = draws_tail(c, L, Sigma, ldq, m, mp, mu, jitter_rel, n_draws, z_host, seed, first_draw,
                             draws_host, eps_host, info);
   const hipError_t e = hipStreamSynchronize(s);
   if (rc != GPMI_OK) return rc;

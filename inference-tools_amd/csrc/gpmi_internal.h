@@ -2,9 +2,11 @@
 // Public C-ABI: include/gpmi.h.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdint>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "gpmi.h"
@@ -71,14 +73,102 @@ struct CovParams : KParams {
   explicit CovParams(const KParams& k) : KParams(k) {}
 };
 
+struct gpmi_ctx;
+
+// ---- ownership of device and pinned host memory ------------------------------------------------------------------
+// Every allocation of the library passes through BufMem (the only place that calls the HIP allocator: plain hipMalloc /
+// hipFree - callers rely on hipFree waiting for the device before it releases -, no pool, no stream-ordered allocator),
+// which keeps the process-wide totals gpmi_live_bytes reports.
+struct BufMem {
+  static inline std::atomic<int64_t> live[2];  // bytes held now: [0] device, [1] pinned host
+  // *p <- `bytes` of device memory, or of pinned host memory with the hipHostMalloc `flags`.  On failure *p is null, the
+  // text goes to c->err (c may be null) and the result is GPMI_ERR_NOMEM / GPMI_ERR_HIP.
+  static int get(gpmi_ctx* c, void** p, size_t bytes, bool pinned, unsigned flags);
+  static void give(void* p, size_t bytes, bool pinned) {
+    if (!p) return;
+    (void)(pinned ? hipHostFree(p) : hipFree(p));
+    live[pinned ? 1 : 0] -= (int64_t)bytes;
+  }
+};
+
+// Typed, move-only owner of `capacity()` elements of device memory (PINNED: of pinned host memory).  Converts to T*, so
+// it is used where the pointer was.  A failed allocation leaves it empty: null pointer, capacity 0.
+template <class T, bool PINNED = false>
+class DevBuf {
+  T* p_ = nullptr;
+  int64_t cap_ = 0;
+
+ public:
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p_(std::exchange(o.p_, nullptr)), cap_(std::exchange(o.cap_, 0)) {}
+  DevBuf& operator=(DevBuf&& o) noexcept {  // releases what it held, at once
+    if (this != &o) {
+      release();
+      p_ = std::exchange(o.p_, nullptr);
+      cap_ = std::exchange(o.cap_, 0);
+    }
+    return *this;
+  }
+  ~DevBuf() { release(); }
+  operator T*() const { return p_; }
+  T* get() const { return p_; }  // (where no conversion applies: reinterpret_cast)
+  int64_t capacity() const { return cap_; }
+  void release() {
+    BufMem::give(p_, sizeof(T) * (size_t)cap_, PINNED);
+    p_ = nullptr;
+    cap_ = 0;
+  }
+  // `count` elements, contents undefined; what the buffer held before is freed first.  flags: hipHostMalloc's (PINNED)
+  int alloc(gpmi_ctx* c, int64_t count, unsigned flags = 0) {
+    release();
+    if (int rc = BufMem::get(c, reinterpret_cast<void**>(&p_), sizeof(T) * (size_t)count, PINNED, flags)) return rc;
+    cap_ = count;
+    return GPMI_OK;
+  }
+  // alloc, then zeros that have ARRIVED: filled and waited for on the null stream (api_internal.h: ZERO_SYNC)
+  int alloc_zeroed(gpmi_ctx* c, int64_t count);
+  // at least `count` elements: nothing if it is large enough, else freed and allocated anew (contents lost)
+  int reserve(gpmi_ctx* c, int64_t count, unsigned flags = 0) { return cap_ >= count ? GPMI_OK : alloc(c, count, flags); }
+};
+template <class T>
+using PinBuf = DevBuf<T, true>;
+
 struct ProfSlot {
   hipEvent_t e0, e1;
   int klass;
   double flops, bytes;
 };
 
+// The memory of a lane, as bases of Lane so that each group is released by assigning an empty one (api.hip: lane_free,
+// potrf_flow.hip: potrf_flow_free) at its place in the teardown order.
+struct LaneBufs {
+  DevBuf<double> A;         // np x ld scratch (K then L)
+  DevBuf<double> invD;      // (np/128) x 128 x 128 inverses of the diagonal blocks
+  DevBuf<double> B2;        // second np x ld matrix (L^-T for the gradient / LOO paths), allocated lazily
+  // inverses of the 512 x 512 diagonal blocks of L (many-right-hand-side solves), built lazily from invD
+  DevBuf<double> inv2;      // ceil(nt / 4) x 512 x 512
+  DevBuf<double> inv2_t;    // scratch: ceil(nt / 4) x 256 x 256
+  DevBuf<double> gws;       // gradient partial sums
+  DevBuf<double> vec;       // 4 x np work vectors
+  DevBuf<double> red;       // small reduction outputs (device)
+  DevBuf<int> info;         // device info word
+  PinBuf<double> h_red;     // pinned host mirror of red
+  PinBuf<int> h_info;       // pinned host mirror of info
+  // fused panel column of the stream-ordered chain (potrf_panel.hip): GPMI_PANEL_FL_INTS ints, zeroed once at the
+  // allocation - the row counters are monotone
+  DevBuf<int> panel_flags;
+};
+// flag-ordered factorisation of the chain-bound part (potrf_flow.hip): task lists of a tail of flow_m tile rows
+struct LaneFlowBufs {
+  DevBuf<char> flow_tasks;  // FlowTask records
+  DevBuf<int> flow_off;
+  DevBuf<int> flow_flags;
+};
+
 // One independent evaluation lane: a stream with its own n x n scratch matrix and vectors.
-struct Lane {
+struct Lane : LaneBufs, LaneFlowBufs {
   hipStream_t stream = nullptr;    // full-chip stream: covariance build, solves, small factorisations
   bool owns_stream = true;         // false (lanes 2..): the stream is lane 0's or lane 1's (api.hip: lane_streams)
   // look-ahead pairs (CU-masked, disjoint; lanes 0 and 1 only, created with the lane): pair k factors the next panel on
@@ -105,31 +195,12 @@ struct Lane {
   bool identity_ready = false;  // EarlyWork has written the identity into B2 for the inverse factor that follows
   bool pair_checked = false;       // potrf_pair_quiesce has run for the factorisation being enqueued (potrf.hip)
   hipEvent_t ev_la = nullptr, ev_panel = nullptr, ev_join = nullptr, ev_main = nullptr, ev_slice = nullptr;
-  double* A = nullptr;      // np x ld scratch (K then L)
-  double* invD = nullptr;   // (np/128) x 128 x 128 inverses of the diagonal blocks
-  double* B2 = nullptr;     // second np x ld matrix (L^-T for the gradient / LOO paths), allocated lazily
-  // inverses of the 512 x 512 diagonal blocks of L (many-right-hand-side solves), built lazily from invD
-  double* inv2 = nullptr;    // ceil(nt / 4) x 512 x 512
-  double* inv2_t = nullptr;  // scratch: ceil(nt / 4) x 256 x 256
-  bool inv2_valid = false;
-  double* gws = nullptr;    // gradient partial sums
-  int64_t gws_doubles = 0;
-  double* vec = nullptr;    // 4 x np work vectors
-  double* red = nullptr;    // small reduction outputs (device)
-  int* info = nullptr;      // device info word
-  double* h_red = nullptr;  // pinned host mirror of red
-  int* h_info = nullptr;    // pinned host mirror of info
-  // flag-ordered factorisation of the chain-bound part (potrf_flow.hip): task lists of a tail of flow_m tile rows
-  void* flow_tasks = nullptr;
-  int* flow_off = nullptr;
-  int* flow_flags = nullptr;
+  bool inv2_valid = false;  // inv2 holds the blocks of the factor in A
+  // the task lists in LaneFlowBufs
   int flow_m = 0, flow_nwg = 0, flow_nlists = 0;
   int64_t flow_ntasks = 0;
   double flow_flops_update = 0.0, flow_flops_trsm = 0.0;
-  // fused panel column of the stream-ordered chain (potrf_panel.hip): GPMI_PANEL_FL_INTS ints, zeroed once here - the row
-  // counters are monotone -, and the number of fused launches the lane has enqueued so far
-  int* panel_flags = nullptr;
-  unsigned panel_seq = 0;
+  unsigned panel_seq = 0;  // fused panel-column launches (panel_flags) the lane has enqueued so far
 };
 // Lane::panel_flags: the row-block counters of the inverse on lines of their own (32 r), the abort word
 constexpr int GPMI_PANEL_FL_INVROW = 0, GPMI_PANEL_FL_ABORT = 256, GPMI_PANEL_FL_INTS = 288;
@@ -137,40 +208,92 @@ constexpr int GPMI_PANEL_FL_INVROW = 0, GPMI_PANEL_FL_ABORT = 256, GPMI_PANEL_FL
 // device state of the linear-inversion entry points (gpmi_linv_*): m data values, model matrix A (m x n)
 struct LinvState {
   int64_t m = 0, mp = 0, ldm = 0;
-  double* A = nullptr;     // mp x ld   model matrix, zero padded
-  double* At = nullptr;    // np x ldm  its transpose
-  double* y = nullptr;     // mp
-  double* sig2 = nullptr;  // mp        y_err^2, 1 in the padding (keeps the padded J positive definite)
-  double* zero = nullptr;  // np        zeros (the prior covariance carries no data noise)
-  double* K = nullptr;     // np x ld   prior covariance (later A^T J^-1 A, K - X X^T)
-  double* T = nullptr;     // mp x ld   A K (later J^-1 A)
-  double* J = nullptr;     // mp x ldm  A K A^T + Sigma, then its factor L
-  double* J2 = nullptr;    // mp x ldm  L^-T, then J^-1          (gradient only)
-  double* Q = nullptr;     // np x ldm  K A^T                    (posterior only)
-  double* X = nullptr;     // np x ldm  K A^T L^-T               (posterior only)
-  double* invD = nullptr;  // 128-wide inverse diagonal blocks of L
-  double* inv2 = nullptr;  // 512-wide
-  double* inv2_t = nullptr;
-  double* panel = nullptr; // mp x 544 (in-place many-right-hand-side solve)
-  double* vec = nullptr;   // 8 x max(mp, np) work vectors
-  double* gws = nullptr;
-  int64_t gws_doubles = 0;
+  DevBuf<double> A;     // mp x ld   model matrix, zero padded
+  DevBuf<double> At;    // np x ldm  its transpose
+  DevBuf<double> y;     // mp
+  DevBuf<double> sig2;  // mp        y_err^2, 1 in the padding (keeps the padded J positive definite)
+  DevBuf<double> zero;  // np        zeros (the prior covariance carries no data noise)
+  DevBuf<double> K;     // np x ld   prior covariance (later A^T J^-1 A, K - X X^T)
+  DevBuf<double> T;     // mp x ld   A K (later J^-1 A)
+  DevBuf<double> J;     // mp x ldm  A K A^T + Sigma, then its factor L
+  DevBuf<double> J2;    // mp x ldm  L^-T, then J^-1          (gradient only)
+  DevBuf<double> Q;     // np x ldm  K A^T                    (posterior only)
+  DevBuf<double> X;     // np x ldm  K A^T L^-T               (posterior only)
+  DevBuf<double> invD;  // 128-wide inverse diagonal blocks of L
+  DevBuf<double> inv2;  // 512-wide
+  DevBuf<double> inv2_t;
+  DevBuf<double> panel; // mp x 544 (in-place many-right-hand-side solve)
+  DevBuf<double> vec;   // 8 x max(mp, np) work vectors
+  DevBuf<double> gws;
 };
 
 struct KdeState;  // kde.hip
 struct gpmi_sgp;  // sparse.hip
 
-struct gpmi_ctx {
+// The device memory of a handle in the groups that are released together, as bases of gpmi_ctx: a group is released by
+// assigning an empty one (api.hip: free_data, free_batch_ws, ensure_*), which also zeroes the group's capacity.
+// the data set (gpmi_set_data) and the fitted alpha
+struct DataBufs {
+  DevBuf<double> x;      // np x d (rows >= n are zero)
+  DevBuf<double> y;      // np
+  DevBuf<double> noise;  // np diagonal data variances (zero padded)
+  DevBuf<double> ycov;   // n x n dense y covariance or empty
+  DevBuf<double> alpha;  // np — fitted alpha
+};
+// prediction workspace, sized together for mq_cap query rows (ensure_query_ws)
+struct QueryBufs {
+  DevBuf<double> Q;     // mq_cap x ld
+  DevBuf<double> Q2;    // second panel (spatial derivatives)
+  DevBuf<double> pts;   // mq_cap x d
+  DevBuf<double> pvec;  // vectors of length mq_cap * (2 + 2 d)
+  int64_t mq_cap = 0;
+};
+// gradient batches, sized together for bgrad_cap problems of bgrad_ntheta parameters (ensure_batch_grad_ws)
+struct BatchGradBufs {
+  DevBuf<double> bB2;     // second matrix per problem (L^-T)
+  DevBuf<double> bGws;    // partial sums of the fused contraction
+  DevBuf<double> bGout;   // (n_theta + 1) results per problem
+  PinBuf<double> h_bGout;
+  int bgrad_cap = 0, bgrad_ntheta = 0;
+};
+// batched small-problem workspace (gpmi_lml_batch for np <= 4096): `bcap` matrices side by side (ensure_batch_ws), and
+// what the batch entry points add per problem
+struct BatchBufs : BatchGradBufs {
+  int bcap = 0;
+  DevBuf<double> bA, bInv, bVec, bRed, bMu;
+  DevBuf<int> bInfo;
+  DevBuf<KParams> bParams;
+  DevBuf<CovParams> bSum;  // the per-problem parameters of a lockstep batch of sums (bcap of them)
+  PinBuf<double> h_bRed;
+  PinBuf<int> h_bInfo;
+  DevBuf<double> bNoise;   // gpmi_lml_grad_batch_noise: one noise-variance vector per problem
+  DevBuf<double> bQ;       // gpmi_predict_batch: per problem two panels of GPMI_PREDICT_PANEL x ld (K*, K* L^-T)
+  DevBuf<double> bLoo;     // gpmi_loo_grad_batch: 4 vectors per problem (diag K^-1, c1, sqrt c2, p)
+  // gpmi_lml_grad_batch_mix (ensure_batch_mix_ws, bMix_cap problems): per problem the window weights g_m and the row sums
+  // h_m (GPMI_MAX_MIX x np each), the sub-kernels' parameters (GPMI_MAX_MIX arrays of bcap KParams) and the WhiteNoise
+  // variances
+  DevBuf<double> bMixG, bMixH;
+  DevBuf<double> bMixW;    // the caller's row-sum weights (gpmi_*_grad_batch_mix: hw)
+  DevBuf<KParams> bMixP;
+  DevBuf<double> bMixExtra;
+  int bMix_cap = 0;
+};
+// fitted mixture model (gpmi_fit_mix): the training-point weights g and the third query panel
+struct MixBufs {
+  int mix_nk = 0;
+  DevBuf<double> mix_g;        // nk x np (row m: g_m; padding 1 for m = 0, 0 otherwise)
+  DevBuf<double> mix_scratch;  // np x ld
+  DevBuf<double> mix_zero;     // np zeros
+  DevBuf<double> Q3;           // third query panel (mq_cap x ld at its allocation)
+};
+
+struct gpmi_ctx : DataBufs, QueryBufs, BatchBufs, MixBufs {
   int device = 0;
   int ncu = 256;      // compute units of the device
   int pair_cus[GPMI_NPAIRS] = {32};  // CUs of the panel stream of look-ahead pair k (the update stream has the rest)
   std::string err;
   // data
   int64_t n = 0, d = 0, np = 0, ld = 0;
-  double* x = nullptr;      // np x d (rows >= n are zero)
-  double* y = nullptr;      // np
-  double* noise = nullptr;  // np diagonal data variances (zero padded)
-  double* ycov = nullptr;   // n x n dense y covariance or nullptr
   // fitted state lives in lanes[0]
   std::vector<Lane> lanes;
   bool fitted = false;
@@ -180,70 +303,21 @@ struct gpmi_ctx {
   CovParams fit_params;
   int sum_nk = 0;                   // gpmi_set_sum: components of this handle's GPMI_KERNEL_SUM (0: none declared)
   int sum_kinds[GPMI_MAX_SUM] = {};
-  double* alpha = nullptr;  // np (device) — fitted alpha
-  // prediction workspace
-  double* Q = nullptr;      // mq_cap x ld
-  double* Q2 = nullptr;     // second panel (spatial derivatives)
-  int64_t mq_cap = 0;
-  double* pts = nullptr;    // mq_cap x d
-  double* pvec = nullptr;   // vectors of length mq_cap * (2 + 2 d)
-  double* trsm_panel = nullptr;  // rows x 544 scratch of the in-place many-right-hand-side solve
-  int64_t trsm_panel_rows = 0;
-  // host staging (pinned)
-  double* h_stage = nullptr;
-  int64_t h_stage_bytes = 0;
-  // batched small-problem workspace (gpmi_lml_batch for np <= 4096): `bcap` matrices side by side
-  int bcap = 0;
-  double* bA = nullptr;
-  double* bInv = nullptr;
-  double* bVec = nullptr;
-  double* bRed = nullptr;
-  double* bMu = nullptr;
-  double* bB2 = nullptr;     // second matrix per problem (L^-T), gradient batches only
-  double* bGws = nullptr;    // partial sums of the fused contraction
-  double* bNoise = nullptr;  // gpmi_lml_grad_batch_noise: one noise-variance vector per problem
-  int bNoise_cap = 0;
-  // gpmi_lml_grad_batch_mix: per problem the window weights g_m and the row sums h_m (GPMI_MAX_MIX x np each), the
-  // sub-kernels' parameters (GPMI_MAX_MIX arrays of bcap KParams) and the WhiteNoise variances
-  double* bMixG = nullptr;
-  double* bMixH = nullptr;
-  double* bMixW = nullptr;  // the caller's row-sum weights (gpmi_*_grad_batch_mix: hw)
-  KParams* bMixP = nullptr;
-  double* bMixExtra = nullptr;
-  int bMix_cap = 0;
-  double* bQ = nullptr;      // gpmi_predict_batch: per problem two panels of GPMI_PREDICT_PANEL x ld (K*, K* L^-T)
-  int bQ_cap = 0;
-  double* bLoo = nullptr;    // gpmi_loo_grad_batch: 4 vectors per problem (diag K^-1, c1, sqrt c2, p)
-  int bLoo_cap = 0;
-  double* bGout = nullptr;   // (n_theta + 1) results per problem
-  double* h_bGout = nullptr;
-  int bgrad_cap = 0, bgrad_ntheta = 0;
-  int* bInfo = nullptr;
-  KParams* bParams = nullptr;
-  CovParams* bSum = nullptr;  // the per-problem parameters of a lockstep batch of sums (bcap of them)
+  DevBuf<double> trsm_panel;  // rows x 544 scratch of the in-place many-right-hand-side solve
+  PinBuf<char> h_stage;       // host staging of the lockstep chunks (RowStage)
   // asynchronous lockstep batches (gpmi_lml_batch_submit / _wait): two slots = the two halves of the workspace, on the
   // streams of lanes 1 and 2; evaluations pending per slot (0: free), pinned staging of their inputs
   int bpend[2] = {0, 0};
-  char* h_bStage[2] = {nullptr, nullptr};
-  int64_t h_bStage_bytes[2] = {0, 0};
-  double* h_bRed = nullptr;
-  int* h_bInfo = nullptr;
+  PinBuf<char> h_bStage[2];
   LinvState linv;
-  // fitted mixture model (gpmi_fit_mix): sub-kernel parameters and the training-point weights g (nk x np)
-  int mix_nk = 0;
-  KParams mix_p[4];
-  double* mix_g = nullptr;        // nk x np (row m: g_m; padding 1 for m = 0, 0 otherwise)
-  double* mix_scratch = nullptr;  // np x ld
-  double* mix_zero = nullptr;     // np zeros
-  double* Q3 = nullptr;           // third query panel (mq_cap x ld)
-  int64_t q3_cap = 0;
+  KParams mix_p[4];  // gpmi_fit_mix: the sub-kernels' parameters (MixBufs::mix_nk of them)
   // RCCL result gather (comm.hip)
   void* comm = nullptr;
   int comm_rank = 0, comm_world = 1;
   hipStream_t comm_stream = nullptr;
-  double* comm_buf = nullptr;
-  int64_t comm_buf_doubles = 0;
+  DevBuf<double> comm_buf;
   hipStream_t dev_masked = nullptr;  // tools: CU-masked stream of the device-pointer entry points (GPMI_DEV_CUS)
+  std::vector<DevBuf<char>> dev_allocs;  // tools: what gpmi_dev_alloc has handed out and gpmi_dev_free not taken back
   KdeState* kde = nullptr;  // kde.hip: stream, workspaces and live objects of the gpmi_kde_* entry points
   // sparse.hip: the live objects of the gpmi_sgp_* entry points and the stream they share (created with the first one)
   std::vector<gpmi_sgp*> sgp_live;
@@ -252,7 +326,7 @@ struct gpmi_ctx {
   hipEvent_t t0 = nullptr, t1 = nullptr;
   unsigned prof_mask = 0;
   // device-stamped launches (trailing-update class): {min start, max end} per launch
-  unsigned long long* stamp_pool = nullptr;
+  DevBuf<unsigned long long> stamp_pool;
   std::vector<double> stamp_flops, stamp_bytes;
   std::vector<int> stamp_class;
   std::vector<ProfSlot> prof_slots;
@@ -263,6 +337,26 @@ struct gpmi_ctx {
   double prof_bytes[GPMI_PROF_NCLASS] = {};
   int64_t prof_launches[GPMI_PROF_NCLASS] = {};
 };
+
+inline int BufMem::get(gpmi_ctx* c, void** p, size_t bytes, bool pinned, unsigned flags) {
+  const hipError_t e = pinned ? hipHostMalloc(p, bytes, flags) : hipMalloc(p, bytes);
+  if (e == hipSuccess) {
+    live[pinned ? 1 : 0] += (int64_t)bytes;
+    return GPMI_OK;
+  }
+  *p = nullptr;
+  if (c) c->err = std::string(pinned ? "hipHostMalloc" : "hipMalloc") + " of " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e);
+  return e == hipErrorOutOfMemory ? GPMI_ERR_NOMEM : GPMI_ERR_HIP;
+}
+template <class T, bool PINNED>
+int DevBuf<T, PINNED>::alloc_zeroed(gpmi_ctx* c, int64_t count) {
+  if (int rc = alloc(c, count)) return rc;
+  hipError_t e = hipMemset(p_, 0, sizeof(T) * (size_t)count);
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  if (e == hipSuccess) return GPMI_OK;
+  if (c) c->err = std::string("zeroing a new buffer: ") + hipGetErrorString(e);
+  return GPMI_ERR_HIP;
+}
 
 // kde.hip: destroy the handle's density objects and their stream / workspaces (gpmi_destroy)
 void kde_release_all(gpmi_ctx* c);

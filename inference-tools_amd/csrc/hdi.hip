@@ -373,11 +373,10 @@ int gpmi_hdi_columns(gpmi_ctx* c, int64_t n, int64_t m, int64_t row_stride, int6
   const size_t part_bytes = large ? kde_align256(sizeof(WinPart) * (size_t)n_frac * nblk * mb_max) : 0;
   const size_t out_bytes = kde_align256(16 * (size_t)n_frac * mb_max);
   const size_t flag_bytes = kde_align256(4 * (size_t)mb_max);
-  if (int rc = kde_grow_device(c, reinterpret_cast<void**>(&st->d_work), &st->d_work_bytes,
-                               l_bytes + raw_bytes + a_bytes + b_bytes + part_bytes + out_bytes + flag_bytes))
+  if (int rc = st->reserve_work(c, l_bytes + raw_bytes + a_bytes + b_bytes + part_bytes + out_bytes + flag_bytes))
     return rc;
-  if (int rc = kde_grow_pinned(c, st, l_bytes + out_bytes + flag_bytes)) return rc;
-  char* w = reinterpret_cast<char*>(st->d_work);
+  if (int rc = st->reserve_pinned(c, l_bytes + out_bytes + flag_bytes)) return rc;
+  char* w = st->d_work;
   long long* d_L = reinterpret_cast<long long*>(w);
   double* d_raw = reinterpret_cast<double*>(w + l_bytes);
   double* d_a = reinterpret_cast<double*>(w + l_bytes + raw_bytes);

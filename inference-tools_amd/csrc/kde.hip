@@ -218,7 +218,7 @@ void launch_cv_partial(int H, hipStream_t st, dim3 grid, const double* s, int64_
 struct gpmi_kde {
   gpmi_ctx* ctx = nullptr;
   int64_t n = 0, n_regions = 0;
-  double* s = nullptr;  // n sorted samples (device)
+  DevBuf<double> s;  // n sorted samples (device)
   std::vector<int> lo, hi;
 };
 
@@ -230,54 +230,23 @@ int kde_state(gpmi_ctx* c, KdeState*& st) {
   return GPMI_OK;
 }
 
-int kde_grow_pinned(gpmi_ctx* c, KdeState* st, size_t bytes) {
-  if (bytes <= st->h_bytes) return GPMI_OK;
-  if (st->h_stage) (void)hipHostFree(st->h_stage);
-  st->h_stage = nullptr;
-  st->h_bytes = 0;
-  const size_t cap = std::max(bytes, (size_t)1 << 16);
-  HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&st->h_stage), cap, hipHostMallocPortable));
-  st->h_bytes = cap;
-  return GPMI_OK;
-}
-
-int kde_grow_device(gpmi_ctx* c, void** ptr, size_t* have, size_t bytes) {
-  if (bytes <= *have) return GPMI_OK;
-  if (*ptr) (void)hipFree(*ptr);
-  *ptr = nullptr;
-  *have = 0;
-  const size_t cap = std::max(bytes, (size_t)1 << 16);
-  HIPCHK(c, hipMalloc(ptr, cap));
-  *have = cap;
-  return GPMI_OK;
-}
-
 namespace {
-
-int grow_pinned(gpmi_ctx* c, KdeState* st, size_t bytes) { return kde_grow_pinned(c, st, bytes); }
-int grow_device(gpmi_ctx* c, void** ptr, size_t* have, size_t bytes) { return kde_grow_device(c, ptr, have, bytes); }
 size_t align256(size_t b) { return kde_align256(b); }
-
-void kde_free(gpmi_kde* k) {
-  if (k->s) (void)hipFree(k->s);
-  delete k;
-}
-
 }  // namespace
 
 void kde_release_all(gpmi_ctx* c) {
   KdeState* st = c->kde;
   if (!st) return;
   if (st->stream) (void)hipStreamSynchronize(st->stream);
-  for (gpmi_kde* k : st->live) kde_free(k);
+  for (gpmi_kde* k : st->live) delete k;
   st->live.clear();
   for (gpmi_kde2d* k : st->live2d) kde2d_free(k);
   st->live2d.clear();
   for (gpmi_unimodal* k : st->live_uni) unimodal_free(k);
   st->live_uni.clear();
-  if (st->h_stage) (void)hipHostFree(st->h_stage);
-  if (st->d_in) (void)hipFree(st->d_in);
-  if (st->d_work) (void)hipFree(st->d_work);
+  st->h_stage.release();
+  st->d_in.release();
+  st->d_work.release();
   if (st->stream) (void)hipStreamDestroy(st->stream);
   delete st;
   c->kde = nullptr;
@@ -304,12 +273,9 @@ int gpmi_kde_create(gpmi_ctx* c, int64_t n, const double* sample, int64_t n_regi
   k->n_regions = n_regions;
   k->lo.assign(lo, lo + n_regions);
   k->hi.assign(hi, hi + n_regions);
-  hipError_t e = hipMalloc(&k->s, sizeof(double) * n);
-  if (e == hipSuccess) e = hipMemcpy(k->s, sample, sizeof(double) * n, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    c->err = std::string("gpmi_kde_create: ") + hipGetErrorString(e);
-    kde_free(k);
-    return e == hipErrorOutOfMemory ? GPMI_ERR_NOMEM : GPMI_ERR_HIP;
+  if (int rc = kde_upload(c, k->s, sample, n, "gpmi_kde_create")) {
+    delete k;
+    return rc;
   }
   st->live.push_back(k);
   *out = k;
@@ -325,7 +291,7 @@ int gpmi_kde_destroy(gpmi_kde* k) {
   if (int rc = set_device(c)) return rc;
   HIPCHK(c, hipStreamSynchronize(st->stream));
   st->live.erase(it);
-  kde_free(k);
+  delete k;
   return GPMI_OK;
 }
 
@@ -395,7 +361,7 @@ int gpmi_kde_eval(gpmi_kde* k, int64_t m, const double* x, const int64_t* region
                o_ig = align256(o_gf + 4 * (ngroups + 1)), o_ic = align256(o_ig + 4 * items),
                in_bytes = align256(o_ic + 4 * items);
   const size_t out_bytes = 2 * align256(8 * m);
-  if (int rc = grow_pinned(c, st, in_bytes + out_bytes)) return rc;
+  if (int rc = st->reserve_pinned(c, in_bytes + out_bytes)) return rc;
   char* h = st->h_stage;
   double* hx = reinterpret_cast<double*>(h + o_x);
   int* hlo = reinterpret_cast<int*>(h + o_lo);
@@ -417,10 +383,10 @@ int gpmi_kde_eval(gpmi_kde* k, int64_t m, const double* x, const int64_t* region
   const bool want_pdf = pdf_sum != nullptr, want_cdf = cdf_sum != nullptr;
   const size_t part = align256(8 * (size_t)std::max<int64_t>(items, 1) * KDE_PTS);
   const size_t outv = align256(8 * m);
-  if (int rc = grow_device(c, reinterpret_cast<void**>(&st->d_in), &st->d_in_bytes, in_bytes)) return rc;
-  if (int rc = grow_device(c, reinterpret_cast<void**>(&st->d_work), &st->d_work_bytes, 2 * part + 2 * outv)) return rc;
+  if (int rc = st->reserve_in(c, in_bytes)) return rc;
+  if (int rc = st->reserve_work(c, 2 * part + 2 * outv)) return rc;
   char* d = st->d_in;
-  char* w = reinterpret_cast<char*>(st->d_work);
+  char* w = st->d_work;
   double* d_ppdf = want_pdf ? reinterpret_cast<double*>(w) : nullptr;
   double* d_pcdf = want_cdf ? reinterpret_cast<double*>(w + part) : nullptr;
   double* d_opdf = want_pdf ? reinterpret_cast<double*>(w + 2 * part) : nullptr;
@@ -483,9 +449,9 @@ int gpmi_kde_cv_logprob(gpmi_ctx* c, int64_t n, const double* samples, int n_wid
   // staged: sorted samples | rh | lnorm ; device work: partials | block sums
   const size_t o_s = 0, o_rh = align256(8 * n), o_ln = align256(o_rh + 8 * CV_MAXH), in_bytes = align256(o_ln + 8 * CV_MAXH);
   const size_t part_bytes = align256(8 * (size_t)nsp * HB * n), bs_bytes = align256(8 * (size_t)ntiles * HB);
-  if (int rc = grow_pinned(c, st, in_bytes + bs_bytes)) return rc;
-  if (int rc = grow_device(c, reinterpret_cast<void**>(&st->d_in), &st->d_in_bytes, in_bytes)) return rc;
-  if (int rc = grow_device(c, reinterpret_cast<void**>(&st->d_work), &st->d_work_bytes, part_bytes + bs_bytes)) return rc;
+  if (int rc = st->reserve_pinned(c, in_bytes + bs_bytes)) return rc;
+  if (int rc = st->reserve_in(c, in_bytes)) return rc;
+  if (int rc = st->reserve_work(c, part_bytes + bs_bytes)) return rc;
   char* h = st->h_stage;
   double* hs = reinterpret_cast<double*>(h + o_s);
   std::memcpy(hs, samples, 8 * n);
@@ -493,8 +459,8 @@ int gpmi_kde_cv_logprob(gpmi_ctx* c, int64_t n, const double* samples, int n_wid
   const double* d_s = reinterpret_cast<const double*>(st->d_in + o_s);
   double* d_rh = reinterpret_cast<double*>(st->d_in + o_rh);
   double* d_ln = reinterpret_cast<double*>(st->d_in + o_ln);
-  double* d_part = st->d_work;
-  double* d_bs = reinterpret_cast<double*>(reinterpret_cast<char*>(st->d_work) + part_bytes);
+  double* d_part = st->work();
+  double* d_bs = reinterpret_cast<double*>(st->d_work + part_bytes);
   const double* hbs = reinterpret_cast<const double*>(h + in_bytes);
   const double sqrt2pi = std::sqrt(2.0 * 3.14159265358979323846);
   bool first = true;

@@ -175,18 +175,13 @@ __global__ __launch_bounds__(256) void kde2d_grid_partial(const d2_t* __restrict
 struct gpmi_kde2d {
   gpmi_ctx* ctx = nullptr;
   int64_t n = 0, ntiles = 0;
-  d2_t* s = nullptr;    // n binned samples (device)
-  int* perm = nullptr;  // perm[i]: the caller's index of binned sample i (device)
-  d4_t* box = nullptr;  // ntiles boxes {xlo, xhi, ylo, yhi} (device)
+  DevBuf<d2_t> s;    // n binned samples (device)
+  DevBuf<int> perm;  // perm[i]: the caller's index of binned sample i (device)
+  DevBuf<d4_t> box;  // ntiles boxes {xlo, xhi, ylo, yhi} (device)
   std::vector<d4_t> hbox;
 };
 
-void kde2d_free(gpmi_kde2d* k) {
-  if (k->s) (void)hipFree(k->s);
-  if (k->perm) (void)hipFree(k->perm);
-  if (k->box) (void)hipFree(k->box);
-  delete k;
-}
+void kde2d_free(gpmi_kde2d* k) { delete k; }
 
 namespace {
 
@@ -262,16 +257,12 @@ int gpmi_kde2d_create(gpmi_ctx* c, int64_t n, const double* x, const double* y, 
     }
     k->hbox[tl] = bx;
   }
-  hipError_t e = hipMalloc(&k->s, sizeof(d2_t) * n);
-  if (e == hipSuccess) e = hipMalloc(&k->perm, sizeof(int) * n);
-  if (e == hipSuccess) e = hipMalloc(&k->box, sizeof(d4_t) * ntiles);
-  if (e == hipSuccess) e = hipMemcpy(k->s, s.data(), sizeof(d2_t) * n, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(k->perm, perm.data(), sizeof(int) * n, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(k->box, k->hbox.data(), sizeof(d4_t) * ntiles, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    c->err = std::string("gpmi_kde2d_create: ") + hipGetErrorString(e);
-    kde2d_free(k);
-    return e == hipErrorOutOfMemory ? GPMI_ERR_NOMEM : GPMI_ERR_HIP;
+  int rc = kde_upload(c, k->s, s.data(), n, "gpmi_kde2d_create");
+  if (!rc) rc = kde_upload(c, k->perm, perm.data(), n, "gpmi_kde2d_create");
+  if (!rc) rc = kde_upload(c, k->box, k->hbox.data(), ntiles, "gpmi_kde2d_create");
+  if (rc) {
+    delete k;
+    return rc;
   }
   st->live2d.push_back(k);
   *out = k;
@@ -304,17 +295,17 @@ int gpmi_kde2d_eval(gpmi_ctx* c, gpmi_kde2d* k, int64_t m, const double* a, cons
   const int64_t mb = std::min(m, K2_BATCH);
   const size_t in_bytes = kde_align256(16 * (size_t)mb), out_bytes = kde_align256(8 * (size_t)mb);
   const size_t part_bytes = kde_align256(8 * (size_t)K2_MAXSPLIT * mb);
-  if (int rc = kde_grow_pinned(c, st, in_bytes + out_bytes)) return rc;
-  if (int rc = kde_grow_device(c, reinterpret_cast<void**>(&st->d_in), &st->d_in_bytes, in_bytes)) return rc;
-  if (int rc = kde_grow_device(c, reinterpret_cast<void**>(&st->d_work), &st->d_work_bytes, part_bytes + out_bytes)) return rc;
-  d2_t* hp = reinterpret_cast<d2_t*>(st->h_stage);
+  if (int rc = st->reserve_pinned(c, in_bytes + out_bytes)) return rc;
+  if (int rc = st->reserve_in(c, in_bytes)) return rc;
+  if (int rc = st->reserve_work(c, part_bytes + out_bytes)) return rc;
+  d2_t* hp = reinterpret_cast<d2_t*>(st->h_stage.get());
   char* hout = st->h_stage + in_bytes;
-  double* d_out = reinterpret_cast<double*>(reinterpret_cast<char*>(st->d_work) + part_bytes);
+  double* d_out = reinterpret_cast<double*>(st->d_work + part_bytes);
   for (int64_t i0 = 0; i0 < m; i0 += K2_BATCH) {
     const int64_t mm = std::min(K2_BATCH, m - i0);
     for (int64_t i = 0; i < mm; ++i) hp[i] = d2_t{a[i0 + i], b[i0 + i]};
     HIPCHK(c, hipMemcpyAsync(st->d_in, hp, 16 * (size_t)mm, hipMemcpyHostToDevice, st->stream));
-    if (int rc = enqueue_direct(c, st, k, reinterpret_cast<const d2_t*>(st->d_in), mm, qx, qy, st->d_work, d_out)) return rc;
+    if (int rc = enqueue_direct(c, st, k, reinterpret_cast<const d2_t*>(st->d_in.get()), mm, qx, qy, st->work(), d_out)) return rc;
     HIPCHK(c, hipMemcpyAsync(hout, d_out, 8 * (size_t)mm, hipMemcpyDeviceToHost, st->stream));
     HIPCHK(c, hipStreamSynchronize(st->stream));
     std::memcpy(sum + i0, hout, 8 * (size_t)mm);
@@ -335,13 +326,13 @@ int gpmi_kde2d_self(gpmi_ctx* c, gpmi_kde2d* k, double qx, double qy, double* su
   const int64_t per = (ntiles + nsplit - 1) / nsplit * K2_TILE;
   const int64_t nsp = (n + per - 1) / per;
   const size_t part_bytes = kde_align256(8 * (size_t)nsp * n), out_bytes = kde_align256(8 * (size_t)n);
-  if (int rc = kde_grow_pinned(c, st, out_bytes)) return rc;
-  if (int rc = kde_grow_device(c, reinterpret_cast<void**>(&st->d_work), &st->d_work_bytes, part_bytes + out_bytes)) return rc;
-  double* d_out = reinterpret_cast<double*>(reinterpret_cast<char*>(st->d_work) + part_bytes);
+  if (int rc = st->reserve_pinned(c, out_bytes)) return rc;
+  if (int rc = st->reserve_work(c, part_bytes + out_bytes)) return rc;
+  double* d_out = reinterpret_cast<double*>(st->d_work + part_bytes);
   hipLaunchKernelGGL(kde2d_partial<true>, dim3((unsigned)ntiles, (unsigned)nsp), dim3(256), 0, st->stream, k->s, n, k->s, n,
-                     per, k->box, qx, qy, st->d_work);
+                     per, k->box, qx, qy, st->work());
   HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(kde2d_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st->stream, st->d_work, n, (int)nsp,
+  hipLaunchKernelGGL(kde2d_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st->stream, st->work(), n, (int)nsp,
                      k->perm, d_out);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(st->h_stage, d_out, 8 * (size_t)n, hipMemcpyDeviceToHost, st->stream));
@@ -380,18 +371,18 @@ int gpmi_kde2d_grid(gpmi_ctx* c, gpmi_kde2d* k, int64_t gx, const double* xa, in
   ARGCHK(c, nsp <= 65535, "gpmi_kde2d_grid: too many ranges");
   const size_t o_y = kde_align256(8 * (size_t)gx), in_bytes = kde_align256(o_y + 8 * (size_t)gy);
   const size_t part_bytes = kde_align256(8 * (size_t)nsp * cells), out_bytes = kde_align256(8 * (size_t)cells);
-  if (int rc = kde_grow_pinned(c, st, in_bytes + out_bytes)) return rc;
-  if (int rc = kde_grow_device(c, reinterpret_cast<void**>(&st->d_in), &st->d_in_bytes, in_bytes)) return rc;
-  if (int rc = kde_grow_device(c, reinterpret_cast<void**>(&st->d_work), &st->d_work_bytes, part_bytes + out_bytes)) return rc;
+  if (int rc = st->reserve_pinned(c, in_bytes + out_bytes)) return rc;
+  if (int rc = st->reserve_in(c, in_bytes)) return rc;
+  if (int rc = st->reserve_work(c, part_bytes + out_bytes)) return rc;
   std::memcpy(st->h_stage, xa, 8 * (size_t)gx);
   std::memcpy(st->h_stage + o_y, ya, 8 * (size_t)gy);
   HIPCHK(c, hipMemcpyAsync(st->d_in, st->h_stage, in_bytes, hipMemcpyHostToDevice, st->stream));
-  double* d_out = reinterpret_cast<double*>(reinterpret_cast<char*>(st->d_work) + part_bytes);
+  double* d_out = reinterpret_cast<double*>(st->d_work + part_bytes);
   hipLaunchKernelGGL(kde2d_grid_partial, dim3((unsigned)bxn, (unsigned)byn, (unsigned)nsp), dim3(256), 0, st->stream, k->s, n,
-                     per, reinterpret_cast<const double*>(st->d_in), (int)gx, reinterpret_cast<const double*>(st->d_in + o_y),
-                     (int)gy, qx, qy, st->d_work);
+                     per, reinterpret_cast<const double*>(st->d_in.get()), (int)gx, reinterpret_cast<const double*>(st->d_in + o_y),
+                     (int)gy, qx, qy, st->work());
   HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(kde2d_finish, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st->stream, st->d_work, cells, (int)nsp,
+  hipLaunchKernelGGL(kde2d_finish, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st->stream, st->work(), cells, (int)nsp,
                      nullptr, d_out);
   HIPCHK(c, hipGetLastError());
   char* hout = st->h_stage + in_bytes;

@@ -16,20 +16,34 @@ struct KdeState {
   std::vector<gpmi_kde*> live;
   std::vector<gpmi_kde2d*> live2d;
   std::vector<gpmi_unimodal*> live_uni;
-  char* h_stage = nullptr;  // pinned staging of inputs and outputs
-  size_t h_bytes = 0;
-  char* d_in = nullptr;     // device copy of the staged inputs
-  size_t d_in_bytes = 0;
-  double* d_work = nullptr; // partials / outputs
-  size_t d_work_bytes = 0;
+  PinBuf<char> h_stage;  // pinned staging of inputs and outputs
+  DevBuf<char> d_in;     // device copy of the staged inputs
+  DevBuf<char> d_work;   // partials / outputs
+  double* work() const { return reinterpret_cast<double*>(d_work.get()); }
+  // at least `bytes` of each, 64 KiB to begin with
+  static int64_t floor64k(size_t bytes) { return (int64_t)std::max(bytes, (size_t)1 << 16); }
+  int reserve_pinned(gpmi_ctx* c, size_t bytes) { return h_stage.reserve(c, floor64k(bytes), hipHostMallocPortable); }
+  int reserve_in(gpmi_ctx* c, size_t bytes) { return d_in.reserve(c, floor64k(bytes)); }
+  int reserve_work(gpmi_ctx* c, size_t bytes) { return d_work.reserve(c, floor64k(bytes)); }
 };
 
 // kde.hip
 int kde_state(gpmi_ctx* c, KdeState*& st);  // the handle's state, created (with its stream) on first use
-int kde_grow_pinned(gpmi_ctx* c, KdeState* st, size_t bytes);
-int kde_grow_device(gpmi_ctx* c, void** ptr, size_t* have, size_t bytes);
+// buf <- the n elements at `host`, for a new object of the entry point `who` (which the error text names)
+template <class T>
+int kde_upload(gpmi_ctx* c, DevBuf<T>& buf, const T* host, int64_t n, const char* who) {
+  int rc = buf.alloc(c, n);
+  if (!rc) {
+    const hipError_t e = hipMemcpy(buf, host, sizeof(T) * (size_t)n, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      c->err = hipGetErrorString(e);
+      rc = GPMI_ERR_HIP;
+    }
+  }
+  if (rc) c->err = std::string(who) + ": " + c->err;
+  return rc;
+}
 inline size_t kde_align256(size_t b) { return (b + 255) & ~(size_t)255; }
-// kde2d.hip
+// kde2d.hip, unimodal.hip: delete the object (its type is complete only there)
 void kde2d_free(gpmi_kde2d* k);
-// unimodal.hip
 void unimodal_free(gpmi_unimodal* k);

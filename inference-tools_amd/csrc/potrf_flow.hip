@@ -1081,12 +1081,7 @@ bool potrf_flow_enabled(gpmi_ctx* c, Lane& lane, int m) {
 }
 
 void potrf_flow_free(Lane& lane) {
-  if (lane.flow_tasks) (void)hipFree(lane.flow_tasks);
-  if (lane.flow_off) (void)hipFree(lane.flow_off);
-  if (lane.flow_flags) (void)hipFree(lane.flow_flags);
-  lane.flow_tasks = nullptr;
-  lane.flow_off = nullptr;
-  lane.flow_flags = nullptr;
+  static_cast<LaneFlowBufs&>(lane) = LaneFlowBufs();
   lane.flow_m = 0;
   lane.flow_nwg = 0;
 }
@@ -1111,9 +1106,9 @@ bool potrf_flow_tail(gpmi_ctx* c, Lane& lane, double* A, int64_t ld, double* inv
     FlowLists fl = flow_build(m, nwg);
     flow_lists_override(m, nwg, fl);
     const size_t total = fl.tasks.size();
-    if (hipMalloc(&lane.flow_tasks, sizeof(FlowTask) * (total ? total : 1)) != hipSuccess ||
-        hipMalloc(&lane.flow_off, sizeof(int) * fl.off.size()) != hipSuccess ||
-        hipMalloc(&lane.flow_flags, sizeof(int) * flow_flag_ints(m, (int)fl.off.size() - 1)) != hipSuccess ||
+    if (lane.flow_tasks.alloc(nullptr, sizeof(FlowTask) * (total ? total : 1)) != GPMI_OK ||
+        lane.flow_off.alloc(nullptr, fl.off.size()) != GPMI_OK ||
+        lane.flow_flags.alloc(nullptr, flow_flag_ints(m, (int)fl.off.size() - 1)) != GPMI_OK ||
         (total && hipMemcpy(lane.flow_tasks, fl.tasks.data(), sizeof(FlowTask) * total, hipMemcpyHostToDevice) !=
                       hipSuccess) ||
         hipMemcpy(lane.flow_off, fl.off.data(), sizeof(int) * fl.off.size(), hipMemcpyHostToDevice) != hipSuccess) {
@@ -1143,7 +1138,7 @@ bool potrf_flow_tail(gpmi_ctx* c, Lane& lane, double* A, int64_t ld, double* inv
   fa.invD = invD0;
   fa.ld = ld;
   fa.m = m;
-  fa.tasks = static_cast<const FlowTask*>(lane.flow_tasks);
+  fa.tasks = reinterpret_cast<const FlowTask*>(lane.flow_tasks.get());
   fa.off = lane.flow_off;
   fa.nlists = nlists;
   fa.flags = fl;
@@ -1155,8 +1150,8 @@ bool potrf_flow_tail(gpmi_ctx* c, Lane& lane, double* A, int64_t ld, double* inv
   static const char* trace_path = std::getenv("GPMI_FLOW_TRACE");
   const int64_t ntasks = lane.flow_ntasks;
   const int64_t trace_words = 4 * ntasks + (int64_t)m * (GPMI_STAMP_WORDS + 4);
-  unsigned long long* trace = nullptr;
-  if (trace_path && hipMalloc(&trace, sizeof(unsigned long long) * trace_words) == hipSuccess)
+  DevBuf<unsigned long long> trace;
+  if (trace_path && trace.alloc(nullptr, trace_words) == GPMI_OK)
     (void)hipMemsetAsync(trace, 0, sizeof(unsigned long long) * trace_words, sf);
   fa.trace = trace;
   unsigned long long* ctrace = trace ? trace + 4 * ntasks : nullptr;  // per column: potrf_diag's 24 words, Tc 2, Uc 2
@@ -1272,7 +1267,7 @@ bool potrf_flow_tail(gpmi_ctx* c, Lane& lane, double* A, int64_t ld, double* inv
     (void)hipMemcpy(h.data(), trace, sizeof(unsigned long long) * trace_words, hipMemcpyDeviceToHost);
     (void)hipMemcpy(ht.data(), lane.flow_tasks, sizeof(FlowTask) * ntasks, hipMemcpyDeviceToHost);
     (void)hipMemcpy(ho.data(), lane.flow_off, sizeof(int) * (nlists + 1), hipMemcpyDeviceToHost);
-    (void)hipFree(trace);
+    trace.release();
     if (FILE* fp = std::fopen(trace_path, "wb")) {
       const int64_t hdr[4] = {m, nlists, ntasks, GPMI_STAMP_WORDS + 4};
       std::fwrite(hdr, sizeof(hdr), 1, fp);

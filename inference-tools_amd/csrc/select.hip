@@ -236,31 +236,35 @@ extern "C" int gpmi_select_points(gpmi_ctx* c, int64_t n, int64_t d, const doubl
   // device memory of the call, released at return
   const int nblocks = select_blocks(n);
   const int mm = (int)m_max;
-  DevBuf bx, bw, bd, bV, bpart, bidx, btr, bpv, bword;
-  HIPCHK(c, hipMalloc(&bV.p, sizeof(double) * (size_t)n * (size_t)m_max));
-  HIPCHK(c, hipMalloc(&bx.p, sizeof(double) * (size_t)n * (size_t)d));
-  if (weight) HIPCHK(c, hipMalloc(&bw.p, sizeof(double) * (size_t)n));
-  HIPCHK(c, hipMalloc(&bd.p, sizeof(double) * (size_t)n));
-  HIPCHK(c, hipMalloc(&bpart.p, sizeof(SelPartial) * 2 * (size_t)nblocks));
-  HIPCHK(c, hipMalloc(&bidx.p, sizeof(int64_t) * (size_t)m_max));
-  HIPCHK(c, hipMalloc(&btr.p, sizeof(double) * (size_t)(m_max + 1)));
-  HIPCHK(c, hipMalloc(&bpv.p, sizeof(double) * (size_t)m_max));
-  HIPCHK(c, hipMalloc(&bword.p, sizeof(int) * 2));
+  DevBuf<double> bx, bw, bd, bV, btr, bpv;
+  DevBuf<SelPartial> bpart;
+  DevBuf<int64_t> bidx;
+  DevBuf<int> bword;
+  if (int rc = bV.alloc(c, n * m_max)) return rc;
+  if (int rc = bx.alloc(c, n * d)) return rc;
+  if (weight)
+    if (int rc = bw.alloc(c, n)) return rc;
+  if (int rc = bd.alloc(c, n)) return rc;
+  if (int rc = bpart.alloc(c, 2 * nblocks)) return rc;
+  if (int rc = bidx.alloc(c, m_max)) return rc;
+  if (int rc = btr.alloc(c, m_max + 1)) return rc;
+  if (int rc = bpv.alloc(c, m_max)) return rc;
+  if (int rc = bword.alloc(c, 2)) return rc;
   HIPCHK(c, hipStreamSynchronize(s));
-  HIPCHK(c, hipMemcpy(bx.p, x, sizeof(double) * (size_t)n * (size_t)d, hipMemcpyHostToDevice));
-  if (weight) HIPCHK(c, hipMemcpy(bw.p, weight, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-  ZERO_SYNC(c, bword.p, sizeof(int) * 2);
+  HIPCHK(c, hipMemcpy(bx, x, sizeof(double) * (size_t)n * (size_t)d, hipMemcpyHostToDevice));
+  if (weight) HIPCHK(c, hipMemcpy(bw, weight, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+  ZERO_SYNC(c, bword, sizeof(int) * 2);
 
   SelState st;
-  st.x = bx.as<double>();
-  st.w = weight ? bw.as<double>() : nullptr;
-  st.dvar = bd.as<double>();
-  st.V = bV.as<double>();
-  st.part = bpart.as<SelPartial>();
-  st.index = bidx.as<int64_t>();
-  st.trace = btr.as<double>();
-  st.pivot_var = bpv.as<double>();
-  st.word = bword.as<int>();
+  st.x = bx;
+  st.w = weight ? bw : nullptr;
+  st.dvar = bd;
+  st.V = bV;
+  st.part = bpart;
+  st.index = bidx;
+  st.trace = btr;
+  st.pivot_var = bpv;
+  st.word = bword;
   st.n = n;
   st.nblocks = nblocks;
   st.m_max = mm;

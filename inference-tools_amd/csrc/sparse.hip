@@ -31,31 +31,28 @@
 struct gpmi_sgp {
   gpmi_ctx* ctx = nullptr;
   int64_t n = 0, d = 0, m = 0, mp = 0, ld = 0;
-  double *x = nullptr, *z = nullptr, *r = nullptr, *nv = nullptr;  // n x d, m x d, n, n
-  double *w = nullptr, *alpha = nullptr;                           // n each: 1 / sigma_i^2, alpha
+  DevBuf<double> x, z, r, nv;  // n x d, m x d, n, n
+  DevBuf<double> w, alpha;     // n each: 1 / sigma_i^2, alpha
   bool have_targets = false;
   // mp x ld work matrices (roles in sgp_factor / sgp_gradient) and the inverse diagonal blocks of the two factors
-  double* M[9] = {};
-  double *invD1 = nullptr, *invD2 = nullptr;
-  double* vec = nullptr;   // 4 x mp: b, L^-1 b, c, gamma
-  double* red = nullptr;   // 128 small results
-  int* info = nullptr;     // 2 words
-  double* part = nullptr;  // SGP_RED_BLOCKS x 4 partial sums over the data
+  DevBuf<double> M[9];
+  DevBuf<double> invD1, invD2;
+  DevBuf<double> vec;   // 4 x mp: b, L^-1 b, c, gamma
+  DevBuf<double> red;   // 128 small results
+  DevBuf<int> info;     // 2 words
+  DevBuf<double> part;  // SGP_RED_BLOCKS x 4 partial sums over the data
   // panels (allocated at first use): three of max(mp (R + 32), R ld) doubles, three vectors of R, the contraction's partials
-  double* P[3] = {};
-  double* pvec = nullptr;
-  double* ws = nullptr;
-  int64_t panel_cap = 0;
+  DevBuf<double> P[3], pvec, ws;
+  int64_t panel_cap = 0;  // rows the five hold
   // the gradient by Z (allocated at first use): the partials per run of data tiles, the mp x d accumulator
-  double *zws = nullptr, *zacc = nullptr;
-  int64_t zws_cap = 0;
+  DevBuf<double> zws, zacc;
   // query staging: 1024 x d points, 2 x 1024 results
-  double *q_pts = nullptr, *q_out = nullptr;
+  DevBuf<double> q_pts, q_out;
   // the derivatives by the query point (allocated at first use): the partials per run of inducing tiles and the two
   // results of a query panel, (mp / 128 + 1) x 2 x 1024 x d doubles
-  double* qws = nullptr;
+  DevBuf<double> qws;
   // the fit: L^-1, L_B^-1 (mp x ld), c and gamma = L^-T L_B^-T c (mp each), the kernel
-  double *fLinv = nullptr, *fLBinv = nullptr, *fc = nullptr, *fgamma = nullptr;
+  DevBuf<double> fLinv, fLBinv, fc, fgamma;
   KParams fp = {};
   bool fitted = false;
 };
@@ -542,16 +539,6 @@ unsigned blocks(int64_t n) { return (unsigned)((n + SGP_NT - 1) / SGP_NT); }
 // workgroups of sgp_weights_kernel: one element per thread up to SGP_RED_BLOCKS workgroups, a grid-stride loop beyond
 unsigned weights_blocks(int64_t n) { return (unsigned)std::min<int64_t>(SGP_RED_BLOCKS, (n + SGP_NT - 1) / SGP_NT); }
 
-void sgp_free(gpmi_sgp* g) {
-  for (double* q : {g->x, g->z, g->r, g->nv, g->w, g->alpha, g->invD1, g->invD2, g->vec, g->red, g->part, g->pvec, g->ws, g->zws, g->zacc,
-                    g->q_pts, g->q_out, g->qws, g->fLinv, g->fLBinv, g->fc, g->fgamma, g->P[0], g->P[1], g->P[2]})
-    if (q) (void)hipFree(q);
-  for (double* q : g->M)
-    if (q) (void)hipFree(q);
-  if (g->info) (void)hipFree(g->info);
-  delete g;
-}
-
 // the ranges gpmi_sgp_create, sgp_params and gpmi_sgp_schedule share
 bool sgp_n_ok(int64_t n) { return n >= 2 && n <= ((int64_t)1 << 30); }
 bool sgp_m_ok(int64_t m) { return m >= 1 && m <= GPMI_SGP_MAX_M; }
@@ -597,16 +584,14 @@ int64_t sgp_panel_rows(const gpmi_sgp* g, int64_t panel_rows) { return sgp_panel
 int sgp_ensure_panels(gpmi_sgp* g, int64_t R) {
   gpmi_ctx* c = g->ctx;
   if (R <= g->panel_cap) return GPMI_OK;
-  for (double** q : {&g->P[0], &g->P[1], &g->P[2], &g->pvec, &g->ws}) {
-    if (*q) (void)hipFree(*q);
-    *q = nullptr;
-  }
   g->panel_cap = 0;
+  for (DevBuf<double>* q : {&g->P[0], &g->P[1], &g->P[2], &g->pvec, &g->ws}) q->release();
   const int64_t each = std::max(g->mp * (R + 32), R * g->ld);
-  for (int k = 0; k < 3; ++k) HIPCHK(c, hipMalloc(&g->P[k], sizeof(double) * each));
-  HIPCHK(c, hipMalloc(&g->pvec, sizeof(double) * 3 * R));
+  for (int k = 0; k < 3; ++k)
+    if (int rc = g->P[k].alloc(c, each)) return rc;
+  if (int rc = g->pvec.alloc(c, 3 * R)) return rc;
   const int64_t tiles = (std::max(R, g->mp) / KT) * (g->mp / KT);
-  HIPCHK(c, hipMalloc(&g->ws, sizeof(double) * tiles * (GPMI_MAX_D + 2)));
+  if (int rc = g->ws.alloc(c, tiles * (GPMI_MAX_D + 2))) return rc;
   g->panel_cap = R;
   return GPMI_OK;
 }
@@ -614,15 +599,9 @@ int sgp_ensure_panels(gpmi_sgp* g, int64_t R) {
 // the workspace of the Z pass for panels of R rows
 int sgp_ensure_zws(gpmi_sgp* g, int64_t R) {
   gpmi_ctx* c = g->ctx;
-  if (!g->zacc) HIPCHK(c, hipMalloc(&g->zacc, sizeof(double) * g->mp * g->d));
-  const int64_t need = (int64_t)std::max(zruns(R, g->mp), zruns(g->mp, g->mp)) * g->mp * g->d;
-  if (need <= g->zws_cap) return GPMI_OK;
-  if (g->zws) (void)hipFree(g->zws);
-  g->zws = nullptr;
-  g->zws_cap = 0;
-  HIPCHK(c, hipMalloc(&g->zws, sizeof(double) * need));
-  g->zws_cap = need;
-  return GPMI_OK;
+  if (!g->zacc)
+    if (int rc = g->zacc.alloc(c, g->mp * g->d)) return rc;
+  return g->zws.reserve(c, (int64_t)std::max(zruns(R, g->mp), zruns(g->mp, g->mp)) * g->mp * g->d);
 }
 
 // names of the work matrices: G, A (K_mm -> L; later T), LiT (L^-T), Linv, W1 (L^-1 G; later L^-T L_B^-T), W2 (H; later S,
@@ -883,17 +862,16 @@ void sgp_query_panel(gpmi_sgp* g, hipStream_t s, const double* pts_dev, int64_t 
 // for, Sigma (mpq x ldq).  (An error return may leave work on these in flight: hipFree waits for the device before it
 // releases.)
 struct PosteriorBufs {
-  DevBuf P, VU, mu, Sigma;
+  DevBuf<double> P, VU, mu, Sigma;
   int64_t mpq = 0, ldq = 0;
   int alloc(gpmi_sgp* g, int64_t mq, bool want_sigma) {
     gpmi_ctx* c = g->ctx;
     mpq = round_up(mq, GPMI_NB);
     ldq = mpq + 32;
-    HIPCHK(c, hipMalloc(&P.p, sizeof(double) * mpq * g->d));
-    HIPCHK(c, hipMalloc(&VU.p, sizeof(double) * 2 * mpq * g->ld));
-    HIPCHK(c, hipMalloc(&mu.p, sizeof(double) * mpq));
-    if (want_sigma) HIPCHK(c, hipMalloc(&Sigma.p, sizeof(double) * mpq * ldq));
-    return GPMI_OK;
+    if (int rc = P.alloc(c, mpq * g->d)) return rc;
+    if (int rc = VU.alloc(c, 2 * mpq * g->ld)) return rc;
+    if (int rc = mu.alloc(c, mpq)) return rc;
+    return want_sigma ? Sigma.alloc(c, mpq * ldq) : GPMI_OK;
   }
 };
 
@@ -904,10 +882,10 @@ int sgp_posterior_sigma(gpmi_sgp* g, const double* pts, int64_t mq, PosteriorBuf
   hipStream_t s = c->sgp_stream;
   const int64_t mp = g->mp, ld = g->ld, mpq = b.mpq, ldq = b.ldq;
   const int ntq = (int)(mpq / GPMI_NB);
-  double *pts_dev = b.P.as<double>(), *V = b.VU.as<double>(), *U = V + mpq * ld, *Sigma = b.Sigma.as<double>();
+  double *pts_dev = b.P, *V = b.VU, *U = V + mpq * ld, *Sigma = b.Sigma;
   HIPCHK(c, hipMemcpyAsync(pts_dev, pts, sizeof(double) * mq * g->d, hipMemcpyHostToDevice, s));
   sgp_query_panel(g, s, pts_dev, mq, mpq, U, V, U);  // (K_qm in the place U takes)
-  launch_rows_dot(s, U, ld, mpq, mp, g->fc, b.mu.as<double>());
+  launch_rows_dot(s, U, ld, mpq, mp, g->fc, b.mu);
   if (Sigma) {
     // Sigma = K_qq - V V^T + U U^T on the lower tiles; the product only subtracts, so the sign is turned in between
     launch_kbuild_cross(s, g->fp, pts_dev, mq, mpq, pts_dev, mq, mpq, Sigma, ldq);
@@ -924,7 +902,7 @@ int sgp_posterior_sigma(gpmi_sgp* g, const double* pts, int64_t mq, PosteriorBuf
 
 void sgp_release_all(gpmi_ctx* c) {
   if (c->sgp_stream) (void)hipStreamSynchronize(c->sgp_stream);
-  for (gpmi_sgp* g : c->sgp_live) sgp_free(g);
+  for (gpmi_sgp* g : c->sgp_live) delete g;
   c->sgp_live.clear();
   if (c->sgp_stream) (void)hipStreamDestroy(c->sgp_stream);
   c->sgp_stream = nullptr;
@@ -962,27 +940,31 @@ int gpmi_sgp_create(gpmi_ctx* c, int64_t n, int64_t d, const double* x, int64_t 
   g->mp = round_up(m, GPMI_NB);
   g->ld = g->mp + 32;  // rows 256-byte aligned, off a power-of-two pitch
   const int64_t mp = g->mp, ld = g->ld, nd = mp / GPMI_NB * GPMI_NB * GPMI_NB;
-  auto alloc = [&](auto& ptr, size_t bytes) { return hipMalloc(reinterpret_cast<void**>(&ptr), bytes); };
-  hipError_t e = alloc(g->x, sizeof(double) * n * d);
-  if (e == hipSuccess) e = alloc(g->z, sizeof(double) * mp * d);
-  for (double** q : {&g->r, &g->nv, &g->w, &g->alpha})
-    if (e == hipSuccess) e = alloc(*q, sizeof(double) * n);
-  for (double*& q : g->M)
-    if (e == hipSuccess) e = alloc(q, sizeof(double) * mp * ld);
-  for (double** q : {&g->fLinv, &g->fLBinv})
-    if (e == hipSuccess) e = alloc(*q, sizeof(double) * mp * ld);
-  if (e == hipSuccess) e = alloc(g->fc, sizeof(double) * mp);
-  if (e == hipSuccess) e = alloc(g->fgamma, sizeof(double) * mp);
-  if (e == hipSuccess) e = alloc(g->invD1, sizeof(double) * nd);
-  if (e == hipSuccess) e = alloc(g->invD2, sizeof(double) * nd);
-  if (e == hipSuccess) e = alloc(g->vec, sizeof(double) * 4 * mp);
-  if (e == hipSuccess) e = alloc(g->red, sizeof(double) * 128);
-  if (e == hipSuccess) e = alloc(g->info, sizeof(int) * 2);
-  if (e == hipSuccess) e = alloc(g->part, sizeof(double) * SGP_RED_BLOCKS * 4);
-  if (e == hipSuccess) e = alloc(g->q_pts, sizeof(double) * SGP_QPANEL * d);
-  if (e == hipSuccess) e = alloc(g->q_out, sizeof(double) * 2 * SGP_QPANEL);
+  int rc = g->x.alloc(c, n * d);
+  if (!rc) rc = g->z.alloc(c, mp * d);
+  for (DevBuf<double>* q : {&g->r, &g->nv, &g->w, &g->alpha})
+    if (!rc) rc = q->alloc(c, n);
+  for (DevBuf<double>& q : g->M)
+    if (!rc) rc = q.alloc(c, mp * ld);
+  for (DevBuf<double>* q : {&g->fLinv, &g->fLBinv})
+    if (!rc) rc = q->alloc(c, mp * ld);
+  if (!rc) rc = g->fc.alloc(c, mp);
+  if (!rc) rc = g->fgamma.alloc(c, mp);
+  if (!rc) rc = g->invD1.alloc(c, nd);
+  if (!rc) rc = g->invD2.alloc(c, nd);
+  if (!rc) rc = g->vec.alloc(c, 4 * mp);
+  if (!rc) rc = g->red.alloc(c, 128);
+  if (!rc) rc = g->info.alloc(c, 2);
+  if (!rc) rc = g->part.alloc(c, SGP_RED_BLOCKS * 4);
+  if (!rc) rc = g->q_pts.alloc(c, SGP_QPANEL * d);
+  if (!rc) rc = g->q_out.alloc(c, 2 * SGP_QPANEL);
+  if (rc) {
+    c->err = "gpmi_sgp_create: " + c->err;
+    delete g;
+    return rc;
+  }
   // potrf_diag writes the block-lower part of an inverse only: the zeros above stay from here (api.hip: lane_alloc, ZERO_SYNC)
-  if (e == hipSuccess) e = hipMemset(g->invD1, 0, sizeof(double) * nd);
+  hipError_t e = hipMemset(g->invD1, 0, sizeof(double) * nd);
   if (e == hipSuccess) e = hipMemset(g->invD2, 0, sizeof(double) * nd);
   if (e == hipSuccess) e = hipMemset(g->z, 0, sizeof(double) * mp * d);
   if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
@@ -990,7 +972,7 @@ int gpmi_sgp_create(gpmi_ctx* c, int64_t n, int64_t d, const double* x, int64_t 
   if (e == hipSuccess) e = hipMemcpy(g->z, z, sizeof(double) * m * d, hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     c->err = std::string("gpmi_sgp_create: ") + hipGetErrorString(e);
-    sgp_free(g);
+    delete g;
     return e == hipErrorOutOfMemory ? GPMI_ERR_NOMEM : GPMI_ERR_HIP;
   }
   c->sgp_live.push_back(g);
@@ -1006,7 +988,7 @@ int gpmi_sgp_destroy(gpmi_sgp* g) {
   if (int rc = set_device(c)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->sgp_stream));
   c->sgp_live.erase(it);
-  sgp_free(g);
+  delete g;
   return GPMI_OK;
 }
 
@@ -1116,7 +1098,8 @@ int gpmi_sgp_spatial_derivatives(gpmi_sgp* g, const double* pts, int64_t mq, dou
   if (int rc = sgp_ensure_panels(g, SGP_QPANEL)) return rc;
   const int64_t m = g->m, mp = g->mp, ld = g->ld, d = g->d;
   const int64_t per = (int64_t)SGP_QPANEL * d;  // one result, or one run's partials, of a panel
-  if (!g->qws) HIPCHK(c, hipMalloc(&g->qws, sizeof(double) * 2 * (qruns(mp) + 1) * per));
+  if (!g->qws)
+    if (int rc = g->qws.alloc(c, 2 * (qruns(mp) + 1) * per)) return rc;
   double *ws_mean = g->qws, *ws_var = ws_mean + qruns(mp) * per, *out_mean = ws_var + qruns(mp) * per, *out_var = out_mean + per;
   hipStream_t s = c->sgp_stream;
   const int nt = (int)(mp / GPMI_NB);
@@ -1165,10 +1148,10 @@ int gpmi_sgp_posterior(gpmi_sgp* g, const double* pts, int64_t mq, double* mean,
   int rc = sgp_posterior_sigma(g, pts, mq, b);
   hipError_t e = hipSuccess;
   if (rc == GPMI_OK) {
-    e = hipMemcpyAsync(mean, b.mu.p, sizeof(double) * mq, hipMemcpyDeviceToHost, s);
+    e = hipMemcpyAsync(mean, b.mu, sizeof(double) * mq, hipMemcpyDeviceToHost, s);
     if (cov && e == hipSuccess) {
-      launch_mirror_lower(s, b.Sigma.as<double>(), b.ldq, b.mpq);
-      e = hipMemcpy2DAsync(cov, sizeof(double) * mq, b.Sigma.p, sizeof(double) * b.ldq, sizeof(double) * mq, (size_t)mq,
+      launch_mirror_lower(s, b.Sigma, b.ldq, b.mpq);
+      e = hipMemcpy2DAsync(cov, sizeof(double) * mq, b.Sigma, sizeof(double) * b.ldq, sizeof(double) * mq, (size_t)mq,
                            hipMemcpyDeviceToHost, s);
     }
   }
@@ -1206,11 +1189,11 @@ int gpmi_sgp_posterior_draws(gpmi_sgp* g, const double* pts, int64_t mq, double 
     rc = sgp_posterior_sigma(g, pts, mq, b);
   }
   hipError_t e = hipSuccess;
-  if (rc == GPMI_OK && mean) e = hipMemcpyAsync(mean, b.mu.p, sizeof(double) * mq, hipMemcpyDeviceToHost, c->sgp_stream);
+  if (rc == GPMI_OK && mean) e = hipMemcpyAsync(mean, b.mu, sizeof(double) * mq, hipMemcpyDeviceToHost, c->sgp_stream);
   // the tail runs on the lane's stream: Sigma and mu are complete before it reads them
   const hipError_t e1 = hipStreamSynchronize(c->sgp_stream);
   if (rc == GPMI_OK && e == hipSuccess && e1 == hipSuccess)
-    rc = draws_tail(c, L, b.Sigma.as<double>(), ldq, mq, mpq, b.mu.as<double>(), jitter_rel, n_draws, z_host, seed, first_draw,
+    rc = draws_tail(c, L, b.Sigma, ldq, mq, mpq, b.mu, jitter_rel, n_draws, z_host, seed, first_draw,
                     draws_host, eps_host, info);
   const hipError_t e2 = hipStreamSynchronize(L.stream);  // (before Sigma is released, whatever the tail returned)
   if (rc != GPMI_OK) return rc;

@@ -86,13 +86,10 @@ bool unimodal_live(gpmi_unimodal* k, gpmi_ctx* c) {
 struct gpmi_unimodal {
   gpmi_ctx* ctx = nullptr;
   int64_t n = 0;
-  double* s = nullptr;
+  DevBuf<double> s;
 };
 
-void unimodal_free(gpmi_unimodal* k) {
-  if (k->s) (void)hipFree(k->s);
-  delete k;
-}
+void unimodal_free(gpmi_unimodal* k) { delete k; }
 
 extern "C" {
 
@@ -108,12 +105,9 @@ int gpmi_unimodal_create(gpmi_ctx* c, int64_t n, const double* sample, gpmi_unim
   gpmi_unimodal* k = new gpmi_unimodal();
   k->ctx = c;
   k->n = n;
-  hipError_t e = hipMalloc(&k->s, sizeof(double) * n);
-  if (e == hipSuccess) e = hipMemcpy(k->s, sample, sizeof(double) * n, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    c->err = std::string("gpmi_unimodal_create: ") + hipGetErrorString(e);
-    unimodal_free(k);
-    return e == hipErrorOutOfMemory ? GPMI_ERR_NOMEM : GPMI_ERR_HIP;
+  if (int rc = kde_upload(c, k->s, sample, n, "gpmi_unimodal_create")) {
+    delete k;
+    return rc;
   }
   st->live_uni.push_back(k);
   *out = k;
@@ -146,10 +140,10 @@ int gpmi_unimodal_logpdf_sums(gpmi_ctx* c, gpmi_unimodal* k, int64_t stride, int
   const int64_t nchunks = (n_fit + 256 * (int64_t)ipt - 1) / (256 * (int64_t)ipt);
   const int per = (int)((nchunks + 255) / 256);
   const size_t part_bytes = kde_align256(8 * (size_t)nchunks * UNI_ARGS), out_bytes = kde_align256(8 * (size_t)n_theta);
-  if (int rc = kde_grow_pinned(c, st, out_bytes)) return rc;
-  if (int rc = kde_grow_device(c, reinterpret_cast<void**>(&st->d_work), &st->d_work_bytes, part_bytes + out_bytes)) return rc;
-  double* d_part = st->d_work;
-  double* d_out = reinterpret_cast<double*>(reinterpret_cast<char*>(st->d_work) + part_bytes);
+  if (int rc = st->reserve_pinned(c, out_bytes)) return rc;
+  if (int rc = st->reserve_work(c, part_bytes + out_bytes)) return rc;
+  double* d_part = st->work();
+  double* d_out = reinterpret_cast<double*>(st->d_work + part_bytes);
   UniTheta th;
   std::memset(&th, 0, sizeof(th));
   for (int t0 = 0; t0 < n_theta; t0 += UNI_ARGS) {

@@ -60,6 +60,7 @@ SIGNATURES = {
     "gpmi_destroy": (C.c_int, [_vp]),
     "gpmi_last_error": (C.c_char_p, [_vp]),
     "gpmi_sync": (C.c_int, [_vp]),
+    "gpmi_live_bytes": (C.c_int, [C.POINTER(_i64)]),
     "gpmi_set_data": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _i64, _i64]),
     "gpmi_fit": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _ip]),
     "gpmi_lml": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double, _dp, _dp, _ip]),

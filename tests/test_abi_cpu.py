@@ -20,7 +20,7 @@ def declared_symbols():
 def test_header_declares_the_path():
     syms = declared_symbols()
     for must in ("gpmi_set_data", "gpmi_fit", "gpmi_lml", "gpmi_lml_batch", "gpmi_lml_grad", "gpmi_predict",
-                 "gpmi_sgp_schedule", "gpmi_select_schedule"):
+                 "gpmi_sgp_schedule", "gpmi_select_schedule", "gpmi_live_bytes"):
         assert must in syms
 
 
@@ -73,6 +73,18 @@ def test_ctypes_table_matches_header():
 
     assert sorted(_lib.SIGNATURES) == declared_symbols()
     _lib.load()
+
+
+def test_live_bytes_without_a_device():
+    """gpmi_live_bytes takes no handle and makes no HIP call: without a device nothing can have been allocated and both
+    totals are zero (with one, other tests of the session may hold handles: not negative)."""
+    from inference_amd import _lib
+
+    lib = _lib.load()
+    out = (ctypes.c_int64 * 2)(-7, -7)
+    assert lib.gpmi_live_bytes(out) == 0
+    assert list(out) == [0, 0] if _lib.device_count() == 0 else min(out) >= 0
+    assert lib.gpmi_live_bytes(None) == -1  # GPMI_ERR_ARG
 
 
 def test_no_silent_cpu_path():
