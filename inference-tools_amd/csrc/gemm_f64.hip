@@ -49,7 +49,6 @@ struct GemmArgs {
   // full 128 x 128 tiles, see launch_gemm_nt_split).  split == 0: the launch covers the tiles [tile_base, tile_base +
   // gridDim.x) of the logical tile list (launch_gemm_nt_range; 0 for whole products)
   int split, tile_base;
-  FlowHook hook;  // potrf_flow.hip: flags published / awaited at the start of a chain launch
   // > 0 (lockstep batches of a multiple of 8 problems): a one-dimensional launch of 8 x zlocal_tiles x (batch / 8)
   // workgroups in which problem z runs entirely on XCD z % 8 (workgroup n -> XCD n % 8), its zlocal_tiles tiles in their
   // logical order: a problem's operand panels are fetched into ONE L2 instead of all eight
@@ -131,7 +130,6 @@ __device__ inline void tile_of(int id, int ntr, int ntc, int& ti, int& tj) {
 template <int TILES, int OP, int BKN, int BM, int BN>
 __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
   __shared__ double smem[staged_lds_doubles<BKN, BM, BN>()];  // [buffer][A | B]
-  flow_hook_enter(g.hook);
   int ti, tj;
   // k-skipped launches have tiles of very different length (128 (ntr - ti) k-steps): deal them out
   // round-robin over the XCDs instead of in contiguous chunks, or the XCD holding the long tiles ends last
@@ -176,7 +174,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
   double* Cg = g.C + bz * g.sC + (int64_t)ti * BM * g.ldc + (int64_t)tj * BN;
   if constexpr (OP == OP_ASSIGN && BKN == 0 && BN == 128 && BM <= 64) {
     if (g.kskip == 3) {
-      staged_tile<OP, BKN, BM, BN, CST_NT, LD_PLAIN, true>(Ag, Bg, Cg, g.lda, g.ldb, g.ldc, (kend - kbeg) / BK, smem);
+      staged_tile<OP, BKN, BM, BN, CST_NT, true>(Ag, Bg, Cg, g.lda, g.ldb, g.ldc, (kend - kbeg) / BK, smem);
     } else {
       staged_tile<OP, BKN, BM, BN>(Ag, Bg, Cg, g.lda, g.ldb, g.ldc, (kend - kbeg) / BK, smem);
     }
@@ -222,7 +220,6 @@ __device__ __attribute__((noinline)) void dma64_quarter(const gemm_glb_double_t*
 template <int TILES, int OP>
 __global__ __launch_bounds__(256, GPMI_DMA_WGS) void gemm_dma_kernel(GemmArgs g) {
   __shared__ double smem[DMA128_LDS_DOUBLES];
-  flow_hook_enter(g.hook);
   int ti, tj;
   if (g.mixed_full > 0 && (int)blockIdx.x >= g.mixed_full) {
     // a quarter of one of the launch's last tiles (dispatched behind every full tile: it runs where the last round frees a CU)
@@ -271,41 +268,9 @@ __global__ __launch_bounds__(256, GPMI_DMA_WGS) void gemm_dma_kernel(GemmArgs g)
                                      ((__builtin_amdgcn_s_memrealtime() - r_start) & 0xffffffffull);
 }
 
-// 256 x 128 tiles (gemm_tiles::dma256_tile), experiment GPMI_GEMM_256=1: whole products with even tile counts only
-template <int TILES, int OP>
-__global__ __launch_bounds__(512, 1) void gemm_dma256_kernel(GemmArgs g) {
-  __shared__ double smem[DMA256_LDS_DOUBLES];
-  int ti, tj;  // ti: 256-row tile, tj: 128-column tile
-  const int id = xcd_remap(blockIdx.x, gridDim.x);
-  const int nr2 = g.ntr >> 1;
-  if (TILES == TILES_RECT) {
-    ti = id / g.ntc;
-    tj = id - ti * g.ntc;
-  } else {
-    const int h = g.ntc >> 1, tri = h * (h + 1);
-    if (id < tri) {
-      int r = (int)((sqrtf(4.0f * id + 1.0f) - 1.0f) * 0.5f);
-      while (r * (r + 1) > id) --r;
-      while ((r + 1) * (r + 2) <= id) ++r;
-      ti = r;
-      tj = id - r * (r + 1);
-    } else {
-      ti = h + (id - tri) / g.ntc;
-      tj = (id - tri) % g.ntc;
-    }
-  }
-  (void)nr2;
-  const int64_t bz = blockIdx.z;
-  const double* __restrict__ Ag = g.A + bz * g.sA + (int64_t)ti * 256 * g.lda;
-  const double* __restrict__ Bg = g.B + bz * g.sB + (int64_t)tj * 128 * g.ldb;
-  double* Cg = g.C + bz * g.sC + (int64_t)ti * 256 * g.ldc + (int64_t)tj * 128;
-  dma256_tile<OP>(Ag, Bg, Cg, g.lda, g.ldb, g.ldc, g.k / DMA_BK, smem, TILES == TILES_LOWER && tj == 2 * ti + 1);
-}
-
 template <int TILES, int OP>
 __global__ __launch_bounds__(256, 4) void gemm_dma64_kernel(GemmArgs g) {
   __shared__ double smem[DMA64_LDS_DOUBLES];
-  flow_hook_enter(g.hook);
   int ti, tj;
   const WgId me = wg_id(g.kskip, g.zlocal_tiles);
   const int wid = me.wid;
@@ -403,7 +368,7 @@ void launch_gemm_part(hipStream_t s, GemmTiles tiles, GemmOp op, bool b_kmajor, 
   // the panel TRSM with the caller's word that B (the inverse of a diagonal block) is lower triangular
   if (bt.b_lower_tri && kskip == 0 && bn == 128 && bm <= 64 && ntc == 1 && k == 128 && !b_kmajor && op == OP_ASSIGN) kskip = 3;
   GemmArgs g{C, A, B, ldc, lda, ldb, ntr * (128 / bm), ntc * (128 / bn), k, kskip, stamp,
-             bt.sC, bt.sA, bt.sB, part == 2 ? 1 : 0, (part == 2 || part == 3) ? (int)nfull : 0, bt.hook, 0, 0};
+             bt.sC, bt.sA, bt.sB, part == 2 ? 1 : 0, (part == 2 || part == 3) ? (int)nfull : 0, 0, 0};
   int64_t nwg;
   if (tiles == TILES_RECT)
     nwg = (int64_t)g.ntr * g.ntc;
@@ -435,20 +400,6 @@ void launch_gemm_part(hipStream_t s, GemmTiles tiles, GemmOp op, bool b_kmajor, 
   // consistent because BOTH tile sizes of their C -= A B^T launches are ring kernels (this one and gemm_dma64_kernel)
   // and their in-place TRSM is register-staged at either tile height.
   static const bool no_dma = std::getenv("GPMI_GEMM_NO_DMA") != nullptr;
-  static const bool tall = std::getenv("GPMI_GEMM_256") != nullptr;
-  if (tall && bm == 128 && bn == 128 && !b_kmajor && part == 0 && kskip == 0 && k % 128 == 0 && ntr % 2 == 0 && ntc % 2 == 0 && !stamp) {
-    const int h = ntc / 2;
-    const int64_t n256 = tiles == TILES_RECT ? (int64_t)(ntr / 2) * ntc : (int64_t)h * (h + 1) + (int64_t)(ntr / 2 - h) * ntc;
-    dim3 grid2((unsigned)n256, 1, (unsigned)bt.count), block2(512);
-    if (tiles == TILES_RECT) {
-      if (op == OP_SUB) hipLaunchKernelGGL((gemm_dma256_kernel<TILES_RECT, OP_SUB>), grid2, block2, 0, s, g);
-      else hipLaunchKernelGGL((gemm_dma256_kernel<TILES_RECT, OP_ASSIGN>), grid2, block2, 0, s, g);
-    } else {
-      if (op == OP_SUB) hipLaunchKernelGGL((gemm_dma256_kernel<TILES_LOWER, OP_SUB>), grid2, block2, 0, s, g);
-      else hipLaunchKernelGGL((gemm_dma256_kernel<TILES_LOWER, OP_ASSIGN>), grid2, block2, 0, s, g);
-    }
-    return;
-  }
   if (!no_dma && bm == 128 && bn == 128 && !b_kmajor && part != 2 && k % 128 == 0) {
     if (tiles == TILES_RECT) {
       if (op == OP_SUB) hipLaunchKernelGGL((gemm_dma_kernel<TILES_RECT, OP_SUB>), grid, block, 0, s, g);

@@ -52,33 +52,6 @@ __device__ __forceinline__ void c_store(double v, double* p) {
     GPMI_C_STORE(v, p);
 }
 
-// Load flavour of a tile body (potrf_flow.hip's protocol experiments): LD_SC1 makes every load of matrix data an
-// agent-scope (sc1) load - C tile, staged operands, LDS-DMA operands.
-constexpr int LD_PLAIN = 0, LD_SC1 = 1;
-template <int LD>
-__device__ __forceinline__ d2_t c_load2(const d2_t* p) {
-  if (LD == LD_SC1) {
-    const double* q = reinterpret_cast<const double*>(p);
-    return d2_t{__hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
-                __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)};
-  }
-  return GPMI_C_LOAD(p);
-}
-template <int LD>
-__device__ __forceinline__ double c_load1(const double* p) {
-  if (LD == LD_SC1) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return GPMI_C_LOAD(p);
-}
-template <int LD>
-__device__ __forceinline__ d2_t op_load2(const d2_t* p) {
-  if (LD == LD_SC1) {
-    const double* q = reinterpret_cast<const double*>(p);
-    return d2_t{__hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
-                __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)};
-  }
-  return *p;
-}
-
 constexpr int BK = 16;
 constexpr int LDS_STRIDE = 18;  // doubles per staged row (16 + 2 pad)
 // operand slabs requested ahead of the MFMAs by the tiles smaller than 128 x 128 (see staged_tile)
@@ -103,7 +76,7 @@ constexpr int staged_lds_doubles() {
 // the very same sums, bit for bit (the skipped terms are products with exact zeros) - and a wave takes the column
 // blocks wc, wc + 2, wc + 4, wc + 6 instead of four neighbouring ones, so that its share of what is left (16 of 32
 // slab steps for wc = 0, 20 for wc = 1) is even: 44 % fewer MFMAs, 37 % less MFMA time per workgroup.
-template <int OP, int BKN, int BM, int BN, int CST = CST_NT, int LD = LD_PLAIN, bool BTRI = false>
+template <int OP, int BKN, int BM, int BN, int CST = CST_NT, bool BTRI = false>
 __device__ __forceinline__ void staged_tile(const double* __restrict__ Ag, const double* __restrict__ Bg, double* Cg,
                                             int64_t lda, int64_t ldb, int64_t ldc, int nk, double* smem) {
   static_assert(!BTRI || (BKN == 0 && BN == 128 && OP == OP_ASSIGN), "BTRI: the in-place panel TRSM only");
@@ -143,9 +116,9 @@ __device__ __forceinline__ void staged_tile(const double* __restrict__ Ag, const
     const char* ab = reinterpret_cast<const char*>(Ag + k0);
     const char* bb = reinterpret_cast<const char*>(BKN ? Bg + (int64_t)k0 * ldb : Bg + k0);
 #pragma unroll
-    for (int i = 0; i < TM; ++i) ra[slot][i] = op_load2<LD>(reinterpret_cast<const d2_t*>(ab + voa[i]));
+    for (int i = 0; i < TM; ++i) ra[slot][i] = *reinterpret_cast<const d2_t*>(ab + voa[i]);
 #pragma unroll
-    for (int i = 0; i < TN; ++i) rb[slot][i] = op_load2<LD>(reinterpret_cast<const d2_t*>(bb + vob[i]));
+    for (int i = 0; i < TN; ++i) rb[slot][i] = *reinterpret_cast<const d2_t*>(bb + vob[i]);
   };
   auto sstore = [&](int buf, int slot) {
     double* sa = smem + buf * BUF_DOUBLES;
@@ -193,7 +166,7 @@ __device__ __forceinline__ void staged_tile(const double* __restrict__ Ag, const
     for (int j = 0; j < TN; ++j) {
       if (OP == OP_SUB) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) acc[i][j][r] = c_load1<LD>(&Cg[(int64_t)(i * 16 + fk + 4 * r) * ldc + j * CSTEP + fr]);
+        for (int r = 0; r < 4; ++r) acc[i][j][r] = GPMI_C_LOAD(&Cg[(int64_t)(i * 16 + fk + 4 * r) * ldc + j * CSTEP + fr]);
       } else {
         acc[i][j] = d4_t{0.0, 0.0, 0.0, 0.0};
       }
@@ -295,7 +268,7 @@ __device__ inline void dma_wait(int newer) {
 }
 
 // nk: 8-deep stages
-template <int OP, int CST = CST_NT, int LD = LD_PLAIN>
+template <int OP, int CST = CST_NT>
 __device__ __forceinline__ void dma128_tile(const double* __restrict__ Ag, const double* __restrict__ Bg, double* Cg,
                                             int64_t lda, int64_t ldb, int64_t ldc, int nk, double* smem) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -324,17 +297,6 @@ __device__ __forceinline__ void dma128_tile(const double* __restrict__ Ag, const
     const double* p1 = a_src1 + k0;
     const double* p2 = b_src0 + k0;
     const double* p3 = b_src1 + k0;
-    if (LD == LD_SC1)
-      asm volatile(
-          "s_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off sc1\n\t"
-          "s_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off sc1\n\t"
-          "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off sc1\n\t"
-          "s_mov_b32 m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off sc1"
-          :
-          : "v"(p0), "v"(p1), "v"(p2), "v"(p3), "s"(base), "s"(base + 256 * 16), "s"(base + DMA_OP_DOUBLES * 8),
-            "s"(base + DMA_OP_DOUBLES * 8 + 256 * 16)
-          : "memory");
-    else
     asm volatile(
         "s_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off\n\t"
         "s_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
@@ -357,7 +319,7 @@ __device__ __forceinline__ void dma128_tile(const double* __restrict__ Ag, const
       for (int r = 0; r < 4; ++r) {
         d2_t cv = d2_t{0.0, 0.0};
         if (OP == OP_SUB)
-          cv = c_load2<LD>(reinterpret_cast<const d2_t*>(&Cg[(int64_t)(i * 16 + fk + 4 * r) * ldc + jp * 32 + 2 * fr]));
+          cv = GPMI_C_LOAD(reinterpret_cast<const d2_t*>(&Cg[(int64_t)(i * 16 + fk + 4 * r) * ldc + jp * 32 + 2 * fr]));
         acc[i][2 * jp][r] = cv[0];
         acc[i][2 * jp + 1][r] = cv[1];
       }
@@ -414,120 +376,13 @@ __device__ __forceinline__ void dma128_tile(const double* __restrict__ Ag, const
                      reinterpret_cast<d2_t*>(&Cg[(int64_t)(i * 16 + fk + 4 * r) * ldc + jp * 32 + 2 * fr]));
 }
 
-// ---- 256 x 128 tiles on the same ring: 8 waves (4 x 2 of 64 x 64), one workgroup per CU -----------------------------------------------
-// The tile VERDICT r03 asked to be tried: the B slab of a stage is shared by four wave rows instead of two (operand
-// bytes per flop x 0.75), at the price of one barrier domain per CU (the two 128 x 128 workgroups of a CU run their
-// stages in anti-phase, one's barrier under the other's MFMAs).  Three 16-byte pieces per thread and stage (two of A's
-// 256 rows, one of B's 128), 24 KiB per stage.  skip_top: the wave rows 0-1 (the upper 128 rows of the tile) take part
-// in the ring but neither compute nor store (the tile on the diagonal of a lower-triangular product).
-constexpr int DMA256_STAGE_DOUBLES = 3 * DMA_OP_DOUBLES;
-constexpr int DMA256_LDS_DOUBLES = DMA_STAGES * DMA256_STAGE_DOUBLES;
-
-template <int OP, int CST = CST_NT, int LD = LD_PLAIN>
-__device__ __forceinline__ void dma256_tile(const double* __restrict__ Ag, const double* __restrict__ Bg, double* Cg,
-                                            int64_t lda, int64_t ldb, int64_t ldc, int nk, double* smem, bool skip_top) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1;
-  const int fr = lane & 15, fk = lane >> 4;
-  const int row0 = tid >> 2, slot = tid & 3;                   // 0 .. 127
-  const int q0 = (slot - 2 * ((row0 >> 2) & 3)) & 3;
-  const double* a_src0 = Ag + (int64_t)row0 * lda + 2 * q0;
-  const double* a_src1 = a_src0 + (int64_t)128 * lda;
-  auto bperm = [](int R) {
-    const int t = (R >> 4) & 3, f = R & 15;
-    return (R & 64) + ((t & 2) << 4) + 2 * f + (t & 1);
-  };
-  const double* b_src0 = Bg + (int64_t)bperm(row0) * ldb + 2 * q0;
-  const unsigned lds0 = (unsigned)(uintptr_t)smem;
-  const unsigned wave_off = (unsigned)__builtin_amdgcn_readfirstlane(wave * 64 * 16);
-  auto issue = [&](int st, int k0) {
-    const unsigned base = lds0 + (unsigned)st * (DMA256_STAGE_DOUBLES * 8) + wave_off;
-    const double* p0 = a_src0 + k0;
-    const double* p1 = a_src1 + k0;
-    const double* p2 = b_src0 + k0;
-    asm volatile(
-        "s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off\n\t"
-        "s_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off"
-        :
-        : "v"(p0), "v"(p1), "v"(p2), "s"(base), "s"(base + DMA_OP_DOUBLES * 8), "s"(base + 2 * DMA_OP_DOUBLES * 8)
-        : "memory");
-  };
-  for (int st = 0; st < DMA_STAGES - 1 && st < nk; ++st) issue(st, st * DMA_BK);
-
-  const bool idle = skip_top && wr < 2;  // wave-uniform
-  Cg += (int64_t)(wr * 64) * ldc + wc * 64;
-  d4_t acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int jp = 0; jp < 2; ++jp)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        d2_t cv = d2_t{0.0, 0.0};
-        if (OP == OP_SUB && !idle)
-          cv = c_load2<LD>(reinterpret_cast<const d2_t*>(&Cg[(int64_t)(i * 16 + fk + 4 * r) * ldc + jp * 32 + 2 * fr]));
-        acc[i][2 * jp][r] = cv[0];
-        acc[i][2 * jp + 1][r] = cv[1];
-      }
-
-  const int rslot = (fk + 2 * (fr >> 2)) & 3;
-  const int a_off = ((wr * 64 + fr) * 4 + rslot) * 2;
-  const int b_off = 2 * DMA_OP_DOUBLES + ((wc * 64 + fr) * 4 + rslot) * 2;
-  auto wait3 = [](int newer) {
-    if (newer >= 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if (newer >= 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  };
-  auto stage = [&](int kt) {
-    const int ahead = nk - 1 - kt;
-    wait3(3 * (ahead < DMA_STAGES - 2 ? ahead : DMA_STAGES - 2));
-    __syncthreads();
-    const double* sa = smem + (kt % DMA_STAGES) * DMA256_STAGE_DOUBLES;
-    d2_t a[4], b[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) a[t] = *reinterpret_cast<const d2_t*>(sa + a_off + t * 16 * 4 * 2);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) b[t] = *reinterpret_cast<const d2_t*>(sa + b_off + t * 16 * 4 * 2);
-    if (kt + DMA_STAGES - 1 < nk) issue((kt + DMA_STAGES - 1) % DMA_STAGES, (kt + DMA_STAGES - 1) * DMA_BK);
-    if (!idle) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i][h], b[j][h], acc[i][j], 0, 0, OP == OP_SUB ? 1 : 0);
-    }
-  };
-  stage(0);
-  int kt = 1;
-  for (; kt + 3 < nk; kt += 4) {
-    stage(kt);
-    stage(kt + 1);
-    stage(kt + 2);
-    stage(kt + 3);
-  }
-  for (; kt < nk; ++kt) stage(kt);
-  if (idle) return;
-  c_store_begin<CST>();
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int jp = 0; jp < 2; ++jp)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        c_store<CST>((d2_t{acc[i][2 * jp][r], acc[i][2 * jp + 1][r]}),
-                     reinterpret_cast<d2_t*>(&Cg[(int64_t)(i * 16 + fk + 4 * r) * ldc + jp * 32 + 2 * fr]));
-}
-
 // ---- 64 x 64 tiles on the same ring ---------------------------------------------------------------------------------
 // The remainders of split launches, the narrow look-ahead updates (fewer than 384 tiles) and the tail's outer updates
 // run 64 x 64 tiles; with the register-staged kernel they reached 40-47 TFLOP/s at K = 512.  Same scheme as
 // dma128_tile at half the edge: one 16-byte piece per operand, stage and thread (64 rows x 4 pieces), 2 x 2 waves
 // of 32 x 32 (2 x 2 MFMA tiles), 8 KiB per stage.  The MFMAs take the k of a stage in the same groups as the 128 x 128
 // ring kernel ({0,2,4,6}, {1,3,5,7}).
-template <int OP, int CST = CST_NT, int LD = LD_PLAIN>
+template <int OP, int CST = CST_NT>
 __device__ __forceinline__ void dma64_tile(const double* __restrict__ Ag, const double* __restrict__ Bg, double* Cg,
                                            int64_t lda, int64_t ldb, int64_t ldc, int nk, double* smem) {
   constexpr int OPD = 64 * DMA_BK;  // doubles of one operand of one stage
@@ -547,14 +402,6 @@ __device__ __forceinline__ void dma64_tile(const double* __restrict__ Ag, const 
     const unsigned base = lds0 + (unsigned)st * (2 * OPD * 8) + wave_off;
     const double* p0 = a_src + k0;
     const double* p1 = b_src + k0;
-    if (LD == LD_SC1)
-      asm volatile(
-          "s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off sc1\n\t"
-          "s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off sc1"
-          :
-          : "v"(p0), "v"(p1), "s"(base), "s"(base + OPD * 8)
-          : "memory");
-    else
     asm volatile(
         "s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off\n\t"
         "s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off"
@@ -572,7 +419,7 @@ __device__ __forceinline__ void dma64_tile(const double* __restrict__ Ag, const 
     for (int r = 0; r < 4; ++r) {
       d2_t cv = d2_t{0.0, 0.0};
       if (OP == OP_SUB)
-        cv = c_load2<LD>(reinterpret_cast<const d2_t*>(&Cg[(int64_t)(i * 16 + fk + 4 * r) * ldc + 2 * fr]));
+        cv = GPMI_C_LOAD(reinterpret_cast<const d2_t*>(&Cg[(int64_t)(i * 16 + fk + 4 * r) * ldc + 2 * fr]));
       acc[i][0][r] = cv[0];
       acc[i][1][r] = cv[1];
     }
@@ -623,41 +470,12 @@ __device__ __forceinline__ void dma64_tile(const double* __restrict__ Ag, const 
                    reinterpret_cast<d2_t*>(&Cg[(int64_t)(i * 16 + fk + 4 * r) * ldc + 2 * fr]));
 }
 
-// ---- flag hooks of the flag-ordered factorisation (potrf_flow.hip) ------------------------------------------------
-// A launch on the chain stream publishes what the launch BEFORE it in that stream produced (the kernel boundary has
-// made those stores visible device-wide) and waits for the tile-task kernel to have brought its own C tile up to date.
+// ---- flag polls of the flag-ordered kernels (potrf_flow.hip, potrf_panel.hip, potrf_colblock.h) ---------------------
+// Every poll is bounded: past FLOW_SPIN_LIMIT the poller sets the abort word and gives up.
 constexpr int FLOW_SPIN_LIMIT = 1 << 20;  // polls of ~1 us (an s_sleep and a few L2-bypassing loads)
 
 __device__ __forceinline__ int flow_ld(const int* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// called by every thread of the workgroup at the top of a chain kernel
-__device__ __forceinline__ void flow_hook_enter(const FlowHook& h) {
-  if (h.trace && blockIdx.x == 0 && threadIdx.x == 0) h.trace[0] = __builtin_amdgcn_s_memrealtime();
-  if (h.pub && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) {
-    __hip_atomic_store(h.pub, h.pub_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  if (h.wait) {
-    if (threadIdx.x == 0) {
-      int spins = 0;
-      unsigned long long t0 = 0;
-      if (h.wait_ticks) t0 = __builtin_amdgcn_s_memrealtime();
-      while (flow_ld(h.wait) < h.wait_val) {
-        __builtin_amdgcn_s_sleep(4);
-        if ((++spins & 63) == 0 && flow_ld(h.abort)) break;
-        if (spins > FLOW_SPIN_LIMIT) {
-          __hip_atomic_store(h.abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (h.info) atomicCAS(h.info, 0, GPMI_INFO_FLOW_TIMEOUT);  // the chain launches of the tile-task factorisation
-          break;
-        }
-      }
-      if (h.wait_ticks) atomicAdd(h.wait_ticks, __builtin_amdgcn_s_memrealtime() - t0);
-      if (h.trace && blockIdx.x == 0) h.trace[1] = __builtin_amdgcn_s_memrealtime();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-  }
 }
 
 }  // namespace gemm_tiles

@@ -451,19 +451,6 @@ void launch_scale_columns(hipStream_t s, const double* A, const double* sc, doub
 void launch_loo_vectors(hipStream_t s, const double* alpha, const double* ikdiag, double* c1,
                         double* sc2, int64_t n, int64_t np, int batch = 1, int64_t sAlpha = 0, int64_t sLoo = 0);
 
-// flags a chain launch of the flag-ordered factorisation publishes / waits for at its start (potrf_flow.hip,
-// gemm_tiles.h: flow_hook_enter)
-struct FlowHook {
-  int* pub = nullptr;         // *pub = pub_val at the start of the launch (first thread of workgroup 0)
-  int pub_val = 0;
-  const int* wait = nullptr;  // every workgroup: spin until *wait >= wait_val
-  int wait_val = 0;
-  int* abort = nullptr;       // non-zero: somebody timed out; stop waiting.  Set by a poll that times out itself
-  int* info = nullptr;        // receives GPMI_ERR_INTERNAL on a time-out (if still zero)
-  unsigned long long* wait_ticks = nullptr;  // diagnostics: 10 ns ticks spent waiting, summed over the workgroups
-  unsigned long long* trace = nullptr;       // diagnostics: {launch start, wait over} (s_memrealtime), workgroup 0
-};
-
 // batch of independent equal-shape problems in one launch (blockIdx.z): strides in doubles
 struct GemmBatch {
   int count = 1;
@@ -477,7 +464,6 @@ struct GemmBatch {
   // the ring kernels' order (no 32-row register-staged tiles at K > 128, whose use depends on the batch size; round 6:
   // the inverse of a gradient batch of one differed from the same problem's inside a batch of six in the last bits)
   bool ring_order_only = false;
-  FlowHook hook;
 };
 struct BatchShape {
   int count = 1;
@@ -535,8 +521,7 @@ hipStream_t potrf_first_update_stream(gpmi_ctx* c, Lane& lane, int64_t np, bool 
 // waits for whatever an earlier (failed / foreign) call left on the lane's CU-masked pair; before the caller's own enqueues
 void potrf_pair_quiesce(Lane& lane);
 void launch_potrf_diag(hipStream_t s, double* Ablk, int64_t ld, double* invD, int* info, int col0,
-                       unsigned long long* dbg = nullptr, const BatchShape& bs = BatchShape(), int* pub = nullptr,
-                       int pub_val = 0);
+                       unsigned long long* dbg = nullptr, const BatchShape& bs = BatchShape());
 void launch_potrf_diag_fault(hipStream_t s, double* Ablk, int64_t ld, const BatchShape& bs = BatchShape());  // test hook
 // batched, in-order factorisation of bs.count matrices (small problems: no look-ahead)
 void potrf_lower_batched(gpmi_ctx* c, hipStream_t s, double* A, int64_t np, int64_t ld, double* invD,

@@ -31,10 +31,7 @@ __global__ __launch_bounds__(DIAG_THREADS) void potrf_diag_kernel(double* __rest
                                                          double* __restrict__ invD,
                                                          int* __restrict__ info, int col0,
                                                          unsigned long long* __restrict__ dbg,
-                                                         int64_t strideA, int64_t strideInv, int* pub, int pub_val) {
-  // (flag-ordered tail, potrf_flow.hip: this launch publishes what the chain launch before it produced)
-  if (pub && threadIdx.x == 0 && blockIdx.z == 0)
-    __hip_atomic_store(pub, pub_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                                         int64_t strideA, int64_t strideInv) {
   __shared__ potrf_diag::DiagShared sh;
   potrf_diag::potrf_diag_body<false>(A + (int64_t)blockIdx.z * strideA, ld, invD + (int64_t)blockIdx.z * strideInv,
                                      info + blockIdx.z, col0, dbg, sh, potrf_diag::DiagPub());
@@ -64,9 +61,9 @@ void launch_potrf_diag_fault(hipStream_t s, double* Ablk, int64_t ld, const Batc
 }
 
 void launch_potrf_diag(hipStream_t s, double* Ablk, int64_t ld, double* invD, int* info, int col0,
-                       unsigned long long* dbg, const BatchShape& bs, int* pub, int pub_val) {
+                       unsigned long long* dbg, const BatchShape& bs) {
   hipLaunchKernelGGL(potrf_diag_kernel, dim3(1, 1, (unsigned)bs.count), dim3(DIAG_THREADS), 0, s, Ablk, ld, invD,
-                     info, col0, dbg, bs.sMat, bs.sInv, pub, pub_val);
+                     info, col0, dbg, bs.sMat, bs.sInv);
   launch_potrf_diag_fault(s, Ablk, ld, bs);
 }
 

@@ -39,8 +39,8 @@ __device__ __forceinline__ void wait_inv_row(const int* rowflag, int target, con
 // load_inv_rowblock: the B operands - lane (fr, fk): inv[16 row + fr][16 s + 4 fk .. + 3] of the slabs s <= row (`inv`: the
 // inverse, row pitch `pitch` - global memory, or a copy in LDS).
 // colblock_sums: a_slab(s) returns the wave's A operand of slab s - lane (fr, fk): T[fr][16 s + 4 fk .. + 3] of the strip.
-// The sums are those of the register-staged TRSM body (gemm_tiles::staged_tile, BTRI) and of chain_trsm_kernel, bit for
-// bit: k = 16 s + 4 fk + q at MFMA step q of slab s, slabs in ascending order, the slabs beyond the column block (zeros
+// The sums are those of the register-staged TRSM body (gemm_tiles::staged_tile<..., BTRI>), bit for bit:
+// k = 16 s + 4 fk + q at MFMA step q of slab s, slabs in ascending order, the slabs beyond the column block (zeros
 // of the lower-triangular inverse) skipped.  Returns the block in the D layout: lane (fr, fk) element r =
 // X[fk + 4 r][16 row + fr].
 __device__ __forceinline__ void load_inv_rowblock(const double* inv, int pitch, int row, int fr, int fk,

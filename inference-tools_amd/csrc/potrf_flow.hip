@@ -5,10 +5,11 @@
 // In stream order that part costs chain + updates: potrf_diag (29.5 us) -> panel TRSM -> inner update per 128 columns
 // with the chip nearly idle, then a trailing update with the chain idle.  Here the two run side by side:
 //
-//   chain stream (the lane's CU-masked panel stream, ordinary launches in stream order, nothing but the critical path):
-//       D(k)  = potrf_diag of tile (k, k)
-//       Tc(k) = tile (k+1, k) <- tile (k+1, k) invD(k)^T              (4 workgroups of 32 rows)
-//       Uc(k) = tile (k+1, k+1) -= L(k+1, k) L(k+1, k)^T               (3 workgroups of 64 x 64)
+//   chain stream (the lane's CU-masked panel stream, nothing but the critical path): ONE launch per column k
+//   (chain_column_kernel), in stream order, with
+//       D(k)  = potrf_diag of tile (k, k)                              (workgroup 0)
+//       Tc(k) = tile (k+1, k) <- tile (k+1, k) invD(k)^T               (28 workgroups, on 16-row strips, one row
+//       Uc(k) = tile (k+1, k+1) -= L(k+1, k) L(k+1, k)^T                block of the inverse behind D(k))
 //   update stream (the other CUs): ONE persistent launch; every workgroup owns a fixed list of tile tasks and runs it in
 //   order, starting a task when the flags of its inputs are set:
 //       T(i, k), i >= k + 2    panel TRSM of tile (i, k), four 32-row slabs
@@ -88,8 +89,8 @@ struct FlowTask {
 static_assert(sizeof(FlowTask) == 12, "FlowTask layout");
 
 // hot words on lines of their own
-// FL_ROWCNT: 8 words (chain_fused_kernel, chain_column_kernel); FL_INVROW: 8 words on lines of their own (row blocks of
-// the current inverse diagonal block, chain_column_kernel)
+// FL_ROWCNT: 8 words (workgroups that have loaded strip r of T, summed over the columns so far); FL_INVROW: 8 words on
+// lines of their own (row blocks of the current inverse diagonal block) - both chain_column_kernel's
 constexpr int FL_DDONE = 0, FL_ABORT = 32, FL_T0 = 48, FL_STATS = 64, FL_ROWCNT = 96, FL_INVROW = 128, FL_LCNT = 384;
 __host__ __device__ inline int flow_f_off(int m) { return FL_LCNT + ((m + 31) / 32) * 32; }
 __host__ __device__ inline int flow_owner_off(int m) { return flow_f_off(m) + ((m * m + 31) / 32) * 32; }  // one word per list
@@ -134,265 +135,33 @@ __device__ __forceinline__ bool flow_ready(const FlowTask& t, const int* __restr
 // and the matrices as address-space-1 pointers so that the accesses stay ds_ / global_ instructions, not flat_.)
 typedef __attribute__((address_space(3))) double lds_double_t;
 typedef __attribute__((address_space(1))) double glb_double_t;  // (generic pointers would turn every access into flat_)
-// PROTO (GPMI_FLOW_PROTO): how a tile changes hands between CUs.  0: write-through (sc1) stores, acquire on the
-// consumer; 1: the same + an agent release in front of the flag; 2: sc1 stores and sc1 loads of every matrix byte;
-// 3: non-temporal stores + agent release (whole-L2 write-back per task).
-template <int PROTO>
+// How a tile changes hands between CUs: write-through (sc1) stores by the producer, plain loads behind an agent-scope
+// acquire on the consumer.
 __device__ __attribute__((noinline)) void flow_do_T(glb_double_t* C, const glb_double_t* invDk, int64_t ld,
                                                     lds_double_t* smem) {
-  staged_tile<OP_ASSIGN, 0, 32, 128, PROTO == 3 ? CST_NT : CST_SC1, PROTO == 2 ? LD_SC1 : LD_PLAIN, true>(
-      (const double*)C, (const double*)invDk, (double*)C, ld, NB, ld, NB / BK, (double*)smem);
+  staged_tile<OP_ASSIGN, 0, 32, 128, CST_SC1, true>((const double*)C, (const double*)invDk, (double*)C, ld, NB, ld,
+                                                    NB / BK, (double*)smem);
 }
-template <int PROTO>
 __device__ __attribute__((noinline)) void flow_do_U(const glb_double_t* Ai, const glb_double_t* Bj, glb_double_t* C,
                                                     int64_t ld, lds_double_t* smem, int nk) {
   // (nk and the LDS block arrive in vector registers - the function is not inlined and has two callers -; the ring's
   // stage addresses must be scalar: they go through m0)
   lds_double_t* su = (lds_double_t*)(uintptr_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(uintptr_t)smem);
-  dma64_tile<OP_SUB, PROTO == 3 ? CST_NT : CST_SC1, PROTO == 2 ? LD_SC1 : LD_PLAIN>(
-      (const double*)Ai, (const double*)Bj, (double*)C, ld, ld, ld, __builtin_amdgcn_readfirstlane(nk), (double*)su);
+  dma64_tile<OP_SUB, CST_SC1>((const double*)Ai, (const double*)Bj, (double*)C, ld, ld, ld,
+                              __builtin_amdgcn_readfirstlane(nk), (double*)su);
 }
-// ---- the chain's two products per column, on tiles of 16 rows (round 4) ----------------------------------------------
+// ---- the chain: D(k), Tc(k) and Uc(k) of a column in ONE launch -------------------------------------------------------
 // Tc(k): tile (k+1, k) <- tile * invD(k)^T and Uc(k): tile (k+1, k+1) -= X X^T are 128 x 128 x 128 products on the
-// critical path.  The tile bodies of the throughput kernels put one wave on 4 - 8 MFMA tiles (a 32 x 128 TRSM slab: 8 per
-// wave, 4.2 us of MFMA time on its SIMD; a 64 x 64 update tile: 4 per wave over K = 128, the same) - right when the
-// launch has hundreds of workgroups, slow when it has four.  Here every wave owns ONE 16 x 16 tile of the result, takes
-// its operands straight from L2 into registers (all requests in flight at once, no LDS, no barrier in the loop) and runs
-// its 4 .. 32 MFMAs as one chain: 6.2 -> ~3 us and 6.7 -> ~3 us per column.
+// critical path.  The tile bodies of the throughput kernels put one wave on 4 - 8 MFMA tiles - right when the launch has
+// hundreds of workgroups, slow when it has four.  Here every wave owns ONE 16 x 16 tile of the result and runs its
+// 4 .. 32 MFMAs as one chain.
 // The sums are those of the throughput bodies BIT FOR BIT, because a flow-ordered factorisation must equal the stream-
 // ordered one, which runs these tiles inside launches of the generic kernels: the register-staged TRSM body
 // (gemm_tiles::staged_tile, BTRI) feeds k = 16 s + 4 fk + q to MFMA step q of slab s and skips the slabs beyond the
-// column block; the ring body of the update (gemm_tiles::dma64_tile) feeds k = 8 st + 2 fk to the first and
-// 8 st + 2 fk + 1 to the second MFMA of stage st and negates A through the MFMA's BLGP field.  Same operands, same order.
-struct ChainArgs {
-  double* T;         // tile (k+1, k): 128 x 128, Tc's input and output, Uc's operand
-  double* C;         // tile (k+1, k+1): Uc's target
-  const double* invD;  // inverse of diagonal block k (row-major 128 x 128, lower triangular)
-  int64_t ld;
-  FlowHook hook;
-};
-
-// 8 workgroups x 8 waves: workgroup b owns the rows 16 b .. 16 b + 15 (in place: nobody else reads or writes them), wave c
-// the column block c.
-__global__ __launch_bounds__(512) void chain_trsm_kernel(ChainArgs g) {
-  flow_hook_enter(g.hook);
-  const int lane = threadIdx.x & 63, c = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int fr = lane & 15, fk = lane >> 4;
-  const double* arow = g.T + (int64_t)(16 * blockIdx.x + fr) * g.ld + 4 * fk;
-  const double* brow = g.invD + (int64_t)(16 * c + fr) * NB + 4 * fk;
-  d4_t a[NB / 16], b[NB / 16];
-#pragma unroll
-  for (int s = 0; s < NB / 16; ++s)
-    if (s <= c) {  // column block c of a lower-triangular B: zero beyond slab c
-      a[s] = *reinterpret_cast<const d4_t*>(arow + 16 * s);
-      b[s] = *reinterpret_cast<const d4_t*>(brow + 16 * s);
-    }
-  d4_t acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int s = 0; s < NB / 16; ++s)
-    if (s <= c) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s][q], b[s][q], acc, 0, 0, 0);
-    }
-  // every wave of the workgroup has its operands (the MFMAs above waited for them) before anybody overwrites the rows
-  __syncthreads();
-  double* out = g.T + (int64_t)(16 * blockIdx.x + fk) * g.ld + 16 * c + fr;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) out[(int64_t)4 * r * g.ld] = acc[r];
-}
-
-// 9 workgroups x 4 waves: the 36 tiles (i, j), j <= i, of 16 x 16 of the target's lower triangle (diagonal tiles in full)
-__global__ __launch_bounds__(256) void chain_syrk_kernel(ChainArgs g) {
-  flow_hook_enter(g.hook);
-  const int lane = threadIdx.x & 63;
-  const int t = __builtin_amdgcn_readfirstlane((int)(4 * blockIdx.x + (threadIdx.x >> 6)));
-  int i = 0;
-  while ((i + 1) * (i + 2) / 2 <= t) ++i;
-  const int j = t - i * (i + 1) / 2;
-  const int fr = lane & 15, fk = lane >> 4;
-  const double* arow = g.T + (int64_t)(16 * i + fr) * g.ld + 2 * fk;
-  const double* brow = g.T + (int64_t)(16 * j + fr) * g.ld + 2 * fk;
-  double* cp = g.C + (int64_t)(16 * i + fk) * g.ld + 16 * j + fr;
-  d4_t acc;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) acc[r] = cp[(int64_t)4 * r * g.ld];
-  d2_t a[NB / 8], b[NB / 8];
-#pragma unroll
-  for (int st = 0; st < NB / 8; ++st) {
-    a[st] = *reinterpret_cast<const d2_t*>(arow + 8 * st);
-    b[st] = *reinterpret_cast<const d2_t*>(brow + 8 * st);
-  }
-#pragma unroll
-  for (int st = 0; st < NB / 8; ++st)
-#pragma unroll
-    for (int h = 0; h < 2; ++h) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[st][h], b[st][h], acc, 0, 0, 1);  // C - A B^T
-#pragma unroll
-  for (int r = 0; r < 4; ++r) cp[(int64_t)4 * r * g.ld] = acc[r];
-}
-
-// Tc(k) and Uc(k) in ONE launch (GPMI_CHAIN_TILES=2, the default): the update tile (i, j) of 16 x 16 needs the rows i and j of
-// X = T invD^T - two 16 x 128 strips, 64 MFMAs for the eight waves of a workgroup - so every workgroup computes the strips
-// of ITS tile itself instead of waiting a kernel boundary (2.3 us) and an L2 round trip for somebody else's: workgroups
-// 0 .. 27 the off-diagonal tiles (two strips each), 28 .. 31 two diagonal tiles each (two strips as well): 32 equal
-// workgroups, one per CU of the panel stream.  Strips and update take their k in exactly the groups of
-// chain_trsm_kernel / chain_syrk_kernel (bit-identical).  X replaces T in place: the diagonal-pair workgroup of a strip
-// stores it once all eight workgroups that read the strip's rows of T have them in registers (a counter per strip,
-// monotonic over the columns; only those four workgroups ever wait, so the others always finish and free their CUs).
-struct ChainFusedArgs {
-  double* T;
-  double* C;
-  const double* invD;
-  int64_t ld;
-  int* rowcnt;       // 8 counters: workgroups that have loaded strip r of T, summed over the columns so far
-  int rowcnt_target; // 8 x (columns so far, this one included)
-  const int* wait2;  // second flag: tile (k+1, k+1) has taken the columns before k
-  int wait2_val;
-  FlowHook hook;
-};
-constexpr int CF_PITCH = NB + 2;   // X strips, row-major (update operands: 16-byte reads at (row fr, 8 st + 2 fk))
-constexpr int CF_APITCH = NB + 4;  // T strips, row-major (TRSM operands: 32-byte reads at (row fr, 16 s + 4 fk))
-
-__global__ __launch_bounds__(512) void chain_fused_kernel(ChainFusedArgs g) {
-  __shared__ __attribute__((aligned(16))) double Ts[2][16 * CF_APITCH];
-  __shared__ __attribute__((aligned(16))) double Xs[2][16 * CF_PITCH];
-  // the hook of a chain launch (gemm_tiles.h: flow_hook_enter) with BOTH flags in one poll: tile (k+1, k) and tile
-  // (k+1, k+1) have taken the columns before k (normally long set; one L2 round trip for the two)
-  {
-    const FlowHook& h = g.hook;
-    if (h.trace && blockIdx.x == 0 && threadIdx.x == 0) h.trace[0] = __builtin_amdgcn_s_memrealtime();
-    if (h.pub && blockIdx.x == 0 && threadIdx.x == 0)
-      __hip_atomic_store(h.pub, h.pub_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (threadIdx.x == 0) {
-      int spins = 0;
-      unsigned long long t0 = 0;
-      if (h.wait_ticks) t0 = __builtin_amdgcn_s_memrealtime();
-      for (;;) {
-        const int v1 = flow_ld(h.wait), v2 = flow_ld(g.wait2);
-        if (v1 >= h.wait_val && v2 >= g.wait2_val) break;
-        __builtin_amdgcn_s_sleep(4);
-        if ((++spins & 63) == 0 && flow_ld(h.abort)) break;
-        if (spins > FLOW_SPIN_LIMIT) {
-          __hip_atomic_store(h.abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (h.info) atomicCAS(h.info, 0, GPMI_INFO_FLOW_TIMEOUT);
-          break;
-        }
-      }
-      if (h.wait_ticks) atomicAdd(h.wait_ticks, __builtin_amdgcn_s_memrealtime() - t0);
-      if (h.trace && blockIdx.x == 0) h.trace[1] = __builtin_amdgcn_s_memrealtime();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-  }
-  const int tid = threadIdx.x, lane = tid & 63, c = __builtin_amdgcn_readfirstlane((int)(tid >> 6));
-  const int fr = lane & 15, fk = lane >> 4;
-  const int w = (int)blockIdx.x;
-  int r0, r1;  // the two strips of this workgroup: rows 16 r0 .., 16 r1 ..
-  const bool diag_pair = w >= 28;
-  if (diag_pair) {
-    r0 = 2 * (w - 28);
-    r1 = r0 + 1;
-  } else {
-    r0 = 1;
-    while (r0 * (r0 + 1) / 2 <= w) ++r0;  // off-diagonal tiles (i, j), j < i, row by row: w = i (i - 1) / 2 + j
-    r1 = w - r0 * (r0 - 1) / 2;
-  }
-  // ---- operands.  T: wave c fetches slab c (columns 16 c ..) of both strips, once per workgroup, and hands it on through
-  // LDS.  invD: wave c computes column block c of strip 0 and column block 7 - c of strip 1 - row blocks c and 7 - c of the
-  // lower-triangular invD, nine slabs and 36 MFMAs for every wave (one block of both strips per wave: 8 .. 64 MFMAs)
-  const int c1 = 7 - c;
-  const d4_t t0 = *reinterpret_cast<const d4_t*>(g.T + (int64_t)(16 * r0 + fr) * g.ld + 16 * c + 4 * fk);
-  const d4_t t1 = *reinterpret_cast<const d4_t*>(g.T + (int64_t)(16 * r1 + fr) * g.ld + 16 * c + 4 * fk);
-  const double* b0row = g.invD + (int64_t)(16 * c + fr) * NB + 4 * fk;
-  const double* b1row = g.invD + (int64_t)(16 * c1 + fr) * NB + 4 * fk;
-  d4_t b0[NB / 16], b1[NB / 16];
-#pragma unroll
-  for (int s = 0; s < NB / 16; ++s) {
-    if (s <= c) b0[s] = *reinterpret_cast<const d4_t*>(b0row + 16 * s);
-    if (s <= c1) b1[s] = *reinterpret_cast<const d4_t*>(b1row + 16 * s);
-  }
-  // the update tile(s) of this workgroup: one wave each; its C tile is requested now and arrives under the strips
-  const int ntile = diag_pair ? 2 : 1;
-  d4_t acc = {0.0, 0.0, 0.0, 0.0};
-  double* cp = nullptr;
-  if (c < ntile) {
-    const int ti = diag_pair ? (c == 0 ? r0 : r1) : r0, tj = diag_pair ? ti : r1;
-    cp = g.C + (int64_t)(16 * ti + fk) * g.ld + 16 * tj + fr;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = cp[(int64_t)4 * r * g.ld];
-  }
-  *reinterpret_cast<d4_t*>(&Ts[0][fr * CF_APITCH + 16 * c + 4 * fk]) = t0;
-  *reinterpret_cast<d4_t*>(&Ts[1][fr * CF_APITCH + 16 * c + 4 * fk]) = t1;
-  __syncthreads();  // (every wave has its slab of T in registers and in LDS)
-  if (tid == 0) {
-    __hip_atomic_fetch_add(g.rowcnt + r0, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_fetch_add(g.rowcnt + r1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  // ---- the strips (chain_trsm_kernel's sums: k = 16 s + 4 fk + q at step q of slab s, slabs beyond the block skipped)
-  d4_t x0 = {0.0, 0.0, 0.0, 0.0}, x1 = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int s = 0; s < NB / 16; ++s) {
-    if (s <= c) {
-      const d4_t a = *reinterpret_cast<const d4_t*>(&Ts[0][fr * CF_APITCH + 16 * s + 4 * fk]);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) x0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[q], b0[s][q], x0, 0, 0, 0);
-    }
-    if (s <= c1) {
-      const d4_t a = *reinterpret_cast<const d4_t*>(&Ts[1][fr * CF_APITCH + 16 * s + 4 * fk]);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) x1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[q], b1[s][q], x1, 0, 0, 0);
-    }
-  }
-  // X strips to LDS in row-major form (the D layout of the MFMA: lane (fr, fk) holds rows fk + 4 r of its column block)
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    Xs[0][(fk + 4 * r) * CF_PITCH + 16 * c + fr] = x0[r];
-    Xs[1][(fk + 4 * r) * CF_PITCH + 16 * c1 + fr] = x1[r];
-  }
-  __syncthreads();
-  // ---- the update tile(s): chain_syrk_kernel's sums (k = 8 st + 2 fk, + 1; A negated by the MFMA)
-  if (c < ntile) {
-    const double* xa = Xs[diag_pair ? c : 0] + fr * CF_PITCH + 2 * fk;
-    const double* xb = Xs[diag_pair ? c : 1] + fr * CF_PITCH + 2 * fk;
-#pragma unroll
-    for (int st = 0; st < NB / 8; ++st) {
-      const d2_t av = *reinterpret_cast<const d2_t*>(xa + 8 * st);
-      const d2_t bv = *reinterpret_cast<const d2_t*>(xb + 8 * st);
-#pragma unroll
-      for (int h = 0; h < 2; ++h) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[h], bv[h], acc, 0, 0, 1);  // C - A B^T
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) cp[(int64_t)4 * r * g.ld] = acc[r];
-  }
-  if (g.hook.trace && w == 0 && tid == 0) g.hook.trace[2] = g.hook.trace[3] = __builtin_amdgcn_s_memrealtime();
-  if (!diag_pair || c < ntile) return;
-  // ---- X in place of T (the diagonal-pair workgroups, the six waves without a tile, from LDS): strips r0 and r1, once
-  // nobody needs their rows of T any more
-  {
-    int spins = 0;
-    while (flow_ld(g.rowcnt + r0) < g.rowcnt_target || flow_ld(g.rowcnt + r1) < g.rowcnt_target) {
-      __builtin_amdgcn_s_sleep(2);
-      if ((++spins & 63) == 0 && flow_ld(g.hook.abort)) break;
-      if (spins > FLOW_SPIN_LIMIT) {
-        if (lane == 0) {
-          __hip_atomic_store(g.hook.abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (g.hook.info) atomicCAS(g.hook.info, 0, GPMI_INFO_FLOW_TIMEOUT);
-        }
-        break;
-      }
-    }
-  }
-  for (int blk = c - ntile; blk < 16; blk += 8 - ntile) {  // block = (strip, column block)
-    const int st = blk >> 3, cb = blk & 7;
-    const double* xs = Xs[st] + fk * CF_PITCH + 16 * cb + fr;
-    double* o = g.T + (int64_t)(16 * (st ? r1 : r0) + fk) * g.ld + 16 * cb + fr;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) o[(int64_t)4 * r * g.ld] = xs[4 * r * CF_PITCH];
-  }
-}
-
-// ---- D(k), Tc(k) and Uc(k) in ONE launch (round 5, GPMI_CHAIN_TILES=3, the default) ---------------------------------------
-// Until round 4 a column of the chain was potrf_diag, a kernel boundary, and the fused Tc / Uc launch, which could not start
+// column block (potrf_colblock.h); the ring body of the update (gemm_tiles::dma64_tile) feeds k = 8 st + 2 fk to the
+// first and 8 st + 2 fk + 1 to the second MFMA of stage st and negates A through the MFMA's BLGP field.  Same operands,
+// same order.
+// A column of the chain used to be potrf_diag, a kernel boundary, and a fused Tc / Uc launch, which could not start
 // before the whole inverse of the diagonal block existed: 18.5 + 2 + 13 us.  But row block c of the inverse is final after
 // step c of potrf_diag's eight (the inverse is built right-looking), column block c of X = T invD^T needs row block c of the
 // inverse only (X_c = sum_{s <= c} T_s invD[c][s]^T), and the update C -= X X^T takes the column blocks of X in order.
@@ -408,7 +177,6 @@ __global__ __launch_bounds__(512) void chain_fused_kernel(ChainFusedArgs g) {
 //                    reader of those rows has them (FL_ROWCNT, seven readers per strip).
 // Behind potrf_diag's last elimination there is left: the last row block of the inverse (one MFMA chain of 4 + its stores'
 // acknowledgement), the hand-off, 32 MFMAs of the last column block, 4 of the update, the C store: ~6 us instead of 15.
-// Same sums in the same order as chain_trsm_kernel / chain_syrk_kernel, i.e. as the generic tile bodies: bit-identical.
 // Deadlock-free with any number of resident workgroups: workgroup 0 is dispatched first and waits for nobody in the
 // launch; the others wait for workgroup 0 and - the pair workgroups, dispatched last - for workgroups before them.
 struct ChainColArgs {
@@ -428,6 +196,8 @@ struct ChainColArgs {
   unsigned long long* wait_ticks;
   unsigned long long* trace;  // 4 words (worker 0): launch start, flags seen, last MFMA, end
 };
+constexpr int CF_PITCH = NB + 2;   // X strips, row-major (update operands: 16-byte reads at (row fr, 8 st + 2 fk))
+constexpr int CF_APITCH = NB + 4;  // T strips, row-major (TRSM operands: 32-byte reads at (row fr, 16 s + 4 fk))
 constexpr int CC_WORKERS = 28;
 constexpr int CC_READERS = 7;  // workgroups that load a strip of T: 6 off-diagonal tiles + the strip's pair workgroup
 
@@ -546,7 +316,7 @@ __global__ __launch_bounds__(512) void chain_column_kernel(ChainColArgs g) {
     if (row == c || row == 7 - c) {
       const int strip = row == c ? 0 : 1;
       potrf_colblock::wait_inv_row(fl + FL_INVROW + 32 * row, row_target, abortw, give_up);
-      // (chain_trsm_kernel's sums: potrf_colblock.h)
+      // (the sums of gemm_tiles::staged_tile<..., BTRI>: potrf_colblock.h)
       const double* ts = Ts + strip * 16 * CF_APITCH + fr * CF_APITCH + 4 * fk;
       d4_t b[NB / 16];
       potrf_colblock::load_inv_rowblock(g.invD, NB, row, fr, fk, b);
@@ -577,8 +347,8 @@ __global__ __launch_bounds__(512) void chain_column_kernel(ChainColArgs g) {
         for (int r = 0; r < 4; ++r) o[(int64_t)4 * r * g.ld] = x[r];
       }
     }
-    // ---- the tile waves: column block `row` of both strips (chain_syrk_kernel's sums: k = 8 st + 2 fk, + 1; A negated
-    // by the MFMA), as soon as the two blocks are in LDS
+    // ---- the tile waves: column block `row` of both strips (gemm_tiles::dma64_tile's sums: k = 8 st + 2 fk, + 1; A
+    // negated by the MFMA), as soon as the two blocks are in LDS
     if (tile_wave) {
       int polls = 0;
       while (__hip_atomic_load(xs_cnt + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < 2) {
@@ -610,7 +380,6 @@ __global__ __launch_bounds__(512) void chain_column_kernel(ChainColArgs g) {
   }
 }
 
-template <int PROTO>
 __global__ __launch_bounds__(256, 2) void flow_task_kernel(FlowArgs a) {
   __shared__ double smem[DMA128_LDS_DOUBLES];
   __shared__ int sh[8];
@@ -777,7 +546,7 @@ __global__ __launch_bounds__(256, 2) void flow_task_kernel(FlowArgs a) {
     if (t.type == FT_T) {
       // rows [32 s, 32 s + 32) of tile (i, k) <- the same rows times invD(k)^T, in place
       double* C = a.A + ((int64_t)t.i * NB + 32 * t.s) * ld + (int64_t)t.k * NB;
-      flow_do_T<PROTO>((glb_double_t*)C, (const glb_double_t*)(a.invD + (int64_t)t.k * NB * NB), ld, (lds_double_t*)smem);
+      flow_do_T((glb_double_t*)C, (const glb_double_t*)(a.invD + (int64_t)t.k * NB * NB), ld, (lds_double_t*)smem);
       flag = Lcnt + t.i;
     } else if (t.type == FT_U || t.type == FT_ZS) {
       // one column k (K = 128), or - FT_ZS - the four columns of outer panel k (K = 512), on a 64 x 64 sub-tile: the
@@ -787,14 +556,14 @@ __global__ __launch_bounds__(256, 2) void flow_task_kernel(FlowArgs a) {
       double* C = a.A + ((int64_t)t.i * NB + r0) * ld + (int64_t)t.j * NB + c0;
       const double* Ai = a.A + ((int64_t)t.i * NB + r0) * ld + kcol;
       const double* Bj = a.A + ((int64_t)t.j * NB + c0) * ld + kcol;
-      flow_do_U<PROTO>((const glb_double_t*)Ai, (const glb_double_t*)Bj, (glb_double_t*)C, ld, (lds_double_t*)smem,
-                       t.type == FT_U ? NB / DMA_BK : OBT * NB / DMA_BK);
+      flow_do_U((const glb_double_t*)Ai, (const glb_double_t*)Bj, (glb_double_t*)C, ld, (lds_double_t*)smem,
+                t.type == FT_U ? NB / DMA_BK : OBT * NB / DMA_BK);
       flag = F + t.i * a.m + t.j;
     } else {
       double* C = a.A + (int64_t)t.i * NB * ld + (int64_t)t.j * NB;
       const double* Ai = a.A + (int64_t)t.i * NB * ld + (int64_t)t.k * OBT * NB;
       const double* Bj = a.A + (int64_t)t.j * NB * ld + (int64_t)t.k * OBT * NB;
-      dma128_tile<OP_SUB, PROTO == 3 ? CST_NT : CST_SC1, PROTO == 2 ? LD_SC1 : LD_PLAIN>(Ai, Bj, C, ld, ld, ld, OBT * NB / DMA_BK, smem);
+      dma128_tile<OP_SUB, CST_SC1>(Ai, Bj, C, ld, ld, ld, OBT * NB / DMA_BK, smem);
       flag = F + t.i * a.m + t.j;
     }
     // publish: the tile was stored write-through (sc1); every wave's stores acknowledged, workgroup barrier, flag
@@ -802,10 +571,6 @@ __global__ __launch_bounds__(256, 2) void flow_task_kernel(FlowArgs a) {
     __syncthreads();
     if (a.trace && tid == 0) a.trace[4 * (int64_t)n + 2] = __builtin_amdgcn_s_memrealtime();
     if (tid == 0) {
-      if (PROTO == 1 || PROTO == 3) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
       if (n != a.fault) __hip_atomic_fetch_add(flag, (int)t.fadd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (a.trace) a.trace[4 * (int64_t)n + 3] = __builtin_amdgcn_s_memrealtime();
     }
@@ -1059,14 +824,8 @@ void flow_gate_leave(int device, hipStream_t s, bool launched = true) {
 // GPMI_FLOW=0 keeps the stream-ordered schedule everywhere; GPMI_FLOW_MIN=<tile rows> (default 8) is the smallest
 // tail worth a task kernel
 bool potrf_flow_enabled(gpmi_ctx* c, Lane& lane, int m) {
-  static const bool on = [] {
-    const char* e = std::getenv("GPMI_FLOW");
-    return !e || std::atoi(e) != 0;
-  }();
-  static const int min_rows = [] {
-    const char* e = std::getenv("GPMI_FLOW_MIN");
-    return e ? std::atoi(e) : 8;
-  }();
+  static const bool on = env_int("GPMI_FLOW", 1) != 0;
+  static const int min_rows = env_int("GPMI_FLOW_MIN", 8);
   // the task kernel keeps a 64 KiB operand ring + 4 KiB of list state in static LDS and counts on two workgroups per CU
   // (gfx950: 160 KiB per CU); a part with less takes the stream-ordered schedule
   static const bool lds_ok = [&] {
@@ -1093,11 +852,7 @@ bool potrf_flow_tail(gpmi_ctx* c, Lane& lane, double* A, int64_t ld, double* inv
   const int m = nt - t0;
   hipStream_t sf = lane.stream, sp = lane.sp[0], su = lane.su[0];
   const int ncu_u = c->ncu - c->pair_cus[0];
-  static const int wgs_per_cu = [] {
-    const char* e = std::getenv("GPMI_FLOW_WGS");
-    const int v = e ? std::atoi(e) : 2;
-    return (v == 1 || v == 2) ? v : 2;
-  }();
+  static const int wgs_per_cu = env_int("GPMI_FLOW_WGS", 2) == 1 ? 1 : 2;
   // (a lone resident workgroup must be able to adopt every list: never more lists than FLOW_MAX_LISTS)
   const int nwg = wgs_per_cu * ncu_u < FLOW_MAX_WGS ? wgs_per_cu * ncu_u : FLOW_MAX_WGS;
   if (!flow_gate_try(c->device)) return false;
@@ -1154,7 +909,7 @@ bool potrf_flow_tail(gpmi_ctx* c, Lane& lane, double* A, int64_t ld, double* inv
   if (trace_path && trace.alloc(nullptr, trace_words) == GPMI_OK)
     (void)hipMemsetAsync(trace, 0, sizeof(unsigned long long) * trace_words, sf);
   fa.trace = trace;
-  unsigned long long* ctrace = trace ? trace + 4 * ntasks : nullptr;  // per column: potrf_diag's 24 words, Tc 2, Uc 2
+  unsigned long long* ctrace = trace ? trace + 4 * ntasks : nullptr;  // per column: potrf_diag's 24 words, worker 0's 4
   static const bool want_stats = std::getenv("GPMI_FLOW_STATS") != nullptr;
   unsigned long long* stats = want_stats ? reinterpret_cast<unsigned long long*>(fl + FL_STATS) : nullptr;
   fa.stats = stats;
@@ -1167,15 +922,8 @@ bool potrf_flow_tail(gpmi_ctx* c, Lane& lane, double* A, int64_t ld, double* inv
     (void)hipStreamWaitEvent(su, lane.ev_join, 0);
   }
   lane_run_early(lane, sf);  // (sf idles until the join: the alpha phase's factor-independent launches, Lane::EarlyWork)
-  static const int proto = [] {
-    const char* e = std::getenv("GPMI_FLOW_PROTO");
-    return e ? std::atoi(e) : 0;
-  }();
   const dim3 grid((unsigned)nwg);
-  if (proto == 1) hipLaunchKernelGGL(flow_task_kernel<1>, grid, dim3(256), 0, su, fa);
-  else if (proto == 2) hipLaunchKernelGGL(flow_task_kernel<2>, grid, dim3(256), 0, su, fa);
-  else if (proto == 3) hipLaunchKernelGGL(flow_task_kernel<3>, grid, dim3(256), 0, su, fa);
-  else hipLaunchKernelGGL(flow_task_kernel<0>, grid, dim3(256), 0, su, fa);
+  hipLaunchKernelGGL(flow_task_kernel, grid, dim3(256), 0, su, fa);
 
   // the chain
   int* Lcnt = fl + FL_LCNT;
@@ -1186,72 +934,26 @@ bool potrf_flow_tail(gpmi_ctx* c, Lane& lane, double* A, int64_t ld, double* inv
       double* Akk = A0 + (int64_t)k * NB * ld + (int64_t)k * NB;
       double* invDk = invD0 + (int64_t)k * NB * NB;
       unsigned long long* ck = ctrace ? ctrace + (int64_t)k * (GPMI_STAMP_WORDS + 4) : nullptr;
-      // GPMI_CHAIN_TILES=0: the generic kernels (32-row TRSM slabs, 64 x 64 update tiles) as until round 3; 1: the two
-      // 16 x 16-tile kernels; 2: both products in one launch behind potrf_diag (round 4); 3 (default, round 5): potrf_diag
-      // and both products in ONE launch, the products one row block of the inverse behind the factorisation - same bits
-      static const int chain_mode = env_int("GPMI_CHAIN_TILES", 3);
-      if (chain_mode == 3) {
-        ChainColArgs ca{};
-        ca.Akk = Akk;
-        ca.invD = invDk;
-        ca.ld = ld;
-        ca.info = info;
-        ca.col0 = (t0 + k) * NB;
-        ca.dbg = ck;
-        ca.pub = k > 0 ? Lcnt + k : nullptr;  // (the strip X of column k - 1 was stored by the launch before this one)
-        ca.pub_val = 4 * k;
-        ca.flags = fl;
-        ca.k = k;
-        ca.wait1 = F + (k + 1) * m + k;
-        ca.wait2 = F + (k + 1) * m + (k + 1);
-        ca.wait_val = 4 * k;
-        ca.wait_ticks = stats ? stats + 4 : nullptr;
-        ca.trace = ck ? ck + GPMI_STAMP_WORDS : nullptr;
-        const bool has_next = k + 1 < m;
-        if (!has_next) ca.wait1 = ca.wait2 = nullptr;
-        hipLaunchKernelGGL(chain_column_kernel, dim3(has_next ? 1 + CC_WORKERS : 1), dim3(512), 0, sp, ca);
-        launch_potrf_diag_fault(sp, Akk, ld);
-        continue;
-      }
-      // (fused: the strip X of column k - 1 was stored by the launch before this one; potrf_diag publishes it)
-      const bool pub_here = chain_mode == 2 && k > 0;
-      launch_potrf_diag(sp, Akk, ld, invDk, info, (t0 + k) * NB, ck, BatchShape(), pub_here ? Lcnt + k : nullptr, 4 * k);
-      if (k + 1 < m) {
-        double* A21 = Akk + (int64_t)NB * ld;
-        const bool chain_tiles = chain_mode != 0;
-        GemmBatch tc;
-        tc.ncu_hint = c->pair_cus[0];
-        tc.b_lower_tri = true;
-        tc.hook.pub = fl + FL_DDONE;
-        tc.hook.pub_val = k + 1;
-        tc.hook.wait = F + (k + 1) * m + k;
-        tc.hook.wait_val = 4 * k;
-        tc.hook.abort = fl + FL_ABORT;
-        tc.hook.info = info;
-        tc.hook.wait_ticks = stats ? stats + 4 : nullptr;
-        tc.hook.trace = ck ? ck + GPMI_STAMP_WORDS : nullptr;
-        GemmBatch uc;
-        uc.hook.pub = Lcnt + k + 1;
-        uc.hook.pub_val = 4 * (k + 1);
-        uc.hook.wait = F + (k + 1) * m + (k + 1);
-        uc.hook.wait_val = 4 * k;
-        uc.hook.abort = fl + FL_ABORT;
-        uc.hook.info = info;
-        uc.hook.wait_ticks = stats ? stats + 5 : nullptr;
-        uc.hook.trace = ck ? ck + GPMI_STAMP_WORDS + 2 : nullptr;
-        if (chain_mode == 2) {
-          ChainFusedArgs fa2{A21, A21 + NB, invDk, ld, fl + FL_ROWCNT, 8 * (k + 1), uc.hook.wait, uc.hook.wait_val, tc.hook};
-          hipLaunchKernelGGL(chain_fused_kernel, dim3(32), dim3(512), 0, sp, fa2);
-        } else if (chain_tiles) {
-          ChainArgs ta{A21, A21 + NB, invDk, ld, tc.hook};
-          hipLaunchKernelGGL(chain_trsm_kernel, dim3(NB / 16), dim3(512), 0, sp, ta);
-          ChainArgs ua{A21, A21 + NB, invDk, ld, uc.hook};
-          hipLaunchKernelGGL(chain_syrk_kernel, dim3(9), dim3(256), 0, sp, ua);
-        } else {
-          launch_gemm_nt(sp, TILES_RECT, OP_ASSIGN, A21, ld, A21, ld, invDk, NB, 1, 1, NB, nullptr, tc);
-          launch_gemm_nt(sp, TILES_LOWER, OP_SUB, A21 + NB, ld, A21, ld, A21, ld, 1, 1, NB, nullptr, uc);
-        }
-      }
+      ChainColArgs ca{};
+      ca.Akk = Akk;
+      ca.invD = invDk;
+      ca.ld = ld;
+      ca.info = info;
+      ca.col0 = (t0 + k) * NB;
+      ca.dbg = ck;
+      ca.pub = k > 0 ? Lcnt + k : nullptr;  // (the strip X of column k - 1 was stored by the launch before this one)
+      ca.pub_val = 4 * k;
+      ca.flags = fl;
+      ca.k = k;
+      ca.wait1 = F + (k + 1) * m + k;
+      ca.wait2 = F + (k + 1) * m + (k + 1);
+      ca.wait_val = 4 * k;
+      ca.wait_ticks = stats ? stats + 4 : nullptr;
+      ca.trace = ck ? ck + GPMI_STAMP_WORDS : nullptr;
+      const bool has_next = k + 1 < m;
+      if (!has_next) ca.wait1 = ca.wait2 = nullptr;
+      hipLaunchKernelGGL(chain_column_kernel, dim3(has_next ? 1 + CC_WORKERS : 1), dim3(512), 0, sp, ca);
+      launch_potrf_diag_fault(sp, Akk, ld);
     }
   }
   (void)hipEventRecord(lane.ev_panel, sp);
@@ -1283,9 +985,8 @@ bool potrf_flow_tail(gpmi_ctx* c, Lane& lane, double* A, int64_t ld, double* inv
     (void)hipMemcpy(h, stats, sizeof(h), hipMemcpyDeviceToHost);
     std::fprintf(stderr,
                  "[flow] m=%d tasks=%llu polls=%llu | per workgroup: waiting %.1f us, in tasks %.1f us | chain waited: "
-                 "Tc %.1f us, Uc %.1f us\n",
-                 m, h[3], h[2], h[0] * 0.01 / grid.x, h[1] * 0.01 / grid.x,
-                 h[4] * 0.01 / (env_int("GPMI_CHAIN_TILES", 3) == 3 ? (double)CC_WORKERS : 4.0), h[5] * 0.01 / 3.0);
+                 "%.1f us per worker\n",
+                 m, h[3], h[2], h[0] * 0.01 / grid.x, h[1] * 0.01 / grid.x, h[4] * 0.01 / CC_WORKERS);
   }
   return true;
 }

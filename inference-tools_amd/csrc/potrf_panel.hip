@@ -14,8 +14,9 @@
 //                     inverse is complete, in LDS, and nothing waits.
 // Behind potrf_diag's last elimination there is left, for the resident workers: the last row block of the inverse, the
 // hand-off, 32 MFMAs per wave and the store: 6 - 7 us.  A tile beyond the resident set costs its CU 11 us (8.6 of MFMAs).
-// The sums are chain_trsm_kernel's, i.e. those of the generic TRSM launch at either tile height (potrf_colblock.h): the
-// factor, the inverses, the log-determinant and info are bit-identical to the two-launch form (GPMI_PANEL_FUSED=0).
+// The sums are those of gemm_tiles::staged_tile<..., BTRI>, i.e. of the generic TRSM launch at either tile height
+// (potrf_colblock.h): the factor, the inverses, the log-determinant and info are bit-identical to the two-launch form
+// (GPMI_PANEL_FUSED=0).
 //
 // Flags: a block of ints the lane owns (Lane::panel_flags), zeroed once at its allocation and never again - the counters
 // are monotone: launch number `seq` of the lane (Lane::panel_seq) finds DIAG_INVERSE * seq in every row counter and waits for

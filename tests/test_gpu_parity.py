@@ -1686,9 +1686,6 @@ def test_schedule_variants_agree(tmp_path):
         {"GPMI_LOOKAHEAD_MIN": "24", "GPMI_KBUILD_NO_SPLIT": "1"},
         {"GPMI_M32_MAX": "0", "GPMI_SPLIT_PCT": "0", "GPMI_BIG_MIN": "64"},
         {"GPMI_FLOW": "0"},  # the last 52 tile rows in stream order instead of as flag-ordered tile tasks
-        {"GPMI_CHAIN_TILES": "2"},  # the tail's chain: potrf_diag + one fused launch per column (round 4) instead of ONE launch
-        {"GPMI_CHAIN_TILES": "1"},  # ... two 16 x 16-tile launches behind potrf_diag
-        {"GPMI_CHAIN_TILES": "0"},  # ... and the generic tile kernels
         {"GPMI_LOOKAHEAD_MIN": "84", "GPMI_FLOW_NEAR_WGS": "64", "GPMI_FLOW_NEAR": "0", "GPMI_FLOW_NEAR_D": "5"},
         # (round 6) the task lists of rounds 3-5: one list per workgroup, whole 128 x 128 chunks in q order
         {"GPMI_FLOW_SPLIT": "0", "GPMI_FLOW_QUARTER": "99999"},
@@ -1711,7 +1708,7 @@ def test_schedule_variants_agree(tmp_path):
             continue
         for q in ("alpha", "logdet", "mu", "sig"):
             check(r[q + "0"], base[q + "0"], 1e-11, f"{q} under {extra}")
-            if "GPMI_FLOW" in extra or "GPMI_FLOW_NEAR" in extra or "GPMI_CHAIN_TILES" in extra:  # same sums: same bits
+            if "GPMI_FLOW" in extra or "GPMI_FLOW_NEAR" in extra:  # same sums: same bits
                 assert np.array_equal(r[q + "0"], base[q + "0"]), (extra, q)
 
 
@@ -1765,8 +1762,8 @@ def test_flow_tail_is_bit_identical_to_stream_order(tmp_path, n):
     """The flag-ordered tile-task factorisation of the chain-bound part (csrc/potrf_flow.hip: persistent task kernel
     beside the bare panel chain; the whole matrix at these sizes) against the stream-ordered schedule (GPMI_FLOW=0):
     same tile bodies, same order of summation for every element, hence the SAME BITS in alpha, log det, mean and sigma -
-    also with another deal of the tasks and with every matrix byte loaded at agent scope (GPMI_FLOW_PROTO=2).  A tile
-    used before its inputs were final, or a stale cache line, is an O(1) difference here."""
+    also with another deal of the tasks.  A tile used before its inputs were final, or a stale cache line, is an O(1)
+    difference here."""
     import os
     import subprocess
     import sys
@@ -1776,7 +1773,7 @@ def test_flow_tail_is_bit_identical_to_stream_order(tmp_path, n):
     res = []
     # (round 6: the default lists hold every chunk as four quarter tasks, the urgent ones in lists of their own; the fourth
     # variant is the one-list schedule of rounds 3-5 with whole 128 x 128 chunks - the ring bodies sum alike)
-    for k, extra in enumerate(({"GPMI_FLOW": "0"}, {}, {"GPMI_FLOW_NEAR_WGS": "16", "GPMI_FLOW_PROTO": "2", "GPMI_FLOW_WGS": "1"},
+    for k, extra in enumerate(({"GPMI_FLOW": "0"}, {}, {"GPMI_FLOW_NEAR_WGS": "16", "GPMI_FLOW_WGS": "1"},
                                {"GPMI_FLOW_SPLIT": "0", "GPMI_FLOW_QUARTER": "99999"},
                                {"GPMI_FLOW_URGENT": "99", "GPMI_FLOW_QUARTER": "1"})):
         out = str(tmp_path / f"f{k}.npz")
