@@ -1,6 +1,6 @@
 """Error / warning texts of the density estimators, of the matrix plot and of the chains' plot checks.  The wording, line
 breaks and indentation follow the reference (pdf/kde.py:53-60, pdf/base.py:41-48, pdf/hdi.py:27-91, plotting.py:91-135,
-plotting.py:331-333, plotting.py:416-434, plotting.py:481-518, mcmc/base.py:218-237, mcmc/utilities.py:90, :98-148, mcmc/hmc/mass.py, mcmc/hmc/__init__.py:152-157) so that callers that match on messages keep working; the KDE2D texts are this package's own (the
+plotting.py:331-333, plotting.py:416-434, plotting.py:481-518, mcmc/base.py:218-237, mcmc/utilities.py:90, :98-148, mcmc/hmc/mass.py, mcmc/hmc/__init__.py:152-157, mcmc/ensemble.py:93-179) so that callers that match on messages keep working; the KDE2D texts are this package's own (the
 reference has none)."""
 
 
@@ -191,3 +191,64 @@ def lockstep_needs_gradient() -> str:
 def ladders_are_gibbs() -> str:
     return ("advance_ladders drives GibbsChain ladders; advance a ladder of HamiltonianChain objects with "
             "ParallelTempering(chains, batch_value_and_grad=...), which uses advance_lockstep_hmc")
+
+
+def ensemble_positions_type(kind) -> str:
+    return _framed(16, "EnsembleSampler", "error", "'starting_positions' should be a numpy.ndarray, but instead has type:",
+                   f"{kind}")
+
+
+def ensemble_positions_shape(shape) -> str:
+    return _framed(16, "EnsembleSampler", "error", "'starting_positions' should be a numpy.ndarray with shape",
+                   "(n_walkers, n_parameters), where n_walkers >= n_parameters + 1.",
+                   f"Instead, the given array has shape {shape}.")
+
+
+def ensemble_positions_not_finite() -> str:
+    return _framed(16, "EnsembleSampler", "error", "The given 'starting_positions' array contains at least one",
+                   "value which is non-finite.")
+
+
+def ensemble_zero_variance() -> str:
+    return _framed(20, "EnsembleSampler", "error", "The values given in 'starting_positions' have zero variance,",
+                   "and therefore the walkers are unable to move.")
+
+
+def ensemble_zero_variance_columns() -> str:
+    return _framed(20, "EnsembleSampler", "error", "For one or more variables, The values given in 'starting_positions' ",
+                   "have zero variance, and therefore the walkers are unable to move", "in those variables.")
+
+
+def ensemble_colinear() -> str:
+    return _framed(20, "EnsembleSampler", "error", "The values given in 'starting_positions' are approximately",
+                   "co-linear for one or more pair of variables. This will",
+                   "prevent the walkers from moving properly in those variables.")
+
+
+def ensemble_alpha() -> str:
+    return _framed(16, "EnsembleSampler", "error", "The given value of the 'alpha' parameter must be greater than 1.")
+
+
+def ensemble_update(update) -> str:
+    return _framed(16, "EnsembleSampler", "error", "The 'update' argument must be either 'serial' or 'split',",
+                   f"but the value given was {update!r}.")
+
+
+def ensemble_split_walkers(n_walkers, n_parameters) -> str:
+    return _framed(16, "EnsembleSampler", "error", "update='split' moves each half of the walkers against the other half and",
+                   f"needs n_walkers >= 2 * (n_parameters + 1) = {2 * (n_parameters + 1)}, but n_walkers is {n_walkers}.")
+
+
+def ensemble_bounds_type(kind) -> str:
+    return _framed(16, "EnsembleSampler", "error", "'bounds' should be a Bounds object or a pair (lower, upper) of arrays,",
+                   f"but instead has type {kind}.")
+
+
+def ensemble_no_posterior() -> str:
+    return _framed(16, "EnsembleSampler", "error", "Neither 'posterior' nor 'batch_posterior' was given:",
+                   "the sampler has nothing to evaluate the walkers with.")
+
+
+def lockstep_ensembles_mixed(sizes) -> str:
+    return ("advance_lockstep_ensembles evaluates the rows of all samplers in one (rows, n_parameters) batch, but the "
+            f"samplers have n_parameters = {sizes}")
