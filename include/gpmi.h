@@ -445,6 +445,10 @@ int gpmi_predict_dense(gpmi_ctx* ctx, const double* Kq_host, int64_t m, double* 
 /* X = Q L^-T for m right-hand sides given as rows (m x n), and / or their Gram matrix X X^T (m x m): the building
  * block of build_posterior (regression.py:447-448) and of gradient / spatial_derivatives (:374-383, :410-417) */
 int gpmi_solve_rows(gpmi_ctx* ctx, const double* Q_host, int64_t m, double* X_host, double* gram_host);
+/* Z = Q K^-1 = Q L^-T L^-1 for m right-hand sides given as rows (m x n; Z_host m x n), for any fitted model (gpmi_fit or
+ * gpmi_fit_dense): the K^-1 k of spatial_derivatives (regression.py:410) with caller-built rows.  The rows are solved in
+ * place in chunks of 1024, forward then backward, by the code gpmi_spatial_derivatives runs */
+int gpmi_solve_rows_kinv(gpmi_ctx* ctx, const double* Q_host, int64_t m, double* Z_host);
 
 /* ---- kernel-density estimation (GaussianKDE, inference/pdf/kde.py) -------------------
  * A density object holds a sorted sample and its region table on the device; the handle owns it, and gpmi_destroy

@@ -394,6 +394,16 @@ int enqueue_inverse_factor(gpmi_ctx* c, Lane& L, Lane& F) {
   return GPMI_OK;
 }
 
+// c->Q2 (mp rows) <- c->Q2 K^-1 with the factor of lane F, in place: the forward solve through the scratch panel, then the
+// backward one (gpmi_spatial_derivatives, gpmi_solve_rows_kinv)
+int enqueue_rows_kinv(gpmi_ctx* c, Lane& F, hipStream_t s, int64_t mp) {
+  if (int rc = ensure_inv2(c, F, s)) return rc;
+  if (int rc = ensure_trsm_panel(c, mp)) return rc;
+  trsm_rows_forward(c, s, F.A, c->np, c->ld, F.inv2, c->Q2, mp, false, nullptr, c->trsm_panel);
+  trsm_rows_backward(c, s, F.A, c->np, c->ld, F.invD, c->Q2, mp, F.inv2, c->trsm_panel);
+  return GPMI_OK;
+}
+
 // workspace for `want` small problems advancing in lockstep (capped by a 24 GiB budget and 512 matrices: round 6 - 6 GiB /
 // 256 until then; one chunk of 512 evaluations at N = 2048 instead of three of 171 is 3.7 % faster, and two asynchronous
 // slots of 256 carry config 5's 512 chains in two groups: 14 600 -> 15 450 evaluations/s through the tempering driver)

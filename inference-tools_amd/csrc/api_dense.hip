@@ -276,5 +276,27 @@ int gpmi_solve_rows(gpmi_ctx* c, const double* Q_host, int64_t m, double* X_host
   return GPMI_OK;
 }
 
+int gpmi_solve_rows_kinv(gpmi_ctx* c, const double* Q_host, int64_t m, double* Z_host) {
+  if (!c) return GPMI_ERR_ARG;
+  ARGCHK(c, c->fitted, "gpmi_solve_rows_kinv needs a successful fit");
+  ARGCHK(c, Q_host && m > 0 && Z_host, "NULL argument or m <= 0");
+  if (int rc = set_device(c)) return rc;
+  Lane& L = c->lanes[0];
+  hipStream_t s = L.stream;
+  const int64_t chunk = 1024;  // as gpmi_spatial_derivatives, whose pair of in-place solves this is
+  for (int64_t m0 = 0; m0 < m; m0 += chunk) {
+    const int64_t mc = (m - m0 < chunk) ? m - m0 : chunk;
+    const int64_t mp = round_up(mc, GPMI_NB);
+    if (int rc = ensure_query_ws(c, mp)) return rc;
+    if (int rc = upload_query_panel(c, s, c->Q2, Q_host + m0 * c->n, mc, mp)) return rc;
+    if (int rc = enqueue_rows_kinv(c, L, s, mp)) return rc;
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpy2DAsync(Z_host + m0 * c->n, sizeof(double) * c->n, c->Q2, sizeof(double) * c->ld, sizeof(double) * c->n,
+                               (size_t)mc, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+  }
+  return GPMI_OK;
+}
+
 }  // extern "C"
 

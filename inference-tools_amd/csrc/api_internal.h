@@ -172,6 +172,7 @@ int ensure_second_matrix(gpmi_ctx* c, Lane& L);
 int ensure_inv2(gpmi_ctx* c, Lane& F, hipStream_t s);
 int ensure_trsm_panel(gpmi_ctx* c, int64_t rows);
 int enqueue_inverse_factor(gpmi_ctx* c, Lane& L, Lane& F);
+int enqueue_rows_kinv(gpmi_ctx* c, Lane& F, hipStream_t s, int64_t mp);
 void free_batch_ws(gpmi_ctx* c);  // every lockstep buffer, caps to 0
 int ensure_batch_ws(gpmi_ctx* c, int want);
 int ensure_batch_grad_ws(gpmi_ctx* c, int want, int n_theta);

@@ -572,6 +572,14 @@ class GpEngine(_DeviceCommMixin, _DrawsMixin):
         self.h.call("gpmi_solve_rows", dptr(Q), m, dptr(X), dptr(G))
         return X, G
 
+    def solve_rows_kinv(self, Q):
+        """Z = Q K^-1 for the rows of Q (m x n): the forward and the backward row solve with the fitted factor."""
+        Q = as_f64(Q)
+        m = Q.shape[0]
+        Z = np.empty((m, self.n))
+        self.h.call("gpmi_solve_rows_kinv", dptr(Q), m, dptr(Z))
+        return Z
+
     # -- instrumentation ----------------------------------------------------------------
     def timer_start(self):
         self.h.call("gpmi_timer_start")

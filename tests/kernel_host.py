@@ -10,6 +10,8 @@ summation order, tile shape or schedule, an fp64 kernel must then return the hos
   * Cholesky: L0 has identity 128 x 128 diagonal blocks and integers from {-span .. span} in every block below them;
     A = L0 L0^T.  Every pivot a blocked factorisation with 128-wide (or narrower, aligned) blocks meets is exactly 1,
     every inverse diagonal block exactly I, every TRSM and trailing update integer arithmetic: the factor is L0.
+  * K^-1: int_nilpotent_chol_case keeps the entries of L0 below the diagonal tiles to blocks between a few groups of
+    tile rows, so that L0^-1 and K^-1 = L0^-T L0^-1 are small-integer matrices as well.
 
 Bounded cases.  rho_* are componentwise backward-error ratios in units of u = 2^-53, with the residual accumulated in
 np.longdouble (64-bit mantissa: its own rounding is 2^-11 u per operation and cannot reach the caps they are compared
@@ -77,6 +79,61 @@ def int_chol_case(n, seed, span=1, f32=None):
     else:
         A = L0 @ L0.T
     return L0, A
+
+
+def int_nilpotent_chol_case(groups, seed, n=None):
+    """(L0, W, A) with W = L0^-1 a small-integer matrix: an integer factor whose INVERSE is exact too, for the paths that
+    form L^-T and K^-1 = L^-T L^-1 (int_chol_case's inverse grows like 128^(nt - 1) and leaves 2^53 after a few tiles).
+    The tile rows are cut into len(groups) consecutive groups of groups[i] 128-tiles; L0 = I + M with integers from
+    {-1, 0, 1} in the blocks (group_i, group_j), i > j, and nothing else: M^g = 0 for g groups, so
+    W = I - M + M^2 - ... +- M^(g-1), and A = L0 L0^T factors to L0 with every pivot 1 as for int_chol_case.
+    n below 128 * sum(groups) returns the leading n x n parts (the leading part of a unit lower triangular matrix
+    inverts to the leading part of its inverse; A is then the leading part of the full A).
+
+    Sufficient condition for exactness, asserted here: with aW = I + |M| + ... + |M|^(g-1) >= |W|, |L0| entrywise, every
+    intermediate of a blocked substitution on the identity is bounded entrywise by aW, a product with an inverse block
+    sums at most 512 and K^-1 = W^T W at most n products of two such entries: n * aW.max()^2 < 2^53 covers the whole
+    path, whatever the order of summation.  The matrix products below are formed in fp64 and are exact for the same
+    reason (the partial sums of aW are non-negative integers below aW.max())."""
+    full = TILE * int(sum(groups))
+    n = full if n is None else n
+    assert 0 < n <= full and len(groups) >= 1
+    rng = np.random.default_rng(seed)
+    M = rng.integers(-1, 2, (full, full)).astype(np.float64)
+    grp = np.repeat(np.arange(len(groups)), np.asarray(groups) * TILE)
+    M[grp[:, None] <= grp[None, :]] = 0.0
+    M = M[:n, :n]
+    I = np.eye(n)
+    aM = np.abs(M)
+    aW, W = I.copy(), I.copy()
+    for _ in range(len(groups) - 1):  # Horner: I + |M| (I + |M| (...)),  I - M (I - M (...))
+        aW = I + aM @ aW
+        W = I - M @ W
+    bound = n * float(aW.max()) ** 2
+    assert bound < 2.0 ** 53, f"groups {tuple(groups)} at n = {n}: n aW.max()^2 = 2^{np.log2(bound):.1f} is not below 2^53"
+    L0 = I + M
+    A = L0 @ L0.T
+    return L0, W, A
+
+
+# (n, groups) of the exact K^-1 cases (seed NILPOTENT_SEED); 900 is the 1024 case cut to 900 rows; 768 has six tiles
+# (nt % 4 == 2), the last outer block made of a tile of the second group and the third group's only tile
+NILPOTENT_SEED = 1
+NILPOTENT_CASES = [(384, (1, 1, 1)), (640, (1, 1, 1, 1, 1)), (768, (2, 3, 1)), (896, (2, 2, 2, 1)), (900, (3, 3, 2)),
+                   (1024, (3, 3, 2)), (1536, (3, 3, 3, 3)), (2176, (5, 4, 4, 4))]
+# (n, m) of the exact Z = Q K^-1 cases on int_chol_case(n): Z0 m x n from {-1, 0, 1}, Q = Z0 A
+ROWS_KINV_CASES = [(384, 1), (640, 129), (768, 129), (896, 127), (1024, 513), (2176, 129), (2176, 1024), (2176, 1025),
+                   (6656, 1024)]
+
+
+def rows_kinv_case(A, m, seed):
+    """(Z0, Q = Z0 A) for the exact backward row solve, with the condition that keeps every product with a 512 x 512
+    inverse block (entries below 2^15, 512 terms) an exact integer sum asserted."""
+    n = A.shape[0]
+    Z0 = np.random.default_rng(seed).integers(-1, 2, (m, n)).astype(np.float64)
+    Q = Z0 @ A  # exact: |A| <= n, every partial sum an integer below n^2
+    assert 512 * np.abs(Q).max() * 2.0 ** 15 < 2.0 ** 53
+    return Z0, Q
 
 
 def spd_case(n, kind, seed):
@@ -255,6 +312,30 @@ def inverse_residual(A, iK, rows=None):
     return float(np.abs(R).max())
 
 
+def loo_vectors(alpha, ikdiag):
+    """(c1, c2) of the leave-one-out gradient in longdouble: var = 1 / diag(K^-1), c1 = alpha var,
+    c2 = var (1 + var alpha^2) / 2."""
+    var = 1 / _ld(ikdiag)
+    a = _ld(alpha)
+    return a * var, var * (1 + var * a * a) / 2
+
+
+def rho_loo_p(p, iK, alpha, ikdiag):
+    """max_i |p - K^-1 c1|_i / (|K^-1| |c1|)_i for an exactly known K^-1 (integer data)."""
+    c1, _ = loo_vectors(alpha, ikdiag)
+    R = _ld(p) - _ld(iK) @ c1
+    return _ratio(R, np.abs(iK) @ np.abs(c1.astype(np.float64)))
+
+
+def rho_loo_w(Wm, iK, alpha, ikdiag, rows=None):
+    """max |W - K^-1 diag(c2) K^-1| / (|K^-1| diag(c2) |K^-1|) over the given rows (default check_rows), K^-1 exact."""
+    n = iK.shape[0]
+    rows = check_rows(n) if rows is None else rows
+    _, c2 = loo_vectors(alpha, ikdiag)
+    R = _ld(Wm[rows]) - (_ld(iK[rows]) * c2) @ _ld(iK).T
+    return _ratio(R, (np.abs(iK[rows]) * c2.astype(np.float64)) @ np.abs(iK).T)
+
+
 def kappa_blocks(L, b):
     """The largest 2-norm condition number of the b x b diagonal blocks of the factor L (the last one may be smaller):
     what a multiplication by an explicitly inverted diagonal block can cost in backward error."""
@@ -304,6 +385,22 @@ def cap_solve_rows(n, k512=0.0):
 
 def cap_alpha(n, k128=0.0):
     return 3 * (n + 1) * (1 + k128) ** 2
+
+
+def cap_loo_p(n):
+    """p = K^-1 c1 with K^-1 exact: an n-term dot product in any order of summation (each term one product and at most
+    n - 1 additions, or FMAs: n roundings) of c1 = alpha * (1 / d), two roundings: (1 + delta)^(n + 2), gamma_(n+2) <
+    (n + 3) u for n u << 1; one more unit for the rounding of p's own reference."""
+    return n + 4
+
+
+def cap_loo_w(n):
+    """W = G G^T, G = K^-1 diag(s), s = sqrt(c2).  c2 as computed: var = 1 / d (1 rounding, used twice), var alpha alpha
+    (2 more), 1 + . (1; the terms are positive, the sum's relative error is no larger than the term's), the product with
+    var / 2 (1; the halving is exact): at most 6 relative roundings under the square root, which halves them, plus its
+    own: s within (1 + delta)^4 of sqrt(c2).  G_ij = K^-1_ij s_j: 5.  A term G_ij G_kj of the n-term dot product carries
+    10 and collects n more in any order of summation: gamma_(n+10) < (n + 11) u; one more unit as for p."""
+    return n + 12
 
 
 def cap_inverse(n, cond_a, k128=0.0):

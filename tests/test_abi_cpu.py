@@ -20,7 +20,7 @@ def declared_symbols():
 def test_header_declares_the_path():
     syms = declared_symbols()
     for must in ("gpmi_set_data", "gpmi_fit", "gpmi_lml", "gpmi_lml_batch", "gpmi_lml_grad", "gpmi_predict",
-                 "gpmi_sgp_schedule", "gpmi_select_schedule", "gpmi_live_bytes"):
+                 "gpmi_sgp_schedule", "gpmi_select_schedule", "gpmi_live_bytes", "gpmi_solve_rows", "gpmi_solve_rows_kinv"):
         assert must in syms
 
 

@@ -51,6 +51,97 @@ def test_integer_sweeps_are_exact_on_the_host():
     assert np.array_equal(W @ L0[:512, :512], np.eye(512))
 
 
+# ---- the exact K^-1 cases (int_nilpotent_chol_case) and the exact Z = Q K^-1 cases
+@pytest.mark.parametrize("n,groups", kh.NILPOTENT_CASES, ids=[f"n{n}" for n, _ in kh.NILPOTENT_CASES])
+def test_nilpotent_factor_and_its_inverse_are_exact(n, groups):
+    """L0 W == I and A == L0 L0^T hold exactly, W and K^-1 are integer matrices inside the asserted bound, and LAPACK
+    and the plain substitutions reproduce L0, W^T, W^T W and Z0 bit for bit: what parts F and G ask of the device."""
+    L0, W, A = kh.int_nilpotent_chol_case(groups, kh.NILPOTENT_SEED, n)
+    I = np.eye(n)
+    assert L0.shape == W.shape == A.shape == (n, n)
+    assert np.array_equal(L0 @ W, I) and np.array_equal(W @ L0, I)
+    assert np.array_equal(A, L0 @ L0.T) and np.array_equal(A, A.T)
+    assert np.array_equal(W, np.round(W)) and np.array_equal(W, np.tril(W)) and np.array_equal(np.diag(W), np.ones(n))
+    for s in range(0, n, kh.TILE):  # identity diagonal tiles
+        assert np.array_equal(L0[s:s + kh.TILE, s:s + kh.TILE], np.eye(min(kh.TILE, n - s)))
+    iK = W.T @ W
+    assert np.array_equal(iK, np.round(iK)) and n * np.abs(W).max() ** 2 < 2.0 ** 53
+    # the inverse is not trivial: entries beyond {-1, 0, 1} (products of blocks), and of its 512-wide diagonal blocks of
+    # more than one tile (what build_inv2 forms) at most the first is the identity (n = 2176: its group has five tiles)
+    assert np.abs(W).max() > 1
+    dense = [np.count_nonzero(W[s:s + 512, s:s + 512]) > 512 + 1000 for s in range(0, n - kh.TILE, 512)]
+    assert all(dense[1:]) and (dense[0] or n == 2176)
+    if n == 384:  # the same in integer arithmetic
+        Li, Wi = L0.astype(np.int64), W.astype(np.int64)
+        assert np.array_equal(Li @ Wi, np.eye(n, dtype=np.int64))
+        assert np.array_equal(Li @ Li.T, A.astype(np.int64)) and np.array_equal(Wi.T @ Wi, iK.astype(np.int64))
+    assert np.array_equal(np.linalg.cholesky(A), L0)
+    if n <= 1024:  # (the plain substitutions are O(n) NumPy calls of O(n^2) each)
+        assert np.array_equal(kh.substitute_rows(L0, I), W.T)
+        assert np.array_equal(kh.inverse_spd(L0), iK)
+        Z0, Q = kh.rows_kinv_case(A, 5, seed=n)
+        assert np.array_equal(kh.substitute_back_rows(L0, kh.substitute_rows(L0, Q)), Z0)
+    a0 = np.random.default_rng(n + 1).integers(-3, 4, n).astype(float)
+    assert np.array_equal(iK @ (A @ a0), a0)
+
+
+def test_nilpotent_case_cut_is_the_leading_part():
+    L0, W, A = kh.int_nilpotent_chol_case((3, 3, 2), kh.NILPOTENT_SEED)
+    L1, W1, A1 = kh.int_nilpotent_chol_case((3, 3, 2), kh.NILPOTENT_SEED, 900)
+    assert np.array_equal(L1, L0[:900, :900]) and np.array_equal(W1, W[:900, :900]) and np.array_equal(A1, A[:900, :900])
+
+
+def test_nilpotent_builder_refuses_a_partition_beyond_2_to_53():
+    with pytest.raises(AssertionError, match="not below 2\\^53"):
+        kh.int_nilpotent_chol_case((2, 2, 2, 2, 2, 2), kh.NILPOTENT_SEED)
+
+
+def test_tile_report_names_a_wrong_entry_of_the_inverse():
+    L0, W, A = kh.int_nilpotent_chol_case((1, 1, 1), kh.NILPOTENT_SEED)
+    iK = W.T @ W
+    assert kh._tile_report(iK != iK.copy(), "differ from W^T W") == []
+    bad = iK.copy()
+    bad[300, 140] += 1.0
+    msgs = kh._tile_report(bad != iK, "differ from W^T W", bad, iK)
+    assert len(msgs) == 1 and msgs[0].startswith("tile (2, 1): 1 entries differ from W^T W") and "[300, 140]" in msgs[0], msgs
+
+
+@pytest.mark.parametrize("n,m", kh.ROWS_KINV_CASES[:-1], ids=[f"n{n}-m{m}" for n, m in kh.ROWS_KINV_CASES[:-1]])
+def test_rows_kinv_case_meets_its_condition(n, m):
+    """Q = Z0 A of part G stays inside the condition rows_kinv_case asserts, and the two plain substitutions return Z0
+    (on a few of the rows: they are O(n) NumPy calls each)."""
+    L0, A = kh.int_chol_case(n, seed=n + 9)
+    Z0, Q = kh.rows_kinv_case(A, m, seed=n + 37 * m)
+    assert np.array_equal(Q, np.round(Q))
+    rows = slice(0, min(m, 3))
+    assert np.array_equal(kh.substitute_back_rows(L0, kh.substitute_rows(L0, Q[rows])), Z0[rows])
+
+
+@needs_longdouble
+@pytest.mark.parametrize("n,groups", [c for c in kh.NILPOTENT_CASES if c[0] <= 1024],
+                         ids=[f"n{n}" for n, _ in kh.NILPOTENT_CASES if n <= 1024])
+def test_plain_numpy_meets_the_leave_one_out_caps(n, groups):
+    """p = K^-1 c1 and W = K^-1 diag(c2) K^-1 evaluated in plain fp64 NumPy from the exact K^-1, in the order of
+    operations of the device (c1 = alpha (1 / d), G = K^-1 diag(sqrt c2), W = G G^T), meet cap_loo_p and cap_loo_w; a
+    relative perturbation of 1e-10 in one entry does not."""
+    L0, W, A = kh.int_nilpotent_chol_case(groups, kh.NILPOTENT_SEED, n)
+    iK = W.T @ W
+    a0 = np.random.default_rng(n + 1).integers(-3, 4, n).astype(float)
+    d = np.diag(iK).copy()
+    var = 1.0 / d
+    p = iK @ (a0 * var)
+    G = iK * np.sqrt(0.5 * var * (1.0 + var * a0 * a0))
+    Wm = G @ G.T
+    rho_p, rho_w = kh.rho_loo_p(p, iK, a0, d), kh.rho_loo_w(Wm, iK, a0, d)
+    print(f"\nreference n={n}: rho_loo_p {rho_p:.2f} (cap {kh.cap_loo_p(n)}), rho_loo_w {rho_w:.2f} (cap {kh.cap_loo_w(n)})")
+    assert rho_p <= kh.cap_loo_p(n) and rho_w <= kh.cap_loo_w(n)
+    p2, W2 = p.copy(), Wm.copy()
+    i = int(np.argmax(np.abs(p)))
+    p2[i] *= 1 + 1e-10
+    W2[0, 0] *= 1 + 1e-10
+    assert kh.rho_loo_p(p2, iK, a0, d) > 1e3 and kh.rho_loo_w(W2, iK, a0, d) > 1e3
+
+
 def test_builders_are_deterministic():
     a, b = kh.int_gemm_case(256, 128, 48, 160, 80, 176, 1, seed=9), kh.int_gemm_case(256, 128, 48, 160, 80, 176, 1, seed=9)
     for key in ("C0", "A", "B", "E"):

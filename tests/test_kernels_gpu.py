@@ -1,6 +1,7 @@
 """
 Kernel-level tests of the fp64 hot path: gpmi_dev_gemm_nt (gemm_f64.hip), gpmi_dev_potrf (potrf.hip, potrf_flow.hip,
-potrf_diag.h), `info`, and the sweeps and many-right-hand-side solves behind the dense entry points (solve.hip).
+potrf_diag.h), `info`, the sweeps and many-right-hand-side solves behind the dense entry points (solve.hip), and K^-1,
+the leave-one-out pieces and the backward row solve (parts F and G).
 
 Sharpness comes from integer data (tests/kernel_host.py): every operation is then exact, so the device must return the
 host result bit for bit whatever the summation order, tile shape or schedule, and a failure names the 128 x 128 tiles
@@ -335,8 +336,11 @@ def solve_engines():
     _SOLVE.clear()
 
 
-@pytest.mark.parametrize("m", [1, 127, 129, 513])
-@pytest.mark.parametrize("n", [640, 2176])
+# m = 1664 (n = 640 only): mt = 13 tile rows, where the out-of-place product with the inverse blocks leaves the 32-row tiles
+SOLVE_ROWS = [(n, m) for n in (640, 2176) for m in (1, 127, 129, 513)] + [(640, 1664)]
+
+
+@pytest.mark.parametrize("n,m", SOLVE_ROWS, ids=[f"{n}-{m}" for n, m in SOLVE_ROWS])
 def test_solve_rows_and_predict_dense_integer_exact(solve_engines, n, m):
     """X = Q L0^-T for Q = X0 L0^T with X0 from {-1, 0, 1}, its Gram matrix, and predict_dense on the same rows: all
     required bit for bit.  Why every intermediate of the many-right-hand-side path (solve.hip: build_inv2,
@@ -350,8 +354,9 @@ def test_solve_rows_and_predict_dense_integer_exact(solve_engines, n, m):
         X0 and L0;
       * the Gram matrix sums n products of entries of X0 (|G| <= n) and is therefore exactly symmetric; kalpha sums
         q_j a0_j (|.| <= 3 n^2), sumsq sums x^2.
-    The wide-block backward solve (trsm_rows_backward) is not on the path of these entry points (it serves L^-T and
-    the spatial derivatives); lml_dense(want_inverse=True) below exercises the inverse's path."""
+    The backward row solve (trsm_rows_backward) and the in-place forward one are not on the path of these entry points:
+    parts F and G below.  m = 1664 (mt = 13 > 12) moves the product with the inverse blocks from 32 x 32 register-staged
+    tiles to the 64 x 64 ring kernel with the contraction cut at the diagonal (kskip 2)."""
     eng, L0, a0 = solve_engines(n)
     X0 = np.random.default_rng(n + 31 * m).integers(-1, 2, (m, n)).astype(float)
     Q = X0 @ L0.T
@@ -418,3 +423,180 @@ def test_backward_error_bounds(dev, n, kind):
     assert np.array_equal(iK, iK.T), "K^-1 of lml_dense is not bit-symmetric"
     assert res <= kh.cap_inverse(n, cond, k128)
     assert np.array_equal(alpha2, alpha) or kh.rho_solve(A, alpha2, r) <= kh.cap_alpha(n, k128)
+
+
+# =========================================================================================== F. K^-1 and leave-one-out
+# Exact on the factors of kernel_host.int_nilpotent_chol_case, whose inverse W = L0^-1 is a small-integer matrix.  The
+# path (api_single.hip: LN_INVERSE | LN_SYRK | LN_MIRROR, lane_loo_middle) and what each size reaches:
+#   * L^-T from the identity: trsm_rows_forward IN PLACE (Qout == nullptr: the product with the 512 x 512 inverse block
+#     goes to the scratch panel, copy_panel_kernel brings it back) with upper_rhs (block row t joins at its own outer
+#     block: mt = Je).  The products have kskip 2 and run on 32 x 32 tiles up to mt = 12; n = 2176 adds mt = 16 (w = 4:
+#     gemm_dma64_kernel<TILES_RECT, OP_ASSIGN>, the 64 x 64 ring kernel with the shortened contraction) and mt = 17
+#     (w = 1: the 32 x 128 one-tile-column form);
+#   * build_inv2: nt % 4 == 3 (the 1 x 2 corner) at n = 384 and 896, 0 at 1024 and 1536, 1 at 640 and 2176, 2 at 768; n = 900 is
+#     the 1024 case cut to 900 rows, the identity padding inside the last tile;
+#   * K^-1 = L^-T L^-1: lane_syrk(.., 1), always 128 x 128 tiles, gemm_dma_kernel<TILES_LOWER, OP_ASSIGN> with the
+#     contraction of tile row ti started at kbeg = 128 ti; then mirror_lower_kernel;
+#   * diag K^-1: rows_sumsq over L^-T and launch_negate.
+_NIL = {}
+
+
+@pytest.fixture(scope="module")
+def nil_cases():
+    """One case per n, built once: dict(L0, W, A, iK = W^T W, a0 in [-3, 3], y = A a0, v = L0^T a0)."""
+
+    def get(n):
+        if n not in _NIL:
+            L0, W, A = kh.int_nilpotent_chol_case(dict(kh.NILPOTENT_CASES)[n], kh.NILPOTENT_SEED, n)
+            a0 = np.random.default_rng(n + 1).integers(-3, 4, n).astype(float)
+            _NIL[n] = dict(L0=L0, W=W, A=A, iK=W.T @ W, a0=a0, y=A @ a0, v=L0.T @ a0)  # exact: integers below 3 n^2
+        return _NIL[n]
+
+    yield get
+    _NIL.clear()
+
+
+NIL_N = [n for n, _ in kh.NILPOTENT_CASES]
+
+
+@pytest.mark.parametrize("n", NIL_N)
+def test_inverse_integer_exact(nil_cases, n):
+    """lml_dense(A, 0, want_alpha, want_inverse) on A = L0 L0^T with y = A a0, twice on one engine: info == 0,
+    alpha == a0, K^-1 == W^T W in every entry (structural zeros, the identity block of the last group and both
+    triangles included; a failure names its tiles), K^-1 bit-symmetric, and lml == -(v . v) / 2 with v = L0^T a0
+    (ln 1 = 0; v . v is an integer below 9 n^3).  Why it is exact: kernel_host.int_nilpotent_chol_case."""
+    c = nil_cases(n)
+    eng = _engine(n, c["y"])
+    try:
+        for rep in range(2):
+            lml, alpha, iK, info = eng.lml_dense(c["A"], np.zeros(n), want_alpha=True, want_inverse=True)
+            assert info == 0
+            bad = np.flatnonzero(alpha != c["a0"])
+            assert bad.size == 0, f"alpha differs at {bad[:8]} (128-blocks {sorted(set((bad // 128).tolist()))[:8]})"
+            fail_with_tiles(kh._tile_report(iK != c["iK"], "differ from W^T W", iK, c["iK"]),
+                            f"lml_dense K^-1 n={n} (evaluation {rep})")
+            assert np.array_equal(iK, iK.T), "K^-1 of lml_dense is not bit-symmetric"
+            assert lml == -0.5 * (c["v"] @ c["v"])
+    finally:
+        eng.close()
+
+
+@needs_longdouble
+@pytest.mark.parametrize("n", NIL_N)
+def test_leave_one_out_pieces_exact_and_bounded(nil_cases, n):
+    """loo_dense(A, 0, want_gradient_pieces=True) on the same matrices: alpha == a0 and diag K^-1 == diag(W^T W)
+    exactly.  p = K^-1 c1 and W_out = K^-1 diag(c2) K^-1 are not integer (c1 = alpha / d and sqrt(c2) come from a
+    division and a square root); with K^-1 itself exact they are held to componentwise caps in units of u, residuals in
+    longdouble against c1, c2 evaluated in longdouble from a0 and the exact diagonal:
+      |p - K^-1 c1| <= (n + 4) u |K^-1| |c1|                          (kernel_host.cap_loo_p)
+      |W_out - K^-1 diag(c2) K^-1| <= (n + 12) u |K^-1| diag(c2) |K^-1|   (kernel_host.cap_loo_w)
+    Each is the n-term dot-product bound for any order of summation - a term is rounded once as a product and at most
+    n - 1 times in the additions (or n times by FMAs): (1 + delta)^n - plus the roundings of the operands: 2 for c1 (the
+    reciprocal and the product), 10 for a product of two entries of G = K^-1 diag(sqrt c2) (under the root 1 / d, two
+    products with alpha, the addition, the product with var / 2 - var counted twice: 6 roundings, halved by the root, plus
+    the root's own and the scaling of the column: 5 per entry); gamma_(n + 2) < (n + 3) u, gamma_(n + 10) < (n + 11) u,
+    and one unit for the reference.  tests/test_kernel_host_cpu.py: plain fp64 NumPy meets both.  W_out is the SYRK
+    without k-skipping (lane_syrk(.., 0)) of the column-scaled inverse and must be bit-symmetric."""
+    c = nil_cases(n)
+    eng = _engine(n, c["y"])
+    try:
+        alpha, ikdiag, p, Wm, info = eng.loo_dense(c["A"], np.zeros(n), want_gradient_pieces=True)
+    finally:
+        eng.close()
+    assert info == 0
+    bad = np.flatnonzero(alpha != c["a0"])
+    assert bad.size == 0, f"alpha differs at {bad[:8]}"
+    d = np.diag(c["iK"]).copy()
+    bad = np.flatnonzero(ikdiag != d)
+    assert bad.size == 0, f"diag K^-1 differs at {bad[:8]}: got {ikdiag[bad[:4]]}, want {d[bad[:4]]}"
+    rho_p = kh.rho_loo_p(p, c["iK"], c["a0"], d)
+    rho_w = kh.rho_loo_w(Wm, c["iK"], c["a0"], d)
+    print(f"\nKERNEL-RHO loo n={n}: rho_loo_p {rho_p:.2f} (cap {kh.cap_loo_p(n)}) | rho_loo_w {rho_w:.2f} (cap {kh.cap_loo_w(n)})")
+    assert rho_p <= kh.cap_loo_p(n)
+    assert rho_w <= kh.cap_loo_w(n)
+    assert np.array_equal(Wm, Wm.T), "W of loo_dense is not bit-symmetric"
+
+
+# =========================================================================================== G. Z = Q K^-1
+# solve_rows_kinv runs the pair of in-place row solves of the spatial derivatives on caller-built rows: the in-place
+# trsm_rows_forward WITHOUT upper_rhs, then trsm_rows_backward - per outer block, from the last to the first, the k-major
+# product with the untransposed inverse block (kskip 4, kbeg = tj * BN, the mirrored tile-column order; 32 x 32 tiles at
+# every shape the 1024-row chunk allows), the k-major K = 512 OP_SUB update of the columns to the left (64 x 64
+# register-staged tiles; 128 x 128 from mt * J >= 384 tiles on) and the copy of the panel back into Q.
+# On the dense int_chol_case(n): the global inverse is never formed, only the 512-block inverses (entries below 2^15, see
+# test_solve_rows_and_predict_dense_integer_exact).  Z0 from {-1, 0, 1}, Q = Z0 A; the forward solve returns X = Z0 L0
+# (|x| <= n) from right-hand sides whose partial sums are sums of products of entries of X and L0 (below n^2), the
+# backward one Z0 from X; a product with an inverse block sums 512 products of an entry bounded like Q and one below 2^15:
+# 512 |Q|.max 2^15 < 2^53, asserted by kernel_host.rows_kinv_case.
+def _rows_kinv_check(eng, A, n, m):
+    Z0, Q = kh.rows_kinv_case(A, m, seed=n + 37 * m)
+    Z = eng.solve_rows_kinv(Q)
+    fail_with_tiles(kh._tile_report(Z != Z0, "differ from Z0", Z, Z0), f"solve_rows_kinv n={n} m={m}")
+
+
+# (2176, 1024): mt * w * 16 = 512, the last shape of the backward product on 32 x 32 tiles by its own rule; (2176, 1025):
+# a second chunk of one row; (6656, 1024), the slow one: the smallest shape whose update has mt * J >= 384 tiles and
+# runs gemm_nt_kernel<TILES_RECT, OP_SUB, k-major, 128, 128>
+@pytest.mark.parametrize("n,m", kh.ROWS_KINV_CASES,
+                         ids=[f"n{n}-m{m}{'-slow' if n == 6656 else ''}" for n, m in kh.ROWS_KINV_CASES])
+def test_rows_kinv_integer_exact(solve_engines, n, m):
+    """Z = Q K^-1 through solve_rows_kinv equals Z0 bit for bit; a failure names its tiles."""
+    if n != 6656:
+        eng, L0, a0 = solve_engines(n)
+        _rows_kinv_check(eng, kh.int_chol_case(n, seed=n + 9)[1], n, m)  # (the matrix the engine was fitted with)
+        return
+    L0, A = kh.int_chol_case(n, seed=n + 9)
+    eng = _engine(n, np.zeros(n))
+    try:
+        assert eng.fit_dense(A, np.zeros(n))[2] == 0
+        _rows_kinv_check(eng, A, n, m)
+    finally:
+        eng.close()
+
+
+def test_rows_kinv_narrow_steps_integer_exact(tmp_path):
+    """The same at (2176, 129) over the 128-wide steps of the backward solve (GPMI_BACKWARD_OB=0: one in-place k-major
+    product with invD_k and one K = 128 update per tile column).  The switch is read once per process: a fresh child."""
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, m = 2176, 129
+    code = (
+        "import sys\n"
+        f"sys.path[:0] = [{root!r}, {os.path.join(root, 'inference-tools_amd')!r}, {os.path.join(root, 'tests')!r}]\n"
+        "import numpy as np, kernel_host as kh\n"
+        "from inference_amd._engine import GpEngine\n"
+        "n, m = int(sys.argv[2]), int(sys.argv[3])\n"
+        "L0, A = kh.int_chol_case(n, seed=n + 9)\n"
+        "Z0, Q = kh.rows_kinv_case(A, m, seed=n + 37 * m)\n"
+        "eng = GpEngine(np.zeros((n, 1)), np.zeros(n))\n"
+        "info = eng.fit_dense(A, np.zeros(n))[2]\n"
+        "Z = eng.solve_rows_kinv(Q)\n"
+        "eng.close()\n"
+        "np.savez(sys.argv[1], info=np.array([info]), Z=Z, Z0=Z0)\n")
+    out = str(tmp_path / "narrow.npz")
+    run = subprocess.run([sys.executable, "-c", code, out, str(n), str(m)], env=dict(os.environ, GPMI_BACKWARD_OB="0"),
+                         capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, run.stderr[-2000:]
+    r = dict(np.load(out))
+    assert r["info"][0] == 0
+    fail_with_tiles(kh._tile_report(r["Z"] != r["Z0"], "differ from Z0", r["Z"], r["Z0"]),
+                    f"solve_rows_kinv n={n} m={m} over 128-wide steps")
+
+
+def test_rows_kinv_leaves_the_engine_intact(solve_engines):
+    """solve_rows_kinv solves in place in the query workspace and reuses the cached inverse blocks: solve_rows and
+    predict_dense on the same engine still return their exact results afterwards, and so does a second call."""
+    n, m = 2176, 129
+    eng, L0, a0 = solve_engines(n)
+    A = kh.int_chol_case(n, seed=n + 9)[1]
+    _rows_kinv_check(eng, A, n, m)
+    X0 = np.random.default_rng(n + 31 * m).integers(-1, 2, (m, n)).astype(float)
+    Q = X0 @ L0.T
+    X = eng.solve_rows(Q)[0]
+    fail_with_tiles(kh._tile_report(X != X0, "differ from X0", X, X0), f"solve_rows after solve_rows_kinv n={n} m={m}")
+    ka, ss = eng.predict_dense(Q)
+    assert np.array_equal(ka, Q @ a0) and np.array_equal(ss, (X0 ** 2).sum(1))
+    _rows_kinv_check(eng, A, n, m + 1)
