@@ -758,6 +758,49 @@ int gpmi_sgp_spatial_derivatives(gpmi_sgp* sgp, const double* pts_host /* mq x d
  * m outside 1 .. GPMI_SGP_MAX_M, panel_rows outside 0 .. 32768, out NULL.  The tests use it to prove which branch they ran. */
 int gpmi_sgp_schedule(int64_t n, int64_t m, int64_t panel_rows, int64_t out[6]);
 
+/* ---- lockstep batches of the bound: T hyper-parameter vectors on one object, x, Z and the noise data shared ----
+ * gpmi_sgp_bound_batch evaluates F - and, where grad is not NULL, dF/dtheta in gpmi_sgp_bound's layout - for the T rows of
+ * thetas_host with the WhiteNoise variance white_var_host[t] each.  Every launch of gpmi_sgp_bound's two passes carries a
+ * chunk of problems side by side, and the host is waited for once per chunk, not per panel or factorisation.
+ * Residuals: gpmi_sgp_set_observations puts y itself (n doubles more) and the data variances on the device (the variances
+ * are the object's one copy, the one gpmi_sgp_set_targets writes); row t then works on r_t = y - mu_const_host[t], one
+ * subtraction per point on the device (the bits of the host's y - c), or on r_t = y - mus_host[t] (T x n: any mean
+ * function).  Exactly one of the two is given.  Nothing of r_t comes from gpmi_sgp_set_targets: a row does not depend on
+ * the object's history, and the batch call leaves the residual of gpmi_sgp_set_targets, the kept fit and every later
+ * single evaluation bit-identical.
+ * Results per row: F[t]; grad (n_theta + 1 values); sum_alpha[t] = sum_i alpha_ti, reduced on the device in a fixed order
+ * (the gradient by a constant mean); alpha_host (n values, for other mean functions); info[t] in gpmi_sgp_bound's
+ * numbering.  Each may be NULL but F and info.  A row with info[t] > 0 is not an error: its other results are
+ * unspecified, it writes nowhere but into its own slices and changes no other row.
+ * Bits: every sum has an order fixed by (n, m, d, panel_rows) alone, nothing uses atomics, no product takes a tile shape
+ * that depends on the number of problems in its launch: a row's F, gradient, sum_alpha and alpha are the same bits alone,
+ * at any position of any batch, under any max_chunk and on a repeated call, and F is the same with and without the
+ * gradient.  Equality with gpmi_sgp_bound's bits is not promised (its products may take other tile shapes).
+ * GPMI_ERR_ARG, before anything is touched: T < 0 (T = 0 returns GPMI_OK at once), a call before
+ * gpmi_sgp_set_observations, both or neither of mu_const_host / mus_host, the argument errors of gpmi_sgp_bound for any
+ * row - among them noise_var_i + white_var[t] not positive and finite, decided on the host from the range of the
+ * variances -, max_chunk < 0.
+ * Memory: the workspace belongs to the object, grows on demand, is kept between calls and released with the object.
+ * Doubles per problem, with P the rows of a panel, ld = m_pad + 32:
+ *   9 m_pad ld + 256 m_pad + (4 m_pad + 3 P) + 128 + 4096 + 3 max(m_pad (P + 32), P ld) + 2 n + 2,
+ *   and where a gradient, sum_alpha or alpha is asked for  n + max(P, m_pad) m_pad (d + 2) / 4096  more,
+ * plus the problem's parameters (about 550 bytes).  chunk = min(T, 1024, max_chunk if > 0, budget / bytes per problem), at
+ * least 1; the budget is GPMI_BATCH_GIB GiB (1 .. 200, by default and otherwise 24), the cap of the other lockstep batches.
+ * Chunks run one after another.
+ * gpmi_sgp_batch_schedule (host only, no device call) returns what a call with these arguments does, from the function the
+ * call itself uses: out = {chunk, number of chunks, bytes per problem, P, panels, m_pad}; want_grad: any of grad,
+ * sum_alpha, alpha_host; budget_bytes = 0: the library's.  GPMI_ERR_ARG on the ranges of gpmi_sgp_schedule, d outside
+ * 1 .. 64, T, max_chunk or budget_bytes negative, out NULL. */
+int gpmi_sgp_set_observations(gpmi_sgp* sgp, const double* y_host /* n */, const double* noise_var_host /* n, or NULL: zero */);
+int gpmi_sgp_bound_batch(gpmi_sgp* sgp, int kernel, int64_t T, const double* thetas_host /* T x n_theta */, int n_theta,
+                         const double* white_var_host /* T */, const double* mu_const_host /* T, or NULL */,
+                         const double* mus_host /* T x n, or NULL */, double jitter_rel, int64_t panel_rows,
+                         int64_t max_chunk /* 0: automatic */, double* F /* T */,
+                         double* grad /* T x (n_theta + 1), or NULL */, double* sum_alpha /* T, or NULL */,
+                         double* alpha_host /* T x n, or NULL */, int* info /* T */);
+int gpmi_sgp_batch_schedule(int64_t n, int64_t m, int64_t d, int64_t panel_rows, int64_t T, int want_grad,
+                            int64_t max_chunk, int64_t budget_bytes, int64_t out[6]);
+
 /* Greedy conditional-variance selection of inducing points among the rows of x: the pivoted partial Cholesky factorisation
  * of K_nn (the greedy MAP of a k-DPP; Burt, Rasmussen and van der Wilk, JMLR 2020).  It needs no gpmi_sgp object and no
  * gpmi_set_data.  The work is done in unit prior variance, C = K / a^2: theta has the layout of gpmi_sgp_bound, theta[0] =

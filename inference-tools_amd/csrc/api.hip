@@ -404,23 +404,28 @@ int enqueue_rows_kinv(gpmi_ctx* c, Lane& F, hipStream_t s, int64_t mp) {
   return GPMI_OK;
 }
 
+// the byte cap of a lockstep workspace (api_internal.h)
+int64_t batch_budget_bytes() {
+  static const int64_t budget_gib = [] {
+    const char* e = std::getenv("GPMI_BATCH_GIB");
+    const int v = e ? std::atoi(e) : 24;
+    return (int64_t)(v >= 1 && v <= 200 ? v : 24);
+  }();
+  return budget_gib << 30;
+}
+
 // workspace for `want` small problems advancing in lockstep (capped by a 24 GiB budget and 512 matrices: round 6 - 6 GiB /
 // 256 until then; one chunk of 512 evaluations at N = 2048 instead of three of 171 is 3.7 % faster, and two asynchronous
 // slots of 256 carry config 5's 512 chains in two groups: 14 600 -> 15 450 evaluations/s through the tempering driver)
 int ensure_batch_ws(gpmi_ctx* c, int want) {
   const int64_t per = c->np * c->ld * (int64_t)sizeof(double);
   // matrices of one lockstep chunk: GPMI_BATCH_GIB (GiB of them) and GPMI_BATCH_MAX (their number) bound the workspace
-  static const int64_t budget_gib = [] {
-    const char* e = std::getenv("GPMI_BATCH_GIB");
-    const int v = e ? std::atoi(e) : 24;
-    return (int64_t)(v >= 1 && v <= 200 ? v : 24);
-  }();
   static const int max_chunk = [] {
     const char* e = std::getenv("GPMI_BATCH_MAX");
     const int v = e ? std::atoi(e) : 512;
     return v >= 2 && v <= 4096 ? v : 512;
   }();
-  int cap = (int)((budget_gib << 30) / per);
+  int cap = (int)(batch_budget_bytes() / per);
   if (cap > max_chunk) cap = max_chunk;
   if (cap < 1) cap = 1;
   if (want > cap) want = cap;

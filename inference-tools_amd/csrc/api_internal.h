@@ -174,6 +174,7 @@ int ensure_trsm_panel(gpmi_ctx* c, int64_t rows);
 int enqueue_inverse_factor(gpmi_ctx* c, Lane& L, Lane& F);
 int enqueue_rows_kinv(gpmi_ctx* c, Lane& F, hipStream_t s, int64_t mp);
 void free_batch_ws(gpmi_ctx* c);  // every lockstep buffer, caps to 0
+int64_t batch_budget_bytes();     // GPMI_BATCH_GIB (1 .. 200 GiB, else and by default 24) in bytes: the cap of a lockstep workspace
 int ensure_batch_ws(gpmi_ctx* c, int want);
 int ensure_batch_grad_ws(gpmi_ctx* c, int want, int n_theta);
 int ensure_query_ws(gpmi_ctx* c, int64_t mp);

@@ -23,6 +23,8 @@
 // four products per panel for the rows t(q)^T = (L^-T (L_B^-T u - v))^T, then sgp_qgrad_kernel: one profile evaluation
 // weighted twice, by gamma and by t(q).
 // Every reduction has a fixed order, nothing uses atomics: a call repeated gives the same bits.
+// Lockstep batches (gpmi_sgp_bound_batch: T hyper-parameter vectors on one object) run the launches of the two passes with a
+// chunk of problems in blockIdx.z, on the same kernels, and wait for the host once per chunk (sgp_batch_chunk, below).
 #include <limits>
 
 #include "api_internal.h"
@@ -55,6 +57,19 @@ struct gpmi_sgp {
   DevBuf<double> fLinv, fLBinv, fc, fgamma;
   KParams fp = {};
   bool fitted = false;
+  // lockstep batches (gpmi_sgp_bound_batch): y itself, the range of the noise variances as the host saw them go up (nv is
+  // shared with gpmi_sgp_set_targets) and the workspace of `cap` problems side by side, grown on demand
+  DevBuf<double> y;
+  bool have_obs = false;
+  double nv_lo = 0.0, nv_hi = 0.0;
+  bool nv_nan = false;
+  struct BatchWs {
+    int64_t cap = 0, panel = 0;
+    bool grad = false;
+    DevBuf<double> M[9], invD1, invD2, vec, red, part, P[3], w, r, alpha, ws, white, mu;
+    DevBuf<int> info;  // [0, cap): K_mm + eps I, [cap, 2 cap): B
+    DevBuf<KParams> params;
+  } bw;
 };
 
 namespace {
@@ -72,11 +87,20 @@ constexpr int RED_NOISE = 8;  // sum_i [alpha_i^2 - w_i + w_i^2 (a^2 - k_i^T T k
 constexpr int RED_GRAD = 16;  // n_theta partial derivatives
 
 // w_i = 1 / (nv_i + white) and, per workgroup, the partial sums [r^T W r, sum ln sigma^2, sum w, bad] over its
-// grid-strided share of the data (bad: variances that are not positive and finite; their w is 0)
+// grid-strided share of the data (bad: variances that are not positive and finite; their w is 0).
+// The kernels below take a lockstep batch in blockIdx.z: problem z reads and writes its arrays `z * stride` doubles behind
+// the pointers (SgpStrides; all 0 for the single evaluation) and, where a scalar differs by problem, takes it from an
+// array of one value per problem in the place of the argument (whites, pdev; nullptr: the argument).
 __global__ __launch_bounds__(SGP_NT) void sgp_weights_kernel(const double* __restrict__ r, const double* __restrict__ nv,
-                                                             double white, int64_t n, double* __restrict__ w,
-                                                             double* __restrict__ part) {
+                                                             double white, const double* __restrict__ whites, int64_t n,
+                                                             double* __restrict__ w, double* __restrict__ part, int64_t sN,
+                                                             int64_t sPart) {
   __shared__ double red[4];
+  const int64_t z = blockIdx.z;
+  if (whites) white = whites[z];
+  r += z * sN;
+  w += z * sN;
+  part += z * sPart;
   double rwr = 0.0, lns = 0.0, sw = 0.0, bad = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * SGP_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * SGP_NT) {
     const double s2 = nv[i] + white;
@@ -103,9 +127,12 @@ __global__ __launch_bounds__(SGP_NT) void sgp_weights_kernel(const double* __res
 
 // out[j] (+)= sum_t ws[t][j], t < nrows, in a fixed order: thread-strided partial sums, then a tree (workgroup j)
 __global__ __launch_bounds__(SGP_NT) void sgp_colsum_kernel(const double* __restrict__ ws, int64_t nrows, int width,
-                                                            double* __restrict__ out, int accumulate) {
+                                                            double* __restrict__ out, int accumulate, int64_t sWs,
+                                                            int64_t sOut) {
   __shared__ double red[4];
   const int j = blockIdx.x;
+  ws += (int64_t)blockIdx.z * sWs;
+  out += (int64_t)blockIdx.z * sOut;
   double acc = 0.0;
   for (int64_t t = threadIdx.x; t < nrows; t += SGP_NT) acc += ws[t * width + j];
   const double v = block_sum(acc, red);
@@ -114,17 +141,22 @@ __global__ __launch_bounds__(SGP_NT) void sgp_colsum_kernel(const double* __rest
 
 // K[i][j] *= sqrt(w[j]), i < rows (grid.y), j < cols
 __global__ __launch_bounds__(SGP_NT) void sgp_scale_cols_kernel(double* __restrict__ K, int64_t ld, int64_t cols,
-                                                                const double* __restrict__ w) {
-  const int64_t j = (int64_t)blockIdx.x * SGP_NT + threadIdx.x, i = blockIdx.y;
-  if (j < cols) K[i * ld + j] *= sqrt(w[j]);
+                                                                const double* __restrict__ w, int64_t sK, int64_t sN) {
+  const int64_t j = (int64_t)blockIdx.x * SGP_NT + threadIdx.x, i = blockIdx.y, z = blockIdx.z;
+  if (j < cols) K[z * sK + i * ld + j] *= sqrt(w[z * sN + j]);
 }
 
 // b[i] (+)= sum_j Kw[i][j] r[j] sqrt(w[j]), j < cols; workgroup i
 __global__ __launch_bounds__(SGP_NT) void sgp_bvec_kernel(const double* __restrict__ Kw, int64_t ld, int64_t cols,
                                                           const double* __restrict__ r, const double* __restrict__ w,
-                                                          double* __restrict__ b, int accumulate) {
+                                                          double* __restrict__ b, int accumulate, int64_t sK, int64_t sN,
+                                                          int64_t sVec) {
   __shared__ double red[4];
-  const int64_t i = blockIdx.x;
+  const int64_t i = blockIdx.x, z = blockIdx.z;
+  Kw += z * sK;
+  r += z * sN;
+  w += z * sN;
+  b += z * sVec;
   double acc = 0.0;
   for (int64_t j = threadIdx.x; j < cols; j += SGP_NT) acc = fma(Kw[i * ld + j], r[j] * sqrt(w[j]), acc);
   const double v = block_sum(acc, red);
@@ -132,17 +164,23 @@ __global__ __launch_bounds__(SGP_NT) void sgp_bvec_kernel(const double* __restri
 }
 
 // A[i][i] += eps for i < m; = 1 in the padding (the cross build leaves zeros there)
-__global__ void sgp_pad_diag_kernel(double* __restrict__ A, int64_t ld, int64_t m, int64_t mp, double eps) {
+// (pdev: eps = jitter a^2 of problem z)
+__global__ void sgp_pad_diag_kernel(double* __restrict__ A, int64_t ld, int64_t m, int64_t mp, double eps, double jitter,
+                                    const KParams* __restrict__ pdev, int64_t sMat) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= mp) return;
+  if (pdev) eps = __dmul_rn(jitter, pdev[blockIdx.z].a2);  // (rounded on its own, as the host's product is)
+  A += (int64_t)blockIdx.z * sMat;
   if (i < m) A[i * ld + i] += eps;
   else A[i * ld + i] = 1.0;
 }
 
 // dst = src^T (mp x mp, 64 x 64 tiles through LDS)
 __global__ __launch_bounds__(SGP_NT) void sgp_transpose_kernel(const double* __restrict__ src, double* __restrict__ dst,
-                                                               int64_t ld) {
+                                                               int64_t ld, int64_t sMat) {
   __shared__ double t[64][65];
+  src += (int64_t)blockIdx.z * sMat;
+  dst += (int64_t)blockIdx.z * sMat;
   const int ti = blockIdx.y, tj = blockIdx.x;
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   for (int r = ty; r < 64; r += 4) t[r][tx] = src[((int64_t)ti * 64 + r) * ld + (int64_t)tj * 64 + tx];
@@ -151,8 +189,11 @@ __global__ __launch_bounds__(SGP_NT) void sgp_transpose_kernel(const double* __r
 }
 
 // B = 1/2 (H + H^T) + I
-__global__ __launch_bounds__(SGP_NT) void sgp_sym_b_kernel(const double* __restrict__ H, double* __restrict__ B, int64_t ld) {
+__global__ __launch_bounds__(SGP_NT) void sgp_sym_b_kernel(const double* __restrict__ H, double* __restrict__ B, int64_t ld,
+                                                           int64_t sMat) {
   __shared__ double t[64][65];
+  H += (int64_t)blockIdx.z * sMat;
+  B += (int64_t)blockIdx.z * sMat;
   const int ti = blockIdx.y, tj = blockIdx.x;
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   for (int r = ty; r < 64; r += 4) t[r][tx] = H[((int64_t)tj * 64 + r) * ld + (int64_t)ti * 64 + tx];
@@ -166,8 +207,14 @@ __global__ __launch_bounds__(SGP_NT) void sgp_sym_b_kernel(const double* __restr
 // out = [sum ln LB_ii, sum H_ii, sum c_i^2], i < m; one workgroup
 __global__ __launch_bounds__(SGP_NT) void sgp_mm_reduce_kernel(const double* __restrict__ LB, const double* __restrict__ H,
                                                                int64_t ld, int64_t m, const double* __restrict__ c,
-                                                               double* __restrict__ out) {
+                                                               double* __restrict__ out, int64_t sMat, int64_t sVec,
+                                                               int64_t sOut) {
   __shared__ double red[4];
+  const int64_t z = blockIdx.z;
+  LB += z * sMat;
+  H += z * sMat;
+  c += z * sVec;
+  out += z * sOut;
   double a = 0.0, b = 0.0, q = 0.0;
   for (int64_t i = threadIdx.x; i < m; i += SGP_NT) {
     a += log(LB[i * ld + i]);
@@ -184,16 +231,20 @@ __global__ __launch_bounds__(SGP_NT) void sgp_mm_reduce_kernel(const double* __r
 
 // C = A - B (mp rows in grid.y, mp columns)
 __global__ __launch_bounds__(SGP_NT) void sgp_sub_kernel(const double* __restrict__ A, const double* __restrict__ B,
-                                                         double* __restrict__ C, int64_t ld, int64_t mp) {
-  const int64_t j = (int64_t)blockIdx.x * SGP_NT + threadIdx.x, i = blockIdx.y;
-  if (j < mp) C[i * ld + j] = A[i * ld + j] - B[i * ld + j];
+                                                         double* __restrict__ C, int64_t ld, int64_t mp, int64_t sMat) {
+  const int64_t j = (int64_t)blockIdx.x * SGP_NT + threadIdx.x, i = blockIdx.y, o = (int64_t)blockIdx.z * sMat;
+  if (j < mp) C[o + i * ld + j] = A[o + i * ld + j] - B[o + i * ld + j];
 }
 
 // out[j] = sum_a K[j][a] M[j][a], a < m; workgroup j
 __global__ __launch_bounds__(SGP_NT) void sgp_rowdot2_kernel(const double* __restrict__ K, const double* __restrict__ M,
-                                                             int64_t ld, int64_t m, double* __restrict__ out) {
+                                                             int64_t ld, int64_t m, double* __restrict__ out, int64_t sK,
+                                                             int64_t sVec) {
   __shared__ double red[4];
-  const int64_t j = blockIdx.x;
+  const int64_t j = blockIdx.x, z = blockIdx.z;
+  K += z * sK;
+  M += z * sK;
+  out += z * sVec;
   double acc = 0.0;
   for (int64_t a = threadIdx.x; a < m; a += SGP_NT) acc = fma(K[j * ld + a], M[j * ld + a], acc);
   const double v = block_sum(acc, red);
@@ -203,10 +254,18 @@ __global__ __launch_bounds__(SGP_NT) void sgp_rowdot2_kernel(const double* __res
 // alpha_j = w_j (r_j - kg_j) and, with q (k_j^T T k_j), the noise-gradient term of the point; j < rows
 __global__ __launch_bounds__(SGP_NT) void sgp_alpha_kernel(const double* __restrict__ r, const double* __restrict__ w,
                                                            const double* __restrict__ kg, const double* __restrict__ q,
-                                                           double a2, int64_t rows, double* __restrict__ alpha,
-                                                           double* __restrict__ term) {
-  const int64_t j = (int64_t)blockIdx.x * SGP_NT + threadIdx.x;
+                                                           double a2, const KParams* __restrict__ pdev, int64_t rows,
+                                                           double* __restrict__ alpha, double* __restrict__ term, int64_t sN,
+                                                           int64_t sVec) {
+  const int64_t j = (int64_t)blockIdx.x * SGP_NT + threadIdx.x, z = blockIdx.z;
   if (j >= rows) return;
+  if (pdev) a2 = pdev[z].a2;
+  r += z * sN;
+  w += z * sN;
+  alpha += z * sN;
+  kg += z * sVec;
+  if (q) q += z * sVec;
+  term += z * sVec;
   const double wj = w[j], a = wj * (r[j] - kg[j]);
   alpha[j] = a;
   if (q) term[j] = a * a - wj + wj * wj * (a2 - q[j]);
@@ -260,16 +319,34 @@ __device__ __forceinline__ void pair_weights(int64_t gi0, int64_t nu, int64_t gj
 // in two halves of eight elements (kfun.h: kprofiles) and one pass over the dimensions for the length scales.
 // square != 0: U and V are the same points (the K_mm term) and the diagonal carries diag_eps: d(K + eps I)_ii / d ln a =
 // 2 (a^2 + eps).  Reads Mw only where i < nu and j < nv; VALU-bound (the fp64 exp and the d-term sums).
-template <int KERNEL>
-__global__ __launch_bounds__(SGP_NT) void sgp_contract_kernel(KParams p, const double* __restrict__ U, int64_t nu,
+// BATCHED: a lockstep batch in blockIdx.z - problem z takes its parameters from pdev[z] (p_one is not read), diag_eps =
+// jitter a_z^2 (diag_eps carries the relative jitter), and its weights, vectors and partials `z * stride` behind the
+// pointers (ContractStrides); U and V are shared.  The tile's arithmetic is the same code either way.
+struct ContractStrides {
+  int64_t mw, rs, u, v, ws;
+};
+
+template <int KERNEL, bool BATCHED>
+__global__ __launch_bounds__(SGP_NT) void sgp_contract_kernel(KParams p_one, const KParams* __restrict__ pdev,
+                                                              const double* __restrict__ U, int64_t nu,
                                                               const double* __restrict__ V, int64_t nv,
                                                               const double* __restrict__ Mw, int64_t ld,
                                                               const double* __restrict__ rs, const double* __restrict__ uvec,
                                                               const double* __restrict__ vvec, double m_scale,
                                                               double uv_scale, int square, double diag_eps, int n_theta,
-                                                              double* __restrict__ ws) {
+                                                              double* __restrict__ ws, ContractStrides st) {
   extern __shared__ double sc_lds[];
   __shared__ double red[4];
+  const KParams& p = BATCHED ? pdev[blockIdx.z] : p_one;
+  if (BATCHED) {
+    const int64_t z = blockIdx.z;
+    diag_eps = __dmul_rn(diag_eps, p.a2);  // (rounded on its own, as the host's product is)
+    Mw += z * st.mw;
+    if (rs) rs += z * st.rs;
+    uvec += z * st.u;
+    vvec += z * st.v;
+    ws += z * st.ws;
+  }
   const int ti = blockIdx.y, tj = blockIdx.x;
   const int tid = threadIdx.x, d = p.d;
   double* su = sc_lds;
@@ -338,8 +415,22 @@ void launch_contract(hipStream_t s, const KParams& p, const double* U, int64_t n
   const dim3 grid((unsigned)(nvp / KT), (unsigned)(nup / KT));
   const size_t lds = contract_lds_bytes(p.d);
   with_stationary_kernel(p.kernel, [&](auto K) {  // (sgp_params admits no other kind)
-    hipLaunchKernelGGL(sgp_contract_kernel<decltype(K)::value>, grid, dim3(SGP_NT), lds, s, p, U, nu, V, nv, Mw, ld, rs, uvec,
-                       vvec, m_scale, uv_scale, square, diag_eps, n_theta, ws);
+    hipLaunchKernelGGL((sgp_contract_kernel<decltype(K)::value, false>), grid, dim3(SGP_NT), lds, s, p, nullptr, U, nu, V, nv, Mw,
+                       ld, rs, uvec, vvec, m_scale, uv_scale, square, diag_eps, n_theta, ws, ContractStrides{});
+  });
+}
+
+// the same for the B problems of a lockstep chunk (pdev[z], all of kind `kernel` in d dimensions; jitter_rel: the diagonal
+// of the square form carries jitter_rel a_z^2)
+void launch_contract_batched(hipStream_t s, int kernel, int d, const KParams* pdev, int B, const double* U, int64_t nu, int64_t nup,
+                             const double* V, int64_t nv, int64_t nvp, const double* Mw, int64_t ld, const double* rs,
+                             const double* uvec, const double* vvec, double m_scale, double uv_scale, int square,
+                             double jitter_rel, int n_theta, double* ws, const ContractStrides& st) {
+  const dim3 grid((unsigned)(nvp / KT), (unsigned)(nup / KT), (unsigned)B);
+  const size_t lds = contract_lds_bytes(d);
+  with_stationary_kernel(kernel, [&](auto K) {
+    hipLaunchKernelGGL((sgp_contract_kernel<decltype(K)::value, true>), grid, dim3(SGP_NT), lds, s, KParams{}, pdev, U, nu, V, nv,
+                       Mw, ld, rs, uvec, vvec, m_scale, uv_scale, square, jitter_rel, n_theta, ws, st);
   });
 }
 
@@ -616,7 +707,7 @@ void nt_square(hipStream_t s, double* C, const double* A, const double* B, int64
 // dst <- (factor at A)^-1, through its transpose in `scratch`
 void inverse_factor(hipStream_t s, const double* A, const double* invD, double* scratch, double* dst, int64_t mp, int64_t ld) {
   trsm_identity_batched(s, A, mp, ld, invD, scratch, BatchShape());
-  hipLaunchKernelGGL(sgp_transpose_kernel, dim3((unsigned)(mp / KT), (unsigned)(mp / KT)), dim3(SGP_NT), 0, s, scratch, dst, ld);
+  hipLaunchKernelGGL(sgp_transpose_kernel, dim3((unsigned)(mp / KT), (unsigned)(mp / KT)), dim3(SGP_NT), 0, s, scratch, dst, ld, 0);
 }
 
 int read_info(gpmi_sgp* g, int slot, int& inf) {
@@ -642,8 +733,8 @@ int sgp_factor(gpmi_sgp* g, const KParams& p, double white, double jitter, int64
   double hred[4] = {};
   {
     const unsigned nblk = weights_blocks(n);
-    hipLaunchKernelGGL(sgp_weights_kernel, dim3(nblk), dim3(SGP_NT), 0, s, g->r, g->nv, white, n, g->w, g->part);
-    hipLaunchKernelGGL(sgp_colsum_kernel, dim3(4), dim3(SGP_NT), 0, s, g->part, (int64_t)nblk, 4, g->red + RED_DATA, 0);
+    hipLaunchKernelGGL(sgp_weights_kernel, dim3(nblk), dim3(SGP_NT), 0, s, g->r, g->nv, white, nullptr, n, g->w, g->part, 0, 0);
+    hipLaunchKernelGGL(sgp_colsum_kernel, dim3(4), dim3(SGP_NT), 0, s, g->part, (int64_t)nblk, 4, g->red + RED_DATA, 0, 0, 0);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(hred, g->red + RED_DATA, sizeof(hred), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
@@ -657,9 +748,9 @@ int sgp_factor(gpmi_sgp* g, const KParams& p, double white, double jitter, int64
     {
       ProfScope ps(c, s, GPMI_PROF_SGP_BUILD, 0.0, 8.0 * mp * P);
       launch_kbuild_cross(s, p, g->z, m, mp, g->x + j0 * d, rows, P, Kp, ldp);  // (zeros in rows >= m and columns >= rows)
-      hipLaunchKernelGGL(sgp_scale_cols_kernel, dim3(blocks(rows), (unsigned)m), dim3(SGP_NT), 0, s, Kp, ldp, rows, g->w + j0);
+      hipLaunchKernelGGL(sgp_scale_cols_kernel, dim3(blocks(rows), (unsigned)m), dim3(SGP_NT), 0, s, Kp, ldp, rows, g->w + j0, 0, 0);
       hipLaunchKernelGGL(sgp_bvec_kernel, dim3((unsigned)m), dim3(SGP_NT), 0, s, Kp, ldp, rows, g->r + j0, g->w + j0, b,
-                         j0 > 0 ? 1 : 0);
+                         j0 > 0 ? 1 : 0, 0, 0, 0);
     }
     {
       ProfScope ps(c, s, GPMI_PROF_SGP_GRAM, (double)P * mp * (mp + GPMI_NB), 8.0 * (mp * P + 0.5 * mp * mp));
@@ -673,7 +764,7 @@ int sgp_factor(gpmi_sgp* g, const KParams& p, double white, double jitter, int64
     launch_mirror_lower(s, G, ld, mp);
     launch_negate(s, G, mp * ld);
     launch_kbuild_cross(s, p, g->z, m, mp, g->z, m, mp, A, ld);
-    hipLaunchKernelGGL(sgp_pad_diag_kernel, dim3(blocks(mp)), dim3(SGP_NT), 0, s, A, ld, m, mp, jitter * p.a2);
+    hipLaunchKernelGGL(sgp_pad_diag_kernel, dim3(blocks(mp)), dim3(SGP_NT), 0, s, A, ld, m, mp, jitter * p.a2, 0.0, nullptr, 0);
     HIPCHK(c, hipMemsetAsync(g->info, 0, 2 * sizeof(int), s));
     potrf_lower_batched(c, s, A, mp, ld, g->invD1, g->info, BatchShape());
     HIPCHK(c, hipGetLastError());
@@ -688,7 +779,7 @@ int sgp_factor(gpmi_sgp* g, const KParams& p, double white, double jitter, int64
     inverse_factor(s, A, g->invD1, LiT, Linv, mp, ld);
     nt_square(s, W1, Linv, G, mp, ld);   // L^-1 G   (G symmetric)
     nt_square(s, W2, W1, Linv, mp, ld);  // H = L^-1 G L^-T
-    hipLaunchKernelGGL(sgp_sym_b_kernel, dim3((unsigned)(mp / KT), (unsigned)(mp / KT)), dim3(SGP_NT), 0, s, W2, LB, ld);
+    hipLaunchKernelGGL(sgp_sym_b_kernel, dim3((unsigned)(mp / KT), (unsigned)(mp / KT)), dim3(SGP_NT), 0, s, W2, LB, ld, 0);
     potrf_lower_batched(c, s, LB, mp, ld, g->invD2, g->info + 1, BatchShape());
     HIPCHK(c, hipGetLastError());
   }
@@ -703,7 +794,7 @@ int sgp_factor(gpmi_sgp* g, const KParams& p, double white, double jitter, int64
     inverse_factor(s, LB, g->invD2, W3, LBinv, mp, ld);
     launch_rows_dot(s, Linv, ld, mp, mp, b, v1);
     launch_rows_dot(s, LBinv, ld, mp, mp, v1, cc);
-    hipLaunchKernelGGL(sgp_mm_reduce_kernel, dim3(1), dim3(SGP_NT), 0, s, LB, W2, ld, m, cc, g->red + RED_MM);
+    hipLaunchKernelGGL(sgp_mm_reduce_kernel, dim3(1), dim3(SGP_NT), 0, s, LB, W2, ld, m, cc, g->red + RED_MM, 0, 0, 0);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(hmm, g->red + RED_MM, sizeof(hmm), hipMemcpyDeviceToHost, s));
   }
@@ -736,10 +827,11 @@ int sgp_gradient(gpmi_sgp* g, const KParams& p, int n_theta, double white, doubl
   if (grad) {
     nt_square(s, W2, RT, RT, mp, ld);      // S = L^-T B^-1 L^-1
     nt_square(s, Kinv, LiT, LiT, mp, ld);  // L^-T L^-1
-    hipLaunchKernelGGL(sgp_sub_kernel, dim3(blocks(mp), (unsigned)mp), dim3(SGP_NT), 0, s, Kinv, W2, T, ld, mp);
+    hipLaunchKernelGGL(sgp_sub_kernel, dim3(blocks(mp), (unsigned)mp), dim3(SGP_NT), 0, s, Kinv, W2, T, ld, mp, 0);
     nt_square(s, LB, Kinv, G, mp, ld);     // K_mm^-1 G
     nt_square(s, W2, LB, Kinv, mp, ld);    // K_mm^-1 G K_mm^-1
-    hipLaunchKernelGGL(sgp_sub_kernel, dim3(blocks(mp), (unsigned)mp), dim3(SGP_NT), 0, s, W2, T, LB, ld, mp);  // M2 - gamma gamma^T
+    hipLaunchKernelGGL(sgp_sub_kernel, dim3(blocks(mp), (unsigned)mp), dim3(SGP_NT), 0, s, W2, T, LB, ld, mp,
+                       0);  // M2 - gamma gamma^T
   }
   HIPCHK(c, hipGetLastError());
   for (int64_t j0 = 0; j0 < n; j0 += P) {
@@ -749,16 +841,16 @@ int sgp_gradient(gpmi_sgp* g, const KParams& p, int n_theta, double white, doubl
     launch_rows_dot(s, KTp, ld, P, mp, gamma, kg);
     if (grad) {
       launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, Mp, ld, KTp, ld, T, ld, (int)(P / GPMI_NB), nt, (int)mp);  // rows k_j^T T
-      hipLaunchKernelGGL(sgp_rowdot2_kernel, dim3((unsigned)rows), dim3(SGP_NT), 0, s, KTp, Mp, ld, m, q);
+      hipLaunchKernelGGL(sgp_rowdot2_kernel, dim3((unsigned)rows), dim3(SGP_NT), 0, s, KTp, Mp, ld, m, q, 0, 0);
     }
     hipLaunchKernelGGL(sgp_alpha_kernel, dim3(blocks(rows)), dim3(SGP_NT), 0, s, g->r + j0, g->w + j0, kg,
-                       grad ? q : (const double*)nullptr, p.a2, rows, g->alpha + j0, term);
+                       grad ? q : (const double*)nullptr, p.a2, nullptr, rows, g->alpha + j0, term, 0, 0);
     if (grad) {
-      hipLaunchKernelGGL(sgp_colsum_kernel, dim3(1), dim3(SGP_NT), 0, s, term, rows, 1, g->red + RED_NOISE, j0 > 0 ? 1 : 0);
+      hipLaunchKernelGGL(sgp_colsum_kernel, dim3(1), dim3(SGP_NT), 0, s, term, rows, 1, g->red + RED_NOISE, j0 > 0 ? 1 : 0, 0, 0);
       launch_contract(s, p, g->x + j0 * d, rows, P, g->z, m, mp, Mp, ld, g->w + j0, g->alpha + j0, gamma, 1.0, 1.0, 0, 0.0,
                       n_theta, g->ws);
       hipLaunchKernelGGL(sgp_colsum_kernel, dim3((unsigned)n_theta), dim3(SGP_NT), 0, s, g->ws, (P / KT) * (mp / KT), n_theta,
-                         g->red + RED_GRAD, j0 > 0 ? 1 : 0);
+                         g->red + RED_GRAD, j0 > 0 ? 1 : 0, 0, 0);
       if (want_z)  // -sum_j M1_ij a^2 g (z_ik - x_jk) / l_k^2
         if (int rc = launch_zcontract(c, s, p, g->x + j0 * d, rows, P, g->z, m, mp, Mp, ld, g->w + j0, g->alpha + j0, gamma,
                                       -1.0, g->zws, g->zacc, j0 > 0 ? 1 : 0))
@@ -770,7 +862,7 @@ int sgp_gradient(gpmi_sgp* g, const KParams& p, int n_theta, double white, doubl
   // the K_mm term: weights -1/2 M2 = -1/2 (gamma gamma^T + LB), rows and columns are Z
   launch_contract(s, p, g->z, m, mp, g->z, m, mp, LB, ld, nullptr, gamma, gamma, -0.5, -0.5, 1, jitter * p.a2, n_theta, g->ws);
   hipLaunchKernelGGL(sgp_colsum_kernel, dim3((unsigned)n_theta), dim3(SGP_NT), 0, s, g->ws, (mp / KT) * (mp / KT), n_theta,
-                     g->red + RED_GRAD, 1);
+                     g->red + RED_GRAD, 1, 0, 0);
   if (want_z)  // +sum_j M2_ij a^2 g (z_ik - z_jk) / l_k^2: z_i is in row i and column i of K_mm, M2 symmetric - no 1/2
     if (int rc = launch_zcontract(c, s, p, g->z, m, mp, g->z, m, mp, LB, ld, nullptr, gamma, gamma, 1.0, g->zws, g->zacc, 1))
       return rc;
@@ -782,6 +874,26 @@ int sgp_gradient(gpmi_sgp* g, const KParams& p, int n_theta, double white, doubl
   for (int k = 0; k < n_theta; ++k) grad[k] = hg[k];
   grad[0] -= p.a2 * sum_w;  // -1/2 sum w_i da^2 / d ln a
   grad[n_theta] = white > 0.0 ? white * hnoise : 0.0;
+  return GPMI_OK;
+}
+
+// the noise variances go up: their range as the host sees it (gpmi_sgp_bound_batch checks noise_var_i + white_var with it)
+int sgp_upload_noise(gpmi_sgp* g, const double* noise_var) {
+  gpmi_ctx* c = g->ctx;
+  g->nv_lo = g->nv_hi = 0.0;
+  g->nv_nan = false;
+  if (!noise_var) {
+    ZERO_SYNC(c, g->nv, sizeof(double) * g->n);
+    return GPMI_OK;
+  }
+  HIPCHK(c, hipMemcpy(g->nv, noise_var, sizeof(double) * g->n, hipMemcpyHostToDevice));
+  g->nv_lo = std::numeric_limits<double>::infinity();
+  g->nv_hi = -g->nv_lo;
+  for (int64_t i = 0; i < g->n; ++i) {
+    g->nv_nan = g->nv_nan || std::isnan(noise_var[i]);
+    g->nv_lo = std::min(g->nv_lo, noise_var[i]);
+    g->nv_hi = std::max(g->nv_hi, noise_var[i]);
+  }
   return GPMI_OK;
 }
 
@@ -898,6 +1010,290 @@ int sgp_posterior_sigma(gpmi_sgp* g, const double* pts, int64_t mq, PosteriorBuf
   return GPMI_OK;
 }
 
+
+// ---- lockstep batches: T hyper-parameter vectors on one object (gpmi_sgp_bound_batch) ---------------------------------
+// The launches of sgp_factor and sgp_gradient with a chunk of B problems in blockIdx.z of every one of them, on the batch
+// workspace (gpmi_sgp::bw: B copies of the object's work arrays side by side).  The host is waited for once per chunk:
+// a problem whose factorisation fails carries what it holds through the later launches - no index depends on a value -
+// and is reported through its two info words.
+
+constexpr int64_t SGP_BATCH_MAX = 1024;  // problems per chunk at most (blockIdx.z, and the tiles of one GEMM launch)
+constexpr int RED_SALPHA = 12;           // sum_i alpha_i
+constexpr int SGP_RED = 128;             // doubles of a problem's small results (gpmi_sgp::red)
+
+// r_z = y - mu_const[z], or (mu_const == nullptr) y - r_z with the problem's mean function in r_z's place
+__global__ __launch_bounds__(SGP_NT) void sgp_residual_kernel(const double* __restrict__ y, const double* __restrict__ mu_const,
+                                                              int64_t n, double* __restrict__ r) {
+  const int64_t i = (int64_t)blockIdx.x * SGP_NT + threadIdx.x, z = blockIdx.z;
+  if (i >= n) return;
+  r[z * n + i] = y[i] - (mu_const ? mu_const[z] : r[z * n + i]);
+}
+
+// per workgroup the partial sum of its grid-strided share of v_z (n values; sgp_colsum_kernel adds the partials)
+__global__ __launch_bounds__(SGP_NT) void sgp_vecsum_kernel(const double* __restrict__ v, int64_t n, double* __restrict__ part,
+                                                            int64_t sPart) {
+  __shared__ double red[4];
+  const int64_t z = blockIdx.z;
+  double acc = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * SGP_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * SGP_NT) acc += v[z * n + i];
+  const double t = block_sum(acc, red);
+  if (threadIdx.x == 0) part[z * sPart + blockIdx.x] = t;
+}
+
+// The shape of a batch call: a function of its arguments alone (gpmi_sgp_batch_schedule reports it, gpmi_sgp_bound_batch
+// runs it).  Doubles per problem, with mp = m_pad, ld = mp + 32, P the panel rows, S = 4 mp + 3 P:
+//   9 mp ld (work matrices) + 2 mp 128 (inverse diagonal blocks) + S (vectors) + 128 (results) + 4096 (partial sums)
+//   + 3 max(mp (P + 32), P ld) (panels) + 2 n (w, r) + 2 (white_var, mu_const);  with the gradient  + n (alpha)
+//   + (max(P, mp) / 64) (mp / 64) (d + 2) (the contraction's partials);  and sizeof(KParams) + 8 bytes (parameters, info).
+struct SgpBatchPlan {
+  int64_t chunk, nchunks, bytes_per, P, panels, mp, ld, each, S, ws_each;
+};
+
+SgpBatchPlan sgp_batch_plan(int64_t n, int64_t m, int64_t d, int64_t panel_rows, int64_t T, bool want_grad, int64_t max_chunk,
+                            int64_t budget_bytes) {
+  SgpBatchPlan pl;
+  pl.P = sgp_panel_rows(n, panel_rows);
+  pl.mp = round_up(m, GPMI_NB);
+  pl.ld = pl.mp + 32;
+  pl.panels = (n + pl.P - 1) / pl.P;
+  pl.each = std::max(pl.mp * (pl.P + 32), pl.P * pl.ld);
+  pl.S = 4 * pl.mp + 3 * pl.P;
+  pl.ws_each = (std::max(pl.P, pl.mp) / KT) * (pl.mp / KT) * (d + 2);
+  int64_t doubles = 9 * pl.mp * pl.ld + 2 * pl.mp * GPMI_NB + pl.S + SGP_RED + 4 * SGP_RED_BLOCKS + 3 * pl.each + 2 * n + 2;
+  if (want_grad) doubles += n + pl.ws_each;
+  pl.bytes_per = 8 * doubles + (int64_t)sizeof(KParams) + 2 * (int64_t)sizeof(int);
+  if (budget_bytes <= 0) budget_bytes = batch_budget_bytes();
+  int64_t chunk = std::min<int64_t>(T, SGP_BATCH_MAX);
+  if (max_chunk > 0) chunk = std::min(chunk, max_chunk);
+  chunk = std::min(chunk, budget_bytes / pl.bytes_per);
+  pl.chunk = std::max<int64_t>(chunk, 1);
+  pl.nchunks = (T + pl.chunk - 1) / pl.chunk;
+  return pl;
+}
+
+// the batch workspace for `B` problems of plan pl (with the gradient's part if want_grad): kept while it is large enough
+int sgp_ensure_batch(gpmi_sgp* g, const SgpBatchPlan& pl, int64_t B, bool want_grad) {
+  gpmi_ctx* c = g->ctx;
+  gpmi_sgp::BatchWs& w = g->bw;
+  if (B <= w.cap && pl.P <= w.panel && (w.grad || !want_grad)) return GPMI_OK;
+  B = std::max(B, w.cap);
+  want_grad = want_grad || w.grad;
+  const int64_t P = std::max(pl.P, w.panel);
+  const int64_t each = std::max(g->mp * (P + 32), P * g->ld);
+  w = gpmi_sgp::BatchWs();
+  const int64_t mp = g->mp, ld = g->ld, n = g->n;
+  for (DevBuf<double>& q : w.M)
+    if (int rc = q.alloc(c, B * mp * ld)) return rc;
+  // (the zeros above the block-lower parts stay from here: gpmi_sgp_create)
+  if (int rc = w.invD1.alloc_zeroed(c, B * mp * GPMI_NB)) return rc;
+  if (int rc = w.invD2.alloc_zeroed(c, B * mp * GPMI_NB)) return rc;
+  if (int rc = w.vec.alloc(c, B * (4 * mp + 3 * P))) return rc;
+  if (int rc = w.red.alloc(c, B * SGP_RED)) return rc;
+  if (int rc = w.part.alloc(c, B * 4 * SGP_RED_BLOCKS)) return rc;
+  for (DevBuf<double>& q : w.P)
+    if (int rc = q.alloc(c, B * each)) return rc;
+  if (int rc = w.w.alloc(c, B * n)) return rc;
+  if (int rc = w.r.alloc(c, B * n)) return rc;
+  if (int rc = w.white.alloc(c, B)) return rc;
+  if (int rc = w.mu.alloc(c, B)) return rc;
+  if (int rc = w.info.alloc(c, 2 * B)) return rc;
+  if (int rc = w.params.alloc(c, B)) return rc;
+  if (want_grad) {
+    if (int rc = w.alpha.alloc(c, B * n)) return rc;
+    if (int rc = w.ws.alloc(c, B * (std::max(P, mp) / KT) * (mp / KT) * (g->d + 2))) return rc;
+  }
+  w.cap = B;
+  w.panel = P;
+  w.grad = want_grad;
+  return GPMI_OK;
+}
+
+// what a chunk brings back for each of its problems
+struct SgpBatchOut {
+  double* F;
+  double* grad;       // (n_theta + 1) per problem, or null
+  double* sum_alpha;  // or null
+  double* alpha;      // n per problem, or null
+  int* info;
+};
+
+// One chunk: problems [0, B) with the parameters ps, white variances and means (mu_const: B values, or mus: B x n) of the
+// host.  second: the gradient pass runs (grad, sum_alpha or alpha is wanted); want_grad: all of it, else alpha alone.
+int sgp_batch_chunk(gpmi_sgp* g, const SgpBatchPlan& pl, int kernel, int64_t B, const KParams* ps, const double* white,
+                    const double* mu_const, const double* mus, double jitter, int n_theta, bool second, bool want_grad,
+                    const SgpBatchOut& out) {
+  gpmi_ctx* c = g->ctx;
+  hipStream_t s = c->sgp_stream;
+  gpmi_sgp::BatchWs& w = g->bw;
+  const int64_t n = g->n, m = g->m, mp = g->mp, ld = g->ld, d = g->d;
+  const int nt = (int)(mp / GPMI_NB), nb = (int)B;
+  const int64_t P = pl.P, ldp = P + 32, nd = mp * GPMI_NB;
+  // the strides of the workspace as it was allocated (cap and panel may be larger than this call's)
+  const int64_t sMat = mp * ld, sVec = 4 * mp + 3 * w.panel, sPanel = std::max(mp * (w.panel + 32), w.panel * ld);
+  const int64_t sPart = 4 * SGP_RED_BLOCKS, sWs = (std::max(w.panel, mp) / KT) * (mp / KT) * (d + 2);
+  double *G = w.M[MG], *A = w.M[MA], *LiT = w.M[MLIT], *Linv = w.M[MLINV], *W1 = w.M[MW1], *W2 = w.M[MW2], *LB = w.M[MLB],
+         *W3 = w.M[MW3], *LBinv = w.M[MLBINV];
+  double *b = w.vec, *v1 = b + mp, *cc = b + 2 * mp, *gamma = b + 3 * mp, *kg = b + 4 * mp, *q = kg + w.panel, *term = q + w.panel;
+  const KParams* pdev = w.params;
+  int *info1 = w.info, *info2 = w.info + w.cap;
+  BatchShape bs;
+  bs.count = nb;
+  bs.sMat = sMat;
+  bs.sInv = nd;
+  bs.sVec = sVec;
+  GemmBatch sq;  // products of the m x m matrices; ring_order_only: a value must not depend on the problems it shares a launch with
+  sq.count = nb;
+  sq.sC = sq.sA = sq.sB = sMat;
+  sq.ring_order_only = true;
+  auto nt_square_b = [&](double* C, const double* X, const double* Y) {
+    launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, C, ld, X, ld, Y, ld, nt, nt, (int)mp, nullptr, sq);
+  };
+  auto inverse_factor_b = [&](const double* fac, const double* invD, double* scratch, double* dst) {
+    trsm_identity_batched(s, fac, mp, ld, invD, scratch, bs);
+    hipLaunchKernelGGL(sgp_transpose_kernel, dim3((unsigned)(mp / KT), (unsigned)(mp / KT), (unsigned)nb), dim3(SGP_NT), 0, s, scratch,
+                       dst, ld, sMat);
+  };
+  const dim3 tiles_mm((unsigned)(mp / KT), (unsigned)(mp / KT), (unsigned)nb);
+
+  HIPCHK(c, hipMemcpyAsync(w.params.get(), ps, sizeof(KParams) * B, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(w.white.get(), white, sizeof(double) * B, hipMemcpyHostToDevice, s));
+  if (mu_const) HIPCHK(c, hipMemcpyAsync(w.mu.get(), mu_const, sizeof(double) * B, hipMemcpyHostToDevice, s));
+  else HIPCHK(c, hipMemcpyAsync(w.r.get(), mus, sizeof(double) * B * n, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(sgp_residual_kernel, dim3(blocks(n), 1, (unsigned)nb), dim3(SGP_NT), 0, s, g->y, mu_const ? w.mu.get() : nullptr,
+                     n, w.r.get());
+  const unsigned nblk = weights_blocks(n);
+  hipLaunchKernelGGL(sgp_weights_kernel, dim3(nblk, 1, (unsigned)nb), dim3(SGP_NT), 0, s, w.r, g->nv, 0.0, w.white, n, w.w, w.part, n,
+                     sPart);
+  hipLaunchKernelGGL(sgp_colsum_kernel, dim3(4, 1, (unsigned)nb), dim3(SGP_NT), 0, s, w.part, (int64_t)nblk, 4, w.red + RED_DATA, 0,
+                     sPart, (int64_t)SGP_RED);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemsetAsync(G, 0, sizeof(double) * B * sMat, s));
+  HIPCHK(c, hipMemsetAsync(w.vec.get(), 0, sizeof(double) * B * sVec, s));
+  HIPCHK(c, hipMemsetAsync(w.info.get(), 0, sizeof(int) * 2 * w.cap, s));
+  for (int64_t j0 = 0; j0 < n; j0 += P) {
+    const int64_t rows = std::min<int64_t>(P, n - j0);
+    double* Kp = w.P[0];
+    {
+      ProfScope ps_(c, s, GPMI_PROF_SGP_BUILD, 0.0, 8.0 * B * mp * P);
+      launch_kbuild_cross_batched(s, kernel, pdev, nb, g->z, m, mp, g->x + j0 * d, rows, P, Kp, ldp, sPanel, (int)d);
+      hipLaunchKernelGGL(sgp_scale_cols_kernel, dim3(blocks(rows), (unsigned)m, (unsigned)nb), dim3(SGP_NT), 0, s, Kp, ldp, rows,
+                         w.w + j0, sPanel, n);
+      hipLaunchKernelGGL(sgp_bvec_kernel, dim3((unsigned)m, 1, (unsigned)nb), dim3(SGP_NT), 0, s, Kp, ldp, rows, w.r + j0, w.w + j0, b,
+                         j0 > 0 ? 1 : 0, sPanel, n, sVec);
+    }
+    {
+      ProfScope ps_(c, s, GPMI_PROF_SGP_GRAM, (double)B * P * mp * (mp + GPMI_NB), 8.0 * B * (mp * P + 0.5 * mp * mp));
+      GemmBatch gb;
+      gb.count = nb;
+      gb.sC = sMat;
+      gb.sA = gb.sB = sPanel;
+      gb.ring_order_only = true;
+      launch_gemm_nt(s, TILES_LOWER, OP_SUB, G, ld, Kp, ldp, Kp, ldp, nt, nt, (int)P, nullptr, gb);  // -G until the sweep is over
+    }
+    HIPCHK(c, hipGetLastError());
+  }
+  {
+    ProfScope ps_(c, s, GPMI_PROF_SGP_FACTOR, B * (2.0 * mp * mp * mp / 3.0 + 8.0 * mp * mp * mp), 8.0 * 12.0 * B * mp * mp);
+    launch_mirror_lower(s, G, ld, mp, nb, sMat);
+    launch_negate(s, G, B * sMat);
+    launch_kbuild_cross_batched(s, kernel, pdev, nb, g->z, m, mp, g->z, m, mp, A, ld, sMat, (int)d);
+    hipLaunchKernelGGL(sgp_pad_diag_kernel, dim3(blocks(mp), 1, (unsigned)nb), dim3(SGP_NT), 0, s, A, ld, m, mp, 0.0, jitter, pdev,
+                       sMat);
+    potrf_lower_batched(c, s, A, mp, ld, w.invD1, info1, bs);
+    inverse_factor_b(A, w.invD1, LiT, Linv);
+    nt_square_b(W1, Linv, G);   // L^-1 G   (G symmetric)
+    nt_square_b(W2, W1, Linv);  // H = L^-1 G L^-T
+    hipLaunchKernelGGL(sgp_sym_b_kernel, tiles_mm, dim3(SGP_NT), 0, s, W2, LB, ld, sMat);
+    potrf_lower_batched(c, s, LB, mp, ld, w.invD2, info2, bs);
+    inverse_factor_b(LB, w.invD2, W3, LBinv);
+    launch_rows_dot(s, Linv, ld, mp, mp, b, v1, nb, sMat, sVec);
+    launch_rows_dot(s, LBinv, ld, mp, mp, v1, cc, nb, sMat, sVec);
+    hipLaunchKernelGGL(sgp_mm_reduce_kernel, dim3(1, 1, (unsigned)nb), dim3(SGP_NT), 0, s, LB, W2, ld, m, cc, w.red + RED_MM, sMat,
+                       sVec, (int64_t)SGP_RED);
+    HIPCHK(c, hipGetLastError());
+  }
+  if (second) {
+    ProfScope ps_(c, s, GPMI_PROF_SGP_GRAD, 0.0, 0.0);
+    double *T = A, *RT = W1, *Kinv = W3;
+    nt_square_b(RT, LiT, LBinv);  // L^-T L_B^-T
+    launch_rows_dot(s, RT, ld, mp, mp, cc, gamma, nb, sMat, sVec);
+    if (want_grad) {
+      const dim3 rows_mm(blocks(mp), (unsigned)mp, (unsigned)nb);
+      nt_square_b(W2, RT, RT);      // S = L^-T B^-1 L^-1
+      nt_square_b(Kinv, LiT, LiT);  // L^-T L^-1
+      hipLaunchKernelGGL(sgp_sub_kernel, rows_mm, dim3(SGP_NT), 0, s, Kinv, W2, T, ld, mp, sMat);
+      nt_square_b(LB, Kinv, G);     // K_mm^-1 G
+      nt_square_b(W2, LB, Kinv);    // K_mm^-1 G K_mm^-1
+      hipLaunchKernelGGL(sgp_sub_kernel, rows_mm, dim3(SGP_NT), 0, s, W2, T, LB, ld, mp, sMat);  // M2 - gamma gamma^T
+    }
+    HIPCHK(c, hipGetLastError());
+    for (int64_t j0 = 0; j0 < n; j0 += P) {
+      const int64_t rows = std::min<int64_t>(P, n - j0);
+      double *KTp = w.P[0], *Mp = w.P[1];
+      launch_kbuild_cross_batched(s, kernel, pdev, nb, g->x + j0 * d, rows, P, g->z, m, mp, KTp, ld, sPanel, (int)d);
+      launch_rows_dot(s, KTp, ld, P, mp, gamma, kg, nb, sPanel, sVec);
+      if (want_grad) {
+        GemmBatch gb;
+        gb.count = nb;
+        gb.sC = gb.sA = sPanel;
+        gb.sB = sMat;
+        gb.ring_order_only = true;
+        launch_gemm_nt(s, TILES_RECT, OP_ASSIGN, Mp, ld, KTp, ld, T, ld, (int)(P / GPMI_NB), nt, (int)mp, nullptr, gb);
+        hipLaunchKernelGGL(sgp_rowdot2_kernel, dim3((unsigned)rows, 1, (unsigned)nb), dim3(SGP_NT), 0, s, KTp, Mp, ld, m, q, sPanel,
+                           sVec);
+      }
+      hipLaunchKernelGGL(sgp_alpha_kernel, dim3(blocks(rows), 1, (unsigned)nb), dim3(SGP_NT), 0, s, w.r + j0, w.w + j0, kg,
+                         want_grad ? q : (const double*)nullptr, 0.0, pdev, rows, w.alpha + j0, term, n, sVec);
+      if (want_grad) {
+        hipLaunchKernelGGL(sgp_colsum_kernel, dim3(1, 1, (unsigned)nb), dim3(SGP_NT), 0, s, term, rows, 1, w.red + RED_NOISE,
+                           j0 > 0 ? 1 : 0, sVec, (int64_t)SGP_RED);
+        launch_contract_batched(s, kernel, (int)d, pdev, nb, g->x + j0 * d, rows, P, g->z, m, mp, Mp, ld, w.w + j0, w.alpha + j0,
+                                gamma, 1.0, 1.0, 0, 0.0, n_theta, w.ws, ContractStrides{sPanel, n, n, sVec, sWs});
+        hipLaunchKernelGGL(sgp_colsum_kernel, dim3((unsigned)n_theta, 1, (unsigned)nb), dim3(SGP_NT), 0, s, w.ws, (P / KT) * (mp / KT),
+                           n_theta, w.red + RED_GRAD, j0 > 0 ? 1 : 0, sWs, (int64_t)SGP_RED);
+      }
+      HIPCHK(c, hipGetLastError());
+    }
+    if (want_grad) {
+      // the K_mm term: weights -1/2 M2 = -1/2 (gamma gamma^T + LB), rows and columns are Z
+      launch_contract_batched(s, kernel, (int)d, pdev, nb, g->z, m, mp, g->z, m, mp, LB, ld, nullptr, gamma, gamma, -0.5, -0.5, 1,
+                              jitter, n_theta, w.ws, ContractStrides{sMat, 0, sVec, sVec, sWs});
+      hipLaunchKernelGGL(sgp_colsum_kernel, dim3((unsigned)n_theta, 1, (unsigned)nb), dim3(SGP_NT), 0, s, w.ws, (mp / KT) * (mp / KT),
+                         n_theta, w.red + RED_GRAD, 1, sWs, (int64_t)SGP_RED);
+    }
+    if (out.sum_alpha) {
+      hipLaunchKernelGGL(sgp_vecsum_kernel, dim3(nblk, 1, (unsigned)nb), dim3(SGP_NT), 0, s, w.alpha.get(), n, w.part.get(), sPart);
+      hipLaunchKernelGGL(sgp_colsum_kernel, dim3(1, 1, (unsigned)nb), dim3(SGP_NT), 0, s, w.part, (int64_t)nblk, 1, w.red + RED_SALPHA,
+                         0, sPart, (int64_t)SGP_RED);
+    }
+    HIPCHK(c, hipGetLastError());
+  }
+  // the one wait of the chunk: results, info and, if asked for, alpha
+  std::vector<double> hred((size_t)(B * SGP_RED));
+  std::vector<int> hinfo((size_t)(2 * B));
+  HIPCHK(c, hipMemcpyAsync(hred.data(), w.red.get(), sizeof(double) * B * SGP_RED, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(hinfo.data(), info1, sizeof(int) * B, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(hinfo.data() + B, info2, sizeof(int) * B, hipMemcpyDeviceToHost, s));
+  if (out.alpha) HIPCHK(c, hipMemcpyAsync(out.alpha, w.alpha.get(), sizeof(double) * B * n, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  const double LN_2PI = 1.8378770664093454836;
+  for (int64_t t = 0; t < B; ++t) {
+    const double* r = hred.data() + t * SGP_RED;
+    out.info[t] = hinfo[t] != 0 ? hinfo[t] : (hinfo[B + t] != 0 ? (int)m + hinfo[B + t] : 0);
+    const double a2 = ps[t].a2;
+    out.F[t] = -0.5 * ((double)n * LN_2PI + r[RED_DATA + 1] + 2.0 * r[RED_MM] + r[RED_DATA] - r[RED_MM + 2]) -
+               0.5 * (a2 * r[RED_DATA + 2] - r[RED_MM + 1]);
+    if (out.grad) {
+      double* gr = out.grad + t * (n_theta + 1);
+      for (int k = 0; k < n_theta; ++k) gr[k] = r[RED_GRAD + k];
+      gr[0] -= a2 * r[RED_DATA + 2];  // -1/2 sum w_i da^2 / d ln a
+      gr[n_theta] = white[t] > 0.0 ? white[t] * r[RED_NOISE] : 0.0;
+    }
+    if (out.sum_alpha) out.sum_alpha[t] = r[RED_SALPHA];
+  }
+  return GPMI_OK;
+}
+
 }  // namespace
 
 void sgp_release_all(gpmi_ctx* c) {
@@ -1000,12 +1396,95 @@ int gpmi_sgp_set_targets(gpmi_sgp* g, const double* r, const double* noise_var) 
   if (int rc = set_device(c)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->sgp_stream));
   HIPCHK(c, hipMemcpy(g->r, r, sizeof(double) * g->n, hipMemcpyHostToDevice));
-  if (noise_var) {
-    HIPCHK(c, hipMemcpy(g->nv, noise_var, sizeof(double) * g->n, hipMemcpyHostToDevice));
-  } else {
-    ZERO_SYNC(c, g->nv, sizeof(double) * g->n);
-  }
+  if (int rc = sgp_upload_noise(g, noise_var)) return rc;
   g->have_targets = true;
+  return GPMI_OK;
+}
+
+int gpmi_sgp_set_observations(gpmi_sgp* g, const double* y, const double* noise_var) {
+  if (!g) return GPMI_ERR_ARG;
+  gpmi_ctx* c = g->ctx;
+  ARGCHK(c, sgp_live(c, g), "gpmi_sgp_set_observations: not a live object of this handle");
+  ARGCHK(c, y != nullptr, "gpmi_sgp_set_observations: y_host is NULL");
+  if (int rc = set_device(c)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->sgp_stream));
+  if (!g->y)
+    if (int rc = g->y.alloc(c, g->n)) return rc;
+  HIPCHK(c, hipMemcpy(g->y, y, sizeof(double) * g->n, hipMemcpyHostToDevice));
+  if (int rc = sgp_upload_noise(g, noise_var)) return rc;
+  g->have_obs = true;
+  return GPMI_OK;
+}
+
+int gpmi_sgp_batch_schedule(int64_t n, int64_t m, int64_t d, int64_t panel_rows, int64_t T, int want_grad, int64_t max_chunk,
+                            int64_t budget_bytes, int64_t out[6]) {
+  if (!out || !sgp_n_ok(n) || !sgp_m_ok(m) || d < 1 || d > GPMI_MAX_D || !sgp_panel_ok(panel_rows) || T < 0 || max_chunk < 0 ||
+      budget_bytes < 0)
+    return GPMI_ERR_ARG;
+  const SgpBatchPlan pl = sgp_batch_plan(n, m, d, panel_rows, T, want_grad != 0, max_chunk, budget_bytes);
+  out[0] = pl.chunk;
+  out[1] = pl.nchunks;
+  out[2] = pl.bytes_per;
+  out[3] = pl.P;
+  out[4] = pl.panels;
+  out[5] = pl.mp;
+  return GPMI_OK;
+}
+
+int gpmi_sgp_bound_batch(gpmi_sgp* g, int kernel, int64_t T, const double* thetas, int n_theta, const double* white_var,
+                         const double* mu_const, const double* mus, double jitter_rel, int64_t panel_rows, int64_t max_chunk,
+                         double* F, double* grad, double* sum_alpha, double* alpha_host, int* info) {
+  if (!g) return GPMI_ERR_ARG;
+  gpmi_ctx* c = g->ctx;
+  const char* who = "gpmi_sgp_bound_batch";
+  if (!sgp_live(c, g)) return sgp_arg_error(c, who, ": not a live object of this handle");
+  if (T < 0) return sgp_arg_error(c, who, ": T must not be negative");
+  if (T == 0) return GPMI_OK;
+  ARGCHK(c, g->have_obs, "gpmi_sgp_bound_batch: gpmi_sgp_set_observations has not been called");
+  ARGCHK(c, thetas && white_var && F && info, "gpmi_sgp_bound_batch: thetas, white_var_host, F and info must be non-NULL");
+  ARGCHK(c, (mu_const != nullptr) != (mus != nullptr),
+         "gpmi_sgp_bound_batch: exactly one of mu_const_host and mus_host must be given");
+  ARGCHK(c, max_chunk >= 0, "gpmi_sgp_bound_batch: max_chunk must not be negative");
+  ARGCHK(c, kernel != GPMI_KERNEL_SUM && kernel_is_stationary(kernel),
+         "gpmi_sgp: the kernel must be GPMI_KERNEL_SE, _RQ, _M32 or _M52");
+  const int off = kernel_theta_offset(kernel);
+  ARGCHK(c, n_theta == g->d + off, "gpmi_sgp: n_theta does not match the kernel and the data dimension");
+  ARGCHK(c, std::isfinite(jitter_rel) && jitter_rel >= 0.0, "gpmi_sgp: jitter_rel must be finite and not negative");
+  ARGCHK(c, sgp_panel_ok(panel_rows), "gpmi_sgp: panel_rows out of range (0 .. 32768)");
+  std::vector<KParams> ps((size_t)T);
+  for (int64_t t = 0; t < T; ++t) {
+    const double* theta = thetas + t * n_theta;
+    for (int k = 0; k < n_theta; ++k) ARGCHK(c, std::isfinite(theta[k]), "gpmi_sgp: theta must be finite");
+    const double wv = white_var[t];
+    ARGCHK(c, std::isfinite(wv) && wv >= 0.0, "gpmi_sgp: white_var must be finite and not negative");
+    // every noise_var_i + white_var positive and finite: the sum is monotone in noise_var_i, so its range decides
+    ARGCHK(c, !g->nv_nan && g->nv_lo + wv > 0.0 && g->nv_hi + wv < std::numeric_limits<double>::infinity(),
+           "gpmi_sgp: noise_var_i + white_var must be positive and finite for every data point");
+    if (mu_const) ARGCHK(c, std::isfinite(mu_const[t]), "gpmi_sgp_bound_batch: mu_const_host must be finite");
+    KParams& p = ps[(size_t)t];
+    std::memset(&p, 0, sizeof(p));  // (the parameters as sgp_params forms them)
+    p.kernel = kernel;
+    p.d = (int)g->d;
+    const double a = std::exp(theta[0]);
+    p.a2 = a * a;
+    p.kappa = (kernel == GPMI_KERNEL_RQ) ? std::exp(theta[1]) : 1.0;
+    for (int k = 0; k < p.d; ++k) {
+      const double l = std::exp(theta[off + k]);
+      p.inv_l2[k] = 1.0 / (l * l);
+    }
+  }
+  if (int rc = set_device(c)) return rc;
+  const bool second = grad || sum_alpha || alpha_host;
+  const SgpBatchPlan pl = sgp_batch_plan(g->n, g->m, g->d, panel_rows, T, second, max_chunk, 0);
+  if (int rc = sgp_ensure_batch(g, pl, pl.chunk, second)) return rc;
+  for (int64_t t0 = 0; t0 < T; t0 += pl.chunk) {
+    const int64_t B = std::min(pl.chunk, T - t0);
+    const SgpBatchOut out{F + t0, grad ? grad + t0 * (n_theta + 1) : nullptr, sum_alpha ? sum_alpha + t0 : nullptr,
+                          alpha_host ? alpha_host + t0 * g->n : nullptr, info + t0};
+    if (int rc = sgp_batch_chunk(g, pl, kernel, B, ps.data() + t0, white_var + t0, mu_const ? mu_const + t0 : nullptr,
+                                 mus ? mus + t0 * g->n : nullptr, jitter_rel, n_theta, second, grad != nullptr, out))
+      return rc;
+  }
   return GPMI_OK;
 }
 
@@ -1117,7 +1596,7 @@ int gpmi_sgp_spatial_derivatives(gpmi_sgp* g, const double* pts, int64_t mq, dou
       sgp_query_panel(g, s, g->q_pts, rows, rp, Kq, V, U, gb);
       // the same two inverses the other way round (B k-major: no transposes are stored): rows (L_B^-T u)^T, then t^T
       launch_gemm(s, TILES_RECT, OP_ASSIGN, true, 0, W, ld, U, ld, g->fLBinv, ld, ntr, nt, (int)mp, nullptr, gb);
-      hipLaunchKernelGGL(sgp_sub_kernel, dim3(blocks(mp), (unsigned)rp), dim3(SGP_NT), 0, s, W, V, D, ld, mp);
+      hipLaunchKernelGGL(sgp_sub_kernel, dim3(blocks(mp), (unsigned)rp), dim3(SGP_NT), 0, s, W, V, D, ld, mp, 0);
       launch_gemm(s, TILES_RECT, OP_ASSIGN, true, 0, Tq, ld, D, ld, g->fLinv, ld, ntr, nt, (int)mp, nullptr, gb);
       HIPCHK(c, hipGetLastError());
     }

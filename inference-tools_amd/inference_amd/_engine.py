@@ -699,6 +699,21 @@ def sgp_schedule(n, m, panel_rows=0):
     return dict(zip(SGP_SCHEDULE_FIELDS, (int(v) for v in out)))
 
 
+SGP_BATCH_SCHEDULE_FIELDS = ("chunk", "chunks", "bytes_per_problem", "panel", "panels", "m_pad")
+
+
+def sgp_batch_schedule(n, m, d, T, panel_rows=0, want_grad=False, max_chunk=0, budget_bytes=0):
+    """gpmi_sgp_batch_schedule (host only, needs no device): what `SparseEngine.bound_batch` does with T vectors as a dict -
+    problems per chunk, chunks, workspace bytes per problem, rows of x per panel, panels, m padded.  budget_bytes = 0: the
+    library's cap (GPMI_BATCH_GIB).  ValueError outside the library's ranges."""
+    out = (C.c_int64 * 6)()
+    if _lib.load().gpmi_sgp_batch_schedule(int(n), int(m), int(d), int(panel_rows), int(T), int(bool(want_grad)), int(max_chunk),
+                                           int(budget_bytes), out) != 0:
+        raise ValueError(f"sgp_batch_schedule: n = {n}, m = {m}, d = {d}, panel_rows = {panel_rows}, T = {T}, max_chunk = "
+                         f"{max_chunk} or budget_bytes = {budget_bytes} out of range")
+    return dict(zip(SGP_BATCH_SCHEDULE_FIELDS, (int(v) for v in out)))
+
+
 def select_schedule(n):
     """gpmi_select_schedule (host only): the workgroups - block partials - of a selection step over n points."""
     out = (C.c_int64 * 1)()
@@ -756,10 +771,37 @@ class SparseEngine:
                    C.byref(F), dptr(grad), dptr(alpha), C.byref(info))
         return F.value, grad, alpha, info.value
 
+    def set_observations(self, y, noise_var=None):
+        """y itself and the data variances for `bound_batch`: they go up once and stay."""
+        y = as_f64(y)
+        nv = None if noise_var is None else as_f64(noise_var)
+        if y.shape != (self.n,) or (nv is not None and nv.shape != (self.n,)):
+            raise ValueError(f"y and noise_var must have shape ({self.n},)")
+        self._call("gpmi_sgp_set_observations", dptr(y), dptr(nv))
+
+    def bound_batch(self, kernel, thetas, white_vars, jitter, panel_rows=0, *, mu_const=None, mus=None, want_grad=False,
+                    want_alpha=False, max_chunk=0):
+        """gpmi_sgp_bound_batch for the T rows of `thetas`: (F (T,), gradient (T, n_theta + 1) | None, sum_alpha (T,) | None,
+        alpha (T, N) | None, info (T,)).  Exactly one of mu_const (T,) and mus (T, N); sum_alpha comes with the gradient.
+        A row with info > 0 did not factorise: its other entries are unspecified."""
+        thetas = as_f64(np.atleast_2d(thetas))
+        T, n_theta = thetas.shape
+        white = as_f64(np.broadcast_to(np.asarray(white_vars, dtype=float), (T,)))
+        mu_const = None if mu_const is None else as_f64(np.asarray(mu_const, dtype=float).reshape(T))
+        mus = None if mus is None else as_f64(np.asarray(mus, dtype=float).reshape(T, self.n))
+        F, info = np.zeros(T), np.zeros(T, dtype=np.int32)
+        grad = np.zeros((T, n_theta + 1)) if want_grad else None
+        sum_alpha = np.zeros(T) if want_grad else None
+        alpha = np.zeros((T, self.n)) if want_alpha else None
+        self._call("gpmi_sgp_bound_batch", int(kernel), T, dptr(thetas), n_theta, dptr(white), dptr(mu_const), dptr(mus),
+                   float(jitter), int(panel_rows), int(max_chunk), dptr(F), dptr(grad), dptr(sum_alpha), dptr(alpha),
+                   info.ctypes.data_as(C.POINTER(C.c_int)))
+        return F, grad, sum_alpha, alpha, info
+
     def fit(self, kernel, theta, white_var, jitter, panel_rows=0):
         theta = as_f64(theta)
         F, info = C.c_double(0.0), C.c_int(0)
-        self._call("gpmi_sgp_fit", int(kernel), dptr(theta), theta.size, float(white_var), float(jitter), int(panel_rows),
+        self._call("gpmi_sgp_fit",int(kernel), dptr(theta), theta.size, float(white_var), float(jitter), int(panel_rows),
                    C.byref(F), C.byref(info))
         return F.value, info.value
 

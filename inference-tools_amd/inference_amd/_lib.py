@@ -154,6 +154,10 @@ SIGNATURES = {
     "gpmi_sgp_posterior_draws": (C.c_int, [_vp, _dp, _i64, C.c_double, _i64, _dp, _i64, _i64, _dp, _dp, _dp, _ip]),
     "gpmi_sgp_spatial_derivatives": (C.c_int, [_vp, _dp, _i64, _dp, _dp]),
     "gpmi_sgp_schedule": (C.c_int, [_i64, _i64, _i64, C.POINTER(_i64)]),
+    "gpmi_sgp_set_observations": (C.c_int, [_vp, _dp, _dp]),
+    "gpmi_sgp_bound_batch": (C.c_int, [_vp, C.c_int, _i64, _dp, C.c_int, _dp, _dp, _dp, C.c_double, _i64, _i64, _dp, _dp, _dp, _dp,
+                                       _ip]),
+    "gpmi_sgp_batch_schedule": (C.c_int, [_i64, _i64, _i64, _i64, _i64, C.c_int, _i64, _i64, C.POINTER(_i64)]),
     "gpmi_select_schedule": (C.c_int, [_i64, C.POINTER(_i64)]),
     "gpmi_select_points": (C.c_int, [_vp, _i64, _i64, _dp, _dp, C.c_int, _dp, C.c_int, _i64, C.c_double, C.c_double,
                                      C.POINTER(_i64), _dp, _dp, C.POINTER(_i64)]),

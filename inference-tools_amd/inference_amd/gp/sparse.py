@@ -19,7 +19,10 @@ The fitted model answers what `GpRegressor` answers, at O(M m^2) per call whatev
 joint covariance), `sample_posterior` (joint draws; the covariance and the normals stay on the device),
 `spatial_derivatives` / `spatial_derivatives_batch` (gradients of the predictive mean and variance, all four kernels) -
 and through them the acquisition functions of `inference_amd.gp.acquisition` (`update_gp(sparse_model)`).
-Not supported: FITC, `gradient` (the covariance of the gradient), `GpOptimiser`, several GPUs.
+Batches of hyper-parameter vectors (`marginal_likelihood_batch`, `marginal_likelihood_gradient_batch`: one device call,
+gpmi_sgp_bound_batch, every launch carrying all of them) make the lockstep drivers of `inference_amd.mcmc` and the lockstep
+multi-start search (`multistart_bfgs(lockstep=True)`) run on a sparse model as they run on `GpRegressor`.
+Not supported: FITC, `gradient` (the covariance of the gradient), `GpOptimiser`, several GPUs, dF/dZ in batches.
 """
 import ctypes as C
 from copy import copy, deepcopy
@@ -141,11 +144,13 @@ class SparseGpRegressor:
     :param panel_rows: (extension) rows of x per panel of the device sweep; 0: the library's default.
     :param optimise_inducing: True: once the hyper-parameters are set, `optimise_inducing_points` moves Z - at the given
         `hyperpars`, or, if they were searched for, jointly with them from the result of that search.
+    :param lockstep_search: (extension) True: the multi-start search advances all its starts in lockstep on
+        `marginal_likelihood_gradient_batch` (`multistart_bfgs(lockstep=True)`).
     """
 
     def __init__(self, x, y, y_err=None, inducing_points=256, kernel=SquaredExponential, mean=ConstantMean, hyperpars=None,
                  optimizer="bfgs", n_starts=None, seed=None, jitter=1e-8, device=None, y_cov=None, panel_rows=0, optimise_inducing=False,
-                 inducing_method="random"):
+                 inducing_method="random", lockstep_search=False):
         if inducing_method not in INDUCING_METHODS:
             raise ValueError(f"inducing_method = {inducing_method!r}: must be one of {INDUCING_METHODS}")
         if inducing_method == "greedy" and not isinstance(inducing_points, (int, np.integer)):
@@ -218,6 +223,8 @@ class SparseGpRegressor:
         self._device = device
         self._engine = None
         self._targets_mean = None
+        self._observations_up = False
+        self._batch_independent = False
 
         if self.inducing_points is None:
             at = hyperpars if hyperpars is not None else [0.5 * (lo + hi) for lo, hi in self.hp_bounds]
@@ -228,7 +235,8 @@ class SparseGpRegressor:
             if optimizer not in ["bfgs", "diffev"]:
                 optimizer = "bfgs"
                 warn(msg.BAD_OPTIMIZER)
-            hyperpars = self.differential_evo() if optimizer == "diffev" else self.multistart_bfgs(starts=n_starts)
+            hyperpars = (self.differential_evo() if optimizer == "diffev"
+                         else self.multistart_bfgs(starts=n_starts, lockstep=bool(lockstep_search)))
         self.set_hyperparameters(hyperpars)
         if optimise_inducing:
             self.optimise_inducing_points(hyperpars=searched)
@@ -258,6 +266,8 @@ class SparseGpRegressor:
     # ---- the bound -----------------------------------------------------------------------------------------------
     def marginal_likelihood(self, theta) -> float:
         """The variational lower bound F of the log marginal likelihood; -1e50 where a factorisation fails."""
+        if self._batch_independent:
+            return float(self.marginal_likelihood_batch(np.asarray(theta, dtype=float)[None, :])[0])
         theta_stat, white = self._split(theta)
         F, _, _, info = self.engine.bound(self._kernel_id, theta_stat, white, self.jitter, self.panel_rows)
         if info != 0:
@@ -269,6 +279,9 @@ class SparseGpRegressor:
         """(F, dF/dtheta) with the gradient from the device; the mean parameters' part is (d mu / d theta)^T alpha.
         inducing_points=True: (F, dF/dtheta, dF/dZ) with the (m, d) gradient by the inducing inputs."""
         theta = np.asarray(theta, dtype=float)
+        if self._batch_independent and not inducing_points:
+            F, grad = self.marginal_likelihood_gradient_batch(theta[None, :])
+            return float(F[0]), grad[0]
         theta_stat, white = self._split(theta)
         F, g, alpha, info, *zgrad = self.engine.bound(self._kernel_id, theta_stat, white, self.jitter, self.panel_rows, True, True,
                                                       want_zgrad=bool(inducing_points))
@@ -285,6 +298,70 @@ class SparseGpRegressor:
         if inducing_points:
             return float(F), grad, zgrad[0]
         return float(F), grad
+
+    # ---- lockstep batches of the bound (as GpRegressor's: what the lockstep drivers of inference_amd.mcmc call) -------
+    def batch_independent_values(self, on: bool = True):
+        """(extension) on: `marginal_likelihood` and `marginal_likelihood_gradient(theta)` go through a batch of one, whose
+        values are, bit for bit, those of the same theta anywhere inside `marginal_likelihood_batch` /
+        `marginal_likelihood_gradient_batch` - a chain advanced alone then walks the trajectory it walks in lockstep.  The
+        gradient by the inducing inputs (`inducing_points=True`) keeps the single evaluation.  Off (the default): both are
+        the single evaluations."""
+        self._batch_independent = bool(on)
+
+    def _batch_call(self, thetas, want_grad):
+        """(thetas (T, P), means or None, the engine's bound_batch results) for T full hyper-parameter vectors."""
+        thetas = np.atleast_2d(np.asarray(thetas, dtype=float))
+        if thetas.ndim != 2 or thetas.shape[1] != self.n_hyperpars:
+            raise ValueError(msg.wrong_hyperpar_count(self.n_hyperpars, thetas.shape[-1]))
+        if not np.isfinite(thetas).all():
+            raise ValueError("the hyper-parameters of a batch must be finite")
+        if not self._observations_up:
+            self.engine.set_observations(self.y, self._noise_var)
+            self._observations_up = True
+        cov = thetas[:, self.cov_slice]
+        white = np.exp(2.0 * cov[:, self._wn_index]) if self._wn_index is not None else np.zeros(len(thetas))
+        constant = isinstance(self.mean, ConstantMean)
+        means = None if constant else [self.mean.mean_and_gradients(t[self.mean_slice]) for t in thetas]
+        mean_kw = dict(mu_const=thetas[:, 0]) if constant else dict(mus=np.array([mu for mu, _ in means]))
+        out = self.engine.bound_batch(self._kernel_id, np.ascontiguousarray(cov[:, self._stat_slice]), white, self.jitter,
+                                      self.panel_rows, want_grad=want_grad, want_alpha=want_grad and not constant, **mean_kw)
+        return thetas, means, out
+
+    def marginal_likelihood_batch(self, thetas) -> np.ndarray:
+        """(extension) The bound F for T hyper-parameter vectors in one device call (gpmi_sgp_bound_batch: every launch
+        carries all of them); -1e50 where a factorisation fails, with one warning per call.  A row's value does not depend
+        on the rows it shares the call with."""
+        thetas = np.asarray(thetas, dtype=float)
+        if thetas.size == 0:
+            return np.empty(0)
+        _, _, (F, _, _, _, info) = self._batch_call(thetas, False)
+        if (info != 0).any():
+            warn("Cholesky decomposition failure in marginal_likelihood")
+            F[info != 0] = -1e50
+        return F
+
+    def marginal_likelihood_gradient_batch(self, thetas, failed: str = "raise"):
+        """(extension) (F (T,), dF/dtheta (T, P)) for T hyper-parameter vectors in one device call.  A vector whose
+        matrices are not positive definite raises LinAlgError for the whole batch; with `failed="sentinel"` such a row
+        gets -1e50 and a zero gradient instead (one warning per call) and the other rows keep their values."""
+        if failed not in ("raise", "sentinel"):
+            raise ValueError("'failed' must be \"raise\" or \"sentinel\"")
+        thetas = np.asarray(thetas, dtype=float)
+        if thetas.size == 0:
+            return np.empty(0), np.empty((0, self.n_hyperpars))
+        thetas, means, (F, g, sum_alpha, alpha, info) = self._batch_call(thetas, True)
+        grads = np.zeros((len(thetas), self.n_hyperpars))
+        if means is None:
+            grads[:, 0] = sum_alpha  # ConstantMean: d mu / d theta_0 = 1
+        else:
+            for t, (_, mean_grads) in enumerate(means):
+                grads[t, self.mean_slice] = [float(np.dot(dmu, alpha[t])) for dmu in mean_grads]
+        cov_grads = np.zeros((len(thetas), self.cov.n_params))
+        cov_grads[:, self._stat_slice] = g[:, :-1]
+        if self._wn_index is not None:
+            cov_grads[:, self._wn_index] = g[:, -1]
+        grads[:, self.cov_slice] = cov_grads
+        return GpRegressor._failed_rows(F, grads, info, failed)
 
     def set_hyperparameters(self, hyperpars):
         hyperpars = np.asarray(hyperpars, dtype=float)
@@ -367,6 +444,7 @@ class SparseGpRegressor:
         self.inducing_points = z
         self._engine = None
         self._targets_mean = None
+        self._observations_up = False
         self.set_hyperparameters(self.hyperpars)
 
     def optimise_inducing_points(self, hyperpars=True, maxiter=200):
@@ -463,14 +541,29 @@ class SparseGpRegressor:
             return 1e50, np.zeros(self.n_hyperpars)
         return -F, -g
 
-    def multistart_bfgs(self, starts=None):
+    def multistart_bfgs(self, starts=None, lockstep=False):
+        """Multi-start L-BFGS-B on the device gradient, one start after another; lockstep=True: all starts advance together
+        (gp/_lockstep.py), one `marginal_likelihood_gradient_batch` per round, a failed row counted as 1e50 with a zero
+        gradient as `bfgs_cost_func` counts it."""
         if starts is None:
             starts = int(2 * np.sqrt(len(self.hp_bounds))) + 1
         lwr, upr = [np.array([k[i] for k in self.hp_bounds]) for i in [0, 1]]
         starting_positions = [lwr + (upr - lwr) * random(size=len(self.hp_bounds)) for _ in range(starts - 1)]
         starting_positions.append(0.5 * (lwr + upr))
-        results = [fmin_l_bfgs_b(func=self.bfgs_cost_func, x0=x0, approx_grad=False, bounds=self.hp_bounds)
-                   for x0 in starting_positions]
+        if lockstep:
+            from inference_amd.gp._lockstep import lockstep_lbfgsb
+            from warnings import catch_warnings, simplefilter
+
+            def neg_batch(X):
+                with catch_warnings():
+                    simplefilter("ignore")
+                    F, g = self.marginal_likelihood_gradient_batch(X, failed="sentinel")
+                return -F, -g
+
+            results = lockstep_lbfgsb(neg_batch, np.array(starting_positions), self.hp_bounds)
+        else:
+            results = [fmin_l_bfgs_b(func=self.bfgs_cost_func, x0=x0, approx_grad=False, bounds=self.hp_bounds)
+                       for x0 in starting_positions]
         self.search_log = [(np.array(x0), np.array(r[0]), float(r[1])) for x0, r in zip(starting_positions, results)]
         return sorted(results, key=lambda r: r[1])[0][0]
 
@@ -488,6 +581,7 @@ class SparseGpRegressor:
         state = self.__dict__.copy()
         state["_engine"] = None
         state["_targets_mean"] = None
+        state["_observations_up"] = False
         return state
 
     def __str__(self):
