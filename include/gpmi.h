@@ -835,6 +835,56 @@ int gpmi_select_points(gpmi_ctx* ctx, int64_t n, int64_t d, const double* x_host
  * out NULL: GPMI_ERR_ARG. */
 int gpmi_select_schedule(int64_t n, int64_t out[1]);
 
+/* ---- many targets at one set of inputs (MultiTargetGpRegressor) ---------------------
+ * T target vectors observed at the handle's x with its data errors and ONE covariance K(theta) (the matrix of gpmi_fit:
+ * kernel or sum, + extra_diag I, + the data variances; the y of gpmi_set_data takes no part).  With R = Y - 1 m^T (n x T),
+ * K = L L^T, V = L^-1 R and A = K^-1 R:
+ *   lml_t = -1/2 |V[:, t]|^2 - sum_i ln L_ii     (no 2 pi term, as gpmi_lml),     lml = sum_t lml_t,
+ *   d lml / d theta_j = 1/2 sum_ab (A A^T - T K^-1)_ab (dK / d theta_j)_ab,
+ *   mean(q)[t] = k(q)^T A[:, t]  (the caller adds m_t),   var(q) = a^2 - |L^-1 k(q)|^2  (one for all targets).
+ * K is built, factorised and - for the gradient - inverted ONCE per call; per target there are the two O(n^2) solves.
+ * On the device the targets are rows: T_pad x (n_pad + 32) doubles with T_pad = T rounded up to 128, zeros in the padding;
+ * V^T and A^T are one many-right-hand-side forward and one backward solve, the means one product per 2048 query points.
+ * Every sum has an order fixed by (n, T): repeated calls return the same bits, and no call uses atomics.
+ * gpmi_mt_fit leaves the factor where gpmi_fit leaves it (lane 0) and gpmi_mt_predict's variance is gpmi_predict's, bit
+ * for bit.  gpmi_mt_lml, gpmi_mt_lml_grad and gpmi_mt_loo_terms evaluate other hyper-parameters on lane 1: the fit and
+ * every later answer of it keep their bits.
+ * A matrix that does not factorise is reported through info > 0 (lml and lml_t are then -1e50, the other outputs
+ * undefined), not through the status.
+ * GPMI_ERR_ARG, with the handle still usable: T outside 1 .. GPMI_MT_MAX_T; any of these calls before
+ * gpmi_mt_set_targets - a gpmi_set_data drops the targets with the rest of the data set -; gpmi_mt_alpha, gpmi_mt_predict
+ * or gpmi_mt_loo without a successful gpmi_mt_fit as the handle's last fit; the kernel / n_theta errors of gpmi_fit.
+ * Device memory, owned by the handle and released with it or at the next gpmi_set_data / gpmi_mt_set_targets, each buffer
+ * allocated by the first call that needs it: 8 T_pad (n_pad + 32) bytes for the targets, as much for the fit's A^T and for
+ * the evaluations' V^T / A^T; 8 n_pad (T_pad + 32) for the transposed copies; 8 * 2048 (T_pad + 32 + T) for a chunk of
+ * means; three short vectors. */
+#define GPMI_MT_MAX_T 4096
+/* r_host: n x T row-major, the residuals Y - 1 m^T.  Replaces an earlier target matrix of the handle. */
+int gpmi_mt_set_targets(gpmi_ctx* ctx, const double* r_host /* n x T */, int64_t T);
+/* Fit at theta: L into lane 0 by gpmi_fit's own stages, A^T kept for gpmi_mt_alpha / _predict / _loo. */
+int gpmi_mt_fit(gpmi_ctx* ctx, int kernel, const double* theta_host, int n_theta, double extra_diag,
+                double* lml_t_host /* T, or NULL */, double* lml /* or NULL */, int* info);
+int gpmi_mt_lml(gpmi_ctx* ctx, int kernel, const double* theta_host, int n_theta, double extra_diag,
+                double* lml_t_host /* T, or NULL */, double* lml /* or NULL; not both */, int* info);
+/* grad_host: n_theta + 1 values - d lml / d theta_j as gpmi_lml_grad lays them out, then T times its trace_q,
+ * sum_i (sum_t A_it^2 - T (K^-1)_ii): d lml / d extra_diag is half of it.  K^-1 is formed as in gpmi_lml_grad, A A^T / T is
+ * subtracted from its lower tiles by one product with k = T_pad, and gpmi_lml_grad's contraction runs once with u = v = 0;
+ * the transposed copy A / sqrt(T) (n_pad rows) is tiled through LDS. */
+int gpmi_mt_lml_grad(gpmi_ctx* ctx, int kernel, const double* theta_host, int n_theta, double extra_diag, double* lml,
+                     double* grad_host /* n_theta + 1 */, int* info);
+/* The leave-one-out terms at theta: a2_i = sum_t A_it^2 and (K^-1)_ii.  With var_i = 1 / (K^-1)_ii the leave-one-out
+ * log-likelihood of all targets is -1/2 sum_i (var_i a2_i + T ln var_i). */
+int gpmi_mt_loo_terms(gpmi_ctx* ctx, int kernel, const double* theta_host, int n_theta, double extra_diag,
+                      double* a2_host /* n */, double* ikdiag_host /* n */, int* info);
+/* A of the fit, n x T row-major: column t is the alpha of the single-target model of target t. */
+int gpmi_mt_alpha(gpmi_ctx* ctx, double* alpha_host /* n x T */);
+/* mean_host: m x T row-major, k(q)^T A without the offsets m_t; var_host: m values a^2 - |L^-1 k(q)|^2, or NULL. */
+int gpmi_mt_predict(gpmi_ctx* ctx, const double* pts_host /* m x d */, int64_t m, double* mean_host /* m x T */,
+                    double* var_host /* m, or NULL */);
+/* Leave-one-out residuals of the fit: resid_loo[i][t] = A_it / (K^-1)_ii (the prediction is Y_it minus it), and (K^-1)_ii.
+ * Uses lane 1's second matrix for L^-T, as gpmi_loo_diag. */
+int gpmi_mt_loo(gpmi_ctx* ctx, double* resid_loo_host /* n x T */, double* ikdiag_host /* n */);
+
 /* ---- instrumentation ---------------------------------------------------------------
  * HIP-event timing on the handle's own stream (torch.cuda.Event would not see it). */
 int gpmi_timer_start(gpmi_ctx* ctx);

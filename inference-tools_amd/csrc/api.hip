@@ -188,6 +188,7 @@ void free_batch_ws(gpmi_ctx* c) { static_cast<BatchBufs&>(*c) = BatchBufs(); }
 void free_data(gpmi_ctx* c) {
   c->linv = LinvState();
   static_cast<MixBufs&>(*c) = MixBufs();
+  static_cast<MultiBufs&>(*c) = MultiBufs();  // (the targets belong to the data set: gpmi_mt_set_targets again)
   for (size_t i = c->lanes.size(); i-- > 0;) lane_free(c->lanes[i]);  // (lanes >= 2 borrow the streams of lanes 0, 1)
   c->lanes.clear();
   static_cast<DataBufs&>(*c) = DataBufs();

@@ -287,7 +287,22 @@ struct MixBufs {
   DevBuf<double> Q3;           // third query panel (mq_cap x ld at its allocation)
 };
 
-struct gpmi_ctx : DataBufs, QueryBufs, BatchBufs, MixBufs {
+// many targets on one factorisation (api_multi.hip, gpmi_mt_*): mt_T targets stored as rows, mt_Tp = mt_T rounded up to
+// the tile, zero in the padding; each buffer is allocated by the first call that needs it
+struct MultiBufs {
+  int64_t mt_T = 0, mt_Tp = 0, mt_ldt = 0;  // mt_ldt = mt_Tp + 32: the pitch of the arrays with one row per data point
+  bool mt_fitted = false;   // mtA belongs to the factor in lane 0 (gpmi_mt_fit was the last fit and succeeded)
+  DevBuf<double> mtR;       // mt_Tp x ld   residuals Y - m, one target per row
+  DevBuf<double> mtA;       // mt_Tp x ld   A^T = R^T K^-1 of the fit
+  DevBuf<double> mtW;       // mt_Tp x ld   V^T, then A^T of an evaluation on lane 1
+  DevBuf<double> mtAn;      // np x mt_ldt  transposed copies: the upload, A / sqrt(T), A, A_it / (K^-1)_ii
+  DevBuf<double> mtMean;    // 2048 x mt_ldt predictive means of a chunk of query points
+  DevBuf<double> mtVec;     // mt_Tp + 8 + np: |V_t|^2 per target, their sum (at mt_Tp), sum_t A_it^2 per point (at mt_Tp + 8)
+  DevBuf<double> mtZero;    // np zeros: u and v of the contraction
+  PinBuf<double> h_mtVec;   // pinned mirror of mtVec
+};
+
+struct gpmi_ctx : DataBufs, QueryBufs, BatchBufs, MixBufs, MultiBufs {
   int device = 0;
   int ncu = 256;      // compute units of the device
   int pair_cus[GPMI_NPAIRS] = {32};  // CUs of the panel stream of look-ahead pair k (the update stream has the rest)

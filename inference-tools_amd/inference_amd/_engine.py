@@ -610,6 +610,70 @@ class GpEngine(_DeviceCommMixin, _DrawsMixin):
         self.h.call("gpmi_profile_clock", C.byref(ghz))
         return ghz.value
 
+    # -- many targets on one factorisation (gpmi_mt_*) --------------------------------------
+    def mt_set_targets(self, residuals):
+        """gpmi_mt_set_targets: the (n, T) residuals Y - 1 m^T, kept on the device as rows."""
+        r = as_f64(residuals)
+        if r.ndim != 2 or r.shape[0] != self.n:
+            raise ValueError(f"residuals must be ({self.n}, T), got {r.shape}")
+        self.h.call("gpmi_mt_set_targets", dptr(r), r.shape[1])
+        self.mt_targets = r.shape[1]
+
+    def _mt_values(self, name, kernel, theta_cov, extra_diag, per_target):
+        theta = as_f64(theta_cov)
+        lml_t = np.empty(self.mt_targets) if per_target else None
+        lml, info = C.c_double(0.0), C.c_int(0)
+        self.h.call(name, kernel, dptr(theta), theta.size, float(extra_diag), dptr(lml_t), C.byref(lml), C.byref(info))
+        return lml.value, lml_t, info.value
+
+    def mt_fit(self, kernel, theta_cov, extra_diag, per_target=True):
+        """gpmi_mt_fit: (lml, lml_t (T,) | None, info); the factor stays in lane 0, A^T on the device."""
+        return self._mt_values("gpmi_mt_fit", kernel, theta_cov, extra_diag, per_target)
+
+    def mt_lml(self, kernel, theta_cov, extra_diag, per_target=False):
+        """gpmi_mt_lml: (lml, lml_t (T,) | None, info) at other hyper-parameters; the fit is not touched."""
+        return self._mt_values("gpmi_mt_lml", kernel, theta_cov, extra_diag, per_target)
+
+    def mt_lml_grad(self, kernel, theta_cov, extra_diag):
+        """gpmi_mt_lml_grad: (lml, grad (n_theta,), T * trace_q, info)."""
+        theta = as_f64(theta_cov)
+        grad = np.empty(theta.size + 1)
+        lml, info = C.c_double(0.0), C.c_int(0)
+        self.h.call("gpmi_mt_lml_grad", kernel, dptr(theta), theta.size, float(extra_diag), C.byref(lml), dptr(grad),
+                    C.byref(info))
+        return lml.value, grad[:-1].copy(), float(grad[-1]), info.value
+
+    def mt_loo_terms(self, kernel, theta_cov, extra_diag):
+        """gpmi_mt_loo_terms: (a2 (n,) = sum_t A_it^2, diag K^-1 (n,), info)."""
+        theta = as_f64(theta_cov)
+        a2, ikdiag = np.empty(self.n), np.empty(self.n)
+        info = C.c_int(0)
+        self.h.call("gpmi_mt_loo_terms", kernel, dptr(theta), theta.size, float(extra_diag), dptr(a2), dptr(ikdiag),
+                    C.byref(info))
+        return a2, ikdiag, info.value
+
+    def mt_alpha(self):
+        """gpmi_mt_alpha: A = K^-1 R of the fit, (n, T)."""
+        out = np.empty((self.n, self.mt_targets))
+        self.h.call("gpmi_mt_alpha", dptr(out))
+        return out
+
+    def mt_predict(self, pts, want_var=True):
+        """gpmi_mt_predict: (k(q)^T A (m, T) without the offsets, a^2 - |L^-1 k(q)|^2 (m,) | None)."""
+        p = as_f64(pts)
+        m = p.shape[0]
+        mean = np.empty((m, self.mt_targets))
+        var = np.empty(m) if want_var else None
+        self.h.call("gpmi_mt_predict", dptr(p), m, dptr(mean), dptr(var))
+        return mean, var
+
+    def mt_loo(self):
+        """gpmi_mt_loo: (A_it / (K^-1)_ii (n, T), diag K^-1 (n,)) of the fit."""
+        resid = np.empty((self.n, self.mt_targets))
+        ikdiag = np.empty(self.n)
+        self.h.call("gpmi_mt_loo", dptr(resid), dptr(ikdiag))
+        return resid, ikdiag
+
     def sync(self):
         self.h.call("gpmi_sync")
 

@@ -36,6 +36,7 @@ DRAWS_MAX_M = 16384  # GPMI_DRAWS_MAX_M: the most points gpmi_posterior_draws / 
 DRAWS_PANEL = 4096  # GPMI_DRAWS_PANEL: draws per panel of those two
 PROF_SGP_BUILD, PROF_SGP_GRAM, PROF_SGP_FACTOR, PROF_SGP_GRAD = 13, 14, 15, 16  # GPMI_PROF_SGP_*
 SGP_MAX_M = 4096  # GPMI_SGP_MAX_M: the most inducing points a gpmi_sgp object takes
+MT_MAX_T = 4096  # GPMI_MT_MAX_T: the most targets gpmi_mt_set_targets takes
 
 
 class GpmiUnavailable(RuntimeError):
@@ -161,6 +162,14 @@ SIGNATURES = {
     "gpmi_select_schedule": (C.c_int, [_i64, C.POINTER(_i64)]),
     "gpmi_select_points": (C.c_int, [_vp, _i64, _i64, _dp, _dp, C.c_int, _dp, C.c_int, _i64, C.c_double, C.c_double,
                                      C.POINTER(_i64), _dp, _dp, C.POINTER(_i64)]),
+    "gpmi_mt_set_targets": (C.c_int, [_vp, _dp, _i64]),
+    "gpmi_mt_fit": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double, _dp, _dp, _ip]),
+    "gpmi_mt_lml": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double, _dp, _dp, _ip]),
+    "gpmi_mt_lml_grad": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double, _dp, _dp, _ip]),
+    "gpmi_mt_loo_terms": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double, _dp, _dp, _ip]),
+    "gpmi_mt_alpha": (C.c_int, [_vp, _dp]),
+    "gpmi_mt_predict": (C.c_int, [_vp, _dp, _i64, _dp, _dp]),
+    "gpmi_mt_loo": (C.c_int, [_vp, _dp, _dp]),
     "gpmi_timer_start": (C.c_int, [_vp]),
     "gpmi_timer_stop": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "gpmi_profile_enable": (C.c_int, [_vp, C.c_int]),
@@ -270,7 +279,7 @@ class Handle:
                              "gpmi_linv_lml_grad_dense", "gpmi_linv_posterior_dense", "gpmi_loo_terms", "gpmi_loo_grad",
                              "gpmi_loo_terms_mix", "gpmi_dev_potrf", "gpmi_loo_grad_batch", "gpmi_loo_grad_batch_noise", "gpmi_lml_grad_batch_noise",
                              "gpmi_lml_grad_batch_mix", "gpmi_loo_grad_batch_mix", "gpmi_predict_batch", "gpmi_posterior_draws",
-                             "gpmi_mvn_draws"))
+                             "gpmi_mvn_draws", "gpmi_mt_fit", "gpmi_mt_lml", "gpmi_mt_lml_grad", "gpmi_mt_loo_terms"))
 
     def call(self, name, *args):
         if _TRACE_MS is not None:  # GPMI_TRACE_CALLS=<ms>: report every entry-point call that takes longer (debugging aid)
