@@ -255,6 +255,36 @@ constexpr int DMA_BK = 8;
 #define GPMI_DMA_STAGES 4
 #endif
 constexpr int DMA_STAGES = GPMI_DMA_STAGES;
+// Inside one ring stage (profiles/r25_ring_stage.txt; each switch alone leaves every bit of every result as it was):
+//   GPMI_RING_SADDR         the DMA pieces take their source as a uniform base (SGPR pair, advanced by scalar adds) plus a
+//                           per-lane 32-bit byte offset that never changes, instead of a per-lane 64-bit pointer formed
+//                           with vector adds in every stage (a tile spans < 2^32 bytes, as in staged_tile)
+//   GPMI_RING_STATIC_TRIPS  the four-stage trips of the main loop are those whose stages ALL prefetch: their wait is a
+//                           constant vmcnt and nothing in the stage is behind a branch; the last stages run one by one
+//   GPMI_RING_DMA_UNDER     in those trips the pieces are issued between the MFMAs (after MFMA GPMI_RING_DMA_FIRST and
+//                           then every GPMI_RING_DMA_STEP; the 64 x 64 body: GPMI_RING_DMA64_*) instead of in front of
+//                           them: between the barrier and the first MFMA a wave issues its fragment reads and nothing else
+#ifndef GPMI_RING_SADDR
+#define GPMI_RING_SADDR 1
+#endif
+#ifndef GPMI_RING_STATIC_TRIPS
+#define GPMI_RING_STATIC_TRIPS 1
+#endif
+#ifndef GPMI_RING_DMA_UNDER
+#define GPMI_RING_DMA_UNDER 1
+#endif
+#ifndef GPMI_RING_DMA_FIRST
+#define GPMI_RING_DMA_FIRST 2
+#endif
+#ifndef GPMI_RING_DMA_STEP
+#define GPMI_RING_DMA_STEP 4
+#endif
+#ifndef GPMI_RING_DMA64_FIRST
+#define GPMI_RING_DMA64_FIRST 1
+#endif
+#ifndef GPMI_RING_DMA64_STEP
+#define GPMI_RING_DMA64_STEP 2
+#endif
 constexpr int DMA_OP_DOUBLES = 128 * DMA_BK;  // one operand of one stage: 8 KiB
 constexpr int DMA128_LDS_DOUBLES = DMA_STAGES * 2 * DMA_OP_DOUBLES;
 constexpr int DMA64_LDS_DOUBLES = DMA_STAGES * 2 * 64 * DMA_BK;
@@ -267,6 +297,21 @@ __device__ inline void dma_wait(int newer) {
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// a pointer that is the same in every lane, as a scalar (for the "s" operands of the pieces)
+__device__ __forceinline__ const double* ring_uniform(const double* p) {
+  const unsigned long long v = (unsigned long long)(uintptr_t)p;
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+  return reinterpret_cast<const double*>((uintptr_t)(((unsigned long long)hi << 32) | lo));
+}
+// one DMA piece: 16 bytes per lane, 1 KiB per wave, to LDS byte address `dst` (uniform); the source per lane as a
+// pointer or as uniform base + byte offset
+__device__ __forceinline__ void ring_piece(const double* src, unsigned dst) {
+  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(dst) : "memory");
+}
+__device__ __forceinline__ void ring_piece(unsigned voff, const double* sbase, unsigned dst) {
+  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(dst) : "memory");
+}
 // nk: 8-deep stages
 template <int OP, int CST = CST_NT>
 __device__ __forceinline__ void dma128_tile(const double* __restrict__ Ag, const double* __restrict__ Bg, double* Cg,
@@ -277,8 +322,6 @@ __device__ __forceinline__ void dma128_tile(const double* __restrict__ Ag, const
   // this thread's two pieces per operand and stage: p = i * 256 + tid -> row p >> 2, slot p & 3
   const int row0 = tid >> 2, slot = tid & 3;
   const int q0 = (slot - 2 * ((row0 >> 2) & 3)) & 3;          // rows row0 and row0 + 64 have the same (row >> 2) & 3
-  const double* a_src0 = Ag + (int64_t)row0 * lda + 2 * q0;
-  const double* a_src1 = a_src0 + (int64_t)64 * lda;
   // B rows (= columns of C) are permuted on their way into LDS: LDS row 16 t + fr of a wave column block holds
   // column 2 fr + t (t < 2) or 32 + 2 fr + t - 2 of that block, so that MFMA tiles (j, j + 1) of a lane are two
   // ADJACENT columns of C: the C tile is read and written with 16-byte accesses, 256 contiguous bytes per row and
@@ -287,25 +330,28 @@ __device__ __forceinline__ void dma128_tile(const double* __restrict__ Ag, const
     const int t = (R >> 4) & 3, f = R & 15;
     return (R & 64) + ((t & 2) << 4) + 2 * f + (t & 1);
   };
-  const double* b_src0 = Bg + (int64_t)bperm(row0) * ldb + 2 * q0;
-  const double* b_src1 = Bg + (int64_t)bperm(row0 + 64) * ldb + 2 * q0;
   const unsigned lds0 = (unsigned)(uintptr_t)smem;  // LDS byte address of the ring (address space 3 pointers are offsets)
   const unsigned wave_off = (unsigned)__builtin_amdgcn_readfirstlane(wave * 64 * 16);
+  // piece p of a stage: 0, 1 = A rows row0, row0 + 64; 2, 3 = B rows bperm(row0), bperm(row0 + 64)
+  const int64_t src_off[4] = {(int64_t)row0 * lda + 2 * q0, (int64_t)(row0 + 64) * lda + 2 * q0,
+                              (int64_t)bperm(row0) * ldb + 2 * q0, (int64_t)bperm(row0 + 64) * ldb + 2 * q0};
+#if GPMI_RING_SADDR
+  const double* Au = ring_uniform(Ag);
+  const double* Bu = ring_uniform(Bg);
+  const unsigned voff[4] = {(unsigned)(src_off[0] * 8), (unsigned)(src_off[1] * 8), (unsigned)(src_off[2] * 8),
+                            (unsigned)(src_off[3] * 8)};
+#endif
+  auto piece = [&](int p, int st, int k0) {
+    const unsigned dst = lds0 + (unsigned)st * (2 * DMA_OP_DOUBLES * 8) + wave_off + (p >> 1) * (DMA_OP_DOUBLES * 8) + (p & 1) * (256 * 16);
+#if GPMI_RING_SADDR
+    ring_piece(voff[p], (p < 2 ? Au : Bu) + k0, dst);
+#else
+    ring_piece((p < 2 ? Ag : Bg) + src_off[p] + k0, dst);
+#endif
+  };
   auto issue = [&](int st, int k0) {
-    const unsigned base = lds0 + (unsigned)st * (2 * DMA_OP_DOUBLES * 8) + wave_off;
-    const double* p0 = a_src0 + k0;
-    const double* p1 = a_src1 + k0;
-    const double* p2 = b_src0 + k0;
-    const double* p3 = b_src1 + k0;
-    asm volatile(
-        "s_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off\n\t"
-        "s_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\t"
-        "s_mov_b32 m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off"
-        :
-        : "v"(p0), "v"(p1), "v"(p2), "v"(p3), "s"(base), "s"(base + 256 * 16), "s"(base + DMA_OP_DOUBLES * 8),
-          "s"(base + DMA_OP_DOUBLES * 8 + 256 * 16)
-        : "memory");
+#pragma unroll
+    for (int p = 0; p < 4; ++p) piece(p, st, k0);
   };
   for (int st = 0; st < DMA_STAGES - 1 && st < nk; ++st) issue(st, st * DMA_BK);
 
@@ -327,13 +373,24 @@ __device__ __forceinline__ void dma128_tile(const double* __restrict__ Ag, const
   const int rslot = (fk + 2 * (fr >> 2)) & 3;
   const int a_off = ((wr * 64 + fr) * 4 + rslot) * 2;                      // doubles
   const int b_off = DMA_OP_DOUBLES + ((wc * 64 + fr) * 4 + rslot) * 2;
-  auto stage = [&](int kt) {
+  // `full`: a stage of a main-loop trip (GPMI_RING_STATIC_TRIPS) - stage kt + DMA_STAGES - 1 exists, so the wait is the
+  // constant one and the prefetch unconditional.  vmcnt counts whole stages either way: the four pieces of stage
+  // kt + DMA_STAGES - 1 are issued inside stage kt, in front of its MFMAs or between them, and always before the wait
+  // of stage kt + 1, which therefore has exactly the pieces of stages kt + 2 and kt + 3 (8 operations) younger than the
+  // ones it needs.  The ring slot they write, (kt - 1) % DMA_STAGES, was last read in stage kt - 1, by fragment reads
+  // that every wave has consumed in MFMAs before it arrived at the barrier of stage kt.
+  auto stage = [&](int kt, auto full) {
+    constexpr bool under = GPMI_RING_DMA_UNDER && decltype(full)::value;
     const int ahead = nk - 1 - kt;  // stages issued after this one
-    // the first stages also have the 64 C loads behind them: any vmcnt <= 63 covers the stage (in-order return)
-    dma_wait(4 * (ahead < DMA_STAGES - 2 ? ahead : DMA_STAGES - 2));
+    // the first stages also have the tile's 32 C loads (16 bytes each) behind them: younger than every piece issued in
+    // the prologue, so the same count covers the stage (in-order return); stage 0 also waits for the first 24 of them
+    if (decltype(full)::value) dma_wait(4 * (DMA_STAGES - 2));
+    else dma_wait(4 * (ahead < DMA_STAGES - 2 ? ahead : DMA_STAGES - 2));
     __syncthreads();
+    const bool pf = decltype(full)::value || kt + DMA_STAGES - 1 < nk;
+    const int pf_st = (kt + DMA_STAGES - 1) % DMA_STAGES, pf_k0 = (kt + DMA_STAGES - 1) * DMA_BK;
 #ifdef GPMI_DMA_ISSUE_EARLY
-    if (kt + DMA_STAGES - 1 < nk) issue((kt + DMA_STAGES - 1) % DMA_STAGES, (kt + DMA_STAGES - 1) * DMA_BK);
+    if (!under && pf) issue(pf_st, pf_k0);
 #endif
     const double* sa = smem + (kt % DMA_STAGES) * 2 * DMA_OP_DOUBLES;
     d2_t a[4], b[4];
@@ -344,27 +401,46 @@ __device__ __forceinline__ void dma128_tile(const double* __restrict__ Ag, const
 #pragma unroll
     for (int t = 0; t < 4; ++t) b[t] = *reinterpret_cast<const d2_t*>(sa + b_off + t * 16 * 4 * 2);
 #ifndef GPMI_DMA_ISSUE_EARLY
-    if (kt + DMA_STAGES - 1 < nk) issue((kt + DMA_STAGES - 1) % DMA_STAGES, (kt + DMA_STAGES - 1) * DMA_BK);
+    if (!under && pf) issue(pf_st, pf_k0);
 #endif
+    int m = 0;  // MFMAs issued so far
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+        for (int j = 0; j < 4; ++j) {
           acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i][h], b[j][h], acc[i][j], 0, 0, OP == OP_SUB ? 1 : 0);  // f64 MFMA: the BLGP field is neg[A, B, C]: C - A B^T
+          ++m;
+          if (under && m >= GPMI_RING_DMA_FIRST && (m - GPMI_RING_DMA_FIRST) % GPMI_RING_DMA_STEP == 0 &&
+              (m - GPMI_RING_DMA_FIRST) / GPMI_RING_DMA_STEP < 4) {
+            __builtin_amdgcn_sched_barrier(0);  // (the compiler would move the piece out of the MFMA block)
+            piece((m - GPMI_RING_DMA_FIRST) / GPMI_RING_DMA_STEP, pf_st, pf_k0);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
   };
   // first stage peeled off the loop: its MFMAs wait for their own accumulator tile only, the C tile streams in
   // under them instead of in front of the loop
-  stage(0);
+  stage(0, std::false_type{});
   int kt = 1;
-  for (; kt + 3 < nk; kt += 4) {  // four stages per trip: the ring slot of a stage is a compile-time offset from kt's
-    stage(kt);
-    stage(kt + 1);
-    stage(kt + 2);
-    stage(kt + 3);
+  // four stages per trip: the ring slot of a stage is a compile-time offset from kt's
+#if GPMI_RING_STATIC_TRIPS || GPMI_RING_DMA_UNDER
+  for (; kt + 3 + DMA_STAGES - 1 < nk; kt += 4) {  // every stage of the trip prefetches
+    stage(kt, std::true_type{});
+    stage(kt + 1, std::true_type{});
+    stage(kt + 2, std::true_type{});
+    stage(kt + 3, std::true_type{});
   }
-  for (; kt < nk; ++kt) stage(kt);
+#else
+  for (; kt + 3 < nk; kt += 4) {
+    stage(kt, std::false_type{});
+    stage(kt + 1, std::false_type{});
+    stage(kt + 2, std::false_type{});
+    stage(kt + 3, std::false_type{});
+  }
+#endif
+  for (; kt < nk; ++kt) stage(kt, std::false_type{});
   c_store_begin<CST>();
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -392,22 +468,27 @@ __device__ __forceinline__ void dma64_tile(const double* __restrict__ Ag, const 
   // this thread's piece per operand and stage: row tid >> 2, slot tid & 3 (see dma128_tile for the slot swizzle)
   const int row0 = tid >> 2, slot = tid & 3;
   const int q0 = (slot - 2 * ((row0 >> 2) & 3)) & 3;
-  const double* a_src = Ag + (int64_t)row0 * lda + 2 * q0;
   // LDS row 16 t + f of a wave's 32-column block holds column 2 f + t: the two MFMA tiles of a lane are adjacent columns
   const int bcol = (row0 & 32) + 2 * (row0 & 15) + ((row0 >> 4) & 1);
-  const double* b_src = Bg + (int64_t)bcol * ldb + 2 * q0;
   const unsigned lds0 = (unsigned)(uintptr_t)smem;
   const unsigned wave_off = (unsigned)__builtin_amdgcn_readfirstlane(wave * 64 * 16);
+  const int64_t src_off[2] = {(int64_t)row0 * lda + 2 * q0, (int64_t)bcol * ldb + 2 * q0};  // piece 0: A, 1: B
+#if GPMI_RING_SADDR
+  const double* Au = ring_uniform(Ag);
+  const double* Bu = ring_uniform(Bg);
+  const unsigned voff[2] = {(unsigned)(src_off[0] * 8), (unsigned)(src_off[1] * 8)};
+#endif
+  auto piece = [&](int p, int st, int k0) {
+    const unsigned dst = lds0 + (unsigned)st * (2 * OPD * 8) + wave_off + p * (OPD * 8);
+#if GPMI_RING_SADDR
+    ring_piece(voff[p], (p ? Bu : Au) + k0, dst);
+#else
+    ring_piece((p ? Bg : Ag) + src_off[p] + k0, dst);
+#endif
+  };
   auto issue = [&](int st, int k0) {
-    const unsigned base = lds0 + (unsigned)st * (2 * OPD * 8) + wave_off;
-    const double* p0 = a_src + k0;
-    const double* p1 = b_src + k0;
-    asm volatile(
-        "s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off\n\t"
-        "s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off"
-        :
-        : "v"(p0), "v"(p1), "s"(base), "s"(base + OPD * 8)
-        : "memory");
+    piece(0, st, k0);
+    piece(1, st, k0);
   };
   for (int st = 0; st < DMA_STAGES - 1 && st < nk; ++st) issue(st, st * DMA_BK);
 
@@ -432,10 +513,14 @@ __device__ __forceinline__ void dma64_tile(const double* __restrict__ Ag, const 
     else if (newer >= 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   };
-  auto stage = [&](int kt) {
+  auto stage = [&](int kt, auto full) {  // as in dma128_tile, two pieces per stage
+    constexpr bool under = GPMI_RING_DMA_UNDER && decltype(full)::value;
     const int ahead = nk - 1 - kt;
-    wait2(2 * (ahead < DMA_STAGES - 2 ? ahead : DMA_STAGES - 2));
+    if (decltype(full)::value) wait2(2 * (DMA_STAGES - 2));
+    else wait2(2 * (ahead < DMA_STAGES - 2 ? ahead : DMA_STAGES - 2));
     __syncthreads();
+    const bool pf = decltype(full)::value || kt + DMA_STAGES - 1 < nk;
+    const int pf_st = (kt + DMA_STAGES - 1) % DMA_STAGES, pf_k0 = (kt + DMA_STAGES - 1) * DMA_BK;
     const double* sa = smem + (kt % DMA_STAGES) * 2 * OPD;
     d2_t a[2], b[2];
 #pragma unroll
@@ -443,24 +528,42 @@ __device__ __forceinline__ void dma64_tile(const double* __restrict__ Ag, const 
       a[t] = *reinterpret_cast<const d2_t*>(sa + a_off + t * 16 * 4 * 2);
       b[t] = *reinterpret_cast<const d2_t*>(sa + b_off + t * 16 * 4 * 2);
     }
-    if (kt + DMA_STAGES - 1 < nk) issue((kt + DMA_STAGES - 1) % DMA_STAGES, (kt + DMA_STAGES - 1) * DMA_BK);
+    if (!under && pf) issue(pf_st, pf_k0);
+    int m = 0;
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+        for (int j = 0; j < 2; ++j) {
           acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i][h], b[j][h], acc[i][j], 0, 0, OP == OP_SUB ? 1 : 0);
+          ++m;
+          if (under && m >= GPMI_RING_DMA64_FIRST && (m - GPMI_RING_DMA64_FIRST) % GPMI_RING_DMA64_STEP == 0 &&
+              (m - GPMI_RING_DMA64_FIRST) / GPMI_RING_DMA64_STEP < 2) {
+            __builtin_amdgcn_sched_barrier(0);
+            piece((m - GPMI_RING_DMA64_FIRST) / GPMI_RING_DMA64_STEP, pf_st, pf_k0);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
   };
-  stage(0);
+  stage(0, std::false_type{});
   int kt = 1;
-  for (; kt + 3 < nk; kt += 4) {
-    stage(kt);
-    stage(kt + 1);
-    stage(kt + 2);
-    stage(kt + 3);
+#if GPMI_RING_STATIC_TRIPS || GPMI_RING_DMA_UNDER
+  for (; kt + 3 + DMA_STAGES - 1 < nk; kt += 4) {
+    stage(kt, std::true_type{});
+    stage(kt + 1, std::true_type{});
+    stage(kt + 2, std::true_type{});
+    stage(kt + 3, std::true_type{});
   }
-  for (; kt < nk; ++kt) stage(kt);
+#else
+  for (; kt + 3 < nk; kt += 4) {
+    stage(kt, std::false_type{});
+    stage(kt + 1, std::false_type{});
+    stage(kt + 2, std::false_type{});
+    stage(kt + 3, std::false_type{});
+  }
+#endif
+  for (; kt < nk; ++kt) stage(kt, std::false_type{});
   c_store_begin<CST>();
 #pragma unroll
   for (int i = 0; i < 2; ++i)
