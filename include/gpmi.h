@@ -181,6 +181,39 @@ int gpmi_lml_grad_batch(gpmi_ctx* ctx, int kernel, int64_t T, const double* thet
                         const double* extra_diag_host, const double* mus_host, const double* mu_const_host,
                         double* lml, double* grad_theta, double* trace_q, double* alpha_host, int* info);
 
+/* The log-marginal likelihood, its gradient and its exact Hessian from one factorisation (an addition: the reference has
+ * no second derivatives).  With D_i = dK / d theta_i, D_ij the second derivatives, G_i = K^-1 D_i, z_i = G_i alpha,
+ * Q = alpha alpha^T - K^-1 and the prior mean mu = Phi^T m (every mean function of the package is linear):
+ *   H_ij       = 1/2 sum_ab Q_ab (D_ij)_ab - (D_i alpha)^T z_j + 1/2 tr(G_i G_j)     (two covariance parameters)
+ *   H_{m_p m_q} = -phi_p^T K^-1 phi_q,       H_{m_p theta_j} = -phi_p^T z_j
+ * of LML = -1/2 r^T alpha - sum ln L_ii (no 2 pi term, as gpmi_lml).  Derivatives by ln a act on the a^2 part of K, its
+ * a^2 1e-12 jitter included, and not on the noise.
+ *   mu_host   : n prior means at theta's mean parameters;   phi_host : n_mean x n rows d mu / d m_p, or NULL with n_mean = 0
+ *   grad_host : n_theta + 1 values - the kernel's parameters, then ln sigma of extra_diag = sigma^2
+ *   hess_host : (n_mean + n_theta + 1)^2 values, row-major; rows and columns: the mean's parameters, the kernel's, ln sigma
+ * With extra_diag = 0 the last row and column and the last entry of grad_host are zeros.  The matrix is symmetric bit for
+ * bit (i <= j is computed, then mirrored), a repeated call returns the same bits (no atomics, every sum in an order fixed
+ * by n, d and the kernel), and so does a call that splits the parameters into groups (below).
+ * Kernels: GPMI_KERNEL_SE, _RQ, _M32, _M52.  GPMI_ERR_ARG with a message, before anything is launched: GPMI_KERNEL_SUM or a
+ * handle with gpmi_set_sum, a dense y covariance, a NULL pointer that is not optional, n_mean outside 0 .. 1 + 2 x 64.
+ * (Per-point noise variances that are hyper-parameters - gpmi_set_noise - have derivatives this entry point does not
+ * form: the caller differences gpmi_lml_grad for them.)  A matrix that does not factorise: info > 0, the outputs are
+ * untouched, GPMI_OK.  Runs on lane 1 like gpmi_lml_grad: the fitted state of gpmi_fit is not touched.
+ * Workspace: the handle's own buffers, freed with it - per parameter of a group the n x n matrices D_i and G_i.  The
+ * n_theta + 1 parameters form ONE group when 3 (n_theta + 1) padded matrices fit GPMI_HESS_GIB (environment, GiB,
+ * fractions allowed, 0 < v <= 200, default 24; read at every call), else groups of floor(cap / (3 matrices)) parameters,
+ * with a third set of matrices for the G_j of the group a group is paired with; when not even one parameter fits:
+ * GPMI_ERR_ARG.  (A padded matrix: np x (np + 32) doubles, np = n rounded up to 128 plus the reserve.)
+ * Profile classes (they share the ids of the sparse model's stages, which a GpRegressor handle does not run):
+ * GPMI_PROF_HESS_BUILD - the D_i and D_i alpha; _GEMM - the products G_i and z_i; _TRACE - the pair traces;
+ * _CONTRACT - the second-derivative contraction. */
+int gpmi_lml_hessian(gpmi_ctx* ctx, int kernel, const double* theta_host, int n_theta, double extra_diag,
+                     const double* mu_host, const double* phi_host, int n_mean, double* lml_host, double* grad_host,
+                     double* hess_host, int* info);
+/* alpha = K^-1 (y - mu) of the last gpmi_lml_hessian (or gpmi_lml_grad) on this handle, n values: the gradient by the
+ * mean's parameters is Phi alpha. */
+int gpmi_lml_hessian_alpha(gpmi_ctx* ctx, double* alpha_host);
+
 /* ---- prediction (needs a prior gpmi_fit) --------------------------------------------
  * Replaces the per-point loop of GpRegressor.__call__ (regression.py:188-216) by one batched
  * cross-covariance + triangular solve:
@@ -925,6 +958,11 @@ int gpmi_flow_task_lists(int m, int nwg, int64_t cap, int32_t* out, int64_t* nta
 /* gpmi_sgp_spatial_derivatives (tools/sparse_post_bench.py) books the cross build and its four products per panel under
  * GPMI_PROF_SGP_GRAM and the fused derivative kernel with its run sum under GPMI_PROF_SGP_GRAD; gpmi_sgp_posterior_draws
  * books Sigma under GPMI_PROF_DRAWS_SIGMA, and its tail books the classes of gpmi_posterior_draws. */
+/* gpmi_lml_hessian books its four stages under the ids of the sparse model's (one handle runs one or the other) */
+#define GPMI_PROF_HESS_BUILD GPMI_PROF_SGP_BUILD
+#define GPMI_PROF_HESS_GEMM GPMI_PROF_SGP_GRAM
+#define GPMI_PROF_HESS_TRACE GPMI_PROF_SGP_FACTOR
+#define GPMI_PROF_HESS_CONTRACT GPMI_PROF_SGP_GRAD
 #define GPMI_PROF_NCLASS 17
 /* on = 0: off; 1: every class; otherwise a class bitmask shifted left by one (2 << klass) */
 int gpmi_profile_enable(gpmi_ctx* ctx, int on);

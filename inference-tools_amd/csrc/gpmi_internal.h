@@ -302,7 +302,18 @@ struct MultiBufs {
   PinBuf<double> h_mtVec;   // pinned mirror of mtVec
 };
 
-struct gpmi_ctx : DataBufs, QueryBufs, BatchBufs, MixBufs, MultiBufs {
+// gpmi_lml_hessian (api_hessian.hip): the derivative matrices D_i of a group of parameters, the products G_i = K^-1 D_i of
+// that group (hGa) and - only when the parameters do not fit one group - of a second group (hGb), the vectors
+// (D_i alpha, G_i alpha, the mean's features and K^-1 times them) and the partial sums of the contractions; each is
+// allocated by the first call that needs it and grows as later calls ask
+struct HessBufs {
+  DevBuf<double> hD, hGa, hGb;  // g x np x ld each
+  DevBuf<double> hVec;          // (2 (n_theta + 1) + 2 n_mean) x np
+  DevBuf<double> hPart;         // partial sums of the pair traces and of the second-derivative contraction, then the sums
+  PinBuf<double> h_hOut;        // pinned mirror of the sums
+};
+
+struct gpmi_ctx : DataBufs, QueryBufs, BatchBufs, MixBufs, MultiBufs, HessBufs {
   int device = 0;
   int ncu = 256;      // compute units of the device
   int pair_cus[GPMI_NPAIRS] = {32};  // CUs of the panel stream of look-ahead pair k (the update stream has the rest)
@@ -465,6 +476,26 @@ void launch_scale_columns(hipStream_t s, const double* A, const double* sc, doub
                           int64_t np, int batch = 1, int64_t sMat = 0, int64_t sVec = 0);
 void launch_loo_vectors(hipStream_t s, const double* alpha, const double* ikdiag, double* c1,
                         double* sc2, int64_t n, int64_t np, int batch = 1, int64_t sAlpha = 0, int64_t sLoo = 0);
+
+// hessian.hip: the kernels of gpmi_lml_hessian.  Parameters are numbered as theta is laid out (ln a; RQ: ln kappa; ln l_1 ..
+// ln l_d) with ln sigma of the WhiteNoise variance at n_theta.
+// D[m] (np x ld, sMat apart, both triangles, zeros in the padding) = dK / d parameter (p0 + m), m < cnt
+void launch_hess_dbuild(hipStream_t s, const KParams& p, int n_theta, int p0, int cnt, const double* x, int64_t n, int64_t np,
+                        double* D, int64_t ld, int64_t sMat);
+// part[((iA0 + i) PT + jB0 + j) (np / 64) + ta] = sum over the 64-row block ta of a and all b of GA[i][a][b] GB[j][b][a], for the
+// pairs with iA0 + i <= jB0 + j; launch_hess_trace_sum: out[i PT + j] = their sum over ta in ascending order (i <= j)
+void launch_hess_pair_trace(hipStream_t s, const double* GA, int iA0, int nA, const double* GB, int jB0, int nB, int64_t np,
+                            int64_t ld, int64_t sMat, int PT, double* part);
+void launch_hess_trace_sum(hipStream_t s, const double* part, int PT, int64_t np, double* out);
+// out[i nv + j] = sum_a U[i][a] V[j][a] over np values (rows np apart), a fixed order; upper: only i <= j
+void launch_hess_dots(hipStream_t s, const double* U, int nu, const double* V, int nv, int64_t np, bool upper, double* out);
+// 1/2 sum_ab Q_ab of the second-derivative profiles over the lower 64 x 64 tiles of iK (off-diagonal elements twice),
+// Q = alpha alpha^T - K^-1: hess_contract_entries(kernel, d) sums into out - S_km = a^2 g2 q_k q_m for k <= m row by row,
+// then (RQ) the d mixed profiles with ln kappa and the second derivative by ln kappa.  ws: hess_contract_ws_doubles.
+int hess_contract_entries(int kernel, int d);
+int64_t hess_contract_ws_doubles(int64_t np, int kernel, int d);
+int launch_hess_contract(gpmi_ctx* c, hipStream_t s, const KParams& p, const double* x, int64_t n, int64_t np, const double* iK,
+                         int64_t ld, const double* alpha, double* ws, double* out);
 
 // batch of independent equal-shape problems in one launch (blockIdx.z): strides in doubles
 struct GemmBatch {

@@ -355,6 +355,28 @@ class GpEngine(_DeviceCommMixin, _DrawsMixin):
                     C.byref(lml), dptr(grad), C.byref(trq), dptr(alpha), C.byref(info))
         return lml.value, grad, trq.value, alpha, info.value
 
+    def lml_hessian(self, kernel, theta_cov, extra_diag, mu, phi=None):
+        """gpmi_lml_hessian: the LML, its gradient and its exact Hessian from one factorisation.  phi: (n_mean, n) rows
+        d mu / d (mean parameter), or None.  Returns (lml, grad (n_theta + 1,): the kernel's parameters then ln sigma
+        of `extra_diag`, hess (n_mean + n_theta + 1,) squared: mean, kernel, ln sigma, alpha (n,), info); with
+        info != 0 the arrays are None."""
+        theta = as_f64(theta_cov)
+        mu = as_f64(mu)
+        phi = None if phi is None or len(phi) == 0 else as_f64(np.atleast_2d(phi))
+        n_mean = 0 if phi is None else phi.shape[0]
+        if phi is not None and phi.shape[1] != self.n:
+            raise ValueError(f"phi must be (n_mean, {self.n}), got {phi.shape}")
+        nh = n_mean + theta.size + 1
+        lml, info = C.c_double(0.0), C.c_int(0)
+        grad, hess = np.zeros(theta.size + 1), np.zeros((nh, nh))
+        self.h.call("gpmi_lml_hessian", kernel, dptr(theta), theta.size, float(extra_diag), dptr(mu), dptr(phi), n_mean,
+                    C.byref(lml), dptr(grad), dptr(hess), C.byref(info))
+        if info.value != 0:
+            return None, None, None, None, info.value
+        alpha = np.empty(self.n)
+        self.h.call("gpmi_lml_hessian_alpha", dptr(alpha))
+        return lml.value, grad, hess, alpha, 0
+
     def lml_grad_batch(self, kernel, thetas_cov, extra_diag, mus=None, mu_const=None):
         """T evaluations of `lml_grad` in one call (gpmi_lml_grad_batch: lockstep for padded N <= 4096):
         (lml (T,), grad (T, n_theta), trace_q (T,), alpha (T, n), info (T,))."""

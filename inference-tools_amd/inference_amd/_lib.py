@@ -35,6 +35,7 @@ PROF_DRAWS_SIGMA, PROF_DRAWS_FACTOR, PROF_DRAWS_NORMALS, PROF_DRAWS_PRODUCT = 9,
 DRAWS_MAX_M = 16384  # GPMI_DRAWS_MAX_M: the most points gpmi_posterior_draws / gpmi_mvn_draws take
 DRAWS_PANEL = 4096  # GPMI_DRAWS_PANEL: draws per panel of those two
 PROF_SGP_BUILD, PROF_SGP_GRAM, PROF_SGP_FACTOR, PROF_SGP_GRAD = 13, 14, 15, 16  # GPMI_PROF_SGP_*
+PROF_HESS_BUILD, PROF_HESS_GEMM, PROF_HESS_TRACE, PROF_HESS_CONTRACT = 13, 14, 15, 16  # GPMI_PROF_HESS_*: the same ids
 SGP_MAX_M = 4096  # GPMI_SGP_MAX_M: the most inducing points a gpmi_sgp object takes
 MT_MAX_T = 4096  # GPMI_MT_MAX_T: the most targets gpmi_mt_set_targets takes
 
@@ -71,6 +72,8 @@ SIGNATURES = {
     "gpmi_set_streams": (C.c_int, [_vp, C.c_int]),
     "gpmi_set_option": (C.c_int, [_vp, C.c_int, C.c_int]),
     "gpmi_lml_grad": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "gpmi_lml_hessian": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double, _dp, _dp, C.c_int, _dp, _dp, _dp, _ip]),
+    "gpmi_lml_hessian_alpha": (C.c_int, [_vp, _dp]),
     "gpmi_flow_task_lists": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "gpmi_lml_grad_batch": (C.c_int, [_vp, C.c_int, C.c_int64, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
     "gpmi_lml_grad_batch_noise": (C.c_int, [_vp, C.c_int, C.c_int64, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
@@ -273,7 +276,7 @@ class Handle:
         _live_handles.add(self)
 
     # entry points that factorise a matrix from their own inputs: safe to repeat after a failed attempt
-    _REPEATABLE = frozenset(("gpmi_fit", "gpmi_fit_mix", "gpmi_fit_dense", "gpmi_lml", "gpmi_lml_batch", "gpmi_lml_grad",
+    _REPEATABLE = frozenset(("gpmi_fit", "gpmi_fit_mix", "gpmi_fit_dense", "gpmi_lml", "gpmi_lml_batch", "gpmi_lml_grad", "gpmi_lml_hessian",
                              "gpmi_lml_grad_batch", "gpmi_lml_mix", "gpmi_lml_grad_mix", "gpmi_lml_dense", "gpmi_loo_dense",
                              "gpmi_linv_lml", "gpmi_linv_lml_grad", "gpmi_linv_posterior", "gpmi_linv_lml_dense",
                              "gpmi_linv_lml_grad_dense", "gpmi_linv_posterior_dense", "gpmi_loo_terms", "gpmi_loo_grad",

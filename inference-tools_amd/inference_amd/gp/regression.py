@@ -28,7 +28,42 @@ from inference_amd._engine import GpEngine
 from inference_amd.gp import _messages as msg
 from inference_amd.gp._draws import draw_arguments, raise_if_not_positive_definite
 from inference_amd.gp.covariance import heteroscedastic_slice, CovarianceFunction, SquaredExponential, device_plan, sum_kernels
-from inference_amd.gp.mean import ConstantMean, MeanFunction
+from inference_amd.gp.mean import ConstantMean, MeanFunction, _FeatureMean
+
+
+class LaplaceApproximation:
+    """Gaussian approximation N(mean, covariance) of the hyper-parameter posterior around a maximum of the LML
+    (`GpRegressor.laplace_approximation`): covariance = (-hessian)^-1.
+
+    Attributes: `mean` (P,), `lml`, `gradient` (P,), `hessian` (P, P), `covariance` (P, P), `std` (P,), `labels`,
+    `log_evidence` = lml - N/2 ln 2 pi + P/2 ln 2 pi - 1/2 ln det(-hessian) (flat prior of unit density in theta)."""
+
+    def __init__(self, theta, lml, gradient, hessian, n_points, labels):
+        self.mean = np.array(theta, dtype=float)
+        self.lml = float(lml)
+        self.gradient = np.array(gradient, dtype=float)
+        self.hessian = np.array(hessian, dtype=float)
+        self.labels = list(labels)
+        P = self.mean.size
+        neg = -0.5 * (self.hessian + self.hessian.T)
+        evals, evecs = np.linalg.eigh(neg)
+        if not evals[0] > 0.0 or not np.isfinite(evals).all():
+            worst = int(np.argmax(np.abs(evecs[:, 0])))
+            raise LinAlgError(
+                f"the negative Hessian of the LML is not positive definite: smallest eigenvalue {evals[0]:.6g}, mostly along "
+                f"parameter {worst} ({self.labels[worst]}) - theta is not an interior maximum (a maximum on a bound?)")
+        self.covariance = (evecs / evals) @ evecs.T
+        self.covariance = 0.5 * (self.covariance + self.covariance.T)
+        self.std = sqrt(np.diag(self.covariance))
+        self._factor = evecs / sqrt(evals)  # covariance = _factor _factor^T
+        self.log_evidence = (self.lml - 0.5 * n_points * np.log(2 * np.pi) + 0.5 * P * np.log(2 * np.pi)
+                             - 0.5 * float(np.log(evals).sum()))
+
+    def sample(self, n: int, seed=None):
+        """`n` draws of theta, shape (n, P) - rows for `predict_marginalised` / `predict_samples`.  Host NumPy draws
+        (`numpy.random.default_rng(seed)`): the same seed gives the same rows."""
+        z = np.random.default_rng(seed).standard_normal((int(n), self.mean.size))
+        return self.mean + z @ self._factor.T
 
 
 class GpRegressor:
@@ -843,6 +878,85 @@ class GpRegressor:
             g_cov[self._het_slice] = np.exp(2 * theta[self.cov_slice][self._het_slice]) * self.engine.lml_grad_qdiag()
         grad[self.cov_slice] = g_cov
         return lml, grad
+
+    # ---------------------------------------------------------------------------------
+    # (extension) second derivatives of the LML and the Laplace approximation
+    # ---------------------------------------------------------------------------------
+    FD_HESSIAN_STEP = 1e-4  # `method="fd"`: theta_i -/+ FD_HESSIAN_STEP * max(1, |theta_i|)
+
+    def _exact_hessian_ok(self):
+        """The models gpmi_lml_hessian takes: one SquaredExponential / RationalQuadratic / Matern32 / Matern52
+        (+ WhiteNoise), a mean function of this package (they are linear in their parameters), diagonal data errors."""
+        return (not self._generic and self._mix is None and self._het_slice is None and self._y_cov is None
+                and self._kernel_id in (_lib.KERNEL_SE, _lib.KERNEL_RQ, _lib.KERNEL_M32, _lib.KERNEL_M52)
+                and isinstance(self.mean, _FeatureMean))
+
+    def marginal_likelihood_hessian(self, theta: ndarray, method: str = "auto"):
+        """(extension) `(lml, grad, hess)`: the LML (the package's convention: no 2 pi term), its gradient and its
+        (P, P) matrix of second derivatives at `theta`, all in the layout of `hyperpars`.
+
+        method="exact": one factorisation on the device (gpmi_lml_hessian),
+            H_ij = 1/2 sum Q o D_ij - (D_i alpha)^T K^-1 D_j alpha + 1/2 tr(K^-1 D_i K^-1 D_j),  Q = alpha alpha^T - K^-1,
+        with the blocks of the mean's parameters (-Phi K^-1 Phi^T and -Phi K^-1 D_j alpha).  For one SquaredExponential,
+        RationalQuadratic, Matern32 or Matern52, optionally + WhiteNoise, with diagonal data errors; any other model
+        raises NotImplementedError (use "fd").
+        method="fd": central differences of `marginal_likelihood_gradient`, column i from theta_i -/+ h_i with
+            h_i = FD_HESSIAN_STEP * max(1, |theta_i|) (1e-4: about seven digits), symmetrised; 2 P gradient evaluations.
+        method="auto": "exact" where the model allows it, else "fd" (sums, ChangePoint, HeteroscedasticNoise, dense
+            y_cov, plugin kernels, user-defined mean functions).
+        A matrix that is not positive definite raises LinAlgError, as the gradient does."""
+        if method not in ("auto", "exact", "fd"):
+            raise ValueError("'method' must be \"auto\", \"exact\" or \"fd\"")
+        theta = np.asarray(theta, dtype=float)
+        if theta.shape != (self.n_hyperpars,):
+            raise ValueError(msg.wrong_hyperpar_count(self.n_hyperpars, theta.shape[-1] if theta.ndim else 1))
+        if method == "exact" and not self._exact_hessian_ok():
+            raise NotImplementedError("the exact Hessian takes one SquaredExponential / RationalQuadratic / Matern32 / Matern52 "
+                                      "(+ WhiteNoise) with diagonal data errors and a mean function of this package: "
+                                      "use method=\"fd\" for this model")
+        if method == "fd" or not self._exact_hessian_ok():
+            return self._fd_hessian(theta)
+        theta_cov = theta[self.cov_slice]
+        theta_stat, extra = self._split_cov_theta(theta_cov)
+        mu, grad_mu = self.mean.mean_and_gradients(theta[self.mean_slice])
+        phi = np.array(grad_mu, dtype=float).reshape(self.mean.n_params, self.n_points)
+        lml, g_dev, h_dev, alpha, info = self.engine.lml_hessian(self._kernel_id, theta_stat, extra, mu, phi)
+        if info != 0:
+            raise LinAlgError("Matrix is not positive definite")
+        # device order (mean, the kernel's parameters, ln sigma) -> the layout of hyperpars
+        n_mean, n_stat = self.mean.n_params, theta_stat.size
+        idx = np.arange(self.n_hyperpars)
+        idx[n_mean + np.arange(self.cov.n_params)[self._stat_slice]] = n_mean + np.arange(n_stat)
+        if self._wn_index is not None:
+            idx[n_mean + self._wn_index] = n_mean + n_stat
+        grad = np.concatenate([phi @ alpha, g_dev])[idx]
+        return lml, grad, np.ascontiguousarray(h_dev[np.ix_(idx, idx)])
+
+    def _fd_hessian(self, theta):
+        lml, grad = self.marginal_likelihood_gradient(theta)
+        P = self.n_hyperpars
+        H = zeros((P, P))
+        for i in range(P):
+            h = self.FD_HESSIAN_STEP * max(1.0, abs(theta[i]))
+            tp, tm = theta.copy(), theta.copy()
+            tp[i] += h
+            tm[i] -= h
+            H[:, i] = (self.marginal_likelihood_gradient(tp)[1] - self.marginal_likelihood_gradient(tm)[1]) / (tp[i] - tm[i])
+        return lml, grad, 0.5 * (H + H.T)
+
+    def laplace_approximation(self, theta: ndarray = None, method: str = "auto"):
+        """(extension) The Gaussian (Laplace) approximation of the hyper-parameter posterior around `theta` (default:
+        the fitted `hyperpars`, which should be a maximum of the LML inside the bounds): a `LaplaceApproximation` with
+        `mean`, `hessian`, `covariance` = (-H)^-1, `std`, `log_evidence` and `sample(n, seed=None)`.
+
+        `log_evidence` = LML - N/2 ln 2 pi + P/2 ln 2 pi - 1/2 ln det(-H): the integral of the likelihood over theta under
+        a FLAT prior of unit density in theta (the log-parameters and the mean's parameters) - no prior of the user's
+        enters; compare models on the same data and parameter scales only.  (The first 2 pi term restores the
+        normalisation the package's LML leaves out.)  If -H is not positive definite - most often a maximum on a bound -
+        LinAlgError names the smallest eigenvalue and the parameter it belongs to."""
+        theta = np.asarray(self.hyperpars if theta is None else theta, dtype=float)
+        lml, grad, H = self.marginal_likelihood_hessian(theta, method=method)
+        return LaplaceApproximation(theta, lml, grad, H, self.n_points, self.hyperpar_labels)
 
     def marginal_likelihood_gradient_batch(self, thetas: ndarray, failed: str = "raise"):
         """(extension) `marginal_likelihood_gradient` for T hyper-parameter vectors in one device call
