@@ -57,7 +57,7 @@ int gpmi_capacity(gpmi_ctx* c, int64_t* capacity) {
 int gpmi_append_point(gpmi_ctx* c, const double* x_new, double y_new, double noise_var_new, const double* mu,
                       double* alpha_out, double* logdet_out, int* info) {
   if (!c) return GPMI_ERR_ARG;
-  ARGCHK(c, c->fitted && c->fit_params.kernel >= 0 && c->mix_nk == 0, "gpmi_append_point needs a fit by gpmi_fit (SE / RQ / a sum of them)");
+  ARGCHK(c, c->fitted && c->fit_params.kernel >= 0 && c->mix_nk == 0, "gpmi_append_point needs a fit by gpmi_fit (SE / RQ / Matern32 / Matern52 or a sum of them)");
   ARGCHK(c, !c->ycov, "gpmi_append_point: diagonal data errors only");
   ARGCHK(c, c->mt_T == 0, "gpmi_append_point: not on a handle that holds a target matrix (gpmi_mt_set_targets)");
   ARGCHK(c, x_new && mu, "x_new / mu is NULL");

@@ -491,11 +491,13 @@ class GpRegressor:
     def add_point(self, x_new, y_new, y_err_new=None):
         """(extension) Append one training point and re-fit at the CURRENT hyper-parameters.
 
-        With a SquaredExponential / RationalQuadratic kernel (optionally + WhiteNoise), diagonal data errors and
-        free device capacity (`reserve`) this is an O(N^2) update of the fitted state: one new row of the Cholesky
-        factor (a triangular sweep) and a fresh alpha (two sweeps) - `gpmi_append_point`.  In every other case
+        With a SquaredExponential / RationalQuadratic / Matern32 / Matern52 kernel or a sum of them (optionally
+        + WhiteNoise), diagonal data errors and free device capacity (`reserve`) this is an O(N^2) update of the
+        fitted state: one new row of the Cholesky factor (a triangular sweep) and a fresh alpha (two sweeps) -
+        `gpmi_append_point`.  In every other case that is not refused (ChangePoint, plugin kernels, no capacity left)
         the model is rebuilt and re-fitted at the same hyper-parameters (O(N^3), what the reference always does:
-        optimisation.py:177-186 builds a new GpRegressor per added evaluation)."""
+        optimisation.py:177-186 builds a new GpRegressor per added evaluation), with a `reserve` of at least 128.
+        A dense ``y_cov`` and ``HeteroscedasticNoise`` raise NotImplementedError."""
         x_new = np.asarray(x_new, dtype=float).reshape(1, self.n_dimensions)
         y_new = float(np.asarray(y_new).squeeze())
         if self._y_cov is not None:

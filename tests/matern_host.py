@@ -206,51 +206,79 @@ class HostModel:
         return K, out
 
 
-class OracleGp:
-    """GP regression with a constant mean, theta = [mean, covariance parameters], on the host."""
+class LinearMeanHost:
+    """A prior mean for `OracleGp`: mu(q) = m_0 + sum_k m_{1+k} (q_k - <x_k>), centred on the training points x.  Called
+    with (points, m) it returns (mu at the points, the rows d mu / d m_p there (1 + d, M))."""
 
-    def __init__(self, x, y, y_err, model, theta):
+    def __init__(self, x):
+        self.centre = np.asarray(x, float).mean(axis=0)
+        self.n_params = 1 + len(self.centre)
+
+    def __call__(self, points, m):
+        rows = np.vstack([np.ones(len(points)), (np.asarray(points, float) - self.centre[None, :]).T])
+        return np.asarray(m, float) @ rows, rows
+
+
+class OracleGp:
+    """GP regression on the host, theta = [the mean's parameters, covariance parameters].  The prior mean is a constant
+    (one parameter) unless `mean` is given: a callable (points, m) -> (mu at the points, rows d mu / d m_p (n_mean, M)) with
+    an attribute `n_params` (`LinearMeanHost`).  `y_err`: standard deviations (N,), or a dense data covariance (N, N)."""
+
+    def __init__(self, x, y, y_err, model, theta, mean=None):
         self.x, self.y = np.asarray(x, float), np.asarray(y, float)
-        self.sig = np.diag(np.asarray(y_err, float) ** 2)
+        y_err = np.asarray(y_err, float)
+        self.sig = y_err if y_err.ndim == 2 else np.diag(y_err ** 2)
         self.m = model
         self.n = len(self.y)
+        self.mean = mean
+        self.nm = 1 if mean is None else mean.n_params
         self.theta = np.asarray(theta, float)
-        self.K = self.m.build_and_grads(self.theta[1:], grads=False)[0] + self.sig
+        self.K = self.m.build_and_grads(self.theta[self.nm:], grads=False)[0] + self.sig
         self.L = cholesky(self.K, lower=True)
-        self.alpha = self._solve(self.L, self.y - self.theta[0])
+        self.alpha = self._solve(self.L, self.y - self._mu(self.x, self.theta))
 
     @staticmethod
     def _solve(L, b):
         return solve_triangular(L.T, solve_triangular(L, b, lower=True), lower=False)
 
+    def _mu(self, pts, theta):
+        """The prior mean at `pts`: the scalar theta[0] for the constant mean, a vector otherwise."""
+        return theta[0] if self.mean is None else self.mean(pts, theta[:self.nm])[0]
+
+    def _mean_rows(self):
+        """d mu / d m_p at the training points, (n_mean, N)."""
+        return np.ones((1, self.n)) if self.mean is None else self.mean(self.x, self.theta[:self.nm])[1]
+
     def __call__(self, q):
-        Kq = self.m.cross(q, self.x, self.theta[1:])
+        Kq = self.m.cross(q, self.x, self.theta[self.nm:])
         v = solve_triangular(self.L, Kq.T, lower=True)
-        return Kq @ self.alpha + self.theta[0], np.sqrt(np.abs(self.m.prior_var(q, self.theta[1:]) - (v**2).sum(axis=0)))
+        var = self.m.prior_var(q, self.theta[self.nm:]) - (v**2).sum(axis=0)
+        return Kq @ self.alpha + self._mu(q, self.theta), np.sqrt(np.abs(var))
 
     def build_posterior(self, q):
-        Kq = self.m.cross(q, self.x, self.theta[1:])
+        Kq = self.m.cross(q, self.x, self.theta[self.nm:])
         Q = solve_triangular(self.L, Kq.T, lower=True)
-        return Kq @ self.alpha + self.theta[0], self.m.cross(q, q, self.theta[1:]) - Q.T @ Q
+        return Kq @ self.alpha + self._mu(q, self.theta), self.m.cross(q, q, self.theta[self.nm:]) - Q.T @ Q
 
     def _factor(self, theta, grads):
-        K, dK = self.m.build_and_grads(theta[1:], grads=grads)
+        K, dK = self.m.build_and_grads(theta[self.nm:], grads=grads)
         L = cholesky(K + self.sig, lower=True)
         iL = solve_triangular(L, np.eye(self.n), lower=True)
         iK = iL.T @ iL
-        return L, iK, iK @ (self.y - theta[0]), dK
+        return L, iK, iK @ (self.y - self._mu(self.x, theta)), dK
 
     def marginal_likelihood(self, theta):
         theta = np.asarray(theta, float)
         L, _, alpha, _ = self._factor(theta, False)
-        return -0.5 * (self.y - theta[0]) @ alpha - np.log(np.diag(L)).sum()
+        return -0.5 * (self.y - self._mu(self.x, theta)) @ alpha - np.log(np.diag(L)).sum()
 
     def marginal_likelihood_gradient(self, theta):
         theta = np.asarray(theta, float)
         L, iK, alpha, dK = self._factor(theta, True)
         Q = np.outer(alpha, alpha) - iK
-        grad = np.concatenate([[alpha.sum()], [0.5 * (Q * G).sum() for G in dK]])
-        return -0.5 * (self.y - theta[0]) @ alpha - np.log(np.diag(L)).sum(), grad
+        g_mean = [alpha.sum()] if self.mean is None else list(self._mean_rows() @ alpha)
+        grad = np.concatenate([g_mean, [0.5 * (Q * G).sum() for G in dK]])
+        return -0.5 * (self.y - self._mu(self.x, theta)) @ alpha - np.log(np.diag(L)).sum(), grad
 
     def loo_likelihood(self, theta):
         theta = np.asarray(theta, float)
@@ -263,7 +291,7 @@ class OracleGp:
         _, iK, alpha, dK = self._factor(theta, True)
         var = 1.0 / np.diag(iK)
         c1, c2 = alpha * var, 0.5 * var * (1.0 + var * alpha**2)
-        grad = [(c1 * (iK @ np.ones(self.n))).sum()]
+        grad = [(c1 * (iK @ row)).sum() for row in self._mean_rows()]
         for G in dK:
             Z = iK @ G
             grad.append((c1 * (Z @ alpha) - c2 * np.diag(Z @ iK)).sum())
@@ -273,8 +301,8 @@ class OracleGp:
     def gradient(self, q, kind):
         mus, covs = [], []
         for r in q:
-            k = cross(kind, r[None, :], self.x, self.theta[1:])[0]
-            A, R = gradient_terms(kind, r, self.x, self.theta[1:])
+            k = cross(kind, r[None, :], self.x, self.theta[self.nm:])[0]
+            A, R = gradient_terms(kind, r, self.x, self.theta[self.nm:])
             Q = solve_triangular(self.L, (A * k[None, :]).T, lower=True)
             mus.append(A @ (k * self.alpha))
             covs.append(R - Q.T @ Q)
@@ -283,8 +311,8 @@ class OracleGp:
     def spatial_derivatives(self, q, kind):
         dmu, dvar = [], []
         for r in q:
-            k = cross(kind, r[None, :], self.x, self.theta[1:])[0]
-            A, _ = gradient_terms(kind, r, self.x, self.theta[1:])
+            k = cross(kind, r[None, :], self.x, self.theta[self.nm:])[0]
+            A, _ = gradient_terms(kind, r, self.x, self.theta[self.nm:])
             dmu.append(A @ (k * self.alpha))
             dvar.append(-2.0 * (A * k[None, :]) @ self._solve(self.L, k))
         return np.array(dmu), np.array(dvar)

@@ -86,19 +86,8 @@ def mirror(kind, x, y, e, theta, phi, wn, **kw):
     return hh.hessian(kind, x, y, e**2, theta[:n_mean], phi, tk, ln_sigma=theta[-1] if wn else None, **kw)
 
 
-@pytest.mark.parametrize("name", sorted(CASES))
-def test_mirror_against_differences_of_an_independent_gradient(name):
-    """Allowance: ten times what the same difference scheme at the same step leaves between the oracle's LML and its own
-    gradient.  Both sides in the same norm, the one of tests/test_multitarget_cpu.py: the largest deviation over the
-    largest magnitude - for the gradient max |g_j|, for the Hessian the largest sum |T1| + |T2| + |T3| of an entry.
-    Measured at h = 1e-3 (N = 48, d = 2): the scheme on the oracles 2e-12 .. 3e-11, the mirror 1e-12 .. 8e-12, 0.3 to 1.5
-    times the oracle's figure (every case prints its own).  (Entry by entry, relative to that entry's own sum of terms, the differenced gradient
-    disagrees with ITS OWN transpose by 1e-10 .. 3e-9 - the rounding of the oracle's explicit K^-1 divided by h - and
-    with the mirror by as much; that figure is printed and not asserted.)"""
-    kind, wn, linear = CASES[name]
-    x, y, e = dataset()
-    phi = features(x, linear)
-    theta = theta_for(kind, D, wn, linear)
+def assert_mirror_matches_differences(name, kind, x, y, e, theta, phi, wn):
+    """The comparison of `test_mirror_against_differences_of_an_independent_gradient` on given inputs."""
     ind = Independent(kind, x, y, e, wn, phi)
     g0 = ind.grad(theta)
     ref_err = float(np.abs(np.array([fd4(ind.lml, theta, j, H_STEP) for j in range(theta.size)]) - g0).max() / np.abs(g0).max())
@@ -114,6 +103,34 @@ def test_mirror_against_differences_of_an_independent_gradient(name):
     assert err <= 10 * ref_err
     ml = mirror(kind, x, y, e, theta, phi, wn, dtype=np.longdouble)
     assert (np.abs(np.asarray(ml["H"], dtype=float) - m["H"]) / m["scale"]).max() < 1e-9
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_mirror_against_differences_of_an_independent_gradient(name):
+    """Allowance: ten times what the same difference scheme at the same step leaves between the oracle's LML and its own
+    gradient.  Both sides in the same norm, the one of tests/test_multitarget_cpu.py: the largest deviation over the
+    largest magnitude - for the gradient max |g_j|, for the Hessian the largest sum |T1| + |T2| + |T3| of an entry.
+    Measured at h = 1e-3 (N = 48, d = 2): the scheme on the oracles 2e-12 .. 3e-11, the mirror 1e-12 .. 8e-12, 0.3 to 1.5
+    times the oracle's figure (every case prints its own).  (Entry by entry, relative to that entry's own sum of terms, the differenced gradient
+    disagrees with ITS OWN transpose by 1e-10 .. 3e-9 - the rounding of the oracle's explicit K^-1 divided by h - and
+    with the mirror by as much; that figure is printed and not asserted.)"""
+    kind, wn, linear = CASES[name]
+    x, y, e = dataset()
+    phi = features(x, linear)
+    theta = theta_for(kind, D, wn, linear)
+    assert_mirror_matches_differences(name, kind, x, y, e, theta, phi, wn)
+
+
+@pytest.mark.parametrize("name", ["rq_wn_134x22", "rq_wn_70x64"])
+def test_mirror_at_the_wide_pair_table_shapes(name):
+    """The two RationalQuadratic + WhiteNoise shapes of tests/test_hessian_gpu.py with 22 and 64 length scales (253 sums in
+    the length-scale block; 67 parameters in the pair table), on that file's own inputs: the same comparison, the same
+    allowance."""
+    import test_hessian_gpu as device_cases
+
+    kind, x, y, e, theta, wn, linear = device_cases.case_inputs(name)
+    assert kind == "rq" and wn and not linear and theta.size == x.shape[1] + 4
+    assert_mirror_matches_differences(name, kind, x, y, e, theta, features(x, linear), wn)
 
 
 @pytest.mark.parametrize("kind", ["se", "rq", "m32", "m52"])

@@ -29,7 +29,11 @@ CASES = {
     "rq_257x17": ("rq", 257, 17, False, False, False),         # the 64 KiB-LDS builder path, the kappa row and column
     "m32_dup_200x2": ("m32", 200, 2, False, False, True),      # the t = 0 guard of g2
     "m52_linear_640x1": ("m52", 640, 1, False, True, False),   # a second 512 inverse block, n_mean = 2
-    "se_70x64": ("se", 70, 64, False, False, False),           # P = 65: the widest pair table, d = 64
+    "se_70x64": ("se", 70, 64, False, False, False),           # d = 64 without shape or noise parameter: a pair table of 65
+    # the length-scale block has 22 * 23 / 2 = 253 sums: the 256-sum LDS slab flushes inside RQ's kappa tail
+    "rq_wn_134x22": ("rq", 134, 22, True, False, False),
+    # PT = 67, the widest pair table: RQ's contraction with the > 64 KiB LDS opt-in, the kappa rows next to the ln sigma column
+    "rq_wn_70x64": ("rq", 70, 64, True, False, False),
 }
 
 
