@@ -918,6 +918,56 @@ int gpmi_mt_predict(gpmi_ctx* ctx, const double* pts_host /* m x d */, int64_t m
  * Uses lane 1's second matrix for L^-T, as gpmi_loo_diag. */
 int gpmi_mt_loo(gpmi_ctx* ctx, double* resid_loo_host /* n x T */, double* ikdiag_host /* n */);
 
+/* ---- non-Gaussian likelihoods by Laplace's method (GeneralisedGpRegressor) ----------
+ * A latent GP f = m + K a (K: the kernel's covariance of the handle's x with its a^2 1e-12 jitter, no data errors, no
+ * extra_diag; m a constant offset) observed through a log-concave likelihood p(y_i | f_i) with per-point data aux_i:
+ *   GPMI_GGP_LOGISTIC  robust regression: log p = z - 2 softplus(z) - ln s, z = (y - f) / s, aux = s > 0, y real
+ *   GPMI_GGP_POISSON   counts, log link:  log p = y (f + ln e) - e exp(f) - lgamma(y + 1), aux = e > 0, y = 0, 1, 2, ..
+ *   GPMI_GGP_BINOMIAL  k of n, logit link: log p = y f - n softplus(f) + ln C(n, y), aux = n >= 1, y = 0 .. n
+ * The mode of psi(a) = -1/2 a^T (f - m) + sum_i log p(y_i | f_i) is found by Newton's iteration from a = 0 (GPML Alg. 3.1):
+ * with g = d log p / df, W = -d^2 log p / df^2 >= 0, sw = sqrt W a step factorises B = I + sw sw^T o K = L L^T (eigenvalues
+ * >= 1), sets b = W (f - m) + g, a+ = b - sw o B^-1 (sw o K b), f+ = m + K a+, halves the step along a+ - a (at most ten
+ * times) while psi(a+) < psi(a) - 1e-12 |psi(a)|, and stops when max |f+ - f| <= tol (1 + max |f+|).  B is then factorised
+ * once more at the final f, and  log q(y | theta) = psi - sum_i ln L_ii  (GPML eq. 3.32).  Every evaluation starts from
+ * a = 0: a value depends on theta alone.  The host reads one small record per step; everything else stays on the device.
+ * gpmi_ggp_fit runs on lane 0 and keeps the factor for gpmi_ggp_mode / gpmi_ggp_predict; gpmi_ggp_logq and
+ * gpmi_ggp_logq_grad evaluate other hyper-parameters on lane 1: the fit and every later answer of it keep their bits.
+ * No call uses atomics and every sum has an order fixed by the padded n: repeated calls return the same bits.
+ * info: 0 success; k > 0: B was not positive definite (or not finite) at leading minor k; -1: no convergence within
+ * max_iter steps, or psi not finite.  With info != 0 logq is -1e50, the other outputs are undefined, the status is GPMI_OK
+ * and (gpmi_ggp_fit) the handle holds no fit.  out_iters: {Newton steps, step halvings}.
+ * GPMI_ERR_ARG, before anything is launched and with the handle still usable: a likelihood id other than the three; NULL
+ * y / aux; a value of y or aux outside the domain above or not finite; an offset that is not finite; any other call
+ * before gpmi_ggp_set_observations (gpmi_set_data drops the observations with the rest of the data set); a kernel other
+ * than GPMI_KERNEL_SE / _RQ / _M32 / _M52 and the n_theta errors of gpmi_fit; tol not in (0, 1), max_iter < 1; NULL outputs;
+ * gpmi_ggp_mode / gpmi_ggp_predict without a successful gpmi_ggp_fit as the handle's last fit.
+ * Device memory, owned by the handle and released with it or at the next gpmi_set_data: per lane one padded matrix for K
+ * (8 n_pad (n_pad + 32) bytes) beside the lane's own matrix for B and L - and, for gpmi_ggp_logq_grad, the lane's second
+ * matrix -, 18 vectors of n_pad doubles and the block partials; four vectors of n_pad for the observations. */
+#define GPMI_GGP_LOGISTIC 0
+#define GPMI_GGP_POISSON 1
+#define GPMI_GGP_BINOMIAL 2
+/* y_host, aux_host: n values each.  Replaces earlier observations of the handle and drops a fit made from them. */
+int gpmi_ggp_set_observations(gpmi_ctx* ctx, int likelihood, const double* y_host, const double* aux_host, double offset);
+int gpmi_ggp_fit(gpmi_ctx* ctx, int kernel, const double* theta_host, int n_theta, double tol, int max_iter, double* logq,
+                 int* out_iters /* 2 */, int* info);
+int gpmi_ggp_logq(gpmi_ctx* ctx, int kernel, const double* theta_host, int n_theta, double tol, int max_iter, double* logq,
+                  int* out_iters /* 2 */, int* info);
+/* grad_host: d log q / d theta_j, n_theta values, explicit and implicit (through the mode) parts together: with
+ * R = sw sw^T o B^-1, s2 = 1/2 (diag K - diag(K R K)) o d3, w = s2 - R K s2 and u = g + 2 w it is
+ * 1/2 sum_ab [1/2 (u g^T + g u^T) - R]_ab (dK / d theta_j)_ab - one run of gpmi_lml_grad's contraction. */
+int gpmi_ggp_logq_grad(gpmi_ctx* ctx, int kernel, const double* theta_host, int n_theta, double tol, int max_iter,
+                       double* logq, double* grad_host /* n_theta */, int* out_iters /* 2 */, int* info);
+/* the mode f-hat and g = grad log p(y | f-hat) (= a = K^-1 (f-hat - m) at the mode) of the fit, n values each */
+int gpmi_ggp_mode(gpmi_ctx* ctx, double* f_host, double* g_host);
+/* latent mean m + k(q)^T g and variance a^2 - |L^-1 (sw o k(q))|^2 at m points (var_host may be NULL) */
+int gpmi_ggp_predict(gpmi_ctx* ctx, const double* pts_host /* m x d */, int64_t m, double* mean_host, double* var_host);
+/* Y = V K^T for nv = 1 .. 4 vectors (rows of V_host, nv x n; Y_host likewise) with the latent K at theta, built on lane 1:
+ * the product kernel of the Newton steps on its own (tests, tools/generalised_bench.py).  reps >= 1 runs of the product;
+ * ms (may be NULL): the HIP-event time of all of them. */
+int gpmi_ggp_kv(gpmi_ctx* ctx, int kernel, const double* theta_host, int n_theta, const double* V_host, int nv,
+                double* Y_host, int reps, float* ms);
+
 /* ---- instrumentation ---------------------------------------------------------------
  * HIP-event timing on the handle's own stream (torch.cuda.Event would not see it). */
 int gpmi_timer_start(gpmi_ctx* ctx);
@@ -963,6 +1013,14 @@ int gpmi_flow_task_lists(int m, int nwg, int64_t cap, int32_t* out, int64_t* nta
 #define GPMI_PROF_HESS_GEMM GPMI_PROF_SGP_GRAM
 #define GPMI_PROF_HESS_TRACE GPMI_PROF_SGP_FACTOR
 #define GPMI_PROF_HESS_CONTRACT GPMI_PROF_SGP_GRAD
+/* the gpmi_ggp_* entry points (tools/generalised_bench.py) book under the same ids: the likelihood-terms kernel with its
+ * totals, the K V products, the formation of B = I + sw sw^T o K, and the gradient's tail from the scaled solve to the
+ * contraction (its many-right-hand-side solves are booked under GPMI_PROF_TRSM as well); the factorisations and the
+ * triangular sweeps book their own classes (PANEL, SYRK*, FLOW, SOLVE) */
+#define GPMI_PROF_GGP_TERMS GPMI_PROF_SGP_BUILD
+#define GPMI_PROF_GGP_KV GPMI_PROF_SGP_GRAM
+#define GPMI_PROF_GGP_BFORM GPMI_PROF_SGP_FACTOR
+#define GPMI_PROF_GGP_GRAD GPMI_PROF_SGP_GRAD
 #define GPMI_PROF_NCLASS 17
 /* on = 0: off; 1: every class; otherwise a class bitmask shifted left by one (2 << klass) */
 int gpmi_profile_enable(gpmi_ctx* ctx, int on);

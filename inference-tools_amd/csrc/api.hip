@@ -190,6 +190,7 @@ void free_data(gpmi_ctx* c) {
   static_cast<MixBufs&>(*c) = MixBufs();
   static_cast<MultiBufs&>(*c) = MultiBufs();  // (the targets belong to the data set: gpmi_mt_set_targets again)
   static_cast<HessBufs&>(*c) = HessBufs();
+  static_cast<GgpBufs&>(*c) = GgpBufs();  // (the observations belong to the data set: gpmi_ggp_set_observations again)
   for (size_t i = c->lanes.size(); i-- > 0;) lane_free(c->lanes[i]);  // (lanes >= 2 borrow the streams of lanes 0, 1)
   c->lanes.clear();
   static_cast<DataBufs&>(*c) = DataBufs();

@@ -25,7 +25,7 @@ int lane_forward(const LaneEval& ev, const LaneBuild& b, unsigned steps, const d
   if (int rc = lane_prepare(ev, steps, n_theta)) return rc;
   Lane& L = ev.L();
   const bool fit = (steps & LN_FIT_SCHEDULE) != 0;
-  if (ev.lane == 0) c->mt_fitted = false;  // lane 0 gets another factor: gpmi_mt_fit says so again if it is the caller
+  if (ev.lane == 0) c->mt_fitted = c->ggp_fitted = false;  // lane 0 gets another factor: gpmi_mt_fit says so again if it is the caller
   HIPCHK(c, hipMemcpyAsync(ev.mu(), mu_host, sizeof(double) * c->n, hipMemcpyHostToDevice, L.stream));
   if (b.dense) {
     if (int rc = upload_dense_matrix(c, L, b.dense)) return rc;

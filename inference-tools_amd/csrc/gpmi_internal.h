@@ -313,7 +313,25 @@ struct HessBufs {
   PinBuf<double> h_hOut;        // pinned mirror of the sums
 };
 
-struct gpmi_ctx : DataBufs, QueryBufs, BatchBufs, MixBufs, MultiBufs, HessBufs {
+// generalised GP (api_generalised.hip, gpmi_ggp_*): the observations of a non-Gaussian likelihood and, per lane (0: the fit,
+// 1: evaluations at other hyper-parameters), the latent covariance, the work vectors of Newton's iteration, the block
+// partials of its sums and the record the host reads once per step; each lane's buffers are allocated by its first call
+constexpr int GGP_NVEC = 18;  // work vectors per lane (api_generalised.hip: GgpVecs)
+struct GgpBufs {
+  int ggp_lik = -1;           // GPMI_GGP_*; -1: gpmi_ggp_set_observations has not been called for this data set
+  double ggp_offset = 0.0;    // the constant prior mean m of f
+  bool ggp_fitted = false;    // lane 0 holds the factor of B at the mode (gpmi_ggp_fit was the last fit and succeeded)
+  DevBuf<double> ggY, ggAux, ggConst;  // np each: y, the per-point data of the likelihood, the f-independent part of log p
+  DevBuf<double> ggZero;      // np zeros: the latent K carries no data noise
+  DevBuf<double> ggK[2];      // np x ld   latent covariance K (both triangles, identity in the padding)
+  DevBuf<double> ggVec[2];    // GGP_NVEC x np
+  DevBuf<double> ggPart[2];   // ggp_part_doubles(np)
+  DevBuf<double> ggRec[2];    // 8: sum log p, a^T (f - m), max |f - f_prev|, max |f|
+  PinBuf<double> h_ggRec;     // pinned mirror of a record
+  DevBuf<double> ggMean;      // 2048 predictive means of a chunk of query points
+};
+
+struct gpmi_ctx : DataBufs, QueryBufs, BatchBufs, MixBufs, MultiBufs, HessBufs, GgpBufs {
   int device = 0;
   int ncu = 256;      // compute units of the device
   int pair_cus[GPMI_NPAIRS] = {32};  // CUs of the panel stream of look-ahead pair k (the update stream has the rest)
@@ -645,6 +663,29 @@ void launch_rows_sumsq(hipStream_t s, const double* Q, int64_t ld, int64_t mp, i
 // the sweep runs over the 128-wide blocks with invD)
 void trsm_rows_backward(gpmi_ctx* c, hipStream_t s, const double* L, int64_t np, int64_t ld,
                         const double* invD, double* Q, int64_t mp, const double* inv2 = nullptr, double* panel = nullptr);
+
+// generalised.hip: the kernels of the generalised GP (gpmi_ggp_*)
+struct GgpTerms {
+  double *g, *W, *sw, *d3, *b;  // np each: d log p / df, -d^2 log p / df^2, its root, d^3 log p / df^3, W (f - m) + g
+};
+struct GgpKv {
+  const double* v[4];
+  double* y[4];
+};
+int64_t ggp_part_doubles(int64_t np);
+// the likelihood terms at f = fm + offset (a, fm, fm_prev: np each; fm_prev may be null) and the record
+// rec[0..3] = {sum log p, a^T fm, max |fm - fm_prev|, max |f|}; part: ggp_part_doubles(np)
+void launch_ggp_terms(hipStream_t s, int lik, const double* y, const double* aux, const double* lconst, double offset,
+                      const double* a, const double* fm, const double* fm_prev, int64_t n, int64_t np, const GgpTerms& t,
+                      double* part, double* rec);
+// y[q] = K v[q] for q < nv (1 .. 4) in one pass over the np x np matrix K (both triangles stored); the bits of a product do
+// not depend on nv
+void launch_ggp_kv(hipStream_t s, const double* K, int64_t ld, int64_t np, int nv, const GgpKv& a);
+void launch_ggp_blend(hipStream_t s, const double* lo, const double* hi, double step, double* out, int64_t cnt);
+void launch_ggp_newton_a(hipStream_t s, const double* b, const double* sw, const double* t, double* a_new, int64_t np);
+void launch_ggp_s2(hipStream_t s, const double* K, int64_t ld, const double* ss, const double* d3, double* s2, int64_t np);
+void launch_ggp_grad_u(hipStream_t s, const double* g, const double* s2, const double* rt, double* u, int64_t np);
+void launch_ggp_scale_cols(hipStream_t s, double* Q, int64_t ld, int64_t rows, int64_t np, const double* sc);
 
 // predgrad.hip
 void launch_sd_reduce(hipStream_t s, const KParams& p, const double* x, int64_t n, const double* pts,

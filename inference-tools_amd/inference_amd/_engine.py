@@ -696,6 +696,65 @@ class GpEngine(_DeviceCommMixin, _DrawsMixin):
         self.h.call("gpmi_mt_loo", dptr(resid), dptr(ikdiag))
         return resid, ikdiag
 
+    # -- non-Gaussian likelihoods by Laplace's method (gpmi_ggp_*) ---------------------------
+    def ggp_set_observations(self, likelihood, y, aux, offset):
+        """gpmi_ggp_set_observations: the likelihood id, its y and per-point data (n each) and the constant prior mean."""
+        y, aux = as_f64(y), as_f64(aux)
+        if y.shape != (self.n,) or aux.shape != (self.n,):
+            raise ValueError(f"y and aux must be ({self.n},), got {y.shape} and {aux.shape}")
+        self.h.call("gpmi_ggp_set_observations", int(likelihood), dptr(y), dptr(aux), float(offset))
+
+    def _ggp_value(self, name, kernel, theta_cov, tol, max_iter):
+        theta = as_f64(theta_cov)
+        logq, info, iters = C.c_double(0.0), C.c_int(0), (C.c_int * 2)(0, 0)
+        self.h.call(name, kernel, dptr(theta), theta.size, float(tol), int(max_iter), C.byref(logq), iters, C.byref(info))
+        return logq.value, (iters[0], iters[1]), info.value
+
+    def ggp_fit(self, kernel, theta_cov, tol, max_iter):
+        """gpmi_ggp_fit: (log q, (Newton steps, halvings), info); the factor of B at the mode stays in lane 0."""
+        return self._ggp_value("gpmi_ggp_fit", kernel, theta_cov, tol, max_iter)
+
+    def ggp_logq(self, kernel, theta_cov, tol, max_iter):
+        """gpmi_ggp_logq: the same at other hyper-parameters on lane 1; the fit is not touched."""
+        return self._ggp_value("gpmi_ggp_logq", kernel, theta_cov, tol, max_iter)
+
+    def ggp_logq_grad(self, kernel, theta_cov, tol, max_iter):
+        """gpmi_ggp_logq_grad: (log q, grad (n_theta,), (Newton steps, halvings), info)."""
+        theta = as_f64(theta_cov)
+        grad = np.zeros(theta.size)
+        logq, info, iters = C.c_double(0.0), C.c_int(0), (C.c_int * 2)(0, 0)
+        self.h.call("gpmi_ggp_logq_grad", kernel, dptr(theta), theta.size, float(tol), int(max_iter), C.byref(logq),
+                    dptr(grad), iters, C.byref(info))
+        return logq.value, grad, (iters[0], iters[1]), info.value
+
+    def ggp_mode(self):
+        """gpmi_ggp_mode: (f-hat (n,), g = grad log p(y | f-hat) (n,)) of the fit."""
+        f, g = np.empty(self.n), np.empty(self.n)
+        self.h.call("gpmi_ggp_mode", dptr(f), dptr(g))
+        return f, g
+
+    def ggp_predict(self, pts, want_var=True):
+        """gpmi_ggp_predict: (latent mean (m,), latent variance (m,) | None)."""
+        p = as_f64(pts)
+        m = p.shape[0]
+        mean = np.empty(m)
+        var = np.empty(m) if want_var else None
+        self.h.call("gpmi_ggp_predict", dptr(p), m, dptr(mean), dptr(var))
+        return mean, var
+
+    def ggp_kv(self, kernel, theta_cov, V, reps=1, timed=False):
+        """gpmi_ggp_kv: K V^T row by row for 1 .. 4 vectors (rows of V) with the latent K at theta; with `timed` also
+        the HIP-event milliseconds of the `reps` products."""
+        theta = as_f64(theta_cov)
+        V = np.atleast_2d(as_f64(V))
+        if V.shape[1] != self.n:
+            raise ValueError(f"V must be (nv, {self.n}), got {V.shape}")
+        Y = np.empty_like(V)
+        ms = C.c_float(0.0)
+        self.h.call("gpmi_ggp_kv", kernel, dptr(theta), theta.size, dptr(V), V.shape[0], dptr(Y), int(reps),
+                    C.byref(ms) if timed else None)
+        return (Y, ms.value) if timed else Y
+
     def sync(self):
         self.h.call("gpmi_sync")
 

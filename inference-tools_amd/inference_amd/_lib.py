@@ -38,6 +38,8 @@ PROF_SGP_BUILD, PROF_SGP_GRAM, PROF_SGP_FACTOR, PROF_SGP_GRAD = 13, 14, 15, 16  
 PROF_HESS_BUILD, PROF_HESS_GEMM, PROF_HESS_TRACE, PROF_HESS_CONTRACT = 13, 14, 15, 16  # GPMI_PROF_HESS_*: the same ids
 SGP_MAX_M = 4096  # GPMI_SGP_MAX_M: the most inducing points a gpmi_sgp object takes
 MT_MAX_T = 4096  # GPMI_MT_MAX_T: the most targets gpmi_mt_set_targets takes
+GGP_LOGISTIC, GGP_POISSON, GGP_BINOMIAL = 0, 1, 2  # GPMI_GGP_*: the likelihoods of the gpmi_ggp_* entry points
+PROF_GGP_TERMS, PROF_GGP_KV, PROF_GGP_BFORM, PROF_GGP_GRAD = 13, 14, 15, 16  # GPMI_PROF_GGP_*: the same ids
 
 
 class GpmiUnavailable(RuntimeError):
@@ -173,6 +175,13 @@ SIGNATURES = {
     "gpmi_mt_alpha": (C.c_int, [_vp, _dp]),
     "gpmi_mt_predict": (C.c_int, [_vp, _dp, _i64, _dp, _dp]),
     "gpmi_mt_loo": (C.c_int, [_vp, _dp, _dp]),
+    "gpmi_ggp_set_observations": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_double]),
+    "gpmi_ggp_fit": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double, C.c_int, _dp, _ip, _ip]),
+    "gpmi_ggp_logq": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double, C.c_int, _dp, _ip, _ip]),
+    "gpmi_ggp_logq_grad": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double, C.c_int, _dp, _dp, _ip, _ip]),
+    "gpmi_ggp_mode": (C.c_int, [_vp, _dp, _dp]),
+    "gpmi_ggp_predict": (C.c_int, [_vp, _dp, _i64, _dp, _dp]),
+    "gpmi_ggp_kv": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, C.POINTER(C.c_float)]),
     "gpmi_timer_start": (C.c_int, [_vp]),
     "gpmi_timer_stop": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "gpmi_profile_enable": (C.c_int, [_vp, C.c_int]),
@@ -282,7 +291,8 @@ class Handle:
                              "gpmi_linv_lml_grad_dense", "gpmi_linv_posterior_dense", "gpmi_loo_terms", "gpmi_loo_grad",
                              "gpmi_loo_terms_mix", "gpmi_dev_potrf", "gpmi_loo_grad_batch", "gpmi_loo_grad_batch_noise", "gpmi_lml_grad_batch_noise",
                              "gpmi_lml_grad_batch_mix", "gpmi_loo_grad_batch_mix", "gpmi_predict_batch", "gpmi_posterior_draws",
-                             "gpmi_mvn_draws", "gpmi_mt_fit", "gpmi_mt_lml", "gpmi_mt_lml_grad", "gpmi_mt_loo_terms"))
+                             "gpmi_mvn_draws", "gpmi_mt_fit", "gpmi_mt_lml", "gpmi_mt_lml_grad", "gpmi_mt_loo_terms",
+                             "gpmi_ggp_fit", "gpmi_ggp_logq", "gpmi_ggp_logq_grad"))
 
     def call(self, name, *args):
         if _TRACE_MS is not None:  # GPMI_TRACE_CALLS=<ms>: report every entry-point call that takes longer (debugging aid)
