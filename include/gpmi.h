@@ -48,6 +48,19 @@ extern "C" {
  * gpmi_covariance, gpmi_cross_covariance; a sum fit serves gpmi_predict, gpmi_posterior, gpmi_get_K, gpmi_get_L and
  * gpmi_append_point.  Every other entry point returns GPMI_ERR_ARG for it. */
 #define GPMI_KERNEL_SUM 2
+/* Periodic kernel (no counterpart in the reference; scikit-learn's ExpSineSquared, GPy's StdPeriodic): periodic in the
+ * input dimensions declared per handle by gpmi_set_periodic, squared-exponential in the others,
+ *   K = a^2 exp(-sum_k w_k / l_k^2),   w_k = 1/2 dx_k^2 (plain k)   or   2 sin^2(pi dx_k / p_k) (periodic k);
+ * theta = [ln a, ln l_1..ln l_d, ln p_j for the declared dimensions j in ascending order], n_theta = 1 + d + n_per.
+ * d + n_per <= 64: the periods travel in the unused part of the 64 length-scale slots of a parameter block.
+ * Accepted wherever GPMI_KERNEL_SE is by the entry points that take a kernel id through gpmi_fit's argument checks
+ * (gpmi_fit, gpmi_lml, gpmi_lml_batch(_submit), gpmi_lml_grad(_batch)(_noise), gpmi_loo_terms, gpmi_loo_grad(_batch)(_noise),
+ * gpmi_predict(_batch), gpmi_posterior(_draws), gpmi_covariance, gpmi_cross_covariance, gpmi_append_point,
+ * gpmi_spatial_derivatives, gpmi_gradient) and as a component of gpmi_set_sum.  GPMI_ERR_ARG, before anything is
+ * launched, from gpmi_lml_hessian, gpmi_sgp_*, gpmi_select_points, gpmi_mt_*, gpmi_ggp_*, gpmi_linv_* and the *_mix entry
+ * points. */
+#define GPMI_KERNEL_PER 5
+#define GPMI_MAX_PERIODIC 8 /* periodic dimensions of one handle */
 
 #define GPMI_OK 0
 #define GPMI_ERR_ARG (-1)     /* bad argument / call order */
@@ -318,10 +331,17 @@ int gpmi_loo_terms(gpmi_ctx* ctx, int kernel, const double* theta_host, int n_th
 int gpmi_set_noise(gpmi_ctx* ctx, const double* noise_var_host);
 
 /* ---- sums of stationary kernels (GPMI_KERNEL_SUM) ------------------------------------
- * Declares the components of the handle's sum: nk in 2..4, kernels[m] GPMI_KERNEL_SE, _RQ, _M32 or _M52 in the order of
+ * Declares the components of the handle's sum: nk in 2..4, kernels[m] GPMI_KERNEL_SE, _RQ, _M32, _M52 or _PER in the order of
  * the sum.  K = sum_m a_m^2 (C_m + 1e-12 I) + extra_diag I + data errors (every component carries its own jitter,
  * covariance.py:254-255,348); a query point's prior variance is sum_m a_m^2. */
 int gpmi_set_sum(gpmi_ctx* ctx, int nk, const int* kernels);
+/* ---- periodic dimensions (GPMI_KERNEL_PER) ---------------------------------------------
+ * Declares the input dimensions in which the handle's GPMI_KERNEL_PER is periodic: n_per in 1..GPMI_MAX_PERIODIC,
+ * dims[n_per] strictly ascending, each in [0, d).  Called after gpmi_set_data; the declaration is kept until a
+ * gpmi_set_data with another d.  Every GPMI_KERNEL_PER component of a sum shares it.  GPMI_ERR_ARG with a message (the
+ * handle stays usable, an earlier declaration stays in force): NULL dims, n_per out of range, dims not strictly
+ * ascending, a dim >= d, no data set.  GPMI_KERNEL_PER itself is GPMI_ERR_ARG until a declaration exists. */
+int gpmi_set_periodic(gpmi_ctx* ctx, int n_per, const int* dims);
 /* q_i = alpha_i^2 - (K^-1)_ii of the most recent gpmi_lml_grad call (n values): the gradient with respect to
  * ln sigma_i is 1/2 Q_ii 2 sigma_i^2 = sigma_i^2 q_i (covariance.py:682-686, regression.py:561-565). */
 int gpmi_lml_grad_qdiag(gpmi_ctx* ctx, double* qdiag_host);

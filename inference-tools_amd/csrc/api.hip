@@ -208,22 +208,40 @@ int make_params(gpmi_ctx* c, int kernel, const double* theta, int n_theta, doubl
                 KParams& p) {
   ARGCHK(c, c->n > 0, "gpmi_set_data has not been called");
   ARGCHK(c, kernel != GPMI_KERNEL_SUM, "this entry point does not take sums of kernels (GPMI_KERNEL_SUM)");
-  ARGCHK(c, kernel_is_stationary(kernel), "unknown kernel id");
-  const int off = kernel_theta_offset(kernel);  // SE, Matern: 1; RQ: 2
-  ARGCHK(c, n_theta == c->d + off, "n_theta does not match the kernel and the data dimension");
+  ARGCHK(c, kernel_is_single(kernel), "unknown kernel id");
+  const bool per = kernel == GPMI_KERNEL_PER;
+  ARGCHK(c, !per || c->n_per > 0, "GPMI_KERNEL_PER: declare the periodic dimensions with gpmi_set_periodic first");
+  ARGCHK(c, !per || c->d + c->n_per <= GPMI_MAX_D,
+         "GPMI_KERNEL_PER: d plus the number of periodic dimensions exceeds GPMI_MAX_D (64)");
+  const int off = per ? 1 : kernel_theta_offset(kernel);  // SE, Matern, Periodic: 1; RQ: 2
+  ARGCHK(c, n_theta == c->d + off + (per ? c->n_per : 0),
+         per ? "n_theta does not match 1 + d + the periodic dimensions declared by gpmi_set_periodic"
+             : "n_theta does not match the kernel and the data dimension");
   ARGCHK(c, theta != nullptr, "theta is NULL");
   std::memset(&p, 0, sizeof(p));
   p.kernel = kernel;
   p.d = (int)c->d;
   const double a = std::exp(theta[0]);
   p.a2 = a * a;                                             // (a**2), covariance.py:255
-  p.kappa = (kernel == GPMI_KERNEL_RQ) ? std::exp(theta[1]) : 1.0;
+  if (!per) p.kappa = (kernel == GPMI_KERNEL_RQ) ? std::exp(theta[1]) : 1.0;
   p.extra_diag = extra;
   for (int k = 0; k < p.d; ++k) {
     const double l = std::exp(theta[off + k]);
     p.inv_l2[k] = 1.0 / (l * l);
   }
+  if (per) {  // theta = [ln a, ln l_1 .. ln l_d, ln p_j ..]: 1 / p_j = exp(-ln p_j), inf or 0 where that leaves the doubles
+    p.per_mask = 0;  // (KParams: the mask in kappa's place, 1 / p_j behind the d inverse squares)
+    for (int j = 0; j < c->n_per; ++j) {
+      p.per_mask |= 1ull << c->per_dim[j];
+      p.inv_l2[p.d + j] = std::exp(-theta[1 + p.d + j]);
+    }
+  }
   return GPMI_OK;
+}
+
+// parameters of one component kind of this handle's sum
+static int component_n_theta(const gpmi_ctx* c, int kind) {
+  return (kind == GPMI_KERNEL_PER ? 1 + c->n_per : kernel_theta_offset(kind)) + (int)c->d;
 }
 
 int make_cov(gpmi_ctx* c, int kernel, const double* theta, int n_theta, double extra, CovParams& p) {
@@ -233,7 +251,11 @@ int make_cov(gpmi_ctx* c, int kernel, const double* theta, int n_theta, double e
   ARGCHK(c, c->sum_nk >= 2, "GPMI_KERNEL_SUM: declare the components of the sum with gpmi_set_sum first");
   ARGCHK(c, theta != nullptr, "theta is NULL");
   int need = 0;
-  for (int m = 0; m < c->sum_nk; ++m) need += kernel_theta_offset(c->sum_kinds[m]) + (int)c->d;
+  for (int m = 0; m < c->sum_nk; ++m) {
+    ARGCHK(c, c->sum_kinds[m] != GPMI_KERNEL_PER || c->n_per > 0,
+           "GPMI_KERNEL_PER in a sum: declare the periodic dimensions with gpmi_set_periodic first");
+    need += component_n_theta(c, c->sum_kinds[m]);
+  }
   ARGCHK(c, n_theta == need, "n_theta does not match the sum declared by gpmi_set_sum and the data dimension");
   p.kernel = GPMI_KERNEL_SUM;
   p.d = (int)c->d;
@@ -243,7 +265,7 @@ int make_cov(gpmi_ctx* c, int kernel, const double* theta, int n_theta, double e
   int off = 0;
   double a2 = 0.0;
   for (int m = 0; m < p.nk; ++m) {
-    const int nt = kernel_theta_offset(c->sum_kinds[m]) + (int)c->d;
+    const int nt = component_n_theta(c, c->sum_kinds[m]);
     if (int rc = make_params(c, c->sum_kinds[m], theta + off, nt, 0.0, p.comp[m])) return rc;
     a2 += p.comp[m].a2;  // K_qq = sum_m a_m^2 in component order (regression.py:210 through covariance.py:87-90)
     off += nt;
@@ -673,7 +695,9 @@ int gpmi_set_data(gpmi_ctx* c, const double* x, const double* y, const double* n
   ARGCHK(c, x && y && n > 0 && d > 0, "x, y must be non-NULL and n, d positive");
   ARGCHK(c, d <= GPMI_MAX_D, "more spatial dimensions than GPMI_MAX_D (64)");
   if (int rc = set_device(c)) return rc;
+  const int64_t d_before = c->d;  // (free_data zeroes it)
   free_data(c);
+  if (d != d_before) c->n_per = 0;  // gpmi_set_periodic: the declaration belongs to a d
   c->n = n;
   c->d = d;
   c->np = round_up(n + c->reserve, GPMI_NB);
@@ -715,10 +739,24 @@ int gpmi_set_sum(gpmi_ctx* c, int nk, const int* kernels) {
   ARGCHK(c, nk >= 2 && nk <= GPMI_MAX_SUM, "gpmi_set_sum: a sum has 2 to 4 components");
   ARGCHK(c, kernels != nullptr, "kernels is NULL");
   for (int m = 0; m < nk; ++m)
-    ARGCHK(c, kernel_is_stationary(kernels[m]),
-           "gpmi_set_sum: every component is GPMI_KERNEL_SE, GPMI_KERNEL_RQ, GPMI_KERNEL_M32 or GPMI_KERNEL_M52");
+    ARGCHK(c, kernel_is_single(kernels[m]),
+           "gpmi_set_sum: every component is GPMI_KERNEL_SE, GPMI_KERNEL_RQ, GPMI_KERNEL_M32, GPMI_KERNEL_M52 or GPMI_KERNEL_PER");
   c->sum_nk = nk;
   for (int m = 0; m < GPMI_MAX_SUM; ++m) c->sum_kinds[m] = (m < nk) ? kernels[m] : 0;
+  return GPMI_OK;
+}
+
+int gpmi_set_periodic(gpmi_ctx* c, int n_per, const int* dims) {
+  if (!c) return GPMI_ERR_ARG;
+  ARGCHK(c, c->n > 0, "gpmi_set_periodic: gpmi_set_data has not been called");
+  ARGCHK(c, dims != nullptr, "gpmi_set_periodic: dims is NULL");
+  ARGCHK(c, n_per >= 1 && n_per <= GPMI_MAX_PERIODIC, "gpmi_set_periodic: 1 to 8 periodic dimensions (GPMI_MAX_PERIODIC)");
+  for (int j = 0; j < n_per; ++j) {
+    ARGCHK(c, dims[j] >= 0 && dims[j] < c->d, "gpmi_set_periodic: a dimension outside [0, d)");
+    ARGCHK(c, j == 0 || dims[j] > dims[j - 1], "gpmi_set_periodic: dims must be strictly ascending");
+  }
+  c->n_per = n_per;
+  for (int j = 0; j < GPMI_MAX_PERIODIC; ++j) c->per_dim[j] = (j < n_per) ? dims[j] : 0;
   return GPMI_OK;
 }
 

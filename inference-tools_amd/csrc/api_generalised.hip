@@ -59,6 +59,7 @@ int ggp_check_fit(gpmi_ctx* c, const char* who) {
 int ggp_eval_args(gpmi_ctx* c, const char* who, int kernel, const double* theta, int n_theta, double tol, int max_iter,
                   const double* logq, const int* out_iters, const int* info, CovParams& p) {
   if (int rc = ggp_check(c, who)) return rc;
+  NO_PERIODIC(c, kernel);
   if (int rc = make_params(c, kernel, theta, n_theta, 0.0, p)) return rc;
   ARGCHK(c, tol > 0.0 && tol < 1.0, "tol must lie in (0, 1)");
   ARGCHK(c, max_iter >= 1, "max_iter must be at least 1");
@@ -412,6 +413,7 @@ int gpmi_ggp_kv(gpmi_ctx* c, int kernel, const double* theta, int n_theta, const
   if (!c) return GPMI_ERR_ARG;
   if (int rc = ggp_check(c, "gpmi_ggp_kv")) return rc;
   CovParams p;
+  NO_PERIODIC(c, kernel);
   if (int rc = make_params(c, kernel, theta, n_theta, 0.0, p)) return rc;
   ARGCHK(c, V_host && Y_host, "V_host / Y_host is NULL");
   ARGCHK(c, nv >= 1 && nv <= 4 && reps >= 1, "gpmi_ggp_kv: nv outside 1 .. 4 or reps < 1");

@@ -35,6 +35,7 @@ int gpmi_lml_hessian(gpmi_ctx* c, int kernel, const double* theta, int n_theta, 
   ARGCHK(c, kernel != GPMI_KERNEL_SUM && c->sum_nk == 0,
          "gpmi_lml_hessian does not take sums of kernels (GPMI_KERNEL_SUM, gpmi_set_sum): difference gpmi_lml_grad instead");
   KParams p;
+  NO_PERIODIC(c, kernel);
   if (int rc = make_params(c, kernel, theta, n_theta, extra_diag, p)) return rc;
   ARGCHK(c, !c->ycov, "gpmi_lml_hessian needs diagonal data errors (no dense y covariance)");
   ARGCHK(c, extra_diag >= 0.0 && std::isfinite(extra_diag), "extra_diag must be finite and >= 0");

@@ -157,6 +157,19 @@ int lane_alloc(gpmi_ctx* c, Lane& L);
 void lane_free(Lane& L);
 int ensure_lanes(gpmi_ctx* c, size_t count);
 void free_data(gpmi_ctx* c);
+// The entry points without Periodic kernels (the exact Hessian, many targets, the generalised GP, the linear inversion,
+// the ChangePoint mixtures) refuse GPMI_KERNEL_PER - alone or as a component of the handle's sum - before they build
+// parameters or launch anything.
+inline bool uses_periodic(const gpmi_ctx* c, int kernel) {
+  if (kernel == GPMI_KERNEL_PER) return true;
+  if (kernel == GPMI_KERNEL_SUM)
+    for (int m = 0; m < c->sum_nk; ++m)
+      if (c->sum_kinds[m] == GPMI_KERNEL_PER) return true;
+  return false;
+}
+#define NO_PERIODIC(ctx, kernel) \
+  ARGCHK(ctx, !uses_periodic(ctx, kernel), "GPMI_KERNEL_PER is not supported by this entry point")
+
 int make_params(gpmi_ctx* c, int kernel, const double* theta, int n_theta, double extra, KParams& p);
 // make_params for the entry points that also take sums (GPMI_KERNEL_SUM: the layout of gpmi_set_sum)
 int make_cov(gpmi_ctx* c, int kernel, const double* theta, int n_theta, double extra, CovParams& p);

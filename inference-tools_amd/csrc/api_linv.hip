@@ -125,6 +125,7 @@ int gpmi_linv_lml(gpmi_ctx* c, int kernel, const double* theta, int n_theta, dou
   if (!c) return GPMI_ERR_ARG;
   if (int rc = linv_ready(c)) return rc;
   KParams p;
+  NO_PERIODIC(c, kernel);
   if (int rc = make_params(c, kernel, theta, n_theta, extra_diag, p)) return rc;
   return linv_lml_impl(c, p, nullptr, mu, lml, info);
 }
@@ -197,6 +198,7 @@ int gpmi_linv_lml_grad(gpmi_ctx* c, int kernel, const double* theta, int n_theta
   if (!c) return GPMI_ERR_ARG;
   if (int rc = linv_ready(c)) return rc;
   KParams p;
+  NO_PERIODIC(c, kernel);
   if (int rc = make_params(c, kernel, theta, n_theta, extra_diag, p)) return rc;
   ARGCHK(c, grad_theta, "grad_theta is NULL");
   return linv_lml_grad_impl(c, p, n_theta, nullptr, mu, lml, grad_theta, trace_q, nullptr, at_alpha, info);
@@ -251,6 +253,7 @@ int gpmi_linv_posterior(gpmi_ctx* c, int kernel, const double* theta, int n_thet
   if (!c) return GPMI_ERR_ARG;
   if (int rc = linv_ready(c)) return rc;
   KParams p;
+  NO_PERIODIC(c, kernel);
   if (int rc = make_params(c, kernel, theta, n_theta, extra_diag, p)) return rc;
   return linv_posterior_impl(c, p, nullptr, mu, mean, cov, info);
 }

@@ -49,7 +49,7 @@ void launch_lml_grad_batched(const Chunk& k, const BatchParams& p, int n_theta, 
   gpmi_ctx* c = k.c;
   if (p.sum)
     launch_lml_grad_batched(k.stream, c->bSum + k.off, k.B, n_theta, c->x, c->n, c->np, k.A, c->ld, k.bs.sMat, u, v, sV,
-                            c->bGws, c->bGout, (int)c->d);
+                            c->bGws, c->bGout, (int)c->d, uses_periodic(c, GPMI_KERNEL_SUM));
   else
     launch_lml_grad_batched(k.stream, p.kernel, c->bParams + k.off, k.B, n_theta, c->x, c->n, c->np, k.A, c->ld, k.bs.sMat, u,
                             v, sV, c->bGws, c->bGout);
@@ -138,6 +138,7 @@ int make_mix_batch_params(gpmi_ctx* c, const MixBatch& mx, int64_t T, const doub
   for (int64_t t = 0; t < T; ++t) {
     int off = 0;
     for (int m = 0; m < mx.nk; ++m) {
+      NO_PERIODIC(c, mx.kernels[m]);
       if (int rc = make_params(c, mx.kernels[m], thetas + t * mx.tot_nt + off, mx.n_thetas[m], 0.0, ps[(size_t)m * T + t]))
         return rc;
       off += mx.n_thetas[m];

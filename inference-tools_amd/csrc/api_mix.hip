@@ -14,6 +14,7 @@ int mix_prepare(gpmi_ctx* c, int nk, const int* kernels, const double* thetas, c
   ARGCHK(c, kernels && thetas && n_thetas && g_host, "NULL argument");
   int off = 0;
   for (int m = 0; m < nk; ++m) {
+    NO_PERIODIC(c, kernels[m]);
     if (int rc = make_params(c, kernels[m], thetas + off, n_thetas[m], 0.0, ps[m])) return rc;
     off += n_thetas[m];
   }

@@ -172,6 +172,7 @@ int gpmi_mt_fit(gpmi_ctx* c, int kernel, const double* theta, int n_theta, doubl
   if (!c) return GPMI_ERR_ARG;
   if (int rc = mt_check(c, "gpmi_mt_fit")) return rc;
   CovParams p;
+  NO_PERIODIC(c, kernel);
   if (int rc = make_cov(c, kernel, theta, n_theta, extra_diag, p)) return rc;
   if (int rc = set_device(c)) return rc;
   if (int rc = mt_reserve(c, c->mtA, c->mt_Tp)) return rc;
@@ -196,6 +197,7 @@ int gpmi_mt_lml(gpmi_ctx* c, int kernel, const double* theta, int n_theta, doubl
   if (!c) return GPMI_ERR_ARG;
   if (int rc = mt_check(c, "gpmi_mt_lml")) return rc;
   CovParams p;
+  NO_PERIODIC(c, kernel);
   if (int rc = make_cov(c, kernel, theta, n_theta, extra_diag, p)) return rc;
   ARGCHK(c, lml_t || lml, "lml_t and lml are both NULL");
   if (int rc = set_device(c)) return rc;
@@ -217,6 +219,7 @@ int gpmi_mt_lml_grad(gpmi_ctx* c, int kernel, const double* theta, int n_theta, 
   if (!c) return GPMI_ERR_ARG;
   if (int rc = mt_check(c, "gpmi_mt_lml_grad")) return rc;
   CovParams p;
+  NO_PERIODIC(c, kernel);
   if (int rc = make_cov(c, kernel, theta, n_theta, extra_diag, p)) return rc;
   ARGCHK(c, lml && grad, "lml / grad is NULL");
   if (int rc = set_device(c)) return rc;
@@ -252,6 +255,7 @@ int gpmi_mt_loo_terms(gpmi_ctx* c, int kernel, const double* theta, int n_theta,
   if (!c) return GPMI_ERR_ARG;
   if (int rc = mt_check(c, "gpmi_mt_loo_terms")) return rc;
   CovParams p;
+  NO_PERIODIC(c, kernel);
   if (int rc = make_cov(c, kernel, theta, n_theta, extra_diag, p)) return rc;
   ARGCHK(c, a2_host && ikdiag_host, "a2_host / ikdiag_host is NULL");
   if (int rc = set_device(c)) return rc;

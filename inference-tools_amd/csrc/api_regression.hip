@@ -650,8 +650,8 @@ int gpmi_spatial_derivatives(gpmi_ctx* c, const double* pts, int64_t m, double* 
   ARGCHK(c, c->fitted, "gpmi_spatial_derivatives needs a successful gpmi_fit");
   ARGCHK(c, c->fit_params.kernel >= 0 || c->mix_nk > 0,
          "gpmi_spatial_derivatives: the model was fitted with a caller-built covariance (gpmi_fit_dense) - use gpmi_predict_dense / gpmi_solve_rows");
-  ARGCHK(c, c->fit_params.kernel == GPMI_KERNEL_SE || kernel_is_matern(c->fit_params.kernel),
-         "spatial derivatives: SquaredExponential, Matern32 and Matern52 only (not sums of kernels)");
+  ARGCHK(c, c->fit_params.kernel == GPMI_KERNEL_SE || c->fit_params.kernel == GPMI_KERNEL_PER || kernel_is_matern(c->fit_params.kernel),
+         "spatial derivatives: SquaredExponential, Matern32, Matern52 and Periodic only (not sums of kernels)");
   ARGCHK(c, pts && m > 0 && dmu_out && dvar_out, "NULL argument or m <= 0");
   if (int rc = set_device(c)) return rc;
   Lane& L = c->lanes[0];
@@ -687,8 +687,8 @@ int gpmi_gradient(gpmi_ctx* c, const double* pts, int64_t m, double* gmu_out, do
   ARGCHK(c, c->fitted, "gpmi_gradient needs a successful gpmi_fit");
   ARGCHK(c, c->fit_params.kernel >= 0 || c->mix_nk > 0,
          "gpmi_gradient: the model was fitted with a caller-built covariance (gpmi_fit_dense) - use gpmi_predict_dense / gpmi_solve_rows");
-  ARGCHK(c, c->fit_params.kernel == GPMI_KERNEL_SE || kernel_is_matern(c->fit_params.kernel),
-         "gradient: SquaredExponential, Matern32 and Matern52 only (not sums of kernels)");
+  ARGCHK(c, c->fit_params.kernel == GPMI_KERNEL_SE || c->fit_params.kernel == GPMI_KERNEL_PER || kernel_is_matern(c->fit_params.kernel),
+         "gradient: SquaredExponential, Matern32, Matern52 and Periodic only (not sums of kernels)");
   ARGCHK(c, pts && m > 0 && gmu_out && gcov_out, "NULL argument or m <= 0");
   if (int rc = set_device(c)) return rc;
   Lane& L = c->lanes[0];

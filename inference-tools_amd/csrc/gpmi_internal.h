@@ -21,15 +21,38 @@ typedef double d4_t __attribute__((ext_vector_type(4)));
 
 static inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
-// Hyper-parameters of one covariance evaluation, passed by value as a kernel argument.
+// Hyper-parameters of one covariance evaluation, passed by value as a kernel argument.  Its size and the offsets of its
+// fields are fixed (544 bytes: the lockstep staging, the sparse model's schedule and its documented bytes per problem count
+// on them), so the Periodic kernel's own parameters live in fields the other kernels leave unused: the periodic
+// dimensions as a bit mask in the place of RQ's kappa, and 1 / p_j of the j-th periodic dimension (ascending) in
+// inv_l2[d + j] - which is why that kernel asks for d + n_per <= GPMI_MAX_D.
 struct KParams {
-  int kernel;                 // GPMI_KERNEL_SE / _RQ / _M32 / _M52
+  int kernel;                 // GPMI_KERNEL_SE / _RQ / _M32 / _M52 / _PER
   int d;                      // spatial dimensions
   double a2;                  // exp(theta0)^2
-  double kappa;               // RQ: exp(theta1)
+  union {
+    double kappa;                 // RQ: exp(theta1)
+    unsigned long long per_mask;  // Periodic: bit k set - dimension k is periodic
+  };
   double extra_diag;          // WhiteNoise variance added to the diagonal
-  double inv_l2[GPMI_MAX_D];  // 1 / l_k^2
+  double inv_l2[GPMI_MAX_D];  // 1 / l_k^2; Periodic: behind the d of them, 1 / p_j
 };
+static_assert(sizeof(KParams) == 32 + 8 * GPMI_MAX_D, "KParams keeps its layout");
+
+// Whether dimension k of a Periodic kernel is one of its periodic dimensions, and then *ip = 1 / p of it (which may be 0:
+// a period that overflowed).  *cursor counts the periodic dimensions met as k ascends (start it at 0): one bit test per
+// dimension, everything uniform over the workgroup.
+__host__ __device__ inline bool periodic_dim(const KParams& p, int k, int* cursor, double* ip) {
+  if (!((p.per_mask >> k) & 1ull)) return false;
+  *ip = p.inv_l2[p.d + (*cursor)++];
+  return true;
+}
+// the same for one dimension on its own (the predictive-gradient kernels: one dimension per row or per pass)
+__host__ __device__ inline bool periodic_dim(const KParams& p, int k, double* ip) {
+  if (!((p.per_mask >> k) & 1ull)) return false;
+  *ip = p.inv_l2[p.d + __builtin_popcountll(p.per_mask & ((1ull << k) - 1ull))];
+  return true;
+}
 
 // The stationary kernels one KParams can describe, and the number of parameters each has in front of its length scales
 // (ln a; RQ: ln a, ln kappa).  One explicit decision per id: "not SE" does not mean RQ.  -1: not such a kernel.
@@ -59,7 +82,7 @@ inline bool with_stationary_kernel(int kernel, F&& f) {
   }
 }
 
-// A covariance evaluation the entry points hold: one stationary kernel (the KParams base, nk = 0), or a sum of nk = 2..4 of
+// A covariance evaluation the entry points hold: one stationary or Periodic kernel (the KParams base, nk = 0), or a sum of nk = 2..4 of
 // them (GPMI_KERNEL_SUM, gpmi_set_sum).  For a sum the base carries kernel = GPMI_KERNEL_SUM, d, a2 = sum_m a_m^2 (the
 // prior variance of a query point, regression.py:210) and the WhiteNoise variance; comp[m] are the components' own
 // parameters (extra_diag 0).  The launchers of kbuild.hip / grad.hip have CovParams overloads, which launch the fused
@@ -72,6 +95,13 @@ struct CovParams : KParams {
   CovParams() : KParams{} {}
   explicit CovParams(const KParams& k) : KParams(k) {}
 };
+
+// a kernel argument: HIP documents 4 KB as the limit of a launch's arguments
+static_assert(sizeof(CovParams) <= 4096, "CovParams is passed by value to the sum kernels");
+// The kinds a KParams can describe on the builders, the gradient contraction and the lockstep entry points: the
+// stationary kernels and GPMI_KERNEL_PER.  (kernel_is_stationary stays the test of the sparse model, the selection and the
+// Hessian, which do not take the Periodic kernel.)
+__host__ __device__ inline bool kernel_is_single(int kernel) { return kernel_is_stationary(kernel) || kernel == GPMI_KERNEL_PER; }
 
 struct gpmi_ctx;
 
@@ -347,6 +377,8 @@ struct gpmi_ctx : DataBufs, QueryBufs, BatchBufs, MixBufs, MultiBufs, HessBufs, 
   CovParams fit_params;
   int sum_nk = 0;                   // gpmi_set_sum: components of this handle's GPMI_KERNEL_SUM (0: none declared)
   int sum_kinds[GPMI_MAX_SUM] = {};
+  int n_per = 0;                    // gpmi_set_periodic: periodic dimensions of this handle's GPMI_KERNEL_PER (0: none declared)
+  int per_dim[GPMI_MAX_PERIODIC] = {};
   DevBuf<double> trsm_panel;  // rows x 544 scratch of the in-place many-right-hand-side solve
   PinBuf<char> h_stage;       // host staging of the lockstep chunks (RowStage)
   // asynchronous lockstep batches (gpmi_lml_batch_submit / _wait): two slots = the two halves of the workspace, on the
@@ -487,7 +519,7 @@ void launch_lml_grad(hipStream_t s, const CovParams& p, int n_theta, const doubl
                      double* ws, double* out);
 void launch_lml_grad_batched(hipStream_t s, const CovParams* pdev, int batch, int n_theta, const double* x, int64_t n,
                              int64_t np, const double* iK, int64_t ld, int64_t sK, const double* u, const double* v,
-                             int64_t sV, double* ws, double* out, int d);
+                             int64_t sV, double* ws, double* out, int d, bool has_periodic);
 void launch_mirror_lower(hipStream_t s, double* A, int64_t ld, int64_t np, int batch = 1, int64_t sMat = 0);
 // (batch > 1: problem z works on A / G + z sMat and on vectors sVec (sAlpha, sLoo) apart)
 void launch_scale_columns(hipStream_t s, const double* A, const double* sc, double* G, int64_t ld,

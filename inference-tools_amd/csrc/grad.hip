@@ -32,6 +32,8 @@ __device__ inline double block_sum(double v, double* red) {
   return red[0] + red[1] + red[2] + red[3];
 }
 
+constexpr int GRAD_SE_RQ = 0, GRAD_MATERN = 1, GRAD_PERIODIC = 2;
+
 // Matern value and derivative profiles of one element (kmath.h: matern_profile has the formulas): C and g at
 // s = 1/2 sum_k dx_k^2 / l_k^2, with the library's exp as in the SE / RQ branches of the contraction
 __device__ __forceinline__ void matern_cg(bool m32, double s, double& C, double& g) {
@@ -42,27 +44,32 @@ __device__ __forceinline__ void matern_cg(bool m32, double s, double& C, double&
   g = m32 ? 3.0 * e : (5.0 / 3.0) * ((1.0 + t) * e);
 }
 
-// MATERN: the Matern kernels have an instantiation of their own, so that SE / RQ run the code they ran before these
-// were added.
+// KIND: GRAD_SE_RQ, GRAD_MATERN or GRAD_PERIODIC - the Matern kernels and the Periodic kernel have instantiations of
+// their own, so that SE / RQ run the code they ran before these were added.
+// Periodic (GPMI_KERNEL_PER), with u_k = dx_k / p_k and K = a^2 exp(-sum_k w_k / l_k^2):
+//   dK/d ln l_k = 2 K w_k / l_k^2 (plain k: K dx_k^2 / l_k^2, SE's; periodic k: K 4 sin^2(pi u_k) / l_k^2)
+//   dK/d ln p_k = K 2 pi u_k sin(2 pi u_k) / l_k^2
+// partials laid out as theta is: [ln a, ln l_1 .. ln l_d, ln p_j for the periodic dimensions j ascending, trace].  The
+// library's sinpi / cospi here (exact reduction for any u): the contraction is bound by reading K^-1.
 // batch (blockIdx.z, lockstep evaluations of gpmi_lml_grad_batch): problem z takes pdev[z], iK + z sK, u / v + z sV,
 // ws + z sW
-template <bool MATERN>
+template <int KIND>
 __device__ __forceinline__ void lml_grad_body(const KParams& p, int n_theta, const double* __restrict__ x, int64_t n,
                                               const double* __restrict__ iK, int64_t ld,
                                               const double* __restrict__ uvec, const double* __restrict__ vvec,
                                               double* __restrict__ ws);
 
-template <bool MATERN>
+template <int KIND>
 __global__ __launch_bounds__(256) void lml_grad_kernel(KParams p, int n_theta,
                                                        const double* __restrict__ x, int64_t n,
                                                        const double* __restrict__ iK, int64_t ld,
                                                        const double* __restrict__ uvec,
                                                        const double* __restrict__ vvec,
                                                        double* __restrict__ ws) {
-  lml_grad_body<MATERN>(p, n_theta, x, n, iK, ld, uvec, vvec, ws);
+  lml_grad_body<KIND>(p, n_theta, x, n, iK, ld, uvec, vvec, ws);
 }
 
-template <bool MATERN>
+template <int KIND>
 __global__ __launch_bounds__(256) void lml_grad_batched_kernel(const KParams* __restrict__ pdev, int n_theta,
                                                                const double* __restrict__ x, int64_t n,
                                                                const double* __restrict__ iK, int64_t ld,
@@ -70,10 +77,10 @@ __global__ __launch_bounds__(256) void lml_grad_batched_kernel(const KParams* __
                                                                const double* __restrict__ vvec, double* __restrict__ ws,
                                                                int64_t sK, int64_t sV, int64_t sW) {
   const int64_t z = blockIdx.z;
-  lml_grad_body<MATERN>(pdev[z], n_theta, x, n, iK + z * sK, ld, uvec + z * sV, vvec + z * sV, ws + z * sW);
+  lml_grad_body<KIND>(pdev[z], n_theta, x, n, iK + z * sK, ld, uvec + z * sV, vvec + z * sV, ws + z * sW);
 }
 
-template <bool MATERN>
+template <int KIND>
 __device__ __forceinline__ void lml_grad_body(const KParams& p, int n_theta, const double* __restrict__ x, int64_t n,
                                               const double* __restrict__ iK, int64_t ld,
                                               const double* __restrict__ uvec, const double* __restrict__ vvec,
@@ -98,14 +105,21 @@ __device__ __forceinline__ void lml_grad_body(const KParams& p, int n_theta, con
   for (int r = 0; r < 4; ++r)
 #pragma unroll
     for (int c = 0; c < 4; ++c) s[r][c] = 0.0;
-  for (int k = 0; k < d; ++k) {
+  for (int k = 0, cursor = 0; k < d; ++k) {
     const double il2 = p.inv_l2[k];
+    double ip = 0.0;
+    const bool periodic = KIND == GRAD_PERIODIC && periodic_dim(p, k, &cursor, &ip);
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const double dx = su[k * KT + ty * 4 + r] - sv[k * KT + tx * 4 + c];
-        s[r][c] = fma(0.5 * dx * dx, il2, s[r][c]);
+        if (periodic) {
+          const double sn = sinpi(dx * ip);
+          s[r][c] = fma(2.0 * sn * sn, il2, s[r][c]);
+        } else {
+          s[r][c] = fma(0.5 * dx * dx, il2, s[r][c]);
+        }
       }
   }
   // wk = 1/2 * multiplicity * Q_ab * (factor multiplying dx_k^2 / l_k^2 in dK_{scale k})
@@ -126,7 +140,12 @@ __device__ __forceinline__ void lml_grad_body(const KParams& p, int n_theta, con
         if (ga == gb) tq += q;
       }
       const double z = s[r][c];
-      if (MATERN) {
+      if (KIND == GRAD_PERIODIC) {
+        double K = p.a2 * exp(-z);
+        if (ga == gb) K = p.a2 * (exp(-z) + 1e-12);
+        g_amp = fma(w, 2.0 * K, g_amp);   // dK/d ln a = 2 K
+        wk[r][c] = w * K;                 // dK/d ln l_k, dK/d ln p_k = K x (a factor of dx_k alone)
+      } else if (KIND == GRAD_MATERN) {
         double C, g;
         matern_cg(p.kernel == GPMI_KERNEL_M32, z, C, g);
         double K = p.a2 * C;
@@ -151,7 +170,8 @@ __device__ __forceinline__ void lml_grad_body(const KParams& p, int n_theta, con
   }
   const int64_t tile = (int64_t)ti * (ti + 1) / 2 + tj;
   double* out = ws + tile * (n_theta + 1);
-  const int off = MATERN ? 1 : (p.kernel == GPMI_KERNEL_SE) ? 1 : 2;  // SE, Matern: [ln a, ln l]; RQ: [ln a, ln kappa, ln l]
+  // SE, Matern, Periodic: [ln a, ln l]; RQ: [ln a, ln kappa, ln l]
+  const int off = KIND != GRAD_SE_RQ ? 1 : (p.kernel == GPMI_KERNEL_SE) ? 1 : 2;
   double v = block_sum(g_amp, red);
   if (tid == 0) out[0] = v;
   if (off == 2) {
@@ -160,18 +180,30 @@ __device__ __forceinline__ void lml_grad_body(const KParams& p, int n_theta, con
   }
   v = block_sum(tq, red);
   if (tid == 0) out[n_theta] = v;
-  for (int k = 0; k < d; ++k) {
+  for (int k = 0, cursor = 0; k < d; ++k) {
     const double il2 = p.inv_l2[k];
-    double acc = 0.0;
+    double ip = 0.0;
+    const bool periodic = KIND == GRAD_PERIODIC && periodic_dim(p, k, &cursor, &ip);
+    double acc = 0.0, acc_p = 0.0;
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const double dx = su[k * KT + ty * 4 + r] - sv[k * KT + tx * 4 + c];
-        acc = fma(wk[r][c], dx * dx * il2, acc);
+        if (periodic) {
+          const double u = dx * ip, sn = sinpi(u), cs = cospi(u);
+          acc = fma(wk[r][c], 4.0 * sn * sn * il2, acc);                                      // 2 w_k / l_k^2
+          acc_p = fma(wk[r][c], (2.0 * M_PI) * u * (2.0 * sn * cs) * il2, acc_p);             // 2 pi u sin(2 pi u) / l_k^2
+        } else {
+          acc = fma(wk[r][c], dx * dx * il2, acc);
+        }
       }
     v = block_sum(acc, red);
     if (tid == 0) out[off + k] = v;
+    if (periodic) {  // (uniform) ln p of this dimension: behind the d length scales, in the order of the declaration
+      v = block_sum(acc_p, red);
+      if (tid == 0) out[off + d + cursor - 1] = v;
+    }
   }
 }
 
@@ -244,6 +276,10 @@ __global__ void loo_vectors_kernel(const double* __restrict__ alpha, const doubl
 // (the partials of lml_grad_body, with the component's own parameters).  One partial per tile and parameter, laid out
 // [component 1's parameters, ..., component nk's parameters, trace]; the components' weight arrays are held one at a
 // time (wk reuses the registers of s), so a sum costs the kernel no occupancy beyond the 16 weights of Q.
+// HAS_PER: a sum with a Periodic component has an instantiation of its own (the sinpi / cospi of that branch cost the
+// kernel 42 VGPRs and a wave of occupancy), so that the sums of SE / RQ / Matern components keep the code and the
+// registers they had.
+template <bool HAS_PER>
 __device__ __forceinline__ void sum_grad_body(const CovParams& p, int n_theta, const double* __restrict__ x, int64_t n,
                                               const double* __restrict__ iK, int64_t ld,
                                               const double* __restrict__ uvec, const double* __restrict__ vvec,
@@ -292,23 +328,31 @@ __device__ __forceinline__ void sum_grad_body(const CovParams& p, int n_theta, c
   const int nk = __builtin_amdgcn_readfirstlane(p.nk);
   for (int m = 0; m < nk; ++m) {
     const KParams& q = p.comp[m];
-    // (make_cov admits four kinds: SE, RQ, Matern32, Matern52; only RQ has a shape parameter)
+    // (make_cov admits five kinds: SE, RQ, Matern32, Matern52, Periodic; only RQ has a shape parameter)
     const int kind = __builtin_amdgcn_readfirstlane(q.kernel);
     const bool rq = (kind == GPMI_KERNEL_RQ);
     const bool matern = (kind == GPMI_KERNEL_M32 || kind == GPMI_KERNEL_M52);
+    const bool per = HAS_PER && (kind == GPMI_KERNEL_PER);  // (K and the weights as SE's, of the warped s; partials as lml_grad_body's)
     double s[4][4];
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
       for (int c = 0; c < 4; ++c) s[r][c] = 0.0;
-    for (int k = 0; k < d; ++k) {
+    for (int k = 0, cursor = 0; k < d; ++k) {
       const double il2 = q.inv_l2[k];
+      double ip = 0.0;
+      const bool periodic = per && periodic_dim(q, k, &cursor, &ip);
 #pragma unroll
       for (int r = 0; r < 4; ++r)
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           const double dx = su[k * KT + ty * 4 + r] - sv[k * KT + tx * 4 + c];
-          s[r][c] = fma(0.5 * dx * dx, il2, s[r][c]);
+          if (periodic) {
+            const double sn = sinpi(dx * ip);
+            s[r][c] = fma(2.0 * sn * sn, il2, s[r][c]);
+          } else {
+            s[r][c] = fma(0.5 * dx * dx, il2, s[r][c]);
+          }
         }
     }
     double g_amp = 0.0, g_shape = 0.0;
@@ -350,30 +394,45 @@ __device__ __forceinline__ void sum_grad_body(const CovParams& p, int n_theta, c
       if (tid == 0) out[off + 1] = v;
     }
     const int lo = off + (rq ? 2 : 1);
+    int cursor = 0;
     for (int k = 0; k < d; ++k) {
       const double il2 = q.inv_l2[k];
-      double acc = 0.0;
+      double ip = 0.0;
+      const bool periodic = per && periodic_dim(q, k, &cursor, &ip);
+      double acc = 0.0, acc_p = 0.0;
 #pragma unroll
       for (int r = 0; r < 4; ++r)
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           const double dx = su[k * KT + ty * 4 + r] - sv[k * KT + tx * 4 + c];
-          acc = fma(s[r][c], dx * dx * il2, acc);
+          if (periodic) {
+            const double u = dx * ip, sn = sinpi(u), cs = cospi(u);
+            acc = fma(s[r][c], 4.0 * sn * sn * il2, acc);
+            acc_p = fma(s[r][c], (2.0 * M_PI) * u * (2.0 * sn * cs) * il2, acc_p);
+          } else {
+            acc = fma(s[r][c], dx * dx * il2, acc);
+          }
         }
       v = block_sum(acc, red);
       if (tid == 0) out[lo + k] = v;
+      if (periodic) {
+        v = block_sum(acc_p, red);
+        if (tid == 0) out[lo + d + cursor - 1] = v;
+      }
     }
-    off = lo + d;
+    off = lo + d + cursor;  // (a Periodic component: its ln p behind its length scales)
   }
 }
 
+template <bool HAS_PER>
 __global__ __launch_bounds__(256) void sum_grad_kernel(CovParams p, int n_theta, const double* __restrict__ x,
                                                        int64_t n, const double* __restrict__ iK, int64_t ld,
                                                        const double* __restrict__ uvec,
                                                        const double* __restrict__ vvec, double* __restrict__ ws) {
-  sum_grad_body(p, n_theta, x, n, iK, ld, uvec, vvec, ws);
+  sum_grad_body<HAS_PER>(p, n_theta, x, n, iK, ld, uvec, vvec, ws);
 }
 
+template <bool HAS_PER>
 __global__ __launch_bounds__(256) void sum_grad_batched_kernel(const CovParams* __restrict__ pdev, int n_theta,
                                                                const double* __restrict__ x, int64_t n,
                                                                const double* __restrict__ iK, int64_t ld,
@@ -381,7 +440,7 @@ __global__ __launch_bounds__(256) void sum_grad_batched_kernel(const CovParams* 
                                                                const double* __restrict__ vvec, double* __restrict__ ws,
                                                                int64_t sK, int64_t sV, int64_t sW) {
   const int64_t z = blockIdx.z;
-  sum_grad_body(pdev[z], n_theta, x, n, iK + z * sK, ld, uvec + z * sV, vvec + z * sV, ws + z * sW);
+  sum_grad_body<HAS_PER>(pdev[z], n_theta, x, n, iK + z * sK, ld, uvec + z * sV, vvec + z * sV, ws + z * sW);
 }
 
 }  // namespace
@@ -413,13 +472,15 @@ int64_t grad_ws_doubles(int64_t np, int n_theta) {
 void launch_lml_grad(hipStream_t s, const KParams& p, int n_theta, const double* x, int64_t n,
                      int64_t np, const double* iK, int64_t ld, const double* u, const double* v,
                      double* ws, double* out) {
-  assert(kernel_is_stationary(p.kernel) && "a sum of kernels must be passed as a CovParams");
+  assert(kernel_is_single(p.kernel) && "a sum of kernels must be passed as a CovParams");
   const int64_t t = np / KT;
   dim3 grid((unsigned)t, (unsigned)t);
-  if (kernel_is_matern(p.kernel))
-    hipLaunchKernelGGL(lml_grad_kernel<true>, grid, dim3(256), 0, s, p, n_theta, x, n, iK, ld, u, v, ws);
+  if (p.kernel == GPMI_KERNEL_PER)
+    hipLaunchKernelGGL(lml_grad_kernel<GRAD_PERIODIC>, grid, dim3(256), 0, s, p, n_theta, x, n, iK, ld, u, v, ws);
+  else if (kernel_is_matern(p.kernel))
+    hipLaunchKernelGGL(lml_grad_kernel<GRAD_MATERN>, grid, dim3(256), 0, s, p, n_theta, x, n, iK, ld, u, v, ws);
   else
-    hipLaunchKernelGGL(lml_grad_kernel<false>, grid, dim3(256), 0, s, p, n_theta, x, n, iK, ld, u, v, ws);
+    hipLaunchKernelGGL(lml_grad_kernel<GRAD_SE_RQ>, grid, dim3(256), 0, s, p, n_theta, x, n, iK, ld, u, v, ws);
   hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)(n_theta + 1)), dim3(256), 0, s, ws,
                      t * (t + 1) / 2, n_theta + 1, out, (int64_t)0);
 }
@@ -434,7 +495,12 @@ void launch_lml_grad(hipStream_t s, const CovParams& p, int n_theta, const doubl
   }
   const int64_t t = np / KT;
   dim3 grid((unsigned)t, (unsigned)t);
-  hipLaunchKernelGGL(sum_grad_kernel, grid, dim3(256), sum_grad_lds_bytes(p.d), s, p, n_theta, x, n, iK, ld, u, v, ws);
+  bool has_per = false;
+  for (int m = 0; m < p.nk; ++m) has_per = has_per || p.comp[m].kernel == GPMI_KERNEL_PER;
+  if (has_per)
+    hipLaunchKernelGGL(sum_grad_kernel<true>, grid, dim3(256), sum_grad_lds_bytes(p.d), s, p, n_theta, x, n, iK, ld, u, v, ws);
+  else
+    hipLaunchKernelGGL(sum_grad_kernel<false>, grid, dim3(256), sum_grad_lds_bytes(p.d), s, p, n_theta, x, n, iK, ld, u, v, ws);
   hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)(n_theta + 1)), dim3(256), 0, s, ws,
                      t * (t + 1) / 2, n_theta + 1, out, (int64_t)0);
 }
@@ -444,29 +510,37 @@ void launch_lml_grad(hipStream_t s, const CovParams& p, int n_theta, const doubl
 void launch_lml_grad_batched(hipStream_t s, int kernel, const KParams* pdev, int batch, int n_theta, const double* x,
                              int64_t n, int64_t np, const double* iK, int64_t ld, int64_t sK, const double* u,
                              const double* v, int64_t sV, double* ws, double* out) {
-  assert(kernel_is_stationary(kernel) && "a batch of sums is an array of CovParams");
+  assert(kernel_is_single(kernel) && "a batch of sums is an array of CovParams");
   const int64_t t = np / KT;
   const int64_t sW = grad_ws_doubles(np, n_theta);
   dim3 grid((unsigned)t, (unsigned)t, (unsigned)batch);
-  if (kernel_is_matern(kernel))
-    hipLaunchKernelGGL(lml_grad_batched_kernel<true>, grid, dim3(256), 0, s, pdev, n_theta, x, n, iK, ld, u, v, ws, sK, sV,
-                       sW);
+  if (kernel == GPMI_KERNEL_PER)
+    hipLaunchKernelGGL(lml_grad_batched_kernel<GRAD_PERIODIC>, grid, dim3(256), 0, s, pdev, n_theta, x, n, iK, ld, u, v, ws,
+                       sK, sV, sW);
+  else if (kernel_is_matern(kernel))
+    hipLaunchKernelGGL(lml_grad_batched_kernel<GRAD_MATERN>, grid, dim3(256), 0, s, pdev, n_theta, x, n, iK, ld, u, v, ws, sK,
+                       sV, sW);
   else
-    hipLaunchKernelGGL(lml_grad_batched_kernel<false>, grid, dim3(256), 0, s, pdev, n_theta, x, n, iK, ld, u, v, ws, sK, sV,
-                       sW);
+    hipLaunchKernelGGL(lml_grad_batched_kernel<GRAD_SE_RQ>, grid, dim3(256), 0, s, pdev, n_theta, x, n, iK, ld, u, v, ws, sK,
+                       sV, sW);
   hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)(n_theta + 1), 1, (unsigned)batch), dim3(256), 0, s, ws,
                      t * (t + 1) / 2, n_theta + 1, out, sW);
 }
 
-// a batch of sums (every pdev[z] of kind GPMI_KERNEL_SUM, d spatial dimensions)
+// a batch of sums (every pdev[z] of kind GPMI_KERNEL_SUM, d spatial dimensions; has_periodic: a component of the
+// handle's sum is GPMI_KERNEL_PER)
 void launch_lml_grad_batched(hipStream_t s, const CovParams* pdev, int batch, int n_theta, const double* x, int64_t n,
                              int64_t np, const double* iK, int64_t ld, int64_t sK, const double* u, const double* v,
-                             int64_t sV, double* ws, double* out, int d) {
+                             int64_t sV, double* ws, double* out, int d, bool has_periodic) {
   const int64_t t = np / KT;
   const int64_t sW = grad_ws_doubles(np, n_theta);
   dim3 grid((unsigned)t, (unsigned)t, (unsigned)batch);
-  hipLaunchKernelGGL(sum_grad_batched_kernel, grid, dim3(256), sum_grad_lds_bytes(d), s, pdev, n_theta, x, n, iK, ld, u, v,
-                     ws, sK, sV, sW);
+  if (has_periodic)
+    hipLaunchKernelGGL(sum_grad_batched_kernel<true>, grid, dim3(256), sum_grad_lds_bytes(d), s, pdev, n_theta, x, n, iK, ld, u,
+                       v, ws, sK, sV, sW);
+  else
+    hipLaunchKernelGGL(sum_grad_batched_kernel<false>, grid, dim3(256), sum_grad_lds_bytes(d), s, pdev, n_theta, x, n, iK, ld, u,
+                       v, ws, sK, sV, sW);
   hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)(n_theta + 1), 1, (unsigned)batch), dim3(256), 0, s, ws,
                      t * (t + 1) / 2, n_theta + 1, out, sW);
 }

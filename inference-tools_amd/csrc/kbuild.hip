@@ -1,4 +1,4 @@
-// Covariance-matrix build for SquaredExponential / RationalQuadratic / Matern32 / Matern52 on gfx950.
+// Covariance-matrix build for SquaredExponential / RationalQuadratic / Matern32 / Matern52 / Periodic on gfx950.
 //
 // Replaces the reference's N x N x d broadcast tensors (covariance.py:218-219, 254, 315-316, 347)
 // by a tiled kernel: a workgroup stages the two 64-point panels in LDS (transposed, [dim][point]) and
@@ -87,8 +87,20 @@ __device__ inline void kbuild_body(const KParams& p, const double* __restrict__ 
   __syncthreads();
   const int ty = pair_tile::thread_row(tid), tx = pair_tile::thread_col(tid);
   double s[4][4];  // s, then the covariance function of it
-  pair_tile::accumulate_s(p.inv_l2, d, su, sv, ty, tx, s);
-  pair_tile::for_each_profile<KERNEL, false>(p, s, [&](int r, int c, double C) { s[r][c] = C; });
+  if constexpr (KERNEL == GPMI_KERNEL_PER) {
+    // the warped distance and its exp half by half: sinpi_sq and exp_neg each hold eight elements' temporaries
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      double s8[8], C8[8];
+      pair_tile::accumulate_s_periodic<2>(p, d, su, sv, ty, tx, 2 * h, s8);
+      kfun<GPMI_KERNEL_PER>(p, s8, C8);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) s[2 * h + (i >> 2)][i & 3] = C8[i];
+    }
+  } else {
+    pair_tile::accumulate_s(p.inv_l2, d, su, sv, ty, tx, s);
+    pair_tile::for_each_profile<KERNEL, false>(p, s, [&](int r, int c, double C) { s[r][c] = C; });
+  }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int64_t gi = i0 + ty * 4 + r;
@@ -133,7 +145,7 @@ __global__ void add_full_kernel(double* __restrict__ A, int64_t ld, const double
 // accumulates s_m = sum_k 1/2 dx_k^2 / l_{m,k}^2 with that component's length scales and applies its covariance function
 // (kfun, the same lockstep exp / log1p as the single-kernel build), summing in component order - the order of the
 // reference's sum(...) (covariance.py:94-98).  The component's kind is a uniform run-time branch (one per component and
-// half-block), not a template parameter: one kernel serves every combination of two to four SE / RQ / Matern components instead
+// half-block), not a template parameter: one kernel serves every combination of two to four SE / RQ / Matern / Periodic components instead
 // of one instantiation each competing for the instruction cache.  The choice rests on that code size: a per-combination
 // instantiation was not built or timed.  Timings of this form: DESIGN.md (kernel table) and tools/sum_time.py.
 // ksum_body is force-inlined: used by two kernels, the compiler otherwise made it a called function, and the batched
@@ -182,24 +194,29 @@ __device__ __forceinline__ void ksum_body(const CovParams& p, const double* __re
     for (int m = 0; m < nk; ++m) {
       const KParams& q = p.comp[m];
       double sv8[8], cf8[8];
+      const int kind = __builtin_amdgcn_readfirstlane(q.kernel);
+      if (kind == GPMI_KERNEL_PER) {  // the component's warped distance (pair_tile.h)
+        pair_tile::accumulate_s_periodic<2>(q, d, su, sv, ty, tx, 2 * h, sv8);
+      } else {
 #pragma unroll
-      for (int i = 0; i < 8; ++i) sv8[i] = 0.0;
-      for (int k = 0; k < d; ++k) {
-        const double il2 = q.inv_l2[k];
-        double ur[2], vc[4];
+        for (int i = 0; i < 8; ++i) sv8[i] = 0.0;
+        for (int k = 0; k < d; ++k) {
+          const double il2 = q.inv_l2[k];
+          double ur[2], vc[4];
 #pragma unroll
-        for (int r = 0; r < 2; ++r) ur[r] = su[k * KT + ty * 4 + 2 * h + r];
+          for (int r = 0; r < 2; ++r) ur[r] = su[k * KT + ty * 4 + 2 * h + r];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) vc[c] = sv[k * KT + tx * 4 + c];
+          for (int c = 0; c < 4; ++c) vc[c] = sv[k * KT + tx * 4 + c];
 #pragma unroll
-        for (int r = 0; r < 2; ++r)
+          for (int r = 0; r < 2; ++r)
 #pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            double dx = ur[r] - vc[c];
-            sv8[4 * r + c] = fma(0.5 * dx * dx, il2, sv8[4 * r + c]);
-          }
+            for (int c = 0; c < 4; ++c) {
+              double dx = ur[r] - vc[c];
+              sv8[4 * r + c] = fma(0.5 * dx * dx, il2, sv8[4 * r + c]);
+            }
+        }
       }
-      switch (__builtin_amdgcn_readfirstlane(q.kernel)) {  // (make_cov admits these four kinds only)
+      switch (kind) {  // (make_cov admits these five kinds only; Periodic: SE's exp of its own s)
         case GPMI_KERNEL_RQ: kfun<GPMI_KERNEL_RQ>(q, sv8, cf8); break;
         case GPMI_KERNEL_M32: kfun<GPMI_KERNEL_M32>(q, sv8, cf8); break;
         case GPMI_KERNEL_M52: kfun<GPMI_KERNEL_M52>(q, sv8, cf8); break;
@@ -273,10 +290,21 @@ static size_t kb_lds_bytes(int d) { return sizeof(double) * 2 * (size_t)d * KT; 
 // dispatch on the covariance function (a template parameter of the kernels).  A KParams is one stationary kernel: a sum
 // reaches the builders only as a CovParams (the overloads below), so a KParams whose kind is GPMI_KERNEL_SUM is a sliced
 // copy - a bug of the caller.
+// The builders' own dispatch: the stationary kernels and GPMI_KERNEL_PER (with_stationary_kernel also instantiates the
+// sparse-model, selection and Hessian kernels, which do not take the Periodic kernel).
+template <class F>
+static bool with_builder_kernel(int kernel, F&& f) {
+  if (kernel == GPMI_KERNEL_PER) {
+    f(std::integral_constant<int, GPMI_KERNEL_PER>());
+    return true;
+  }
+  return with_stationary_kernel(kernel, f);
+}
+
 template <bool SQUARE>
 static void launch_kb(dim3 grid, hipStream_t s, const KParams& p, const double* U, int64_t nu, const double* V,
                       int64_t nv, const double* noise, double* out, int64_t ld, int lower_only) {
-  [[maybe_unused]] const bool ok = with_stationary_kernel(p.kernel, [&](auto K) {
+  [[maybe_unused]] const bool ok = with_builder_kernel(p.kernel, [&](auto K) {
     hipLaunchKernelGGL((kbuild_kernel<SQUARE, decltype(K)::value>), grid, dim3(256), kb_lds_bytes(p.d), s, p, U, nu, V, nv,
                        noise, out, ld, lower_only);
   });
@@ -347,7 +375,7 @@ void launch_kbuild_square_batched(hipStream_t s, int kernel, const KParams* pdev
                                   int64_t stride, int d, int64_t noise_stride) {
   const unsigned nt = (unsigned)(np / KT);
   dim3 grid(nt * (nt + 1) / 2, 1, (unsigned)batch);  // lower tiles only, one-dimensional (kbuild_body, mode 2)
-  [[maybe_unused]] const bool ok = with_stationary_kernel(kernel, [&](auto K) {
+  [[maybe_unused]] const bool ok = with_builder_kernel(kernel, [&](auto K) {
     hipLaunchKernelGGL(kbuild_batched_kernel<decltype(K)::value>, grid, dim3(256), kb_lds_bytes(d), s, pdev, x, n, noise, A,
                        ld, stride, noise_stride);
   });
@@ -390,7 +418,7 @@ void launch_kbuild_cross_batched(hipStream_t s, int kernel, const KParams* pdev,
                                  int64_t mp, const double* V, int64_t n, int64_t np, double* out, int64_t ld,
                                  int64_t stride, int d) {
   dim3 grid((unsigned)(np / KT), (unsigned)(mp / KT), (unsigned)batch);
-  [[maybe_unused]] const bool ok = with_stationary_kernel(kernel, [&](auto K) {
+  [[maybe_unused]] const bool ok = with_builder_kernel(kernel, [&](auto K) {
     hipLaunchKernelGGL(kbuild_cross_batched_kernel<decltype(K)::value>, grid, dim3(256), kb_lds_bytes(d), s, pdev, U, mu, V,
                        n, out, ld, stride);
   });

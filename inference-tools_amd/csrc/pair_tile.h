@@ -86,6 +86,51 @@ __device__ __forceinline__ void accumulate_s(const double* inv_l2, int d, const 
   }
 }
 
+// The Periodic kernel's s = sum_k w_k / l_k^2 (GPMI_KERNEL_PER) of rows r0 .. r0 + ROWS - 1 of the thread's block, into the
+// ROWS x 4 elements of s8: per dimension a uniform branch between SquaredExponential's term w_k = 1/2 dx_k^2 (the fma of
+// accumulate_s) and the warped w_k = 2 sin^2(pi dx_k / p_k), whose sin^2 goes through kmath::sinpi_sq ROWS x 4 elements
+// in lockstep.  Which dimensions are periodic is one bit test of the kernel's mask per dimension, and 1 / p_j sits behind
+// the d inverse squares (gpmi_internal.h: KParams) - scalar registers, no table in LDS (at d = 56 .. 64 the two panels
+// leave no room for one).  dx -> -dx gives the same bits (rint and |.| are even), so K is symmetric bit for bit; dx = 0
+// gives w = 0 exactly.
+template <int ROWS>
+__device__ __forceinline__ void accumulate_s_periodic(const KParams& p, int d, const double* su, const double* sv, int ty,
+                                                      int tx, int r0, double (&s8)[ROWS * 4]) {
+#pragma unroll
+  for (int i = 0; i < ROWS * 4; ++i) s8[i] = 0.0;
+  const unsigned mask_lo = __builtin_amdgcn_readfirstlane((unsigned)p.per_mask);
+  const unsigned mask_hi = __builtin_amdgcn_readfirstlane((unsigned)(p.per_mask >> 32));
+  const unsigned long long mask = ((unsigned long long)mask_hi << 32) | mask_lo;
+  int cursor = 0;
+  for (int k = 0; k < d; ++k) {
+    const double il2 = p.inv_l2[k];
+    double ur[ROWS], vc[4];
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) ur[r] = su[k * KT + ty * 4 + r0 + r];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) vc[c] = sv[k * KT + tx * 4 + c];
+    if (!((mask >> k) & 1ull)) {
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const double dx = ur[r] - vc[c];
+          s8[4 * r + c] = fma(0.5 * dx * dx, il2, s8[4 * r + c]);
+        }
+    } else {
+      const double ip = p.inv_l2[d + cursor++];
+      double u[ROWS * 4], q[ROWS * 4];
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) u[4 * r + c] = (ur[r] - vc[c]) * ip;
+      kmath::sinpi_sq(u, q);
+#pragma unroll
+      for (int i = 0; i < ROWS * 4; ++i) s8[i] = fma(2.0 * q[i], il2, s8[i]);
+    }
+  }
+}
+
 // The covariance function of the block in two halves of eight elements (rows 2h, 2h + 1): 16 at once cost occupancy, 8
 // already amortise the constants.  PROFILES: f(r, c, C, g, h) with the value and derivative profiles (kprofiles);
 // otherwise f(r, c, C) with kfun<KERNEL> alone (which also serves the kinds KFUN_M32_G / KFUN_M52_G).  f may overwrite

@@ -303,9 +303,14 @@ class GpEngine(_DeviceCommMixin, _DrawsMixin):
         return mu, cov
 
     def set_sum(self, kernels):
-        """gpmi_set_sum: the components (GPMI_KERNEL_SE / _RQ ids, in order) of this handle's GPMI_KERNEL_SUM."""
+        """gpmi_set_sum: the components (GPMI_KERNEL_SE / _RQ / _M32 / _M52 / _PER ids, in order) of this handle's GPMI_KERNEL_SUM."""
         ks = np.ascontiguousarray(kernels, dtype=np.int32)
         self.h.call("gpmi_set_sum", int(ks.size), ks.ctypes.data_as(C.POINTER(C.c_int)))
+
+    def set_periodic(self, dims):
+        """gpmi_set_periodic: the dimensions (strictly ascending) in which this handle's GPMI_KERNEL_PER is periodic."""
+        ds = np.ascontiguousarray(dims, dtype=np.int32)
+        self.h.call("gpmi_set_periodic", int(ds.size), ds.ctypes.data_as(C.POINTER(C.c_int)))
 
     def set_noise(self, noise_var):
         self.h.call("gpmi_set_noise", dptr(as_f64(noise_var)))

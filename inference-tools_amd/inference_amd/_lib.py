@@ -23,6 +23,8 @@ KERNEL_RQ = 1
 KERNEL_SUM = 2  # GPMI_KERNEL_SUM: a sum of stationary kernels declared by gpmi_set_sum
 KERNEL_M32 = 3  # GPMI_KERNEL_M32 / _M52: Matern 3/2 and 5/2, theta laid out as for SE
 KERNEL_M52 = 4
+KERNEL_PER = 5  # GPMI_KERNEL_PER: periodic in the dimensions declared by gpmi_set_periodic, SE in the others
+MAX_PERIODIC = 8  # GPMI_MAX_PERIODIC
 PROF_KBUILD, PROF_SYRK, PROF_PANEL, PROF_SOLVE, PROF_SYRK_REST, PROF_TRSM, PROF_SYRK_SLICE, PROF_FLOW = 0, 1, 2, 3, 4, 5, 6, 7
 PROF_COV = 8  # GPMI_PROF_COV: the kernels of gpmi_cov_columns without the copies
 OPT_LOCKSTEP_ALWAYS, OPT_RESERVE_POINTS, OPT_NO_FLOW = 1, 2, 3
@@ -104,6 +106,7 @@ SIGNATURES = {
     "gpmi_posterior_mix": (C.c_int, [_vp, _dp, _i64, _dp, _dp, _dp]),
     "gpmi_set_noise": (C.c_int, [_vp, _dp]),
     "gpmi_set_sum": (C.c_int, [_vp, C.c_int, _ip]),
+    "gpmi_set_periodic": (C.c_int, [_vp, C.c_int, _ip]),
     "gpmi_lml_grad_qdiag": (C.c_int, [_vp, _dp]),
     "gpmi_linv_set": (C.c_int, [_vp, _dp, _i64, _dp, _dp]),
     "gpmi_linv_lml": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double, _dp, _dp, _ip]),

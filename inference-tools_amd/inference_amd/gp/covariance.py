@@ -117,7 +117,12 @@ class _StationaryDeviceKernel(CovarianceFunction):
             from inference_amd._engine import GpEngine
 
             self._engine = GpEngine(self.x, np.zeros(self.x.shape[0]))
+            self._declare(self._engine)
         return self._engine
+
+    def _declare(self, engine):
+        """What a fresh device handle has to be told about this kernel before it is evaluated (Periodic: its
+        periodic dimensions)."""
 
     def _cross_engine(self, v):
         """Device context holding the points `v` of the second argument of `__call__`: the training points (already
@@ -133,6 +138,7 @@ class _StationaryDeviceKernel(CovarianceFunction):
         if cached is not None:
             cached[1].close()
         eng = GpEngine(v, np.zeros(v.shape[0]))
+        self._declare(eng)
         self._cross = (v.copy(), eng)
         return eng
 
@@ -316,6 +322,115 @@ class Matern52(_Matern):
     def _profiles(t):
         e = exp(-t)
         return (1.0 + t + t * t / 3.0) * e, (5.0 / 3.0) * (1.0 + t) * e
+
+
+class Periodic(_StationaryDeviceKernel):
+    r"""
+    Periodic covariance (no counterpart in the reference; scikit-learn's ``ExpSineSquared``, GPy's ``StdPeriodic``):
+    periodic in the listed input dimensions and squared-exponential in the others,
+
+       K(u, v) = A^2 exp(-sum_k w_k / l_k^2),   w_k = 1/2 (u_k - v_k)^2             k not periodic
+                                                w_k = 2 sin^2(pi (u_k - v_k) / p_k)  k periodic
+       theta = [ln A, ln l_1 .. ln l_d, ln p_j for j in periodic_dims, ascending]
+
+    so an angle next to a radius is `Periodic(periodic_dims=[1])`, and trend + season + noise is
+    `SquaredExponential() + Periodic() + WhiteNoise()`.  A known period (2 pi for an angle) is pinned with equal
+    bounds.  In a periodic dimension l_k is dimensionless (the default bounds of ln l_k are (-2.3, 2.3)).
+
+    :param periodic_dims: the periodic input dimensions: distinct indices in [0, d), at most 8; None: all d (d <= 8).
+    :param hyperpar_bounds: optional list of (lower, upper) tuples, one per parameter;
+        estimated from the data when omitted.
+    """
+
+    _gpmi_kernel = _lib.KERNEL_PER
+    _n_shape_params = 0
+
+    def __init__(self, periodic_dims=None, hyperpar_bounds=None):
+        super().__init__(hyperpar_bounds=hyperpar_bounds)
+        if periodic_dims is not None:
+            dims = [int(k) for k in np.ravel(periodic_dims)]
+            if any(k != q for k, q in zip(dims, np.ravel(periodic_dims))):
+                raise ValueError("Periodic: 'periodic_dims' must hold integers")
+            if len(dims) == 0:
+                raise ValueError("Periodic: 'periodic_dims' is empty - that kernel is SquaredExponential")
+            if len(set(dims)) != len(dims) or min(dims) < 0:
+                raise ValueError("Periodic: 'periodic_dims' must hold distinct, non-negative dimension indices")
+            periodic_dims = sorted(dims)
+        self._requested_dims = periodic_dims
+        self.periodic_dims = periodic_dims  # (None until the data tell d)
+
+    def pass_spatial_data(self, x: ndarray):
+        d = np.shape(x)[1] if np.ndim(x) == 2 else 1
+        dims = list(range(d)) if self._requested_dims is None else self._requested_dims
+        if len(dims) > _lib.MAX_PERIODIC:
+            raise ValueError(f"Periodic: {len(dims)} periodic dimensions - the device kernel takes at most "
+                             f"{_lib.MAX_PERIODIC} (list the periodic ones in 'periodic_dims')")
+        if dims[-1] >= d:
+            raise ValueError(f"Periodic: periodic dimension {dims[-1]} of data with {d} dimensions")
+        if d + len(dims) > msg.MAX_DIMENSIONS:
+            raise ValueError(f"Periodic: {d} dimensions, {len(dims)} of them periodic - the device kernel takes "
+                             f"d + the number of periodic dimensions up to {msg.MAX_DIMENSIONS}")
+        super().pass_spatial_data(x)
+        self.periodic_dims = dims
+        self.n_params = 1 + d + len(dims)
+        self.hyperpar_labels = self._labels(d)
+
+    def _labels(self, d):
+        dims = self.periodic_dims if self.periodic_dims is not None else []
+        return (["Periodic log-amplitude"] + [f"Periodic log-scale {i}" for i in range(d)]
+                + [f"Periodic log-period {j}" for j in dims])
+
+    def _declare(self, engine):
+        engine.set_periodic(self.periodic_dims)
+
+    def estimate_hyperpar_bounds(self, y: ndarray):
+        s = log(y.std())
+        scale = self._scale_bounds()
+        for k in self.periodic_dims:
+            scale[k] = (-2.3, 2.3)  # l is in units of the warped distance there: dimensionless
+        period = []
+        for k in self.periodic_dims:
+            mean_abs, rng = _pairwise_abs_mean_and_range(self.x[:, k])
+            period.append((log(mean_abs) - 3, log(rng) + 1))
+        self.bounds = [(s - 4, s + 4)] + scale + period
+
+    def _split(self, theta):
+        """(a, l (d), p (d, nan where not periodic)) of a parameter vector."""
+        theta = np.asarray(theta, dtype=float)
+        d = theta.size - 1 - len(self.periodic_dims)
+        p = np.full(d, np.nan)
+        p[self.periodic_dims] = exp(theta[1 + d:])
+        return exp(theta[0]), exp(theta[1:1 + d]), p
+
+    def gradient_terms(self, v: ndarray, x: ndarray, theta: ndarray):
+        """(A, R) of the predictive-gradient expressions in SquaredExponential's shapes: A (d, N) with
+        A_kn k_n = dK(v, x_n)/dv_k = k_n delta_k / l_k^2, delta_k = (x - v)_k in a plain dimension and
+        (2 pi / p_k) sin(2 pi (x - v)_k / p_k) in a periodic one; R the prior variance of the derivative along
+        each axis, (a / l_k)^2 resp. (a / l_k)^2 (2 pi / p_k)^2."""
+        a, scales, per = self._split(theta)
+        delta = np.array(x - v[None, :], dtype=float)
+        R = (a / scales) ** 2
+        for k in self.periodic_dims:
+            w = 2.0 * np.pi / per[k]
+            delta[:, k] = w * np.sin(w * delta[:, k])
+            R[k] *= w * w
+        return (delta / scales[None, :] ** 2).T, R
+
+    def covariance_and_gradients(self, theta: ndarray):
+        """K and dK/dtheta_j as dense matrices.  The regressor never calls this (its LML gradient contracts dK on the
+        fly on the device); it is provided for plugin users and is O(N^2 d) in memory."""
+        K = self.build_covariance(theta)
+        _, scales, per = self._split(theta)
+        grads, period_grads = [2.0 * K], []
+        for k, l in enumerate(scales):
+            dx = self.x[:, None, k] - self.x[None, :, k]
+            if k in self.periodic_dims:
+                u = dx / per[k]
+                grads.append(K * (4.0 * np.sin(np.pi * u) ** 2 / l**2))
+                period_grads.append(K * (2.0 * np.pi * u * np.sin(2.0 * np.pi * u) / l**2))
+            else:
+                grads.append((dx**2 / l**2) * K)
+        return K, grads + period_grads
 
 
 class WhiteNoise(CovarianceFunction):
@@ -562,8 +677,10 @@ class ChangePoint(CovarianceFunction):
 
 
 def _is_device_mixture(comp):
+    # (a ChangePoint holding a Periodic takes the host composition of plugin kernels: the mixture entry points of the
+    # device do not take that kernel)
     return (isinstance(comp, ChangePoint) and 2 <= comp.n_kernels <= 4
-            and all(isinstance(K, _StationaryDeviceKernel) for K in comp.cov))
+            and all(isinstance(K, _StationaryDeviceKernel) and not isinstance(K, Periodic) for K in comp.cov))
 
 
 MAX_SUM = 4  # components of a device sum (gpmi_set_sum)
@@ -573,7 +690,7 @@ def device_plan(cov):
     """How `GpRegressor` maps a covariance object onto the device kernels:
     returns (kernel_id, main_component, slice_of_its_theta, white_noise_index or None)
     or None when the object is not a supported combination: one stationary kernel (SquaredExponential /
-    RationalQuadratic / Matern32 / Matern52) or one ChangePoint over such kernels (kernel_id -1), optionally plus one WhiteNoise
+    RationalQuadratic / Matern32 / Matern52 / Periodic) or one ChangePoint over such kernels (kernel_id -1), optionally plus one WhiteNoise
     and / or one HeteroscedasticNoise (see `heteroscedastic_slice`); or a sum of 2 to 4 stationary kernels with at
     most one WhiteNoise, in any order (kernel_id `_lib.KERNEL_SUM`: the main component is the CompositeCovariance
     itself, the "slice" an index array that gathers the stationary components' parameters in component order, and
@@ -589,6 +706,8 @@ def device_plan(cov):
         het = [c for c in cov.components if isinstance(c, HeteroscedasticNoise)]
         if (2 <= len(main) <= MAX_SUM and len(wn) <= 1 and len(main) + len(wn) == len(cov.components)
                 and all(isinstance(c, _StationaryDeviceKernel) for _, c in main)):
+            if len({tuple(c.periodic_dims) for _, c in main if isinstance(c, Periodic)}) > 1:
+                return None  # one declaration of periodic dimensions per handle: disagreeing components compose on the host
             idx = np.concatenate([np.arange(cov.slices[i].start, cov.slices[i].stop) for i, _ in main])
             wn_index = cov.slices[wn[0][0]].start if wn else None
             return _lib.KERNEL_SUM, cov, idx, wn_index
@@ -602,6 +721,16 @@ def device_plan(cov):
 def sum_kernels(cov):
     """Kernel ids of the stationary components of a device sum (`device_plan` kernel id `_lib.KERNEL_SUM`), in order."""
     return [c._gpmi_kernel for c in cov.components if isinstance(c, _StationaryDeviceKernel)]
+
+
+def periodic_dims_of(cov):
+    """The periodic dimensions a device handle has to be told for `cov` (`device_plan` not None): those of its Periodic
+    kernel, alone or inside the sum (where all Periodic components agree), or None when it has none."""
+    parts = cov.components if isinstance(cov, CompositeCovariance) else [cov]
+    for c in parts:
+        if isinstance(c, Periodic):
+            return list(c.periodic_dims)
+    return None
 
 
 def heteroscedastic_slice(cov):

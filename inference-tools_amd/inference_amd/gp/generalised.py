@@ -30,7 +30,7 @@ from scipy.optimize import fmin_l_bfgs_b
 
 from inference_amd._engine import GpEngine
 from inference_amd.gp import _messages as msg
-from inference_amd.gp.covariance import CovarianceFunction, SquaredExponential, _StationaryDeviceKernel
+from inference_amd.gp.covariance import CovarianceFunction, Periodic, SquaredExponential, _StationaryDeviceKernel
 from inference_amd.gp.likelihood import Binomial, Likelihood, Logistic, Poisson, logistic_parts
 
 MAX_COLUMNS = 64  # of x: the covariance kernels' limit
@@ -78,6 +78,9 @@ class GeneralisedGpRegressor:
         self.offset = float(offset)
 
         self.cov = kernel() if isclass(kernel) else kernel
+        if isinstance(self.cov, Periodic):
+            raise NotImplementedError("[ GeneralisedGpRegressor error ] The Periodic covariance function is not served by "
+                                      "the generalised-GP entry points of the device.")
         if not isinstance(self.cov, _StationaryDeviceKernel):
             raise NotImplementedError(
                 f"[ GeneralisedGpRegressor error ] The covariance function {type(self.cov).__name__} is not served: one "

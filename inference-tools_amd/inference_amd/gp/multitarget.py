@@ -29,7 +29,7 @@ from inference_amd import _lib
 from inference_amd._engine import GpEngine
 from inference_amd.gp import _messages as msg
 from inference_amd.gp.covariance import (CovarianceFunction, SquaredExponential, device_plan, heteroscedastic_slice,
-                                         sum_kernels)
+                                         periodic_dims_of, sum_kernels)
 
 
 class MultiTargetGpRegressor:
@@ -65,6 +65,9 @@ class MultiTargetGpRegressor:
 
         self.cov = kernel() if isclass(kernel) else kernel
         self.cov.pass_spatial_data(self.x)
+        if periodic_dims_of(self.cov) is not None:
+            raise NotImplementedError("[ MultiTargetGpRegressor error ] The Periodic covariance function is not served "
+                                      "by the many-target entry points of the device: fit one GpRegressor per target.")
         plan = device_plan(self.cov)
         if plan is None or plan[0] == -1 or heteroscedastic_slice(self.cov) is not None:
             raise NotImplementedError(

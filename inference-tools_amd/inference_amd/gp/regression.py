@@ -27,7 +27,8 @@ from inference_amd import _lib
 from inference_amd._engine import GpEngine
 from inference_amd.gp import _messages as msg
 from inference_amd.gp._draws import draw_arguments, raise_if_not_positive_definite
-from inference_amd.gp.covariance import heteroscedastic_slice, CovarianceFunction, SquaredExponential, device_plan, sum_kernels
+from inference_amd.gp.covariance import (heteroscedastic_slice, CovarianceFunction, SquaredExponential, device_plan,
+                                         periodic_dims_of, sum_kernels)
 from inference_amd.gp.mean import ConstantMean, MeanFunction, _FeatureMean
 
 
@@ -147,6 +148,8 @@ class GpRegressor:
         self._mix = self._stat if self._kernel_id == -1 else None  # ChangePoint: mixture entry points
         # a sum of stationary kernels (GPMI_KERNEL_SUM): the handle learns its components once (gpmi_set_sum)
         self._sum_kernels = sum_kernels(self._stat) if self._kernel_id == _lib.KERNEL_SUM else None
+        # a Periodic kernel, alone or in the sum: the handle learns its periodic dimensions once (gpmi_set_periodic)
+        self._periodic_dims = None if self._generic else periodic_dims_of(self.cov)
         self._het_slice = None if self._generic else heteroscedastic_slice(self.cov)
         self._fit_noise = None
         self._device = device
@@ -199,6 +202,8 @@ class GpRegressor:
                 self.x, self.y, noise_var=self._noise_var, y_cov=self._y_cov, device=self._device,
                 reserve=getattr(self, "_reserve", 0)
             )
+            if getattr(self, "_periodic_dims", None) is not None:
+                self._engine.set_periodic(self._periodic_dims)
             if getattr(self, "_sum_kernels", None) is not None:
                 self._engine.set_sum(self._sum_kernels)
         return self._engine
@@ -590,8 +595,8 @@ class GpRegressor:
             return
         if self._mix is not None:
             self._mix.gradient_terms(None, None, None)  # ChangePoint has none either (covariance.py:38-44)
-        if self._kernel_id not in (_lib.KERNEL_SE, _lib.KERNEL_M32, _lib.KERNEL_M52):
-            # the device has predictive-gradient kernels for these three; RationalQuadratic and sums have no
+        if self._kernel_id not in (_lib.KERNEL_SE, _lib.KERNEL_M32, _lib.KERNEL_M52, _lib.KERNEL_PER):
+            # the device has predictive-gradient kernels for these four; RationalQuadratic and sums have no
             # gradient_terms (covariance.py:38-44): same error as the reference
             self._stat.gradient_terms(None, None, None)
 

@@ -38,14 +38,18 @@ from inference_amd import _lib
 from inference_amd._engine import SparseEngine
 from inference_amd.gp import _messages as msg
 from inference_amd.gp._draws import draw_arguments, raise_if_not_positive_definite
-from inference_amd.gp.covariance import (CompositeCovariance, SquaredExponential, WhiteNoise, _StationaryDeviceKernel,
-                                         device_plan)
+from inference_amd.gp.covariance import (CompositeCovariance, Periodic, SquaredExponential, WhiteNoise,
+                                         _StationaryDeviceKernel, device_plan)
 from inference_amd.gp.mean import ConstantMean
 from inference_amd.gp.regression import GpRegressor
 
 SUPPORTED = ("one of SquaredExponential, RationalQuadratic, Matern32, Matern52 (class or instance), optionally "
              "+ WhiteNoise(), with y_err data errors")
 INDUCING_METHODS = ("random", "greedy")
+
+
+def _has_periodic(cov):
+    return any(isinstance(c, Periodic) for c in (cov.components if isinstance(cov, CompositeCovariance) else [cov]))
 
 
 def _select_on_device(x, m, kernel_id, theta_stat, weights, tol, min_variance, device):
@@ -94,6 +98,9 @@ def select_inducing_points(x, m, kernel, theta_cov, *, weights=None, tol=0.0, mi
     if x.ndim != 2 or x.shape[1] > msg.MAX_DIMENSIONS:
         raise ValueError(f"x must be an (N, d) array with d <= {msg.MAX_DIMENSIONS}, got shape {x.shape}")
     cov = deepcopy(kernel() if isclass(kernel) else kernel)
+    if _has_periodic(cov):
+        raise NotImplementedError("select_inducing_points: the Periodic covariance function is not served by the "
+                                  f"selection kernels of the device; supported: {SUPPORTED}")
     cov.pass_spatial_data(x)
     plan = device_plan(cov)
     if plan is None or not isinstance(plan[1], _StationaryDeviceKernel):
@@ -171,6 +178,9 @@ class SparseGpRegressor:
         self.cov = kernel() if isclass(kernel) else kernel
         self.mean = mean() if isclass(mean) else mean
         main = self.cov
+        if _has_periodic(self.cov):
+            raise NotImplementedError("SparseGpRegressor: the Periodic covariance function is not served by the "
+                                      f"sparse-model kernels of the device; supported: {SUPPORTED}")
         if isinstance(self.cov, CompositeCovariance):
             parts = self.cov.components
             wn = [c for c in parts if isinstance(c, WhiteNoise)]
