@@ -1063,7 +1063,11 @@ int gpmi_dev_download(gpmi_ctx* ctx, void* dst_host, const void* src_dev, int64_
 /* in-place lower Cholesky of the n x n matrix at A_dev, of which only the tiles on and below the diagonal are read.  Untouched: the
  * columns from n on, every 128 x 128 tile strictly above the diagonal, and the part of tile (0, 0) above the diagonal.
  * The part above the diagonal inside the other diagonal tiles is workspace: the trailing updates write whole diagonal
- * tiles (or their two diagonal 64 x 64 quarters), so it returns holding intermediate values of theirs. */
+ * tiles (or their two diagonal 64 x 64 quarters), so it returns holding intermediate values of theirs.
+ * On a bare handle (no gpmi_set_data) the factorisation runs in stream order on the full chip at every n: the
+ * flag-ordered tail and the look-ahead steps need the CU-masked stream pair, which only a handle whose data set has
+ * np >= 5120 owns (the factor is the same bits either way; *info is the order of the first leading minor that fails, or
+ * -6 if a poll of the flag-ordered launch gave up). */
 int gpmi_dev_potrf(gpmi_ctx* ctx, double* A_dev, int64_t n, int64_t ld, int* info);
 /* C (m x n, lower tiles only if lower != 0) -= A (m x k) * B (n x k)^T; k a multiple of 16, A and B may be one buffer.
  * lower != 0 (m >= n): every element on or below the diagonal is updated and no 128 x 128 tile strictly above it is

@@ -185,16 +185,23 @@ CASES = {
     "binomial_rq": ("Binomial", RQ, 257, 17, 1, 3),       # the 64 KiB LDS builders
     "poisson_m32": ("Poisson", M32, 640, 1, 129, 7),      # y = 0 rows, exposures 1 .. 50; a second 512-wide inverse block
 }
+# the case of tests/test_pair_regime_gpu.py: np = 5248 >= 5120, so the handle's first lane owns the CU-masked stream pair
+# and every factorisation of B is one flag-ordered launch of 41 tile rows.  Its inputs are regenerated from the seed;
+# tests/golden/generalised_pair.npz holds the mirror's logq, f, g, mean and var with their allowances (no gradient: the
+# mirror's N^3 einsum per hyper-parameter is not worth it at this size)
+PAIR_CASES = {
+    "poisson_se_pair": ("Poisson", SE, 5130, 2, 300, 13),
+}
 
 
 def make_case(name):
     """Seeded inputs of a case: dict(lik_name, kernel, x, y, aux_arg, theta, theta2, pts)."""
-    lik_name, kernel, n, d, m, seed = CASES[name]
+    lik_name, kernel, n, d, m, seed = CASES[name] if name in CASES else PAIR_CASES[name]
     rng = np.random.default_rng(seed)
     x = rng.uniform(0.0, 1.0, size=(n, d))
     pts = rng.uniform(0.0, 1.0, size=(m, d))
     f = _smooth(x)
-    if name == "poisson_se":
+    if name in ("poisson_se", "poisson_se_pair"):
         aux = np.ones(n)
         y = rng.poisson(np.exp(1.0 + f)).astype(float)
         amp, scale = 0.0, np.log(0.5)
@@ -216,15 +223,15 @@ def make_case(name):
     return dict(lik_name=lik_name, kernel=kernel, x=x, y=y, aux_arg=aux, theta=theta, theta2=theta + 0.15, pts=pts)
 
 
-def mirror_quantities(lik, aux, offset, c, ripple=None):
+def mirror_quantities(lik, aux, offset, c, ripple=None, want_grad=True):
     """The quantities the device is compared in, from the mirror: dict(logq, grad, f, g, mean, var) and the Newton log.
-    `ripple`: applied to the mirror's K and to its cross-covariances."""
+    `ripple`: applied to the mirror's K and to its cross-covariances.  `want_grad` False leaves `grad` out."""
     K = covariance(c["kernel"], c["x"], c["theta"])
     if ripple is not None:
         K = ripple(K)
     res = laplace(lik, c["x"], c["y"], aux, offset, c["kernel"], c["theta"], K=K)
     assert res["info"] == 0, res["info"]
-    grad = gradient(res, c["kernel"], c["x"], c["theta"])
+    grad = gradient(res, c["kernel"], c["x"], c["theta"]) if want_grad else None
     kq = cross_covariance(c["kernel"], c["pts"], c["x"], c["theta"])
     if ripple is not None:
         kq = ripple(kq)
@@ -232,4 +239,6 @@ def mirror_quantities(lik, aux, offset, c, ripple=None):
     v = solve_triangular(res["L"], (kq * res["sw"][None, :]).T, lower=True)
     var = np.exp(2.0 * c["theta"][0]) - (v * v).sum(axis=0)
     q = dict(logq=np.array(res["logq"]), grad=grad, f=res["f"], g=res["g"], mean=mean, var=var)
+    if not want_grad:
+        del q["grad"]
     return q, (res["iterations"], res["halvings"])

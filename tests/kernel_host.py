@@ -168,6 +168,32 @@ def pad_identity(A, ld, fill=C_PAD):
     return buf
 
 
+# ------------------------------------------------------------------- what a flag-ordered launch books as its FLOPs
+FLOW_OUTER = 4  # tile columns per outer panel (csrc/potrf_flow.hip: OBT)
+TILE_UPDATE_FLOPS = 2.0 * TILE ** 3  # one 128 x 128 tile taking one tile column
+
+
+def flow_update_flops(m):
+    """The FLOPs that potrf_flow_tail books under GPMI_PROF_FLOW for a tail of m tile rows (flow_build: flops_update), in
+    closed form.  Tile (i, j), j <= i, takes the tile columns k < j, each of them once, as one-column tasks or inside a
+    K = 512 chunk; the chain launch of column k itself updates tile (k + 1, k + 1), so a diagonal tile (i, i) is left
+    with i - 1 columns; a diagonal tile keeps its lower triangle only and is booked at 3/4:
+        sum_i [ i (i - 1) / 2 + 3/4 max(i - 1, 0) ]  tile updates of 2 * 128^3 FLOPs.
+    Every term is a multiple of 2^19 far below 2^53: the sum is exact in fp64 whatever its order."""
+    units = sum(i * (i - 1) / 2.0 + 0.75 * max(i - 1, 0) for i in range(m))
+    return units * TILE_UPDATE_FLOPS
+
+
+def flow_update_flops_of_lists(tasks):
+    """The same from task lists as gpmi_flow_task_lists returns them (rows of 8 ints; column 0 the type: 0 panel TRSM,
+    1 one-column update of a 64 x 64 sub-tile, 2 K = 512 chunk of a whole tile, 3 K = 512 chunk of a sub-tile): a
+    sub-tile is a quarter of a tile, and a diagonal tile has three of them."""
+    kind = np.asarray(tasks)[:, 0]
+    units = 0.25 * np.count_nonzero(kind == 1) + FLOW_OUTER * np.count_nonzero(kind == 2) \
+        + 0.25 * FLOW_OUTER * np.count_nonzero(kind == 3)
+    return units * TILE_UPDATE_FLOPS
+
+
 # ------------------------------------------------------------------------------------- comparisons that name tiles
 def _bits_equal(a, b):
     return np.ascontiguousarray(a).view(np.int64) == np.ascontiguousarray(b).view(np.int64)

@@ -222,3 +222,23 @@ def test_argument_checks_run_before_any_device_call():
             GeneralisedGpRegressor(x, counts, likelihood=Poisson(), kernel=kernel, hyperpars=np.zeros(3))
     with pytest.raises(NotImplementedError):
         GeneralisedGpRegressor(x, counts, likelihood=object(), kernel=Matern52, hyperpars=np.zeros(3))
+
+
+def test_pair_regime_fixture_belongs_to_its_seeded_case(golden):
+    """tests/golden/generalised_pair.npz holds results only; tests/test_pair_regime_gpu.py regenerates the inputs from the
+    seed.  The two must belong together: shapes, the offset, and the mirror's own stationarity at the stored mode -
+    g = grad log p(y | f) for the regenerated y, which no other data set would satisfy."""
+    g = golden("generalised_pair")
+    for name, (lik_name, kernel, n, d, m, seed) in gh.PAIR_CASES.items():
+        c = gh.make_case(name)
+        assert c["x"].shape == (n, d) and c["pts"].shape == (m, d) and -(-n // 128) * 128 >= 5120
+        assert np.array_equal(c["y"], gh.make_case(name)["y"])
+        lik = Poisson(c["aux_arg"])
+        aux = lik.bind(n)
+        assert float(g[f"{name}_offset"]) == lik.default_offset(c["y"], aux)
+        assert g[f"{name}_f"].shape == g[f"{name}_g"].shape == (n,) and g[f"{name}_mean"].shape == g[f"{name}_var"].shape == (m,)
+        assert g[f"{name}_newton"][0] >= 2 and f"{name}_grad" not in g and f"{name}_x" not in g
+        grad = lik.derivatives(c["y"], g[f"{name}_f"], aux)[0]
+        assert np.abs(grad - g[f"{name}_g"]).max() <= 1e-12 * np.abs(grad).max()
+        for k in ("logq", "f", "g", "mean", "var"):
+            assert float(g[f"{name}_allow_{k}"]) >= 1e-10 * np.abs(g[f"{name}_{k}"]).max() > 0.0

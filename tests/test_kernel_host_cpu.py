@@ -12,7 +12,7 @@ import kernel_host as kh
 needs_longdouble = pytest.mark.skipif(not kh.LONGDOUBLE_OK, reason="np.longdouble has no 64-bit mantissa here")
 
 # (n, span) of every int_chol_case the GPU tests use
-CHOL_SIZES = [(128, 3), (256, 3), (896, 3), (1024, 3), (1152, 3), (2176, 3), (4096, 3), (7168, 3),
+CHOL_SIZES = [(128, 3), (256, 3), (896, 3), (1024, 3), (1152, 3), (2176, 3), (4096, 3), (7168, 3), (7680, 3),
               (127, 1), (129, 1), (640, 1), (1000, 1), (2048, 1), (2176, 1), (4224, 1)]
 
 
@@ -160,6 +160,27 @@ def test_builders_are_deterministic():
     rows = set(kh.check_rows(1152).tolist())
     assert {0, 127, 128, 129, 1023, 1024, 1025, 1151} <= rows and len(rows) <= 2 + 3 * 8 + 32
     assert np.array_equal(kh.check_rows(640), np.arange(640))
+
+
+@pytest.mark.parametrize("m", [1, 2, 8, 9, 17, 32, 41, 48, 52, 56, 60])
+def test_flow_flops_formula_equals_the_shipped_task_lists(m):
+    """kernel_host.flow_update_flops (the look-ahead witness of tests/test_kernels_gpu.py) against the task lists the
+    library ships for a tail of m tile rows, counted task by task; the count does not depend on how many workgroups
+    the lists are dealt to, and tails of 48, 52 and 56 rows and whole matrices of 56 and 60 book different amounts."""
+    import ctypes as C
+
+    from inference_amd import _lib
+
+    lib = _lib.load()
+    for nwg in (448, 64):
+        cnt = C.c_int64(0)
+        assert lib.gpmi_flow_task_lists(m, nwg, 0, None, C.byref(cnt)) == 0
+        tasks = np.zeros((max(cnt.value, 1), 8), dtype=np.int32)
+        tasks[:, 0] = -1
+        assert lib.gpmi_flow_task_lists(m, nwg, cnt.value, tasks.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(cnt)) == 0
+        assert kh.flow_update_flops_of_lists(tasks[:cnt.value]) == kh.flow_update_flops(m)
+    assert kh.flow_update_flops(48) == 18106.75 * 2.0 * 128 ** 3
+    assert len({kh.flow_update_flops(k) for k in (41, 44, 48, 52, 56, 60)}) == 6
 
 
 # ---- sensitivity of the comparison helpers: a host result that is wrong in one place must fail and name the tile

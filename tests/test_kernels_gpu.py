@@ -10,6 +10,14 @@ np.longdouble; tests/test_kernel_host_cpu.py shows that LAPACK and plain substit
 conditions on their own.  Only operand shapes and leading dimensions (n, n + 32, n + 128) that the library or tools/
 use are passed.
 
+Which factorisation schedule a call reaches depends on the HANDLE, not only on n.  The flag-ordered tail (8 to 4095
+tile rows) and the look-ahead steps (52 or more trailing tile rows) need the CU-masked stream pair, which only the first
+lane of a handle whose data set has np >= 5120 owns.  A bare handle - `dev`, `dev_noflow`, parts B and C - factorises
+in stream order on the full chip at EVERY size, whatever GPMI_OPT_NO_FLOW says.  Part H repeats the exact factor and
+`info` on `dev_pair`, a handle that owns the pair, and proves from the library's own launch counters which schedule
+each call took.  Part H comes last: by then every other handle of this file that owns a pair (the n = 6656 engine of
+part G) has been closed.
+
 Which GEMM kernel a shape reaches (launch_gemm_part; `tiles` counts 128 x 128 tiles):
   k <= 128 or tiles < 384 -> 64 x 64 tiles: the LDS-DMA ring kernel when k % 64 == 0 and k >= 128, else register-staged;
       rectangles of at most 48 tiles with k > 128 use 32 x 64 register-staged tiles instead (the (384, 256) rectangles
@@ -34,12 +42,42 @@ needs_longdouble = pytest.mark.skipif(not kh.LONGDOUBLE_OK, reason="np.longdoubl
 class Dev:
     """Device buffers and the device-pointer entry points on one handle (as tools/bench_gemm.py uses them)."""
 
-    def __init__(self, no_flow=False):
+    PAIR_POINTS = 5120  # 40 tile rows: the smallest data set whose first lane gets the CU-masked stream pair
+
+    def __init__(self, no_flow=False, pair=False):
+        """`pair`: the handle is given PAIR_POINTS dummy points (d = 1, distinct x, y = 0, unit noise) before anything
+        else: lane 0 then owns the CU-masked stream pair and gpmi_dev_potrf, which runs on lane 0, borrows it."""
         from inference_amd import _lib
 
+        self.lib = _lib
         self.h = _lib.Handle(0)
+        if pair:
+            n = self.PAIR_POINTS
+            x, y, noise = np.arange(n, dtype=np.float64), np.zeros(n), np.ones(n)
+            self.h.call("gpmi_set_data", _lib.dptr(x), _lib.dptr(y), _lib.dptr(noise), None, n, 1)
         if no_flow:
             self.h.call("gpmi_set_option", _lib.OPT_NO_FLOW, 1)
+
+    def no_flow(self, on):
+        """GPMI_OPT_NO_FLOW, read at every factorisation: 1 keeps the flag-ordered tail off"""
+        self.h.call("gpmi_set_option", self.lib.OPT_NO_FLOW, int(on))
+
+    def stamps(self, on):
+        """The in-kernel stamps of the trailing-update classes (GPMI_PROF_SYRK, _SYRK_REST, _SYRK_SLICE, _FLOW) on or
+        off; the counters start from zero."""
+        self.h.call("gpmi_profile_enable", (2 << self.lib.PROF_SYRK) if on else 0)
+        self.h.call("gpmi_profile_reset")
+
+    def booked(self):
+        """{class: (launches, FLOPs)} of the flag-ordered launches (PROF_FLOW), the update slices on the panel stream
+        (PROF_SYRK_SLICE) and the 128 x 128-tile trailing updates (PROF_SYRK) since the last stamps() or booked()"""
+        out = {}
+        for klass in (self.lib.PROF_FLOW, self.lib.PROF_SYRK_SLICE, self.lib.PROF_SYRK):
+            launches, flops = C.c_int64(-1), C.c_double(-1.0)
+            self.h.call("gpmi_profile_read", klass, C.byref(launches), None, C.byref(flops), None)
+            out[klass] = (launches.value, flops.value)
+        self.h.call("gpmi_profile_reset")
+        return out
 
     def upload(self, a):
         a = np.ascontiguousarray(a, dtype=np.float64)
@@ -207,17 +245,20 @@ def _chol_buffers(n, pad, seed, span=3):
     return L0, A, buf
 
 
-# (n, ld - n, no_flow).  128: the diagonal kernel alone; 896 / 1024: either side of the flag-ordered launch's minimum
-# of 8 tile rows; 1152, 2176: a partial last panel and a partial strip; 4096 without flow: the first trailing update has
-# 406 tiles at K = 512 (128 x 128 kernel, split point, mixed launch); 7168: 56 tile rows, the look-ahead regime.
+# (n, ld - n, no_flow) on the BARE handles: every case runs the stream-ordered schedule on the full chip, because a bare
+# handle has no CU-masked stream pair (the `no_flow` cases differ from the others in their seed and pitch only; the
+# schedules that need the pair are part H's).  128: the diagonal kernel alone; 896 / 1024, 1152, 2176: 7, 8, 9 and 17 tile
+# rows - a partial last panel and a partial strip; 4096: the first trailing update has 406 tiles at K = 512 (128 x 128
+# kernel, split point, mixed launch); 7168: 56 tile rows, fourteen outer panels in stream order.
 POTRF = [(128, 32, 0), (256, 0, 0), (896, 32, 0), (1024, 32, 0), (1152, 128, 0), (2176, 32, 0), (4096, 32, 0),
          (1152, 32, 1), (4096, 32, 1), (7168, 32, 0)]
 
 
 @pytest.mark.parametrize("n,pad,no_flow", POTRF,
-                         ids=[f"n{n}-ld+{p}-{'stream' if nf else 'flow'}{'-slow' if n == 7168 else ''}" for n, p, nf in POTRF])
+                         ids=[f"n{n}-ld+{p}-bare{'-noflow' if nf else ''}{'-slow' if n == 7168 else ''}" for n, p, nf in POTRF])
 def test_potrf_integer_exact(dev, dev_noflow, n, pad, no_flow):
-    """The factor of A = L0 L0^T is L0 bit for bit in every schedule: every pivot is exactly 1 (the refinements of
+    """The factor of A = L0 L0^T is L0 bit for bit (here: on a bare handle, in stream order; part H: the flag-ordered
+    and look-ahead schedules): every pivot is exactly 1 (the refinements of
     rcp_newton, rsqrt_refined and factor16_steps.h return 1.0 for 1.0 whatever the hardware seed), every inverse
     diagonal block I, every TRSM and update integer arithmetic.  The rest of the buffer as include/gpmi.h states it:
     padding columns, strictly-upper tiles and the upper triangle of tile (0, 0) untouched, the upper triangles of the
@@ -241,9 +282,9 @@ def info_case():
     return _chol_buffers(1152, 32, seed=77)
 
 
-@pytest.mark.parametrize("no_flow", [0, 1], ids=["flow", "stream"])
+@pytest.mark.parametrize("no_flow", [0, 1], ids=["bare", "bare-noflow"])
 def test_potrf_info_is_the_leading_minor(dev, dev_noflow, info_case, no_flow):
-    """A[k-1, k-1] lowered by 2 makes the k-th pivot exactly -1 (it is 1 in the sound matrix, and the entry enters no
+    """(Bare handles: stream order either way.)  A[k-1, k-1] lowered by 2 makes the k-th pivot exactly -1 (it is 1 in the sound matrix, and the entry enters no
     earlier pivot): info == k, the order of the first leading minor that is not positive definite.  Only the
     factorisation is called on these matrices."""
     L0, A, buf0 = info_case
@@ -600,3 +641,203 @@ def test_rows_kinv_leaves_the_engine_intact(solve_engines):
     ka, ss = eng.predict_dense(Q)
     assert np.array_equal(ka, Q @ a0) and np.array_equal(ss, (X0 ** 2).sum(1))
     _rows_kinv_check(eng, A, n, m + 1)
+
+
+# =========================================================================================== H. on a handle with the pair
+# gpmi_dev_potrf on a handle whose lane 0 owns the CU-masked stream pair (Dev(pair=True)): the only way the device-pointer
+# entry point reaches potrf_flow.hip and the look-ahead steps of potrf_lower.  Schedule by size (nt tile rows):
+#   nt < 8 (896)                     stream order, no flag-ordered launch
+#   8 <= nt < 56 (1024 .. 4096)      the whole matrix is ONE flag-ordered launch of nt rows
+#   7168 (nt = 56)                   panel 0 in stream order; step 0 overlapped (52 trailing rows: columns of panel 1, panel 1 on
+#                                    the 32-CU stream beside the rest of the update on the others); then a 48-row flag-ordered tail
+#   7680 (nt = 60)                   two overlapped steps in a row (56 and 52 trailing rows: the second waits for the first's
+#                                    ev_main / ev_panel, and for ev_slice if the first had sliced), then the same 48-row tail
+# The witnesses.  With the in-kernel stamps on (gpmi_profile_enable(2 << PROF_SYRK)) potrf_flow_tail books one launch and
+# the FLOPs of its update tasks under GPMI_PROF_FLOW.  Those FLOPs are a function of the tail's tile rows alone
+# (kernel_host.flow_update_flops, checked against the shipped task lists by tests/test_kernel_host_cpu.py): a launch
+# count of 1 with the FLOPs of nt rows says the whole matrix went through the task kernel, a count of 1 with the FLOPs of
+# 48 rows at nt = 56 / 60 says the steps before it were the overlapped ones - a tail entered one step early or late would
+# book 52 or 44 rows, a whole-matrix launch 56 or 60, and they all differ.  (GPMI_PROF_SYRK_SLICE cannot serve at these
+# sizes: slice_tiles of potrf.hip gives (su - chain) / (per_main + per_panel) = 24 tiles at 52 trailing rows and 42 at
+# 56 with 224 + 32 CUs and the fused panel column, both below one round of 64, so no slice is launched; the tests assert
+# that too.)  A count of 0 on this handle where a launch is due, an `info` of GPMI_INFO_FLOW_TIMEOUT (-6), a RuntimeWarning
+# or a handle that has fallen back to GPMI_OPT_NO_FLOW fail the test: nothing here may pass by way of the stream-ordered
+# schedule.
+# Observed on an MI355X: see DESIGN.md section 2.1 for the counts and durations.
+PAIR_TAIL_ROWS = 48  # trailing tile rows at which the look-ahead regime (GPMI_LOOKAHEAD_MIN = 52, outer panels of 4) ends
+
+
+def _flow_rows(n):
+    """Tile rows of the flag-ordered launch of an n x n factorisation on a handle with the pair (0: none)."""
+    nt = n // kh.TILE
+    if nt < 8:
+        return 0
+    return nt if nt - 4 < 52 else PAIR_TAIL_ROWS
+
+
+_PAIR_CASES = {}
+
+
+@pytest.fixture(scope="module")
+def pair_case():
+    """_chol_buffers(n, 32, seed=n); the sizes that both the exact and the info test use are built once and kept."""
+
+    def get(n):
+        if n in _PAIR_CASES:
+            return _PAIR_CASES[n]
+        case = _chol_buffers(n, 32, seed=n)
+        if n in (1152, 2176, 7168):
+            _PAIR_CASES[n] = case
+        return case
+
+    yield get
+    _PAIR_CASES.clear()
+
+
+@pytest.fixture(scope="module")
+def dev_pair():
+    d = Dev(pair=True)
+    yield d
+    d.h.close()
+
+
+def _witness(d, n, expect_rows, what):
+    """Reads and prints the counters of the factorisation just run and holds them to `expect_rows` (0: stream order)."""
+    booked = d.booked()
+    launches, flops = booked[d.lib.PROF_FLOW]
+    slices = booked[d.lib.PROF_SYRK_SLICE][0]
+    print(f"\nFLOW-WITNESS {what} n={n}: FLOW launches {launches}, FLOPs {flops:.6e} (a {expect_rows}-row launch books "
+          f"{kh.flow_update_flops(expect_rows):.6e}), SYRK_SLICE launches {slices}, SYRK launches {booked[d.lib.PROF_SYRK][0]}")
+    assert not getattr(d.h, "_no_flow", False), "the handle has fallen back to the stream-ordered schedule"
+    if expect_rows == 0:
+        assert launches == 0, f"{what} n={n}: a flag-ordered launch where none is due"
+        return
+    assert launches >= 1, f"{what} n={n}: no flag-ordered launch - this call ran in stream order"
+    assert launches == 1 and flops == kh.flow_update_flops(expect_rows), \
+        f"{what} n={n}: {launches} launches booking {flops!r} FLOPs, not one launch of {expect_rows} tile rows"
+    assert slices == 0
+
+
+PAIR_N = [896, 1024, 1152, 2176, 4096, 7168, 7680]
+
+
+@pytest.mark.filterwarnings("error::RuntimeWarning")
+@pytest.mark.parametrize("n", PAIR_N, ids=[f"n{n}-pair{'-slow' if n >= 7168 else ''}" for n in PAIR_N])
+def test_potrf_integer_exact_on_the_pair_handle(dev_pair, pair_case, n):
+    """test_potrf_integer_exact in the flag-ordered and look-ahead schedules (ld = n + 32): factored twice with the
+    flag-ordered tail allowed - the first time with the stamps on, for the witness - and once under GPMI_OPT_NO_FLOW
+    on the same handle (where 7168 and 7680 keep their overlapped steps and finish in stream order).  All three buffers
+    are exact everywhere (kernel_host.chol_mismatches: factor, padding, strictly-upper tiles, tile (0, 0)), the two
+    repeats are bit-identical, and info == 0 (never -6, the time-out of a flag-ordered poll).
+    Witness: GPMI_PROF_FLOW launches and FLOPs, see the comment above - one launch of n / 128 rows for 1024 .. 4096, one
+    of 48 rows for 7168 and 7680 (the look-ahead witness: slice_tiles is 0 at these sizes, so the FLOPs of the tail
+    are what tells an overlapped step from a stream-ordered one), none at 896 and none under GPMI_OPT_NO_FLOW."""
+    d = dev_pair
+    L0, A, buf0 = pair_case(n)
+    rows = _flow_rows(n)
+    p = d.upload(buf0)
+    try:
+        def run(label, stamped, expect_rows):
+            d.put(p, buf0)
+            if stamped:
+                d.stamps(True)
+            info = C.c_int(-7)
+            try:
+                d.h.call("gpmi_dev_potrf", p, n, buf0.shape[1], C.byref(info))
+                if stamped:
+                    _witness(d, n, expect_rows, label)
+            finally:
+                d.stamps(False)
+            assert info.value == 0, f"{label} n={n}: info {info.value}"
+            got = d.download(p, buf0.shape)
+            fail_with_tiles(kh.chol_mismatches(got, buf0, L0), f"gpmi_dev_potrf on the pair handle, {label}, n={n} ld={n + 32}")
+            return got
+
+        first = run("flag-ordered, first", True, rows)
+        second = run("flag-ordered, second", False, rows)
+        same = first.view(np.int64) == second.view(np.int64)
+        fail_with_tiles(kh._tile_report(~same, "differ between two factorisations of the same upload", first, second),
+                        f"gpmi_dev_potrf on the pair handle n={n} repeated")
+        del first, second, same
+        d.no_flow(1)
+        try:
+            run("GPMI_OPT_NO_FLOW", True, 0)
+        finally:
+            d.no_flow(0)
+    finally:
+        d.free(p)
+
+
+def test_bare_handle_books_no_flag_ordered_launch(dev):
+    """The other side of the witness: the same call on a bare handle, at a size part H factors as one flag-ordered
+    launch, books none."""
+    n = 1152
+    L0, A, buf0 = _chol_buffers(n, 32, seed=n)
+    dev.stamps(True)
+    try:
+        (got, info), = dev.potrf(buf0, n)
+        _witness(dev, n, 0, "bare handle")
+    finally:
+        dev.stamps(False)
+    assert info == 0
+    fail_with_tiles(kh.chol_mismatches(got, buf0, L0), f"gpmi_dev_potrf on the bare handle, stamps on, n={n}")
+
+
+# n -> [(label, {row: new diagonal value or None for "lowered by 2"}, expected info)]
+def _pair_info_cases(n):
+    if n == 1152:
+        cases = [(f"pivot {k} = -1", {k - 1: None}, k) for k in INFO_K]
+        cases.append(("pivots 17 and 641 = -1", {640: None, 16: None}, 17))   # the first is reported
+        cases.append(("NaN on the diagonal at row 700", {700: np.nan}, 701))
+        return cases
+    ks = {2176: (2049, 2176),  # the ragged last panel (tile row 16 alone)
+          # first panel, before anything overlaps; the panel factored on the 32-CU stream beside the overlapped update;
+          # inside the flag-ordered tail; the last pivot
+          7168: (100, 642, 4024, 7168)}[n]
+    return [(f"pivot {k} = -1", {k - 1: None}, k) for k in ks]
+
+
+@pytest.mark.filterwarnings("error::RuntimeWarning")
+@pytest.mark.parametrize("n", [1152, 2176, 7168], ids=["n1152-pair", "n2176-pair", "n7168-pair-slow"])
+def test_potrf_info_on_the_pair_handle(dev_pair, pair_case, n):
+    """test_potrf_info_is_the_leading_minor where the failing pivot sits inside the task kernel's launch or beside an
+    overlapped update: every call returns info == k - not GPMI_INFO_FLOW_TIMEOUT, no error, no warning -, every one of
+    them took the flag-ordered schedule (witness as above, stamps on throughout), and after EVERY failing call the next
+    factorisation of the sound matrix on the same handle gives the bits of the first one, which is checked against L0: no
+    flag, abort word or task-list state survives an abandoned factorisation."""
+    d = dev_pair
+    L0, A, buf0 = pair_case(n)
+    rows = _flow_rows(n)
+    ld = buf0.shape[1]
+    p = d.upload(buf0)
+    d.stamps(True)
+    try:
+        def factor(label):
+            info = C.c_int(-7)
+            d.h.call("gpmi_dev_potrf", p, n, ld, C.byref(info))
+            _witness(d, n, rows, label)
+            return info.value
+
+        assert factor("sound") == 0
+        ref = d.download(p, buf0.shape)
+        fail_with_tiles(kh.chol_mismatches(ref, buf0, L0), f"gpmi_dev_potrf on the pair handle n={n}")
+        for label, changes, want in _pair_info_cases(n):
+            kept = {r: buf0[r, r] for r in changes}
+            for r, v in changes.items():
+                buf0[r, r] = kept[r] - 2.0 if v is None else v
+            try:
+                d.put(p, buf0)
+            finally:
+                for r, v in kept.items():
+                    buf0[r, r] = v
+            got = factor(label)
+            assert got == want, f"n={n}, {label}: info {got}, expected {want}"
+            d.put(p, buf0)
+            assert factor(f"sound, after {label}") == 0
+            again = d.download(p, buf0.shape)
+            same = again.view(np.int64) == ref.view(np.int64)
+            fail_with_tiles(kh._tile_report(~same, "differ from the factorisation before the failing one", again, ref),
+                            f"gpmi_dev_potrf on the pair handle n={n}, sound matrix after {label}")
+    finally:
+        d.stamps(False)
+        d.free(p)
